@@ -264,8 +264,32 @@ def harness_ragged(model, device, n_images=256, batch=32, workers=16, seed=4321,
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 64_000_000         # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(dirname, labels, confusion, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the timed path handed its caller, as .npy files two builds can be compared on.
+      labels.npy     [n,H,W] float32  the labels run_batch returned in the last timed step (rank 0's images); when all B images do not
+                                      fit the budget, a fixed seeded sample of n images (same B -> same sample), in batch order
+      confusion.npy  [nc,nc] float64  the confusion matrix after the last timed step, summed over the ranks (the one collective's result)
+    -> {name: shape}"""
+    os.makedirs(dirname, exist_ok=True)
+    header = 4096                                                   # per-file allowance for the .npy header
+    confusion = np.asarray(confusion, np.float64)
+    labels = np.asarray(labels)
+    per_image = labels[0].size * 4
+    room = (budget - 2 * header - confusion.nbytes) // per_image
+    if room < labels.shape[0]:
+        keep = np.sort(np.random.RandomState(0).choice(labels.shape[0], int(room), replace=False))
+        labels = labels[keep]
+    out = {"labels": labels.astype(np.float32), "confusion": confusion}
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def self_launch_argv(argv, n_gpus, port=None):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: the command line this process replaces itself with - the same
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: the command line this process runs as a child - the same
     script and arguments, one rank per GPU under torch.distributed.run on this node (what the driver's own multi-GPU command looks like)."""
     if port is None:
         import socket
@@ -404,7 +428,12 @@ def main(argv=None, hooks=None):
                     help="1: two-stream software pipeline (PAR of batch i overlaps the ViT of batch i+1)")
     ap.add_argument("--split", type=int, default=int(os.environ.get("EXCEL_BENCH_SPLIT", "1")),
                     help="run each batch as this many concurrent sub-batches on separate streams (1 = single stream)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (labels, confusion matrix) as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -415,11 +444,13 @@ def main(argv=None, hooks=None):
         if torch.cuda.device_count() < args.gpus:
             raise SystemExit(f"bench.py --gpus {args.gpus} needs {args.gpus} GPUs, found {torch.cuda.device_count()}")
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-            # launched bare: become the torch.distributed.run launcher of N ranks of this same command
+            # launched bare: run the torch.distributed.run launcher of N ranks of this same command as a fresh child process (this
+            # process has already opened the GPU, so it does not replace itself) and exit with its status
+            import subprocess
             cmd = self_launch_argv(sys.argv[1:] if argv is None else argv, args.gpus)
             print("bench.py: self-launching", " ".join(cmd), file=sys.stderr, flush=True)
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-            os.execv(cmd[0], cmd)
+            sys.exit(subprocess.call(cmd))
     json_out = sys.stdout
     if on_gpu:
         # stdout carries ONE JSON line (the driver's contract).  librccl prints a version banner to file descriptor 1 when its first
@@ -516,8 +547,10 @@ def main(argv=None, hooks=None):
     host_marks = []
     for i in range(args.steps):
         th = time.perf_counter()
-        step_fn(*batches[i % n_batches])
+        labels = step_fn(*batches[i % n_batches])
         host_marks.append(time.perf_counter() - th)                      # host time to ENQUEUE step i: a host-side self-check
+        if i < args.steps - 1:
+            del labels                                                  # only the last step's labels outlive their step (--dump-outputs)
     pipe.drain()
     if on_gpu:
         torch.cuda.synchronize()                                    # (so that gather_ms below is the collective, not the queued steps)
@@ -529,6 +562,11 @@ def main(argv=None, hooks=None):
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # copied before anything else runs the pipeline (the per-kernel pass below adds to pipe.hist, which `total` may be)
+        dumped = dump_outputs(args.dump_outputs, labels.cpu().numpy(), total.cpu().numpy())
+    del labels
     host_steps = host_marks
     prof = None
     if timing:
@@ -583,6 +621,8 @@ def main(argv=None, hooks=None):
             "rccl": rccl_note or ("all_gather of [21,21] int64 over %d rank(s), %.3f ms" % (dist.get_world_size(), gather_ms) if dist.is_initialized() else "no process group"),
             "per_rank_hist_mass": [int(x) for x in per_rank.reshape(per_rank.shape[0], -1).sum(1).tolist()],
         }
+        if dumped:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if prof:
             steps = args.steps
             ms = {k: v["ms"] / steps for k, v in prof_all.items() if v["launches"]}

@@ -12,6 +12,18 @@ TINY512 = VitConfig(width=128, layers=8, heads=2, patch=16, out_dim=512, input_r
 MERGES = ["a n", "t h", "i n", "e r", "o n", "r e", "th e</w>", "c l", "o r", "in g</w>", "a t", "e n", "o u", "a r", "e s</w>", "cl e", "an d</w>"]
 
 
+def write_bpe_from_used_merges(tmp_dir, used, n_merges=49152 - 256 - 2):
+    """A merges file in CLIP's format and of CLIP's length (vocabulary 49 408) from tests/golden/bpe_merges_used.npz: the merges the
+    golden texts look up at their own ranks, every other rank a pair of private-use code points no byte-level word contains."""
+    lines = [f"\ue000{i} \ue001" for i in range(n_merges)]
+    for r, m in zip(used["ranks"], used["merges"]):
+        lines[int(r)] = str(m)
+    path = os.path.join(str(tmp_dir), "bpe_used_merges.txt.gz")
+    with gzip.open(path, "wb") as f:
+        f.write(('"bpe_simple_vocab" - version: golden subset\n' + "\n".join(lines)).encode("utf-8"))
+    return path
+
+
 def make_text_tower(vocab, width=64, layers=2, embed=512, ctx=77, seed=5):
     rs = np.random.RandomState(seed)
     f = np.float32

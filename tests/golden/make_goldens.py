@@ -347,6 +347,40 @@ def gold_text():
     save("text_tiny.npz", tokens=tok, out=out, ensemble=ens, texts=np.array(texts), token_ids=ids, **sd)
 
 
+def gold_bpe():
+    """Every entry of CLIP's merge table the reference's SimpleTokenizer looks up while encoding the texts of text_tiny.npz (and the
+    word of the truncation case), with its rank.  A merges file holding these entries at these ranks (any other line a pair that never
+    occurs) gives the same answer to every lookup the tokenizer makes on these texts, hence the same ids: the BPE test needs no
+    copy of the 1.3 MB vocabulary file."""
+    ft = types.ModuleType("ftfy")
+    ft.fix_text = lambda t: t
+    sys.modules.setdefault("ftfy", ft)
+    st = _load_by_path("ref_simple_tokenizer", os.path.join(REF, "clip/simple_tokenizer.py"))
+    tk = st.SimpleTokenizer(os.path.join(REF, "clip/bpe_simple_vocab_16e6.txt.gz"))
+
+    class Logged(dict):
+        def __init__(self, d):
+            super().__init__(d)
+            self.seen = set()
+
+        def get(self, k, default=None):
+            if dict.__contains__(self, k):
+                self.seen.add(k)
+            return dict.get(self, k, default)
+
+        def __contains__(self, k):
+            if dict.__contains__(self, k):
+                self.seen.add(k)
+            return dict.__contains__(self, k)
+
+    tk.bpe_ranks = Logged(tk.bpe_ranks)
+    for t in [str(t) for t in np.load(os.path.join(HERE, "text_tiny.npz"))["texts"]] + ["word"]:
+        tk.encode(t)
+    seen = sorted(tk.bpe_ranks.seen, key=tk.bpe_ranks.get)
+    save("bpe_merges_used.npz", ranks=np.array([dict.__getitem__(tk.bpe_ranks, m) for m in seen], np.int32),
+         merges=np.array([" ".join(m) for m in seen]))
+
+
 # ---------------------------------------------------------------- 8. one training iteration of the decoder (SURVEY 8f #4)
 def gold_train():
     """scripts/train_voc.py:186-220 with the reference's own modules, losses, affinity labels and optimizer: losses, the
@@ -424,7 +458,7 @@ def gold_train():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["vit_cam", "ops", "attr", "pipeline", "lvc", "decoder", "text", "train"]       # e.g. `make_goldens.py lvc` mints one file
+    which = sys.argv[1:] or ["vit_cam", "ops", "attr", "pipeline", "lvc", "decoder", "text", "bpe", "train"]       # e.g. `make_goldens.py lvc` mints one file
     with torch.no_grad():
         for name in which:
             globals()["gold_" + name]()

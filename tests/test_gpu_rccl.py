@@ -110,7 +110,7 @@ def _infer_lam(world, json_path, n_images=24, batch=4):
 @pytest.mark.timeout(3000)
 @pytest.mark.parametrize("world", [1, 2])
 def test_bench_and_harness_over_rccl(world, tmp_path):
-    """(a) `python bench.py --gpus W` launched BARE (W = 2: it re-executes itself under torch.distributed.run, bench.self_launch_argv; the
+    """(a) `python bench.py --gpus W` launched BARE (W = 2: it runs itself as a child under torch.distributed.run, bench.self_launch_argv; the
     driver's own N > 1 line is the one-rank test above): the JSON line must say that the collective spanned W ranks and carry W non-zero
     per-rank histogram masses.  (b) tools/infer_lam.py:133,164-167: the harness at world W over RCCL - rank-strided shards, ONE all-gather of
     the [21,21] int64 confusion matrix - must gather exactly the matrix a one-rank run computes over the same list (every image scored

@@ -441,7 +441,7 @@ def test_bench_main_world8_gloo_stub_pipeline():
 
 
 def test_bench_self_launch_argv():
-    """`python bench.py --gpus N` launched bare re-executes itself as N ranks under torch.distributed.run on 127.0.0.1, with its own
+    """`python bench.py --gpus N` launched bare runs itself as N ranks under torch.distributed.run on 127.0.0.1, with its own
     arguments passed through (the driver's multi-GPU command has exactly this shape)."""
     import sys
     import bench
@@ -556,14 +556,14 @@ def test_on_disk_formats(tmp_path):
     assert np.array_equal(back, imutils.encode_cmap(lab2))
 
 
-def test_bpe_tokenizer_matches_reference_ids(golden):
+def test_bpe_tokenizer_matches_reference_ids(golden, tmp_path):
     """Token ids minted with the reference's own tokenizer (tests/golden/make_goldens.py gold_text).  CLIP's merges file is
-    not shipped with this repo: the test runs where one is available (EXCEL_BPE_VOCAB or the build container's reference)."""
+    not shipped with this repo: the tokenizer reads one rebuilt from the merges these texts look up (tests/golden/bpe_merges_used.npz,
+    make_goldens.py gold_bpe), or CLIP's own file when EXCEL_BPE_VOCAB names it."""
     import os
     from excel_amd.clip import bpe
-    path = os.environ.get("EXCEL_BPE_VOCAB") or "/root/reference/clip/bpe_simple_vocab_16e6.txt.gz"
-    if not os.path.exists(path):
-        pytest.skip("CLIP BPE merges file not available")
+    from _clip_files import write_bpe_from_used_merges
+    path = os.environ.get("EXCEL_BPE_VOCAB") or write_bpe_from_used_merges(tmp_path, golden("bpe_merges_used.npz"))
     g = golden("text_tiny.npz")
     tk = bpe.BPETokenizer(path)
     assert len(tk.encoder) == 49408 and tk.encoder[bpe.SOT] == 49406 and tk.encoder[bpe.EOT] == 49407
@@ -757,6 +757,64 @@ def test_clip_text_prompt_lists():
     voc, coco = clip_text.text_prompts(21), clip_text.text_prompts(81)
     assert len(voc) == 45 and len(coco) == 103 and voc[0] == "aeroplane" and voc[14].startswith("person with clothes")
     assert voc[20:] == clip_text.BACKGROUND_CATEGORY and coco[80:] == clip_text.BACKGROUND_CATEGORY_COCO
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on one CPU rank with the stand-in pipeline: exactly --steps timed steps, labels.npy is what the LAST of
+    them returned (float32), confusion.npy the matrix after it (float64); a second run with the same arguments writes the same arrays."""
+    import contextlib
+    import io
+    import json
+    import bench
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
+        monkeypatch.delenv(k, raising=False)
+    B, steps = 3, 4
+
+    def run(d):
+        pipe = _BenchStubPipe()
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            bench.main(["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--batch", str(B), "--no-kernel-timing", "--cpu-images", "0",
+                        "--ragged-images", "0", "--dump-outputs", str(d)],
+                       hooks={"device": "cpu", "make_workload": lambda args, r, w, dev: (pipe, _bench_stub_batches(0, 1, B)[0], [np.ones(B)] * 2, None)})
+        return pipe, json.loads(buf.getvalue())
+
+    pipe, out = run(tmp_path / "a")
+    assert pipe.calls == 2 + steps and out["steps"] == steps and out["ms_per_step"] > 0
+    assert out["dump_outputs"]["shapes"] == {"labels": [B, 6, 7], "confusion": [21, 21]}
+    batches, _ = _bench_stub_batches(0, 1, B)
+    imgs, _, gts = batches[(steps - 1) % 2]
+    lab = np.load(tmp_path / "a" / "labels.npy")
+    assert lab.dtype == np.float32 and np.array_equal(lab, (imgs.view(B, -1).numpy() % 21).reshape(B, 6, 7))
+    hist = sum(oracle.evaluate.fast_hist(batches[i % 2][2].numpy().ravel(), (batches[i % 2][0].view(B, -1).numpy() % 21).ravel(), 21)
+               for i in range(steps))
+    conf = np.load(tmp_path / "a" / "confusion.npy")
+    assert conf.dtype == np.float64 and np.array_equal(conf, hist)
+    run(tmp_path / "b")
+    for name in ("labels", "confusion"):
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy")))
+
+
+def test_bench_dump_outputs_budget():
+    """Labels larger than the budget are cut to a fixed seeded sample of whole images; the files stay within the budget."""
+    import tempfile
+    import bench
+    rs = np.random.RandomState(1)
+    labels = rs.randint(0, 21, (40, 64, 64)).astype(np.uint8)
+    conf = rs.randint(0, 1 << 40, (21, 21)).astype(np.int64)
+    budget = 10 * 64 * 64 * 4 + 2 * 4096 + conf.size * 8
+    with tempfile.TemporaryDirectory() as d1, tempfile.TemporaryDirectory() as d2:
+        shapes = bench.dump_outputs(d1, labels, conf, budget=budget)
+        bench.dump_outputs(d2, labels, conf, budget=budget)
+        assert shapes["labels"] == [10, 64, 64]
+        assert sum(os.path.getsize(os.path.join(d1, f)) for f in os.listdir(d1)) <= budget
+        a = np.load(os.path.join(d1, "labels.npy"))
+        assert np.array_equal(a, np.load(os.path.join(d2, "labels.npy")))
+        rows = [next(i for i in range(40) if np.array_equal(labels[i], a[j])) for j in range(10)]
+        assert rows == sorted(rows) and len(set(rows)) == 10
+        assert np.array_equal(np.load(os.path.join(d1, "confusion.npy")), conf.astype(np.float64))
+    with pytest.raises(SystemExit):
+        bench.main(["--gpus", "1", "--steps", "0"])
 
 
 def test_bench_power_sideline_without_rocm_smi(monkeypatch):
