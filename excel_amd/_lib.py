@@ -64,6 +64,16 @@ class RaggedInfo(C.Structure):
                 ("max_plane_pix", C.c_int64), ("table_ints", C.c_int64)]
 
 
+class AugParams(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("flip", C.c_int32), ("h_pad", C.c_int32), ("w_pad", C.c_int32),
+                ("cand_h", C.c_int32 * 10), ("cand_w", C.c_int32 * 10)]
+
+
+class TrainAugInfo(C.Structure):
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("max_h", C.c_int32), ("max_w2", C.c_int32), ("table_ints", C.c_int64),
+                ("workspace_bytes", C.c_int64), ("total_label_pix", C.c_int64)]
+
+
 # name -> (restype, argtypes); mirrors include/excel_hip.h one to one
 SIGNATURES = {
     "excel_last_error": (C.c_char_p, []),
@@ -134,6 +144,9 @@ SIGNATURES = {
     "excel_par_forward_ragged": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, C.POINTER(C.c_int32), c_i, c_i,
                                        C.c_float, C.c_float, c_f, c_f, c_f]),
     "excel_argmax_label_ragged": (c_i, [c_f, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_i, c_f, c_f]),
+    "excel_train_aug_plan": (c_i, [C.POINTER(C.c_int32), C.POINTER(AugParams), c_i, c_i, C.POINTER(TrainAugInfo), C.POINTER(C.c_int32)]),
+    "excel_train_augment_workspace_bytes": (c_sz, [C.POINTER(TrainAugInfo)]),
+    "excel_train_augment": (c_i, [c_f, c_f, c_f, C.POINTER(TrainAugInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f, c_f, c_f, c_f]),
     "excel_argmax_label": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_ll, c_f, c_f, c_f]),
     "excel_confusion_accumulate": (c_i, [c_f, c_f, c_ll, c_i, c_f, c_f]),
     "excel_attr_aggregate": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, C.c_double, c_f, c_f]),

@@ -698,6 +698,29 @@ extern "C" int excel_cam_upsample_bkg_ragged(const float* refined, const int32_t
                                                 (flags & EXCEL_CAMS_ZERO_UNUSED) ? 1 : 0, ST(stream));
 }
 
+// ------------------------------------------------------------------------------------ training augmentation (datasets/voc.py:110-117)
+// aug.hip
+int excel_aug_plan(const int32_t* hw, const excel_aug_params* prm, int B, int S, excel_train_aug_info* info, int32_t* table);
+int excel_launch_train_augment(const unsigned char* hwc, const unsigned char* labels, const int* table, const excel_train_aug_info& info,
+                               const double* mean, const double* stdv, float* img, unsigned char* label, int* img_box, void* workspace,
+                               hipStream_t st);
+extern "C" int excel_train_aug_plan(const int32_t* hw, const excel_aug_params* params, int B, int S, excel_train_aug_info* info, int32_t* table) {
+    return excel_aug_plan(hw, params, B, S, info, table);
+}
+
+extern "C" size_t excel_train_augment_workspace_bytes(const excel_train_aug_info* info) {
+    return info ? (size_t)info->workspace_bytes : 0;
+}
+
+extern "C" int excel_train_augment(const uint8_t* hwc, const uint8_t* labels, const int32_t* table, const excel_train_aug_info* info,
+                                   const double* mean3, const double* std3, float* img, uint8_t* label, int32_t* img_box, void* workspace,
+                                   void* stream) {
+    EXCEL_CHECK_ARG(hwc && labels && table && info && mean3 && std3 && img && label && img_box && workspace, "train_augment: null argument");
+    EXCEL_CHECK_ARG(info->B >= 1 && info->S >= 1 && info->max_h >= 1 && info->max_w2 >= 1 && info->workspace_bytes > 0,
+                    "train_augment: info was not filled by excel_train_aug_plan");
+    return excel_launch_train_augment(hwc, labels, table, *info, mean3, std3, img, label, img_box, workspace, ST(stream));
+}
+
 // ------------------------------------------------------------------------------------ PAR / labels / metric
 extern "C" size_t excel_par_workspace_bytes(int B, int Cmax, int H, int W, int ndil) {
     const size_t hw = (size_t)H * W;

@@ -17,11 +17,12 @@ from torch.utils.data import DataLoader, Dataset
 
 
 class RaggedBatch:
-    """names, hw int32 [B,2], images uint8 [sum 3 H W], labels uint8 [sum H W], cls f32 [B,F] (host tensors, pinned when requested)."""
-    __slots__ = ("names", "hw", "images", "labels", "cls")
+    """names, hw int32 [B,2], images uint8 [sum 3 H W], labels uint8 [sum H W], cls f32 [B,F] (host tensors, pinned when requested);
+    params: the training transform's random draws (ops.aug_params_dtype() [B]) of a training batch, else None."""
+    __slots__ = ("names", "hw", "images", "labels", "cls", "params")
 
-    def __init__(self, names, hw, images, labels, cls):
-        self.names, self.hw, self.images, self.labels, self.cls = names, hw, images, labels, cls
+    def __init__(self, names, hw, images, labels, cls, params=None):
+        self.names, self.hw, self.images, self.labels, self.cls, self.params = names, hw, images, labels, cls, params
 
     def pin_memory(self):                       # DataLoader(pin_memory=True) calls this in its pinning thread
         self.images, self.labels, self.cls = self.images.pin_memory(), self.labels.pin_memory(), self.cls.pin_memory()
@@ -91,6 +92,48 @@ def threaded_batches(dataset, indices, batch_size, num_threads=16, ahead=3):
             yield pack_samples([f.result() for f in pending.popleft()])
 
 
+def epoch_shard(n, epoch, rank, world, seed=0):
+    """DistributedSampler(shuffle=True) without padding: the permutation of epoch `epoch` (seeded by (seed, epoch), the same on every
+    rank), cut to a multiple of `world`, rank r taking positions r, r + world, ...  Shards are disjoint; together they cover all but
+    the n % world samples at the end of the permutation."""
+    perm = np.random.default_rng([int(seed), int(epoch)]).permutation(n)
+    perm = perm[:n - n % world]
+    return perm[rank::world]
+
+
+def train_batches(dataset, batch_size, rank=0, world=1, seed=0, start_epoch=0, num_threads=8, ahead=3):
+    """Endless iterator of training RaggedBatches (with `params`) over epochs start_epoch, start_epoch + 1, ...: each epoch is shuffled
+    and sharded by epoch_shard, cut into `batch_size` batches with the last partial batch dropped (the reference's DataLoader
+    drop_last=True), decoded by a thread pool (see threaded_batches).  `dataset.sample(idx, epoch)` -> (name, image, label, cls, params)
+    (datasets/voc.VOC12ClsDataset)."""
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    n = len(dataset)
+
+    def chunks():
+        epoch = start_epoch
+        while True:
+            idx = epoch_shard(n, epoch, rank, world, seed)
+            nb = len(idx) // batch_size
+            if nb == 0:
+                raise ValueError(f"{n} samples over {world} ranks give no full batch of {batch_size}")
+            for i in range(nb):
+                yield epoch, idx[i * batch_size:(i + 1) * batch_size]
+            epoch += 1
+
+    with ThreadPoolExecutor(max_workers=max(1, num_threads), thread_name_prefix="excel_decode") as pool:
+        pending = deque()
+        src = chunks()
+        while True:
+            while len(pending) < ahead:
+                epoch, idx = next(src)
+                pending.append([pool.submit(dataset.sample, int(j), epoch) for j in idx])
+            items = [f.result() for f in pending.popleft()]
+            rb = pack_samples([it[:4] for it in items])
+            rb.params = np.stack([it[4] for it in items])
+            yield rb
+
+
 class DeviceFeeder:
     """Host -> device staging of ragged batches on a COPY stream, a few batches ahead of the compute stream.
 
@@ -103,12 +146,15 @@ class DeviceFeeder:
         for names, plan, images, cls, labels in DeviceFeeder(ragged_batches(...), device):
             pipe.run_batch_ragged(images, plan, cls, labels)
 
+    With `aug_crop_size` S, batches that carry `params` (train_batches) also get the training transform's table built in the staging
+    thread (ops.TrainAugPlan) and staged on the copy stream with the images: `plan.aug`, for ops.train_augment(..., aug_plan=plan.aug).
+
     A slot (pinned + device buffers) is reused only after the kernels that read it have finished: the CONSUMER's thread records an
     event on its stream when it asks for the next batch and waits for the oldest such event before it lets more than `slots` - 2
     batches be in flight (every host-side event wait stays in the thread that recorded the event: waiting for it from the staging
     thread was measured at ~350 ms per call on this stack)."""
 
-    def __init__(self, batches, device, slots=4):
+    def __init__(self, batches, device, slots=4, aug_crop_size=None):
         import queue
         import threading
         from .. import ops
@@ -117,6 +163,7 @@ class DeviceFeeder:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._batches = batches
+        self._aug_S = aug_crop_size
         self._nslots = slots
         self._free = queue.Queue()
         self._ready = queue.Queue(maxsize=slots)
@@ -190,6 +237,10 @@ class DeviceFeeder:
                     labels = self._stage(slot, "labels", rb.labels)
                     cls = self._stage(slot, "cls", rb.cls)
                     plan.table = self._stage(slot, "table", torch.from_numpy(plan.table_host))
+                    if self._aug_S is not None and getattr(rb, "params", None) is not None:
+                        aug = self._ops.TrainAugPlan(rb.hw, rb.params, self._aug_S, None)
+                        aug.table = self._stage(slot, "aug_table", torch.from_numpy(aug.table_host))
+                        plan.aug = aug
                     ev = torch.cuda.Event()
                     ev.record(self._copy_stream)
                 self._ready.put((i, ev, rb.names, plan, images, cls, labels))

@@ -745,6 +745,79 @@ def normalize_resize_u8_ragged(hwc_packed, plan, S, mean=(123.675, 116.28, 103.5
     return out
 
 
+# ------------------------------------------------------------------ training augmentation (include/excel_hip.h, aug.hip)
+AUG_CANDIDATES = 10
+# one record per image, laid out like excel_aug_params (C alignment: 104 bytes)
+AUG_PARAMS_DTYPE = None
+
+
+def aug_params_dtype():
+    import numpy as np
+    global AUG_PARAMS_DTYPE
+    if AUG_PARAMS_DTYPE is None:
+        AUG_PARAMS_DTYPE = np.dtype([("ratio", "<f8"), ("flip", "<i4"), ("h_pad", "<i4"), ("w_pad", "<i4"),
+                                     ("cand_h", "<i4", (AUG_CANDIDATES,)), ("cand_w", "<i4", (AUG_CANDIDATES,))], align=True)
+        assert AUG_PARAMS_DTYPE.itemsize == C.sizeof(_lib.AugParams)
+    return AUG_PARAMS_DTYPE
+
+
+class TrainAugPlan:
+    """Host half of ops.train_augment: excel_train_aug_plan checks every size and parameter and builds the table of Pillow's
+    BILINEAR coefficients and NEAREST indices (a host function, no device work); `table` is its device copy when `device` is given."""
+
+    def __init__(self, hw, params, S, device):
+        import numpy as np
+        hw = np.ascontiguousarray(np.asarray(hw, np.int32).reshape(-1, 2))
+        params = np.ascontiguousarray(params, dtype=aug_params_dtype())
+        if params.shape != (hw.shape[0],):
+            raise ValueError(f"params: {params.shape[0] if params.ndim else 0} records for {hw.shape[0]} images")
+        self.B, self.S = int(hw.shape[0]), int(S)
+        self.hw, self.params = hw, params
+        self.info = _lib.TrainAugInfo()
+        hp = hw.ctypes.data_as(C.POINTER(C.c_int32))
+        pp = params.ctypes.data_as(C.POINTER(_lib.AugParams))
+        check(lib().excel_train_aug_plan(hp, pp, self.B, self.S, C.byref(self.info), None), "excel_train_aug_plan")
+        table = np.empty(int(self.info.table_ints), np.int32)
+        check(lib().excel_train_aug_plan(hp, pp, self.B, self.S, C.byref(self.info), table.ctypes.data_as(C.POINTER(C.c_int32))),
+              "excel_train_aug_plan")
+        self.table_host = table
+        self.workspace_bytes = int(lib().excel_train_augment_workspace_bytes(C.byref(self.info)))
+        self.table = None
+        if device is not None:        # pinned source: the copy is queued on the current stream, the host does not wait for it
+            self.table = torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
+
+
+def train_augment(images_u8, plan, labels_u8, params, crop_size, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375),
+                  aug_plan=None):
+    """VOC12ClsDataset(aug=True)'s transform (datasets/voc.py:110-117) on the device for a ragged batch: packed uint8 HWC images and
+    uint8 label maps (RaggedPlan layout), `params` = one ops.aug_params_dtype() record per image (the host's random draws)
+    -> (img [B,3,S,S] f32 normalised, label [B,S,S] u8 (255 = pad), img_box [B,4] int32).  Queued on the current stream; no host
+    synchronisation.  `aug_plan` = a TrainAugPlan built ahead for the same batch and params (e.g. by a staging thread)."""
+    S = int(crop_size)
+    if S <= 0:
+        raise ValueError("crop_size must be positive")
+    dev = images_u8.device
+    if aug_plan is None:
+        aug_plan = TrainAugPlan(plan.hw, params, S, dev)
+    if aug_plan.S != S or aug_plan.B != plan.B or aug_plan.table is None:
+        raise ValueError("aug_plan was built for another batch / crop size, or without a device table")
+    n = int(aug_plan.info.total_label_pix)
+    if images_u8.dtype != torch.uint8 or images_u8.numel() != 3 * n:
+        raise ValueError(f"images_u8 must hold {3 * n} uint8 values")
+    if labels_u8.dtype != torch.uint8 or labels_u8.numel() != n:
+        raise ValueError(f"labels_u8 must hold {n} uint8 values")
+    B = plan.B
+    img = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+    label = torch.empty((B, S, S), dtype=torch.uint8, device=dev)
+    box = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ws = _ws(aug_plan.workspace_bytes, dev)
+    m, s = (C.c_double * 3)(*mean), (C.c_double * 3)(*std)
+    check(lib().excel_train_augment(_p(images_u8, torch.uint8), _p(labels_u8, torch.uint8), _p(aug_plan.table, torch.int32),
+                                    C.byref(aug_plan.info), m, s, _p(img), _p(label, torch.uint8), _p(box, torch.int32),
+                                    _p(ws, torch.uint8), _stream()), "excel_train_augment")
+    return img, label, box
+
+
 def cam_upsample_bkg_ragged(refined, ncls, g, plan, out=None, zero_unused=True):
     """refined [B,Smax,P] -> packed cams: (Smax+1) pitched planes per image at its own (H_b, W_b)."""
     refined = f32c(refined)

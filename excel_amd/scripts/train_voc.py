@@ -1,4 +1,5 @@
-"""One training iteration of the decoder: mirror of the loop body of scripts/train_voc.py:172-220.
+"""Decoder training: mirror of scripts/train_voc.py.  `train(args)` is the program (data, loop, logging, checkpoints, validation);
+DecoderTrainer.train_step is one iteration, the loop body of :172-220:
 
   frozen CLIP surgery forward + CAMs (the hot path)      -> attr_maps_raw, attention            :186
   decoder head in training mode                          -> segs, fts_diver, attn_pred          :186 (model/model_excel.py:60-76)
@@ -6,9 +7,22 @@
   seg loss on the up-sampled logits + affinity ("diver") loss on attn_pred, w_diver = 0.1                                       :202-215
   backward of the head, gradient all-reduce over RCCL (DistributedDataParallel's mean), PolyWarmupAdamW step                    :217-219
 
-All tensor work runs in libexcel_hip.so; torch carries device memory and the one collective.  Data loading, augmentation,
-TensorBoard and checkpoint I/O of the reference script are outside this function.
+All tensor work runs in libexcel_hip.so; torch carries device memory and the one collective.  The data path of `train`: decode
+threads read the VOC tree (datasets/voc.VOC12ClsDataset) and draw each sample's augmentation parameters on the host, a copy stream
+stages the ragged batch and the transform's table (datasets/loader.DeviceFeeder), and ops.train_augment applies the reference's
+training transform on the device.  TensorBoard grids are not written.
+
+  python -m excel_amd.scripts.train_voc --data_folder VOC2012 --list_folder datasets/voc --model ViT-B-16.pt --bpe_path ... \
+      [--crop_size 320 --spg 4 --max_iters 30000]
+  python -m torch.distributed.run --nproc-per-node R -m excel_amd.scripts.train_voc ...       (R ranks, gradients all-reduced)
 """
+import argparse
+import datetime
+import logging
+import os
+import time
+
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -91,3 +105,150 @@ class DecoderTrainer:
             self.global_step += 1
         l = losses.tolist()
         return dict(seg_loss=l[0], diver_loss=l[1], lr=lr, aff_pseudos=aff_pseudos)
+
+
+def get_parser():
+    """scripts/train_voc.py:30-83 where the arguments apply, plus the model arguments of tools/infer_lam.py."""
+    from ..tools.infer_lam import _bool
+    p = argparse.ArgumentParser()
+    p.add_argument("--model", default="ExCEL_ViT-B/16", type=str, help="CLIP checkpoint path or name (see tools/infer_lam.py)")
+    p.add_argument("--dataset_name", default="pascal_voc", type=str)
+    p.add_argument("--attr_json", default=None, type=str)
+    p.add_argument("--num_attri", default=112, type=int)
+    p.add_argument("--embedding_dim", default=256, type=int)
+    p.add_argument("--in_channels", default=768, type=int)
+    p.add_argument("--radius", default=8, type=int)
+    p.add_argument("--w_seg", default=1.0, type=float)
+    p.add_argument("--w_diver", default=0.1, type=float)
+    p.add_argument("--max_iters", default=30000, type=int)
+    p.add_argument("--log_iters", default=200, type=int)
+    p.add_argument("--eval_iters", default=2000, type=int)
+    p.add_argument("--warmup_iters", default=50, type=int)
+    p.add_argument("--ignore_index", default=255, type=int)
+    p.add_argument("--save_ckpt", default=True, type=_bool)
+    p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--work_dir", default="w_outputs", type=str)
+    p.add_argument("--data_folder", default="/data/Datasets/VOC/VOC2012/", type=str)
+    p.add_argument("--list_folder", default="datasets/voc", type=str)
+    p.add_argument("--num_classes", default=21, type=int)
+    p.add_argument("--crop_size", default=320, type=int)
+    p.add_argument("--train_set", default="train_aug", type=str)
+    p.add_argument("--val_set", default="train", type=str)
+    p.add_argument("--spg", default=4, type=int, help="samples per GPU")
+    p.add_argument("--lr", default=1e-4, type=float)
+    p.add_argument("--warmup_lr", default=1e-6, type=float)
+    p.add_argument("--wt_decay", default=1e-2, type=float)
+    p.add_argument("--power", default=1, type=float)
+    p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
+    p.add_argument("--num_workers", default=8, type=int, help="decode threads per rank")
+    p.add_argument("--backend", default="nccl")
+    # model arguments of tools/infer_lam.py
+    p.add_argument("--clip_root", default=None, type=str)
+    p.add_argument("--bpe_path", default=None, type=str)
+    p.add_argument("--gemm_mode", default=None, type=str)
+    return p
+
+
+def _fmt_td(seconds):
+    return str(datetime.timedelta(seconds=int(seconds)))
+
+
+def _val_batches(dataset, device):
+    """The reference's val loader (batch 1, normalize_img + HWC->CHW): the package's VOC12SegDataset yields uint8 images, normalised
+    here on the device by ops.normalize_img_u8."""
+    for i in range(len(dataset)):
+        name, image, label, cls = dataset[i]
+        img = ops.normalize_img_u8(torch.from_numpy(np.array(image))[None].to(device))
+        yield [name], img, torch.from_numpy(np.array(label))[None], torch.from_numpy(np.array(cls))[None]
+
+
+def build_model(args, device):
+    """ExCEL_model(mode="train") at the head's initial weights (model/init_head.py), the tower from --model like tools/infer_lam.py."""
+    from ..model import ExCEL_model, init_decoder_state_dict
+    from ..tools.infer_lam import resolve_model_inputs
+    args.training_free = True                       # resolve_model_inputs: no trained head is loaded, training starts from init
+    kw = resolve_model_inputs(args)
+    n_layers = sum(1 for k in kw["state_dict"] if k.startswith("visual.transformer.resblocks.") and k.endswith(".ln_1.weight")) or 12
+    dec = init_decoder_state_dict(num_classes=args.num_classes, in_channels=args.in_channels, embedding_dim=args.embedding_dim,
+                                  crop_size=args.crop_size, seed=args.seed, index=n_layers)
+    return ExCEL_model(clip_model=args.model, embedding_dim=args.embedding_dim, in_channels=args.in_channels, dataset_name=args.dataset_name,
+                       num_classes=args.num_classes, num_atrr_clusters=args.num_attri, json_file=args.attr_json, img_size=args.crop_size,
+                       mode="train", device=device, gemm_mode=args.gemm_mode, decoder_state_dict=dec, **kw)
+
+
+def train(args, model=None):
+    """scripts/train_voc.py:train.  `model`: an ExCEL_model with a decoder head (tests inject a small one); default: built from
+    --model with the head at its initial weights.  -> dict(history=[per-iteration losses], tables=[validation tables], ckpts=[paths])."""
+    from ..datasets import loader, voc
+    from ..engine.validatation_engine import build_validation
+    from ..utils.PAR import PAR
+    world = int(os.environ.get("WORLD_SIZE", 1))
+    rank = int(os.environ.get("RANK", 0))
+    torch.cuda.set_device(args.local_rank)
+    device = torch.device("cuda", args.local_rank)
+    if world > 1 and not dist.is_initialized():
+        dist.init_process_group(backend=args.backend)
+    time0 = time.time()
+    ckpt_dir = os.path.join(args.work_dir, "checkpoints")
+    if rank == 0:
+        os.makedirs(ckpt_dir, exist_ok=True)
+    logging.info("Total gpus: %d, samples per gpu: %d..." % (world, args.spg))
+    if model is None:
+        model = build_model(args, device)
+    par = PAR(num_iter=20, dilations=[1, 2, 4, 8, 12, 24])
+    train_dataset = voc.VOC12ClsDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.train_set, stage="train",
+                                        aug=True, rescale_range=(0.5, 2.0), crop_size=args.crop_size, img_fliplr=True,
+                                        ignore_index=args.ignore_index, num_classes=args.num_classes, seed=args.seed)
+    val_dataset = voc.VOC12SegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.val_set, stage="val",
+                                      ignore_index=args.ignore_index)
+    trainer = DecoderTrainer(model, par, lr=args.lr, wt_decay=args.wt_decay, warmup_iters=args.warmup_iters, max_iters=args.max_iters,
+                             warmup_lr=args.warmup_lr, power=args.power, w_diver=args.w_diver, radius=args.radius,
+                             ignore_index=args.ignore_index, seed=args.seed)
+    batches = loader.train_batches(train_dataset, args.spg, rank=rank, world=world, seed=args.seed, num_threads=args.num_workers)
+    feeder = loader.DeviceFeeder(batches, device, aug_crop_size=args.crop_size)
+    class_list = voc.class_list if args.num_classes == 21 else None
+    history, tables, ckpts, meter = [], [], [], []
+    loss_log = open(os.path.join(args.work_dir, "losses.txt"), "w") if rank == 0 else None
+    it = iter(feeder)
+    try:
+        for n_iter in range(args.max_iters):
+            names, plan, images, cls, labels = next(it)
+            inputs, _, _ = ops.train_augment(images, plan, labels, None, args.crop_size, aug_plan=plan.aug)
+            out = trainer.train_step(inputs, cls, n_iter)
+            rec = dict(iter=n_iter + 1, seg_loss=out["seg_loss"], diver_loss=out["diver_loss"], lr=out["lr"])
+            history.append(rec)
+            meter.append((out["seg_loss"], out["diver_loss"]))
+            if loss_log is not None:
+                loss_log.write("%d %.9g %.9g %.9g\n" % (n_iter + 1, out["seg_loss"], out["diver_loss"], out["lr"]))
+                loss_log.flush()
+            if (n_iter + 1) % args.log_iters == 0 and rank == 0:                                                   # :226-233
+                elapsed = time.time() - time0
+                eta = elapsed / (n_iter + 1) * (args.max_iters - n_iter - 1)
+                m = np.mean(np.asarray(meter), axis=0)
+                meter = []
+                logging.info("Iter: %d; Elasped: %s; ETA: %s; LR: %.3e; seg_loss: %.4f, diver_loss: %.4f"
+                             % (n_iter + 1, _fmt_td(elapsed), _fmt_td(eta), out["lr"], m[0], m[1]))
+            if (n_iter + 1) % args.eval_iters == 0:                                                                 # :245-253
+                if rank == 0:
+                    logging.info("Validating...")
+                    if args.save_ckpt and (n_iter + 1) >= 2:
+                        path = os.path.join(ckpt_dir, "model_iter_%d.pth" % (n_iter + 1))
+                        torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
+                        ckpts.append(path)
+                # the reference resizes to a fixed 320 (engine/validatation_engine.py:20) = its default crop; here: the crop size
+                table = build_validation(model=model, par=par, val_loader=_val_batches(val_dataset, device), device=device,
+                                         num_classes=args.num_classes, resize_size=args.crop_size, class_list=class_list)[0]
+                tables.append(table)
+                if rank == 0:
+                    logging.info("\n" + table)
+    finally:
+        it.close()                      # records the last batch's event, then DeviceFeeder.close waits for it and stops the stager
+        feeder.close()
+        if loss_log is not None:
+            loss_log.close()
+    return dict(history=history, tables=tables, ckpts=ckpts)
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
+    train(get_parser().parse_args())

@@ -403,6 +403,52 @@ int excel_par_forward_ragged(const float* imgs, int h, int w, const float* masks
 int excel_argmax_label_ragged(const float* cams, const int32_t* nchan, const int32_t* cls_idx, const int32_t* table,
                               const excel_ragged_info* info, int Smax, int Cmax, uint8_t* labels_u8, void* stream);
 
+/* ------------------------------------------------------------------ training augmentation (aug.hip)
+ * VOC12ClsDataset(aug=True)'s transform (datasets/voc.py:110-117 over datasets/transforms.py) for a ragged batch of decoded uint8
+ * images and label maps on the device, in the reference's order:
+ *   random_scaling (:25-50)  image -> (int(r*w), int(r*h)) with Pillow BILINEAR, label with Pillow NEAREST (both bit-identical)
+ *   random_fliplr  (:74-87)
+ *   random_crop    (:118-176) pad to max(S,h') x max(S,w') (image 0, label 255), place the image at (H_pad, W_pad), choose the crop
+ *                  among the 10 candidate origins by the cat_max_ratio = 0.75 rule, img_box in padded coordinates (the reference's
+ *                  img_box[1] = min(H_end, H_pad + h'), img_box[3] likewise)
+ *   normalize_img  (:7-14) + HWC->CHW, with excel_normalize_img_u8's arithmetic: (float)(((double)v - mean) / std).
+ * The random draws are made by the caller (host) and passed in `params`; the crop choice is made on the device.
+ * Inputs: hwc = the uint8 [h_b,w_b,3] images back to back, labels = the uint8 [h_b,w_b] maps back to back (the tight layout of the
+ * ragged batches above: image b at byte 3 * loff_b, label b at loff_b).
+ * Outputs: img [B,3,S,S] f32, label [B,S,S] u8, img_box [B,4] int32. */
+#define EXCEL_AUG_CANDIDATES 10
+typedef struct {
+    double ratio;                                  /* random_scaling's ratio, in [1/8, 8] */
+    int32_t flip;                                  /* 1: random_fliplr flipped (random() > 0.5) */
+    int32_t h_pad, w_pad;                          /* placement in the padded image: [0, max(S,h') - h'] x [0, max(S,w') - w'] */
+    int32_t cand_h[EXCEL_AUG_CANDIDATES];          /* candidate crop origins, all 10 drawn: [0, max(S,h') - S] */
+    int32_t cand_w[EXCEL_AUG_CANDIDATES];          /*                                       [0, max(S,w') - S] */
+} excel_aug_params;
+typedef struct {
+    int32_t B, S, max_h, max_w2;                   /* batch, crop size, largest source height, largest rescaled width */
+    int64_t table_ints;                            /* int32 entries of the table */
+    int64_t workspace_bytes;                       /* device workspace excel_train_augment needs */
+    int64_t total_label_pix;                       /* sum h_b * w_b */
+} excel_train_aug_info;
+/* HOST function (no device work): checks every size and parameter and builds the int32 table the kernels read - per image a
+ * record of EXCEL_AUG_REC ints, then Pillow's BILINEAR coefficient tables (per output index: first source index, tap count,
+ * kx (resp. ky) fixed-point weights; double arithmetic, contraction off) and NEAREST index tables of both axes.  Record fields:
+ *   0 h, 1 w, 2 h', 3 w', 4 loff, 5 workspace byte offset of the horizontal pass' output, 6 x-coefficient offset, 7 kx (0: no
+ *   horizontal pass, w' == w), 8 y-coefficient offset, 9 ky (0: no vertical pass), 10 x-index offset, 11 y-index offset, 12 flip,
+ *   13 h_pad, 14 w_pad, 15 max(S,h'), 16 max(S,w'), 18..27 cand_h, 28..37 cand_w.
+ * With table == NULL only `info` is filled.  The caller copies the table (info->table_ints int32) to the device. */
+#define EXCEL_AUG_REC 40
+int excel_train_aug_plan(const int32_t* hw /*host [B,2]*/, const excel_aug_params* params /*host [B]*/, int B, int S,
+                         excel_train_aug_info* info /*host*/, int32_t* table /*host or NULL*/);
+size_t excel_train_augment_workspace_bytes(const excel_train_aug_info* info);
+/* Four launches on `stream`, no host synchronisation: label histograms of the 10 candidate windows through the NEAREST tables,
+ * the crop choice, the horizontal BILINEAR pass restricted to the chosen crop's columns and the source rows its vertical taps read,
+ * and the vertical pass fused with flip, pad, crop, normalisation, the CHW store and the label crop.  mean3 / std3
+ * are host arrays. */
+int excel_train_augment(const uint8_t* hwc, const uint8_t* labels, const int32_t* table, const excel_train_aug_info* info,
+                        const double* mean3 /*host*/, const double* std3 /*host*/, float* img, uint8_t* label, int32_t* img_box,
+                        void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ one-time / auxiliary */
 
 /* attr_aggregate (model/load_attr.py:86-119): text [T,C] (F fg rows first), bank [C,K] -> text_attr [C,T], columns unit-norm.
