@@ -269,33 +269,45 @@ __global__ __launch_bounds__(256) void tr_ln_bwd_kernel(const float* __restrict_
     if (lane == 0) stat[row] = make_float2(mean, rstd);
 }
 
-// dgamma[c] = sum_m dy[m,c] * xhat[m,c], dbeta[c] = sum_m dy[m,c]   (one thread per column, rows in order: reproducible)
-__global__ __launch_bounds__(64) void tr_ln_param_grad_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float2* __restrict__ stat,
-                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, int M, int E) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
-    if (c >= E) return;
-    float g = 0.f, b = 0.f;
-    for (int m = 0; m < M; ++m) {
-        const float2 st = stat[m];
-        const float d = dy[(long long)m * E + c];
-        g += d * (x[(long long)m * E + c] - st.x) * st.y;
-        b += d;
+// Column sums over the M rows, fixed order: block = 64 columns x 4 waves; wave w adds rows w, w+4, ... in double, then the four
+// partials are added in wave order: run-to-run reproducible, and double accumulation instead of one fp32 serial sum per column over
+// up to B*P = 3136 rows.
+// dgamma[c] = sum_m dy[m,c] * xhat[m,c], dbeta[c] = sum_m dy[m,c]
+__global__ __launch_bounds__(256) void tr_ln_param_grad_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float2* __restrict__ stat,
+                                                               float* __restrict__ dgamma, float* __restrict__ dbeta, int M, int E) {
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), w = threadIdx.x >> 6;
+    double g = 0.0, b = 0.0;
+    if (c < E)
+        for (int m = w; m < M; m += 4) {
+            const float2 st = stat[m];
+            const float d = dy[(long long)m * E + c];
+            g += (double)(d * ((x[(long long)m * E + c] - st.x) * st.y));
+            b += (double)d;
+        }
+    __shared__ double red[2][4][64];
+    red[0][w][threadIdx.x & 63] = g;
+    red[1][w][threadIdx.x & 63] = b;
+    __syncthreads();
+    if (w == 0 && c < E) {
+        const int i = threadIdx.x;
+        dgamma[c] = (float)(((red[0][0][i] + red[0][1][i]) + red[0][2][i]) + red[0][3][i]);
+        dbeta[c] = (float)(((red[1][0][i] + red[1][1][i]) + red[1][2][i]) + red[1][3][i]);
     }
-    dgamma[c] = g;
-    dbeta[c] = b;
 }
 
-// out[c] = sum_m a[m*ld + c]   (bias gradients)
-__global__ __launch_bounds__(64) void tr_colsum_kernel(const float* __restrict__ a, float* __restrict__ out, int M, int N, int ld) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
-    if (c >= N) return;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int m = 0;
-    for (; m + 3 < M; m += 4) {
-        s0 += a[(long long)m * ld + c]; s1 += a[(long long)(m + 1) * ld + c]; s2 += a[(long long)(m + 2) * ld + c]; s3 += a[(long long)(m + 3) * ld + c];
+// out[c] = sum_m a[m*ld + c]   (bias gradients; same fixed-order double scheme)
+__global__ __launch_bounds__(256) void tr_colsum_kernel(const float* __restrict__ a, float* __restrict__ out, int M, int N, int ld) {
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), w = threadIdx.x >> 6;
+    double s = 0.0;
+    if (c < N)
+        for (int m = w; m < M; m += 4) s += (double)a[(long long)m * ld + c];
+    __shared__ double red[4][64];
+    red[w][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (w == 0 && c < N) {
+        const int i = threadIdx.x;
+        out[c] = (float)(((red[0][i] + red[1][i]) + red[2][i]) + red[3][i]);
     }
-    for (; m < M; ++m) s0 += a[(long long)m * ld + c];
-    out[c] = (s0 + s1) + (s2 + s3);
 }
 
 // softmax backward over rows: ds = scale * p * (dp - sum_j dp_j p_j); pad columns -> 0.  In place over dp.
@@ -467,11 +479,13 @@ static TrainWs train_ws_layout(const excel_decoder_config& c, int B, int g, char
     w.z1 = take((size_t)L * M * E); w.h1 = take((size_t)L * M * E); w.cat = take(M * (size_t)L * E); w.fts = take(M * E);
     w.inv = take(M); w.fn = take(M * E); w.ap = take((size_t)B * P * P);
     w.xin = take((size_t)nl * M * E); w.qkv = take((size_t)nl * M * 3 * E); w.pm = take((size_t)nl * B * H * P * w.Pp);
-    w.ao = take((size_t)nl * M * E); w.x1 = take((size_t)nl * M * E); w.zm = take((size_t)nl * M * 4 * E); w.hq = take((size_t)nl * M * 4 * E);
+    w.ao = take((size_t)nl * M * E); w.x1 = take((size_t)nl * M * E); w.zm = take((size_t)nl * M * 4 * E);
+    w.hq = take(M * std::max((size_t)nl * 4 * E, (size_t)L * E));      // the backward's d(cat) [M, L*E] reuses it
     w.xfin = take(M * E);
-    w.dx = take(M * E); w.dt1 = take(M * E); w.dt4 = take(M * 4 * E); w.dqkvh = take(M * 3 * E); w.dqkvr = take(M * 3 * E);
+    w.dx = take(M * E); w.dt1 = take(M * E); w.dt4 = take(M * (size_t)std::max(4 * E, c.vit_width));   // also the [M, D] token gather
+    w.dqkvh = take(M * 3 * E); w.dqkvr = take(M * 3 * E);
     w.dpm = take((size_t)B * H * P * w.Pp);
-    const size_t widest = (size_t)(4 * E > L * E ? 4 * E : L * E);
+    const size_t widest = (size_t)std::max(std::max(4 * E, L * E), w.ncp);     // widest dY^T of tr_linear_bwd (linear_pred: nc columns)
     w.tr = take(widest * (size_t)w.Mp > (size_t)B * H * P * w.Pp ? widest * (size_t)w.Mp : (size_t)B * H * P * w.Pp);
     w.tp = take((size_t)B * H * P * w.Pp);
     w.dfn = take(M * E > (size_t)B * P * P ? M * E : (size_t)B * P * P);
@@ -588,7 +602,7 @@ static int tr_linear_bwd(const float* dY, int ldy, const float* X, int ldx, cons
     gw.Kld = ws.Mp;
     TRYD(excel_launch_gemm(gw, false, 1, st));
     if (db) {
-        hipLaunchKernelGGL(tr_colsum_kernel, dim3(cdiv(out, 64)), dim3(64), 0, st, dY, db, M, out, ldy);
+        hipLaunchKernelGGL(tr_colsum_kernel, dim3(cdiv(out, 64)), dim3(256), 0, st, dY, db, M, out, ldy);
         EXCEL_CHECK_LAUNCH("train/colsum");
     }
     if (dX) {                                                      // dX = dY [M,out] . W [out,in]   (NN)
@@ -614,7 +628,8 @@ extern "C" int excel_decoder_train_attn_fts(excel_decoder_t h, int B, int g, con
 extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats, int B, int g, void* workspace, size_t workspace_bytes,
                                       const float* d_seg, const float* d_attn_pred, const excel_decoder_weights* grads, float dropout_p,
                                       unsigned dropout_seed, void* stream) {
-    EXCEL_CHECK_ARG(h && all_feats && workspace && d_seg && grads && grads->fuse && grads->blocks && B > 0 && g > 0, "excel_decoder_backward: bad argument");
+    EXCEL_CHECK_ARG(h && all_feats && workspace && d_seg && grads && grads->fuse && grads->blocks && B > 0 && g > 0 && (g * g) % 4 == 0,
+                    "excel_decoder_backward: bad argument (the token count g*g must be a multiple of 4)");
     const excel_decoder_config& c = h->cfg;
     const int P = g * g, N = P + 1, D = c.vit_width, E = c.embed, L = c.vit_layers, H = c.heads, hd = E / H, nc = c.num_classes, nl = c.dec_layers;
     const int M = B * P;
@@ -649,7 +664,7 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         TRYD(tr_linear_bwd(ws.dt4, 4 * E, ws.dt1, E, bw.fc1_w, W(gb.fc1_w), W(gb.fc1_b), ws.dfn, E, M, 4 * E, E, ws, st));   // dfn <- dy2
         // dx1 = dx + LN2_bwd(dy2)
         hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, x1, ws.dfn, bw.ln2_w, ws.dx, ws.dt1, ws.stat, M, E, 1e-5f);
-        hipLaunchKernelGGL(tr_ln_param_grad_kernel, dim3(cdiv(E, 64)), dim3(64), 0, st, x1, ws.dfn, ws.stat, W(gb.ln2_w), W(gb.ln2_b), M, E);
+        hipLaunchKernelGGL(tr_ln_param_grad_kernel, dim3(cdiv(E, 64)), dim3(256), 0, st, x1, ws.dfn, ws.stat, W(gb.ln2_w), W(gb.ln2_b), M, E);
         // now dt1 = dx1.  x1 = xin + out_proj(ao): dao = dx1 . Wo ; dWo = dx1^T ao
         TRYD(tr_linear_bwd(ws.dt1, E, ao, E, bw.out_proj_w, W(gb.out_proj_w), W(gb.out_proj_b), ws.dx, E, M, E, E, ws, st));       // dx <- dao
         // attention backward per (b,h): dO = dao[:, h*hd:(h+1)*hd]
@@ -692,7 +707,7 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         TRYD(tr_linear_bwd(ws.dqkvr, 3 * E, ws.dx, E, bw.in_proj_w, W(gb.in_proj_w), W(gb.in_proj_b), ws.dfn, E, M, 3 * E, E, ws, st));
         // dxin = dx1 + LN1_bwd(dy1) -> dx
         hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, xin, ws.dfn, bw.ln1_w, ws.dt1, ws.dx, ws.stat, M, E, 1e-5f);
-        hipLaunchKernelGGL(tr_ln_param_grad_kernel, dim3(cdiv(E, 64)), dim3(64), 0, st, xin, ws.dfn, ws.stat, W(gb.ln1_w), W(gb.ln1_b), M, E);
+        hipLaunchKernelGGL(tr_ln_param_grad_kernel, dim3(cdiv(E, 64)), dim3(256), 0, st, xin, ws.dfn, ws.stat, W(gb.ln1_w), W(gb.ln1_b), M, E);
         EXCEL_CHECK_LAUNCH("train/block_bwd");
     }
     // ws.dx = d loss / d fts from the decoder path; add the attn_pred path
@@ -712,9 +727,8 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
     }
     if (dropout_p > 0.f)         // the same mask as the forward (a pure function of seed, image, channel)
         hipLaunchKernelGGL(tr_dropout2d_kernel, dim3((unsigned)cdivl((long long)ME, 256)), dim3(256), 0, st, ws.dx, B, P, E, dropout_p, dropout_seed);
-    // linear_fuse: fts = cat . Wf^T + bf  ->  dcat [M, L*E] in dt4?  (dt4 holds M*4E floats; dcat needs M*L*E) -> use tr-free buffers: z1 area is still needed, so dcat goes to hq[0..] (free now)
-    float* dcat = ws.hq;                                       // nl*M*4E floats >= M*L*E is not guaranteed: checked below
-    EXCEL_CHECK_ARG((size_t)nl * 4 >= (size_t)L, "excel_decoder_backward: scratch for d(cat) too small (need dec_layers*4 >= vit_layers)");
+    // linear_fuse: fts = cat . Wf^T + bf  ->  dcat [M, L*E] in hq (free now; train_ws_layout sizes it for max(4E*nl, L*E))
+    float* dcat = ws.hq;
     TRYD(tr_linear_bwd(ws.dx, E, ws.cat, L * E, h->w.fuse_w, W(grads->fuse_w), W(grads->fuse_b), dcat, L * E, M, E, L * E, ws, st));
     for (int l = 0; l < L; ++l) {
         const excel_fuse_layer_weights& fw = h->fuse[l];
@@ -723,8 +737,7 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         TRYD(tr_linear_bwd(dcat + (size_t)l * E, L * E, ws.h1 + l * ME, E, fw.proj2_w, W(gfw.proj2_w), W(gfw.proj2_b), ws.dt1, E, M, E, E, ws, st));
         hipLaunchKernelGGL(tr_act_bwd_kernel, dim3((unsigned)cdivl((long long)ME, 256)), dim3(256), 0, st, ws.z1 + l * ME, ws.dt1, (long long)ME, 0);
         // z1_l = tok_l . W1^T + b1 with tok_l = rows 1..P of each image of all_feats[l]: dW1 = dz1^T tok (batched over images, summed)
-        // -> gather the token rows once into dt4 ([M, D] needs M*D <= M*4E floats)
-        if ((size_t)D > (size_t)4 * E) { excel_set_error("excel_decoder_backward: vit_width > 4*embed not supported by the scratch layout"); return EXCEL_ERR_ARG; }
+        // -> gather the token rows once into dt4 ([M, max(4E, D)] floats)
         hipMemcpy2DAsync(ws.dt4, sizeof(float) * (size_t)P * D, all_feats + ((size_t)l * B * N + 1) * D, sizeof(float) * (size_t)N * D,
                          sizeof(float) * (size_t)P * D, B, hipMemcpyDeviceToDevice, st);
         TRYD(tr_linear_bwd(ws.dt1, E, ws.dt4, D, fw.proj_w, W(gfw.proj_w), W(gfw.proj_b), nullptr, 0, M, E, D, ws, st));
