@@ -144,6 +144,10 @@ SIGNATURES = {
     "excel_par_forward_ragged": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, C.POINTER(C.c_int32), c_i, c_i,
                                        C.c_float, C.c_float, c_f, c_f, c_f]),
     "excel_argmax_label_ragged": (c_i, [c_f, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_i, c_f, c_f]),
+    "excel_seg_msc_fuse_ragged": (c_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i, c_i, c_f, C.POINTER(RaggedInfo),
+                                        c_f, c_f, c_f]),
+    "excel_seg_resize_argmax_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f]),
+    "excel_seg_softmax_resize": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "excel_train_aug_plan": (c_i, [C.POINTER(C.c_int32), C.POINTER(AugParams), c_i, c_i, C.POINTER(TrainAugInfo), C.POINTER(C.c_int32)]),
     "excel_train_augment_workspace_bytes": (c_sz, [C.POINTER(TrainAugInfo)]),
     "excel_train_augment": (c_i, [c_f, c_f, c_f, C.POINTER(TrainAugInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f, c_f, c_f, c_f]),

@@ -64,30 +64,6 @@ __global__ __launch_bounds__(256) void attr_aggregate_kernel(const float* __rest
     for (int c = tid; c < C; c += 256) out[(long long)c * T + t] = agg[c] / nrm;              // :118
 }
 
-// source index / weights of F.interpolate(mode='bilinear'): ATen area_pixel_compute_source_index (align_corners=False:
-// scale*(dst+0.5)-0.5 clamped at 0) and the two-stage blend, in explicit operations so that every kernel using it rounds alike
-struct BilinearTap { int y0, y1, x0, x1; float ly, lx; };
-__device__ __forceinline__ BilinearTap bilinear_tap(int x, int y, int h, int w, int H, int W, int align_corners) {
-    float fy, fx;
-    if (align_corners) {
-        fy = ((H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f) * (float)y;
-        fx = ((W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f) * (float)x;
-    } else {
-        fy = fmaxf(__fsub_rn(__fmul_rn((float)h / (float)H, (float)y + 0.5f), 0.5f), 0.f);
-        fx = fmaxf(__fsub_rn(__fmul_rn((float)w / (float)W, (float)x + 0.5f), 0.5f), 0.f);
-    }
-    BilinearTap t;
-    t.y0 = min((int)fy, h - 1); t.x0 = min((int)fx, w - 1);
-    t.y1 = min(t.y0 + 1, h - 1); t.x1 = min(t.x0 + 1, w - 1);
-    t.ly = fy - (float)t.y0; t.lx = fx - (float)t.x0;
-    return t;
-}
-__device__ __forceinline__ float bilinear_blend(const BilinearTap& t, float p00, float p01, float p10, float p11) {
-    const float top = fmaf(t.lx, p01, __fmul_rn(1.f - t.lx, p00));
-    const float bot = fmaf(t.lx, p11, __fmul_rn(1.f - t.lx, p10));
-    return fmaf(t.ly, bot, __fmul_rn(1.f - t.ly, top));
-}
-
 __global__ __launch_bounds__(256) void bilinear_resize_kernel(const float* __restrict__ in, float* __restrict__ out, long long planes,
                                                               int h, int w, int H, int W, int align_corners) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

@@ -117,6 +117,15 @@ class ExCEL_model:
 
     __call__ = forward
 
+    def seg_logits(self, img):
+        """model(img)[0] alone - the only output tools/infer_seg_voc.py / infer_seg_coco.py use (:66, :76).  The tower is asked for
+        the decoder's input features only: no last-layers affinity (w_aff), no patch-text CAM, no attn_pred.  Same bits as forward's seg."""
+        if self._dec is None:
+            raise RuntimeError("seg_logits needs the decoder head: build ExCEL_model with decoder_state_dict=")
+        r = self.encoder.encode_image(img, True, None, want_w_aff=False, n_attn_out=0, want_feats=True, feats_as_reference=True,
+                                      want_raw=True, want_features=False)
+        return self._dec.forward(r["feats"])[1]
+
     def check_numerics(self, img, tol=5e-4, fallback=True, reduce=None):
         """Guard of the fast matrix-core modes on the caller's OWN weights and images.  "bf16x3" carries 16 mantissa bits per operand:
         measured against a float64 run of the oracle its CAM error is ~12x that of fp32 arithmetic - 1e-5 on well-conditioned networks

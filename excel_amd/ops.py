@@ -532,6 +532,76 @@ def seg_scale_accumulate(segs, acc, H, W, flip_mean, init, scale=1.0):
     return acc
 
 
+SEG_MAX_SCALES = 8
+
+
+def seg_msc_fuse_ragged(segs, flip_mean, plan, want_planes=True, want_labels=False, label_hw=None):
+    """tools/infer_seg_voc.py:63-82 (coco :62-80) for a ragged batch, all scales in one launch (excel_seg_msc_fuse_ragged).
+    segs: the decoder logits of every scale, [2B,nc,g_s,g_s] each (image b, then its flipped copy at B + b), in the reference's order
+    (scale 1.0 first); flip_mean: one flag per scale; plan: RaggedPlan of the fuse sizes (h_b, w_b).
+    -> (planes, labels): nc pitched planes per image (want_planes) and tight uint8 arg-max labels (want_labels), None where not wanted.
+    Labels are the reference's only where the label size is the fuse size: `label_hw` ([B,2], the label sizes) is checked against the
+    plan when labels are asked for, and a mismatch is refused (use seg_resize_argmax_ragged there)."""
+    import numpy as np
+    segs = [f32c(x) for x in segs]
+    ns = len(segs)
+    if not 1 <= ns <= SEG_MAX_SCALES:
+        raise ValueError(f"seg_msc_fuse_ragged: {ns} scales, need 1..{SEG_MAX_SCALES}")
+    if len(flip_mean) != ns:
+        raise ValueError("seg_msc_fuse_ragged: one flip_mean flag per scale")
+    if not (want_planes or want_labels):
+        raise ValueError("seg_msc_fuse_ragged: ask for planes, labels or both")
+    nc = int(segs[0].shape[1]) if segs[0].dim() == 4 else 0
+    for x in segs:
+        if x.dim() != 4 or x.shape[0] != 2 * plan.B or x.shape[1] != nc or x.shape[2] != x.shape[3] or x.shape[2] < 1:
+            raise ValueError(f"seg_msc_fuse_ragged: every scale must be [2B={2 * plan.B}, nc={nc}, g, g], got {tuple(x.shape)}")
+    if nc < 1:
+        raise ValueError("seg_msc_fuse_ragged: nc >= 1")
+    if want_labels:
+        if label_hw is None:
+            raise ValueError("seg_msc_fuse_ragged: labels need label_hw (the label sizes) to check them against the fuse sizes")
+        if not np.array_equal(np.asarray(label_hw, np.int64).reshape(-1, 2), plan.hw.astype(np.int64)):
+            raise ValueError("seg_msc_fuse_ragged: label sizes differ from the fuse sizes: fuse planes and use seg_resize_argmax_ragged")
+    dev = segs[0].device
+    planes = torch.empty((nc * plan.total_pix,), dtype=torch.float32, device=dev) if want_planes else None
+    labels = torch.empty((plan.total_label_pix,), dtype=torch.uint8, device=dev) if want_labels else None
+    ptrs = (C.c_void_p * ns)(*[x.data_ptr() for x in segs])
+    for x in segs:
+        _p(x)
+    g = (C.c_int32 * ns)(*[int(x.shape[2]) for x in segs])
+    fl = (C.c_int32 * ns)(*[1 if f else 0 for f in flip_mean])
+    check(lib().excel_seg_msc_fuse_ragged(ptrs, g, fl, ns, nc, _p(plan.table, torch.int32), C.byref(plan.info), _p(planes),
+                                          _p(labels, torch.uint8), _stream()), "excel_seg_msc_fuse_ragged")
+    return planes, labels
+
+
+def seg_resize_argmax_ragged(planes, src_plan, dst_plan, nc):
+    """tools/infer_seg_coco.py:86-87: nc pitched planes per image at src_plan's sizes -> tight uint8 arg-max labels at dst_plan's sizes,
+    without the resized logits in memory (excel_seg_resize_argmax_ragged)."""
+    if src_plan.B != dst_plan.B:
+        raise ValueError(f"seg_resize_argmax_ragged: plans of {src_plan.B} and {dst_plan.B} images")
+    if planes.numel() != nc * src_plan.total_pix:
+        raise ValueError(f"seg_resize_argmax_ragged: planes must hold nc * total_pix = {nc * src_plan.total_pix} floats")
+    lab = torch.empty((dst_plan.total_label_pix,), dtype=torch.uint8, device=planes.device)
+    check(lib().excel_seg_resize_argmax_ragged(_p(planes), _p(src_plan.table, torch.int32), C.byref(src_plan.info), _p(dst_plan.table, torch.int32),
+                                               C.byref(dst_plan.info), int(nc), _p(lab, torch.uint8), _stream()), "excel_seg_resize_argmax_ragged")
+    return lab
+
+
+def seg_softmax_resize(planes, plan, b, nc, H, W):
+    """The CRF's input for image b of a packed nc-plane pitched tensor (tools/infer_seg_voc.py:146-147, coco :144-145): bilinear to
+    (H, W) (skipped at the same size), softmax over classes -> tight [nc, H, W] (excel_seg_softmax_resize)."""
+    h, w = int(plan.hw[b, 0]), int(plan.hw[b, 1])
+    wp = (w + 3) // 4 * 4
+    o = nc * int(plan.poff[b])
+    if planes.numel() != nc * plan.total_pix:
+        raise ValueError(f"seg_softmax_resize: planes must hold nc * total_pix = {nc * plan.total_pix} floats")
+    src = planes[o:o + nc * h * wp]
+    prob = torch.empty((nc, int(H), int(W)), dtype=torch.float32, device=planes.device)
+    check(lib().excel_seg_softmax_resize(_p(src), h, w, int(nc), int(H), int(W), _p(prob), _stream()), "excel_seg_softmax_resize")
+    return prob
+
+
 # ------------------------------------------------------------------ CAM
 def clip_feature_surgery(image_features, text_features, num_fg=None, t=2.0, want_full=True):
     """image_features [B,N,C], text_features [T,C] -> (full [B,N,T] | None, slice [B,N-1,F] | None)."""

@@ -6,6 +6,7 @@ records tools/infer_lam.py exchanges with its CRF stage.
                            {"valid_lam": cams [k+1,H,W] f32, "keys_gt": present classes int64}
   crf_keys_to_labels       tools/infer_lam.py:225-227: keys = pad(keys_gt + 1, (1, 0)); label = keys[argmax]
   save_label_png           the colour-coded label image the reference writes with imageio (:228); PIL here
+  voc_test_palette / convert_test_seg2RGB   utils/pyutils.py:183-217: the VOC test-server palette PNG (21 VOC colours, grey after)
 
 Plain numpy / PIL on the host: these are file formats, not compute.  DenseCRF itself (utils/dcrf.py) is excel_amd/utils/dcrf.py over
 excel_dcrf_inference (crf.hip).
@@ -82,4 +83,23 @@ def save_label_png(path, label):
     from PIL import Image
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     Image.fromarray(encode_cmap(np.squeeze(label)).astype(np.uint8)).save(path)
+    return path
+
+
+def voc_test_palette():
+    """The palette of utils/pyutils.py:183-217 (convert_test_seg2RGB), 256 x 3 uint8: index i is grey (i, i, i), except the first 21
+    entries, which are the VOC class colours (colormap()[:21])."""
+    pal = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+    pal[:21] = colormap(21)
+    return pal
+
+
+def convert_test_seg2RGB(label, path):
+    """utils/pyutils.py:183-217: uint8 labels [H,W] -> a palette ("P" mode) PNG at `path`, the format of the VOC test server's
+    results/VOC2012/Segmentation/comp6_test_cls/<name>.png."""
+    from PIL import Image
+    im = Image.fromarray(np.asarray(label).astype(np.uint8))
+    im.putpalette(voc_test_palette().reshape(-1).tolist())
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    im.save(path)
     return path

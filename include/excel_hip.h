@@ -403,6 +403,34 @@ int excel_par_forward_ragged(const float* imgs, int h, int w, const float* masks
 int excel_argmax_label_ragged(const float* cams, const int32_t* nchan, const int32_t* cls_idx, const int32_t* table,
                               const excel_ragged_info* info, int Smax, int Cmax, uint8_t* labels_u8, void* stream);
 
+/* ------------------------------------------------------------------ segmentation evaluation over ragged batches (segeval.hip)
+ * The size-dependent half of tools/infer_seg_voc.py / tools/infer_seg_coco.py: the reference runs one image per step and fuses, resizes
+ * and arg-maxes at that image's size (_validate :58-91); these run a whole ragged batch in one launch per stage, in the layout above.
+ *
+ * excel_seg_msc_fuse_ragged replaces :63-82 (coco :62-80): for ns <= 8 scales, segs[s] = the decoder logits [2B, nc, g_s, g_s] (image b,
+ * then the flipped image b at B + b), for every image at its plan size (h_b, w_b) and every class
+ *   v_s = bilinear (align_corners=False) of scale s at (h_b, w_b); flip_mean[s] ? (v_s + flip_x(v_s of the flipped copy)) / 2 : v_s
+ *   acc = v_0; acc = acc + v_s for s >= 1; the last step multiplies by 1/ns   (torch.mean over the stacked scales, :82)
+ * with the operations, in the order, of a per-image chain of excel_seg_scale_accumulate calls: the same bits.
+ *   planes    (optional) nc pitched planes per image (16-byte aligned; nc * total_pix < 2^31)
+ *   labels_u8 (optional) tight arg-max over classes, first maximum (excel_argmax_label's rule; nc <= 256).  These equal the reference's
+ *             labels only where the label size IS the plan size (VOC, :84-85 is then the identity); callers check that.
+ * segs, g, flip_mean are host arrays of ns entries; the maps they point to are device memory. */
+int excel_seg_msc_fuse_ragged(const float* const* segs /*host [ns]*/, const int32_t* g /*host [ns]*/, const int32_t* flip_mean /*host [ns]*/,
+                              int ns, int nc, const int32_t* table, const excel_ragged_info* info, float* planes, uint8_t* labels_u8,
+                              void* stream);
+
+/* tools/infer_seg_coco.py:86-87 (F.interpolate of the fused logits to labels.shape, then argmax(1)) without the resized logits: planes =
+ * nc pitched planes per image at the sizes of (src_table, src_info) -> tight uint8 labels at the sizes of (dst_table, dst_info), both
+ * plans over the same B images.  Same bits as excel_bilinear_resize + excel_argmax_label per image. */
+int excel_seg_resize_argmax_ragged(const float* planes, const int32_t* src_table, const excel_ragged_info* src_info, const int32_t* dst_table,
+                                   const excel_ragged_info* dst_info, int nc, uint8_t* labels_u8, void* stream);
+
+/* The DenseCRF's input for ONE image (tools/infer_seg_voc.py:146-147 softmax(logit); tools/infer_seg_coco.py:144-145 F.interpolate to
+ * (H, W) then softmax): planes = nc pitched planes (row pitch w rounded up to 4 floats) at (h, w) -> prob tight [nc, H, W], the layout
+ * excel_dcrf_inference takes.  (h, w) == (H, W) skips the resize. */
+int excel_seg_softmax_resize(const float* planes, int h, int w, int nc, int H, int W, float* prob, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation (aug.hip)
  * VOC12ClsDataset(aug=True)'s transform (datasets/voc.py:110-117 over datasets/transforms.py) for a ragged batch of decoded uint8
  * images and label maps on the device, in the reference's order:
