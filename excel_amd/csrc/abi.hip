@@ -704,6 +704,8 @@ int excel_aug_plan(const int32_t* hw, const excel_aug_params* prm, int B, int S,
 int excel_launch_train_augment(const unsigned char* hwc, const unsigned char* labels, const int* table, const excel_train_aug_info& info,
                                const double* mean, const double* stdv, float* img, unsigned char* label, int* img_box, void* workspace,
                                hipStream_t st);
+int excel_launch_train_augment_image(const unsigned char* hwc, const int* table, const excel_train_aug_info& info, const double* mean,
+                                     const double* stdv, float* img, int* img_box, void* workspace, hipStream_t st);
 extern "C" int excel_train_aug_plan(const int32_t* hw, const excel_aug_params* params, int B, int S, excel_train_aug_info* info, int32_t* table) {
     return excel_aug_plan(hw, params, B, S, info, table);
 }
@@ -719,6 +721,14 @@ extern "C" int excel_train_augment(const uint8_t* hwc, const uint8_t* labels, co
     EXCEL_CHECK_ARG(info->B >= 1 && info->S >= 1 && info->max_h >= 1 && info->max_w2 >= 1 && info->workspace_bytes > 0,
                     "train_augment: info was not filled by excel_train_aug_plan");
     return excel_launch_train_augment(hwc, labels, table, *info, mean3, std3, img, label, img_box, workspace, ST(stream));
+}
+
+extern "C" int excel_train_augment_image(const uint8_t* hwc, const int32_t* table, const excel_train_aug_info* info, const double* mean3,
+                                         const double* std3, float* img, int32_t* img_box, void* workspace, void* stream) {
+    EXCEL_CHECK_ARG(hwc && table && info && mean3 && std3 && img && img_box && workspace, "train_augment_image: null argument");
+    EXCEL_CHECK_ARG(info->B >= 1 && info->S >= 1 && info->max_h >= 1 && info->max_w2 >= 1 && info->workspace_bytes > 0,
+                    "train_augment_image: info was not filled by excel_train_aug_plan");
+    return excel_launch_train_augment_image(hwc, table, *info, mean3, std3, img, img_box, workspace, ST(stream));
 }
 
 // ------------------------------------------------------------------------------------ PAR / labels / metric

@@ -9,6 +9,9 @@
 //   aug_hpass_kernel    Pillow's horizontal pass -> uint8 workspace, only the chosen crop's columns and
 //                       the source rows its vertical taps read                                            grid (w'/64, h/4, B)
 //   aug_vpass_kernel    Pillow's vertical pass + flip + pad + crop + normalise + CHW store + label crop   grid (S*S/256, B)
+// The image-only transform of CocoClsDataset(aug=True) (datasets/coco.py:112-142: random_crop with label=None takes the first draw)
+// runs the <false> instances: aug_choose_kernel<false> takes candidate 0 without histograms, aug_vpass_kernel<false> has no label
+// load or store; there is no histogram memset or launch.
 #include "../../include/excel_hip.h"
 #include "common.h"
 #include "excel_internal.h"
@@ -126,15 +129,17 @@ __global__ __launch_bounds__(256) void aug_hist_kernel(const unsigned char* __re
 
 // get_random_cropbox (transforms.py:141-159): the first candidate with at least one non-ignore class and max/sum < 0.75, else the
 // last; then img_box (:165-169).  max/sum < 0.75 is tested as 4 max < 3 sum: with sum < 2^31 the float64 quotient of the reference
-// cannot round across 0.75, so the two agree.
+// cannot round across 0.75, so the two agree.  kHist == false: no label, the first draw is returned (:145-146) - candidate 0, `hist`
+// is not read.
+template <bool kHist>
 __global__ __launch_bounds__(256) void aug_choose_kernel(const int* __restrict__ tab, const int* __restrict__ hist, int S,
                                                          int* __restrict__ choice, int* __restrict__ img_box) {
     __shared__ long long ssum[4];
     __shared__ int smax[4];
     const int b = blockIdx.x, t = threadIdx.x;
     const int* rec = tab + REC * b;
-    int pick = NCAND - 1;
-    for (int c = 0; c < NCAND; ++c) {
+    int pick = kHist ? NCAND - 1 : 0;
+    for (int c = 0; kHist && c < NCAND; ++c) {
         const int v = t == IGNORE ? 0 : hist[((long long)b * NCAND + c) * 256 + t];
         long long s = v;
         int m = v;
@@ -199,7 +204,8 @@ __global__ __launch_bounds__(256) void aug_hpass_kernel(const unsigned char* __r
 
 // ImagingResampleVertical_8bpc on the horizontal pass' rows (or the source rows when the width is unchanged), then flip / pad / crop /
 // normalize_img / HWC->CHW: one thread per output pixel, coalesced fp32 stores of the three planes; the label crop (NEAREST, 255 pad)
-// in the same thread.
+// in the same thread (kLabel == false: no label, `labels` / `out_label` are not touched).
+template <bool kLabel>
 __global__ __launch_bounds__(256) void aug_vpass_kernel(const unsigned char* __restrict__ hwc, const unsigned char* __restrict__ labels,
                                                         const int* __restrict__ tab, const int* __restrict__ choice, int S,
                                                         const unsigned char* __restrict__ ws, double m0, double m1, double m2,
@@ -236,9 +242,11 @@ __global__ __launch_bounds__(256) void aug_vpass_kernel(const unsigned char* __r
             const unsigned char* p = mid + ((long long)ry * w2 + x) * 3;
             v0 = p[0]; v1 = p[1]; v2 = p[2];
         }
-        const int* nx = tab + rec[R_NX];
-        const int* ny = tab + rec[R_NY];
-        lv = labels[rec[R_LOFF] + (long long)ny[ry] * rec[R_W] + nx[x]];
+        if constexpr (kLabel) {
+            const int* nx = tab + rec[R_NX];
+            const int* ny = tab + rec[R_NY];
+            lv = labels[rec[R_LOFF] + (long long)ny[ry] * rec[R_W] + nx[x]];
+        }
     }
     const long long plane = (long long)S * S;
     float* o = out + (long long)b * 3 * plane + i;
@@ -246,7 +254,7 @@ __global__ __launch_bounds__(256) void aug_vpass_kernel(const unsigned char* __r
     o[0] = (float)(((double)v0 - m0) / s0);
     o[plane] = (float)(((double)v1 - m1) / s1);
     o[2 * plane] = (float)(((double)v2 - m2) / s2);
-    out_label[(long long)b * plane + i] = (unsigned char)lv;
+    if constexpr (kLabel) out_label[(long long)b * plane + i] = (unsigned char)lv;
 }
 
 }  // namespace
@@ -324,12 +332,29 @@ int excel_launch_train_augment(const unsigned char* hwc, const unsigned char* la
     }
     hipLaunchKernelGGL(aug_hist_kernel, dim3(cdiv(S, 8), NCAND, B), dim3(256), 0, st, labels, table, S, hist);
     EXCEL_CHECK_LAUNCH("aug_hist");
-    hipLaunchKernelGGL(aug_choose_kernel, dim3(B), dim3(256), 0, st, table, hist, S, choice, img_box);
+    hipLaunchKernelGGL(aug_choose_kernel<true>, dim3(B), dim3(256), 0, st, table, hist, S, choice, img_box);
     EXCEL_CHECK_LAUNCH("aug_choose");
     hipLaunchKernelGGL(aug_hpass_kernel, dim3(cdiv(info.max_w2, 64), cdiv(info.max_h, 4), B), dim3(64, 4), 0, st, hwc, table, choice, S, mid);
     EXCEL_CHECK_LAUNCH("aug_hpass");
-    hipLaunchKernelGGL(aug_vpass_kernel, dim3(cdiv(S * S, 256), B), dim3(256), 0, st, hwc, labels, table, choice, S, mid, mean[0], mean[1],
-                       mean[2], stdv[0], stdv[1], stdv[2], img, label);
+    hipLaunchKernelGGL(aug_vpass_kernel<true>, dim3(cdiv(S * S, 256), B), dim3(256), 0, st, hwc, labels, table, choice, S, mid, mean[0],
+                       mean[1], mean[2], stdv[0], stdv[1], stdv[2], img, label);
     EXCEL_CHECK_LAUNCH("aug_vpass");
+    return EXCEL_OK;
+}
+
+// The image-only transform: the same table and workspace layout (the histogram region is left unused), three launches.
+int excel_launch_train_augment_image(const unsigned char* hwc, const int* table, const excel_train_aug_info& info, const double* mean,
+                                     const double* stdv, float* img, int* img_box, void* workspace, hipStream_t st) {
+    ProfScope prof__(PROF_OTHER, st);
+    const int B = info.B, S = info.S;
+    int* choice = (int*)((char*)workspace + hist_bytes(B));
+    unsigned char* mid = (unsigned char*)workspace + hist_bytes(B) + choice_bytes(B);
+    hipLaunchKernelGGL(aug_choose_kernel<false>, dim3(B), dim3(64), 0, st, table, nullptr, S, choice, img_box);
+    EXCEL_CHECK_LAUNCH("aug_choose_first");
+    hipLaunchKernelGGL(aug_hpass_kernel, dim3(cdiv(info.max_w2, 64), cdiv(info.max_h, 4), B), dim3(64, 4), 0, st, hwc, table, choice, S, mid);
+    EXCEL_CHECK_LAUNCH("aug_hpass");
+    hipLaunchKernelGGL(aug_vpass_kernel<false>, dim3(cdiv(S * S, 256), B), dim3(256), 0, st, hwc, nullptr, table, choice, S, mid, mean[0],
+                       mean[1], mean[2], stdv[0], stdv[1], stdv[2], img, nullptr);
+    EXCEL_CHECK_LAUNCH("aug_vpass_image");
     return EXCEL_OK;
 }

@@ -17,15 +17,18 @@ from torch.utils.data import DataLoader, Dataset
 
 
 class RaggedBatch:
-    """names, hw int32 [B,2], images uint8 [sum 3 H W], labels uint8 [sum H W], cls f32 [B,F] (host tensors, pinned when requested);
-    params: the training transform's random draws (ops.aug_params_dtype() [B]) of a training batch, else None."""
+    """names, hw int32 [B,2], images uint8 [sum 3 H W], labels uint8 [sum H W] (None for samples without label maps), cls f32 [B,F]
+    (host tensors, pinned when requested); params: the training transform's random draws (ops.aug_params_dtype() [B]) of a training
+    batch, else None."""
     __slots__ = ("names", "hw", "images", "labels", "cls", "params")
 
     def __init__(self, names, hw, images, labels, cls, params=None):
         self.names, self.hw, self.images, self.labels, self.cls, self.params = names, hw, images, labels, cls, params
 
     def pin_memory(self):                       # DataLoader(pin_memory=True) calls this in its pinning thread
-        self.images, self.labels, self.cls = self.images.pin_memory(), self.labels.pin_memory(), self.cls.pin_memory()
+        self.images, self.cls = self.images.pin_memory(), self.cls.pin_memory()
+        if self.labels is not None:
+            self.labels = self.labels.pin_memory()
         return self
 
     def __len__(self):
@@ -33,19 +36,28 @@ class RaggedBatch:
 
 
 def pack_samples(items):
-    """[(name, image [h,w,3] u8, label [h,w] u8, cls [F])] -> RaggedBatch.  Label maps must have their image's size."""
+    """[(name, image [h,w,3] u8, label [h,w] u8, cls [F])] -> RaggedBatch.  Label maps must have their image's size.  A batch whose
+    labels are all None (training samples without label maps, datasets/coco.CocoClsDataset) gets RaggedBatch.labels = None; a batch
+    that mixes None and label maps is refused."""
     names, hw, ims, labs, cls = [], [], [], [], []
+    no_label = [it[2] is None for it in items]
+    if any(no_label) and not all(no_label):
+        raise ValueError("a batch mixes samples with and without label maps")
     for name, image, label, c in items:
-        image, label = np.ascontiguousarray(image, np.uint8), np.ascontiguousarray(label, np.uint8)
-        if image.ndim != 3 or image.shape[2] != 3 or image.shape[:2] != label.shape:
-            raise ValueError(f"{name}: image {image.shape} / label {label.shape}: expected [h,w,3] uint8 and [h,w] uint8 of one size")
+        image = np.ascontiguousarray(image, np.uint8)
+        if label is not None:
+            label = np.ascontiguousarray(label, np.uint8)
+        if image.ndim != 3 or image.shape[2] != 3 or (label is not None and image.shape[:2] != label.shape):
+            raise ValueError(f"{name}: image {image.shape} / label {None if label is None else label.shape}: expected [h,w,3] uint8 and "
+                             "[h,w] uint8 of one size")
         names.append(str(name))
         hw.append(image.shape[:2])
         ims.append(image.reshape(-1))
-        labs.append(label.reshape(-1))
+        if label is not None:
+            labs.append(label.reshape(-1))
         cls.append(np.asarray(c, np.float32))
-    return RaggedBatch(names, np.asarray(hw, np.int32), torch.from_numpy(np.concatenate(ims)), torch.from_numpy(np.concatenate(labs)),
-                       torch.from_numpy(np.stack(cls)))
+    labels = torch.from_numpy(np.concatenate(labs)) if labs else None
+    return RaggedBatch(names, np.asarray(hw, np.int32), torch.from_numpy(np.concatenate(ims)), labels, torch.from_numpy(np.stack(cls)))
 
 
 class _Batches(Dataset):
@@ -105,7 +117,7 @@ def train_batches(dataset, batch_size, rank=0, world=1, seed=0, start_epoch=0, n
     """Endless iterator of training RaggedBatches (with `params`) over epochs start_epoch, start_epoch + 1, ...: each epoch is shuffled
     and sharded by epoch_shard, cut into `batch_size` batches with the last partial batch dropped (the reference's DataLoader
     drop_last=True), decoded by a thread pool (see threaded_batches).  `dataset.sample(idx, epoch)` -> (name, image, label, cls, params)
-    (datasets/voc.VOC12ClsDataset)."""
+    (datasets/voc.VOC12ClsDataset; label None: datasets/coco.CocoClsDataset, the batches then carry labels = None)."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     n = len(dataset)
@@ -147,7 +159,8 @@ class DeviceFeeder:
             pipe.run_batch_ragged(images, plan, cls, labels)
 
     With `aug_crop_size` S, batches that carry `params` (train_batches) also get the training transform's table built in the staging
-    thread (ops.TrainAugPlan) and staged on the copy stream with the images: `plan.aug`, for ops.train_augment(..., aug_plan=plan.aug).
+    thread (ops.TrainAugPlan) and staged on the copy stream with the images: `plan.aug`, for ops.train_augment(..., aug_plan=plan.aug)
+    or ops.train_augment_image(..., aug_plan=plan.aug).  A batch without label maps stages no label bytes and yields labels = None.
 
     A slot (pinned + device buffers) is reused only after the kernels that read it have finished: the CONSUMER's thread records an
     event on its stream when it asks for the next batch and waits for the oldest such event before it lets more than `slots` - 2
@@ -234,7 +247,7 @@ class DeviceFeeder:
                 plan = self._ops.RaggedPlan(rb.hw, None)
                 with torch.cuda.stream(self._copy_stream):
                     images = self._stage(slot, "images", rb.images)
-                    labels = self._stage(slot, "labels", rb.labels)
+                    labels = None if rb.labels is None else self._stage(slot, "labels", rb.labels)
                     cls = self._stage(slot, "cls", rb.cls)
                     plan.table = self._stage(slot, "table", torch.from_numpy(plan.table_host))
                     if self._aug_S is not None and getattr(rb, "params", None) is not None:

@@ -888,6 +888,31 @@ def train_augment(images_u8, plan, labels_u8, params, crop_size, mean=(123.675, 
     return img, label, box
 
 
+def train_augment_image(images_u8, plan, params, crop_size, aug_plan=None, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375)):
+    """CocoClsDataset(aug=True)'s transform (datasets/coco.py:112-142) on the device for a ragged batch of packed uint8 HWC images that
+    carry no label map: as train_augment, but the crop is candidate 0 of each record (get_random_cropbox's first draw when the label
+    is None) -> (img [B,3,S,S] f32 normalised, img_box [B,4] int32).  Queued on the current stream; no host synchronisation."""
+    S = int(crop_size)
+    if S <= 0:
+        raise ValueError("crop_size must be positive")
+    dev = images_u8.device
+    if aug_plan is None:
+        aug_plan = TrainAugPlan(plan.hw, params, S, dev)
+    if aug_plan.S != S or aug_plan.B != plan.B or aug_plan.table is None:
+        raise ValueError("aug_plan was built for another batch / crop size, or without a device table")
+    n = int(aug_plan.info.total_label_pix)
+    if images_u8.dtype != torch.uint8 or images_u8.numel() != 3 * n:
+        raise ValueError(f"images_u8 must hold {3 * n} uint8 values")
+    B = plan.B
+    img = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+    box = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ws = _ws(aug_plan.workspace_bytes, dev)
+    m, s = (C.c_double * 3)(*mean), (C.c_double * 3)(*std)
+    check(lib().excel_train_augment_image(_p(images_u8, torch.uint8), _p(aug_plan.table, torch.int32), C.byref(aug_plan.info), m, s,
+                                          _p(img), _p(box, torch.int32), _p(ws, torch.uint8), _stream()), "excel_train_augment_image")
+    return img, box
+
+
 def cam_upsample_bkg_ragged(refined, ncls, g, plan, out=None, zero_unused=True):
     """refined [B,Smax,P] -> packed cams: (Smax+1) pitched planes per image at its own (H_b, W_b)."""
     refined = f32c(refined)

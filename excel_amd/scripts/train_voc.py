@@ -53,7 +53,8 @@ def allreduce_mean_(flat, group=None):
 class DecoderTrainer:
     def __init__(self, model, par, lr=1e-4, wt_decay=1e-2, betas=(0.9, 0.999), warmup_iters=50, max_iters=30000, warmup_lr=1e-6, power=1, caa_thre=0.79,
                  w_diver=0.1, radius=8, ignore_index=255, lvc_iter=14000, seg_aff_iter=24000, dropout_p=0.1, seed=0):
-        """Defaults = scripts/train_voc.py:36-80.  The head's parameters sit in param group 3 (model_excel.py:40-45): lr x 10."""
+        """Defaults = scripts/train_voc.py:36-80.  The head's parameters sit in param group 3 (model_excel.py:40-45): lr x 10.
+        `seg_aff_iter` None: the affinity target stays the pseudo labels at every iteration (scripts/train_coco.py:206)."""
         if model._dec is None:
             raise RuntimeError("DecoderTrainer needs a model built with decoder_state_dict= (initial head weights)")
         self.model, self.par = model, par
@@ -94,7 +95,7 @@ class DecoderTrainer:
                 attr_maps_raw = cure_attr_map(model, inputs, ex_feats=dec.train_attn_fts(ctx))
             aff_pseudos = self.pseudo_labels(inputs, cls_labels, attr_maps_raw, attn_weights, attn_pred, n_iter)
             aff_src = None
-            if n_iter >= self.seg_aff_iter:                                                                          # :204, :210
+            if self.seg_aff_iter is not None and n_iter >= self.seg_aff_iter:                                        # :204, :210
                 aff_src = ops.argmax_label(ops.bilinear_resize(segs, inputs.shape[2], inputs.shape[3], align_corners=False))
             losses, d_seg, d_ap = ops.train_losses(segs, attn_pred, aff_pseudos, radius=self.radius, ignore_index=self.ignore_index,
                                                    w_seg=1.0, w_diver=self.w_diver, aff_labels_u8=aff_src)           # :202-215
@@ -176,10 +177,47 @@ def build_model(args, device):
                        mode="train", device=device, gemm_mode=args.gemm_mode, decoder_state_dict=dec, **kw)
 
 
-def train(args, model=None):
-    """scripts/train_voc.py:train.  `model`: an ExCEL_model with a decoder head (tests inject a small one); default: built from
-    --model with the head at its initial weights.  -> dict(history=[per-iteration losses], tables=[validation tables], ckpts=[paths])."""
-    from ..datasets import loader, voc
+class TrainVariant:
+    """What differs between scripts/train_voc.py and scripts/train_coco.py (the COCO program: scripts/train_coco.py here)."""
+    name = "voc"
+    caa_thre = 0.79              # refine_cams_with_aff threshold (:195)
+    lvc_iter = 14000             # cure_attr_map(ex_feats=fts_diver) + seg_attn from this iteration on (:188, :194)
+    seg_aff_iter = 24000         # affinity target = seg arg-max from this iteration on (:210); None: never
+
+    @staticmethod
+    def datasets(args):
+        """-> (train dataset with sample(idx, epoch), val dataset with __getitem__ -> (name, image, label, cls))."""
+        from ..datasets import voc
+        train = voc.VOC12ClsDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.train_set, stage="train",
+                                    aug=True, rescale_range=(0.5, 2.0), crop_size=args.crop_size, img_fliplr=True,
+                                    ignore_index=args.ignore_index, num_classes=args.num_classes, seed=args.seed)
+        val = voc.VOC12SegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.val_set, stage="val",
+                                  ignore_index=args.ignore_index)
+        return train, val
+
+    @staticmethod
+    def augment(images, plan, labels, args):
+        """the training transform of a staged batch (DeviceFeeder with aug_crop_size) -> inputs [B,3,S,S]"""
+        return ops.train_augment(images, plan, labels, None, args.crop_size, aug_plan=plan.aug)[0]
+
+    @staticmethod
+    def class_list(args):
+        from ..datasets import voc
+        return voc.class_list if args.num_classes == 21 else None
+
+    @staticmethod
+    def first_ckpt_iter(args):
+        return 2                 # `(n_iter + 1) >= 2` (:253)
+
+
+VOC = TrainVariant()
+
+
+def train(args, model=None, variant=VOC):
+    """scripts/train_voc.py:train (scripts/train_coco.py:train with variant=train_coco.COCO).  `model`: an ExCEL_model with a decoder
+    head (tests inject a small one); default: built from --model with the head at its initial weights.
+    -> dict(history=[per-iteration losses], tables=[validation tables], ckpts=[paths])."""
+    from ..datasets import loader
     from ..engine.validatation_engine import build_validation
     from ..utils.PAR import PAR
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -196,24 +234,22 @@ def train(args, model=None):
     if model is None:
         model = build_model(args, device)
     par = PAR(num_iter=20, dilations=[1, 2, 4, 8, 12, 24])
-    train_dataset = voc.VOC12ClsDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.train_set, stage="train",
-                                        aug=True, rescale_range=(0.5, 2.0), crop_size=args.crop_size, img_fliplr=True,
-                                        ignore_index=args.ignore_index, num_classes=args.num_classes, seed=args.seed)
-    val_dataset = voc.VOC12SegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.val_set, stage="val",
-                                      ignore_index=args.ignore_index)
+    train_dataset, val_dataset = variant.datasets(args)
     trainer = DecoderTrainer(model, par, lr=args.lr, wt_decay=args.wt_decay, warmup_iters=args.warmup_iters, max_iters=args.max_iters,
-                             warmup_lr=args.warmup_lr, power=args.power, w_diver=args.w_diver, radius=args.radius,
-                             ignore_index=args.ignore_index, seed=args.seed)
+                             warmup_lr=args.warmup_lr, power=args.power, caa_thre=variant.caa_thre, w_diver=args.w_diver,
+                             radius=args.radius, ignore_index=args.ignore_index, lvc_iter=variant.lvc_iter,
+                             seg_aff_iter=variant.seg_aff_iter, seed=args.seed)
     batches = loader.train_batches(train_dataset, args.spg, rank=rank, world=world, seed=args.seed, num_threads=args.num_workers)
     feeder = loader.DeviceFeeder(batches, device, aug_crop_size=args.crop_size)
-    class_list = voc.class_list if args.num_classes == 21 else None
+    class_list = variant.class_list(args)
+    first_ckpt = variant.first_ckpt_iter(args)
     history, tables, ckpts, meter = [], [], [], []
     loss_log = open(os.path.join(args.work_dir, "losses.txt"), "w") if rank == 0 else None
     it = iter(feeder)
     try:
         for n_iter in range(args.max_iters):
             names, plan, images, cls, labels = next(it)
-            inputs, _, _ = ops.train_augment(images, plan, labels, None, args.crop_size, aug_plan=plan.aug)
+            inputs = variant.augment(images, plan, labels, args)
             out = trainer.train_step(inputs, cls, n_iter)
             rec = dict(iter=n_iter + 1, seg_loss=out["seg_loss"], diver_loss=out["diver_loss"], lr=out["lr"])
             history.append(rec)
@@ -231,7 +267,7 @@ def train(args, model=None):
             if (n_iter + 1) % args.eval_iters == 0:                                                                 # :245-253
                 if rank == 0:
                     logging.info("Validating...")
-                    if args.save_ckpt and (n_iter + 1) >= 2:
+                    if args.save_ckpt and (n_iter + 1) >= first_ckpt:
                         path = os.path.join(ckpt_dir, "model_iter_%d.pth" % (n_iter + 1))
                         torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
                         ckpts.append(path)

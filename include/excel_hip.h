@@ -476,6 +476,14 @@ size_t excel_train_augment_workspace_bytes(const excel_train_aug_info* info);
 int excel_train_augment(const uint8_t* hwc, const uint8_t* labels, const int32_t* table, const excel_train_aug_info* info,
                         const double* mean3 /*host*/, const double* std3 /*host*/, float* img, uint8_t* label, int32_t* img_box,
                         void* workspace, void* stream);
+/* CocoClsDataset(aug=True)'s transform (datasets/coco.py:112-142): the same steps on images that carry no label map.  With label=None
+ * get_random_cropbox returns its first draw (datasets/transforms.py:141-146), so the crop is candidate 0 of every record (no
+ * cat_max_ratio rule) and there is no label output; img_box as above (padded coordinates).  Same table and info (excel_train_aug_plan)
+ * and workspace (excel_train_augment_workspace_bytes) as excel_train_augment.  Three launches on `stream`, no host synchronisation:
+ * the crop origin and img_box, the horizontal pass, the vertical pass fused with flip, pad, crop, normalisation and the CHW store.
+ * Outputs: img [B,3,S,S] f32, img_box [B,4] int32. */
+int excel_train_augment_image(const uint8_t* hwc, const int32_t* table, const excel_train_aug_info* info, const double* mean3 /*host*/,
+                              const double* std3 /*host*/, float* img, int32_t* img_box, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------ one-time / auxiliary */
 
