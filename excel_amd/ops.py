@@ -815,6 +815,92 @@ def normalize_resize_u8_ragged(hwc_packed, plan, S, mean=(123.675, 116.28, 103.5
     return out
 
 
+# ------------------------------------------------------------------ CAM overlay images (include/excel_hip.h, camviz.hip)
+CAM_OVERLAY_MODES = {"max": 0, "per_class": 1}
+_CAM_TABLES = {}
+
+
+def cam_overlay_tables(alpha, device, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375)):
+    """Device copy (float64 [2,768], built once per alpha / normalisation / device) of utils.imutils.cam_overlay_tables."""
+    key = (float(alpha), tuple(mean), tuple(std), str(device))
+    t = _CAM_TABLES.get(key)
+    if t is None:
+        from .utils import imutils
+        t = _CAM_TABLES[key] = torch.from_numpy(imutils.cam_overlay_tables(alpha, mean, std)).to(device)
+    return t
+
+
+def _pinned_upload(a, dtype, device):
+    """small host array -> device, through pinned memory (a pageable copy would make the host wait for the stream)"""
+    import numpy as np
+    h = torch.from_numpy(np.ascontiguousarray(a)).to(dtype).pin_memory()
+    return h.to(device, non_blocking=True)
+
+
+def cam_overlay_ragged(hwc_packed, cams, plan, Cmax, ncls, mode="max", alpha=None, mean=(123.675, 116.28, 103.53),
+                       std=(58.395, 57.12, 57.375)):
+    """tools/infer_lam.py:97-111 for a ragged batch: the jet-coloured CAM blended over the photo, every image at its own size.
+    hwc_packed = the decoded uint8 images (image b at byte 3 * loff_b), cams = Cmax pitched planes per image (plane 0 = background;
+    the pipeline's step buffer may be passed as it is: only x < W_b and planes 1..k_b are read), ncls = the HOST array of k_b (present
+    classes per image, from the batch's one-hot rows).  mode "max": alpha 0.5, one overlay per image with k_b >= 1; "per_class":
+    alpha 0.6, k_b overlays per image.  -> (out: flat uint8 device tensor, off: host int64 [B] byte offset of image b's first overlay);
+    overlay c of image b is out[off_b + 3*c*H_b*W_b :][: 3*H_b*W_b] as [H_b, W_b, 3]; in "max" mode the bytes of an image with k_b = 0
+    are left unwritten."""
+    import numpy as np
+    if mode not in CAM_OVERLAY_MODES:
+        raise ValueError(f"mode must be one of {sorted(CAM_OVERLAY_MODES)}, got {mode!r}")
+    if alpha is None:
+        alpha = 0.5 if mode == "max" else 0.6
+    ncls = np.asarray(ncls, np.int64).reshape(-1)
+    if ncls.shape[0] != plan.B or (ncls < 0).any() or (ncls > Cmax - 1).any():
+        raise ValueError(f"ncls: need {plan.B} values in [0, Cmax - 1 = {Cmax - 1}], got {ncls.tolist()}")
+    if hwc_packed.dtype != torch.uint8 or hwc_packed.numel() != 3 * plan.total_label_pix:
+        raise ValueError(f"hwc_packed must hold {3 * plan.total_label_pix} uint8 values")
+    if cams.numel() < Cmax * plan.total_pix:
+        raise ValueError(f"cams must hold Cmax * total_pix = {Cmax * plan.total_pix} floats, got {cams.numel()}")
+    dev = hwc_packed.device
+    hw = plan.hw.astype(np.int64)
+    if mode == "max":
+        off = 3 * plan.loff[:plan.B]
+        nbytes = 3 * plan.total_label_pix
+    else:
+        sizes = 3 * ncls * hw[:, 0] * hw[:, 1]
+        off = np.concatenate([[0], np.cumsum(sizes)])[:plan.B]
+        nbytes = int(sizes.sum())
+    out = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)[:int(nbytes)]
+    if nbytes == 0:
+        return out, off
+    n_dev = _pinned_upload(ncls, torch.int32, dev)
+    off_dev = _pinned_upload(off, torch.int64, dev) if mode == "per_class" else None
+    tabs = cam_overlay_tables(alpha, dev, mean, std)
+    check(lib().excel_cam_overlay_ragged(_p(hwc_packed, torch.uint8), _p(cams[:Cmax * plan.total_pix]), Cmax, _p(n_dev, torch.int32),
+                                         _p(off_dev, torch.int64), _p(plan.table, torch.int32), C.byref(plan.info), CAM_OVERLAY_MODES[mode],
+                                         _p(tabs, torch.float64), _p(out, torch.uint8), _stream()), "excel_cam_overlay_ragged")
+    return out, off
+
+
+def cam_overlay(hwc, cams, mode="max", alpha=None, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375)):
+    """One image (the per-image path): hwc uint8 [H,W,3], cams tight f32 [1+k,H,W] (refine_cams_with_bkg_weclip's normed maps) ->
+    "max": [H,W,3] (None when k == 0); "per_class": [k,H,W,3]."""
+    if mode not in CAM_OVERLAY_MODES:
+        raise ValueError(f"mode must be one of {sorted(CAM_OVERLAY_MODES)}, got {mode!r}")
+    if alpha is None:
+        alpha = 0.5 if mode == "max" else 0.6
+    cams = f32c(cams)
+    k, H, W = cams.shape[0] - 1, cams.shape[1], cams.shape[2]
+    if hwc.dtype != torch.uint8 or tuple(hwc.shape) != (H, W, 3):
+        raise ValueError(f"hwc must be uint8 [{H},{W},3], got {hwc.dtype} {tuple(hwc.shape)}")
+    if mode == "max" and k == 0:
+        return None
+    out = torch.empty((H, W, 3) if mode == "max" else (k, H, W, 3), dtype=torch.uint8, device=cams.device)
+    if out.numel() == 0:
+        return out
+    tabs = cam_overlay_tables(alpha, cams.device, mean, std)
+    check(lib().excel_cam_overlay(_p(hwc.contiguous(), torch.uint8), _p(cams), k, H, W, CAM_OVERLAY_MODES[mode], _p(tabs, torch.float64),
+                                  _p(out, torch.uint8), _stream()), "excel_cam_overlay")
+    return out
+
+
 # ------------------------------------------------------------------ training augmentation (include/excel_hip.h, aug.hip)
 AUG_CANDIDATES = 10
 # one record per image, laid out like excel_aug_params (C alignment: 104 bytes)

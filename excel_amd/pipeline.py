@@ -82,7 +82,9 @@ class TrainingFreePipeline:
         cls_labels [B,F] f32 one-hot; gts_packed: the uint8 [H_b,W_b] ground-truth maps back to back (255 = ignore) or None.
         Returns the labels as one flat uint8 tensor (image b = plan.label(labels, b)).
         Without `return_intermediates` the cams / PAR output live in uninitialised step buffers (see _buf: pad columns and unused
-        channels are undefined); with it they are fresh tensors whose unused parts are zero."""
+        channels are undefined); with it they are fresh tensors whose unused parts are zero.
+        `self.last_cams` is the step's cams (smax + 1 pitched planes per image) until the next step on the same stream overwrites it:
+        a consumer queued on that stream right after the step (the --save_cam overlay) reads them without a copy."""
         dev = hwc_packed.device
         B = plan.B
         g = S // 16
@@ -94,6 +96,7 @@ class TrainingFreePipeline:
         keep = return_intermediates
         cams = ops.cam_upsample_bkg_ragged(refined, ncls, g, plan, zero_unused=keep,
                                            out=None if keep else self._buf("cams", C * plan.total_pix, device=dev))   # affutils.py:164-166
+        self.last_cams = cams
         ws = self._buf("par_ws", ops.lib().excel_par_ragged_workspace_bytes(plan.total_pix, C), torch.uint8, dev)
         par_out = ops.par_forward_ragged(inputs, cams, plan, C, self.dilations, self.num_iter, nchan=nchan, ws=ws,
                                          out=None if keep else self._buf("par_out", C * plan.total_pix, device=dev))   # affutils.py:84

@@ -13,6 +13,13 @@ Differences from the reference, all deliberate:
     (clip.load, model/model_excel.py:25); the class + background prompts are encoded with the checkpoint's text tower
     (model/model_excel.py:31-33; needs CLIP's BPE merges file: --bpe_path / $EXCEL_BPE_VOCAB).  `--model_path` = the trained
     decoder checkpoint, required only with `--training_free false` (the reference loads and then ignores it otherwise, :150-152);
+  * `--save_cam true` writes the CAM overlay images of :97-111 (jet-coloured CAM blended over the photo, JPEG quality 75): per present
+    class into --cs_cam_dir with --save_cls_specific_cam true (the reference's default), else the max over the classes into --cam_dir.
+    The blend runs on the device right after each step (ops.cam_overlay_ragged, one launch per batch; the per-image path uses
+    ops.cam_overlay); only the overlay bytes come back, into pinned memory, and a small thread pool encodes the files while the next
+    batches run.  Deliberate differences: per-class file names use the data set's own class list (the reference's voc.class_list[idx+1],
+    :111, fails on COCO classes >= 20), and an image without a present class writes no max overlay (the reference's torch.max raises).
+    Directories follow :242-267 (cam_output_dirs); --refine_with_aff only picks the aff_lam / seeds_lam tag there, as in the reference;
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -47,6 +54,11 @@ def get_parser():
     p.add_argument("--resize_size", default=448, type=int)
     p.add_argument("--infer_set", default="train", type=str)
     p.add_argument("--training_free", default=True, type=_bool)
+    p.add_argument("--refine_with_aff", default=True, type=_bool, help="only names the output tag (aff_lam / seeds_lam, :242-246)")
+    p.add_argument("--save_cls_specific_cam", default=True, type=_bool, help="with --save_cam: one overlay per present class (:104-111)")
+    p.add_argument("--save_cam", default=False, type=_bool, help="write the CAM overlay images (:97-111)")
+    p.add_argument("--cam_dir", default=None, type=str, help="max-overlay directory (default: cam_output_dirs)")
+    p.add_argument("--cs_cam_dir", default=None, type=str, help="per-class overlay directory (default: cam_output_dirs)")
     p.add_argument("--data_folder", default=None, type=str, help="VOC2012 root (JPEGImages/, SegmentationClassAug/): real data instead of --synthetic")
     p.add_argument("--list_folder", default=None, type=str, help="directory with <infer_set>.txt and cls_labels_onehot.npy")
     p.add_argument("--u8_input", default=False, type=_bool, help="feed decoded uint8 HWC images and normalise on the device")
@@ -82,6 +94,80 @@ def get_parser():
                    help="auto: with several ranks on the node every rank pins itself (decode pool included) to its own share of the host cores")
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
     return p
+
+
+# ------------------------------------------------------------------ CAM overlay images (tools/infer_lam.py:97-111, :242-267)
+DEFAULT_CAM_ROOT = "lam_cams"       # stands in for the part before "checkpoints/" when there is no --model_path
+
+
+def cam_output_dirs(model_path, infer_set, training_free=True, refine_with_aff=True):
+    """The reference's output locations (:242-267): base = <model_path before "checkpoints/">/<infer_set>, then
+    <infer_set>_<ckpt>_<tag>_img (max overlays) and <infer_set>_<ckpt>_<tag>_class_specific_img (per-class overlays).  A model path
+    without "checkpoints/" uses the checkpoint's own directory (infer_seg_voc.output_dirs' rule); no model path uses
+    ./lam_cams/<infer_set>/<infer_set>_none_<tag>_..."""
+    tag = ("lam_training_free" if training_free else "lam_optimized") + ("/aff_lam" if refine_with_aff else "/seeds_lam")
+    if not model_path:
+        root, ckpt = DEFAULT_CAM_ROOT, "none"
+    elif "checkpoints/" in model_path:
+        root, ckpt = model_path.split("checkpoints/")[0], model_path.split("checkpoints/")[-1]
+    else:
+        root, ckpt = os.path.dirname(os.path.abspath(model_path)), os.path.basename(model_path)
+    ckpt = ckpt.replace(".pth", "")
+    base = os.path.normpath(os.path.join(root, infer_set))
+    return {"tag": tag, "cam_dir": os.path.join(base, f"{infer_set}_{ckpt}_{tag}_img"),
+            "cs_cam_dir": os.path.join(base, f"{infer_set}_{ckpt}_{tag}_class_specific_img")}
+
+
+def default_cam_writers(local_world=1):
+    """JPEG encoder threads per rank: a quarter of this rank's CPU share (at least 1).  The decode pool gives these up (build_validation)."""
+    return max(1, host_cpu_budget() // max(local_world, 1) // 4)
+
+
+def class_names(args):
+    """The data set's own class list (index 0 = background)."""
+    if "coco" in args.dataset_name:
+        from ..datasets import coco
+        return coco.class_list
+    return VOC_CLASSES
+
+
+class _CamSaver:
+    """--save_cam: device overlays of a batch / an image -> JPEG files through imutils.CamOverlayWriter."""
+
+    def __init__(self, args, writers):
+        from ..utils import imutils
+        self.per_class = bool(getattr(args, "save_cls_specific_cam", True))
+        self.mode = "per_class" if self.per_class else "max"
+        dirs = cam_output_dirs(getattr(args, "model_path", None), args.infer_set, bool(getattr(args, "training_free", True)),
+                               bool(getattr(args, "refine_with_aff", True)))
+        self.dir = (getattr(args, "cs_cam_dir", None) or dirs["cs_cam_dir"]) if self.per_class else (getattr(args, "cam_dir", None) or dirs["cam_dir"])
+        os.makedirs(self.dir, exist_ok=True)
+        self.names = class_names(args)
+        self.writer = imutils.CamOverlayWriter(writers)
+
+    def _items(self, name, present, H, W, off):
+        if not self.per_class:
+            return [(os.path.join(self.dir, name + ".jpg"), int(off), H, W)] if len(present) else []
+        return [(os.path.join(self.dir, f"{name}_{self.names[int(c) + 1]}.jpg"), int(off) + 3 * j * H * W, H, W) for j, c in enumerate(present)]
+
+    def ragged(self, names, plan, images, cams, Cmax, cls_host):
+        from .. import ops
+        present = [np.flatnonzero(row != 0) for row in cls_host]              # cls_compact's order
+        out, off = ops.cam_overlay_ragged(images, cams, plan, Cmax, [len(p) for p in present], self.mode)
+        items = []
+        for b, name in enumerate(names):
+            items += self._items(str(name), present[b], int(plan.hw[b, 0]), int(plan.hw[b, 1]), off[b])
+        self.writer.submit(out, items)
+
+    def image(self, name, hwc, normed, cls_lst):
+        from .. import ops
+        out = ops.cam_overlay(hwc, normed, self.mode)
+        if out is not None:
+            H, W = int(normed.shape[1]), int(normed.shape[2])
+            self.writer.submit(out.view(-1), self._items(str(name), np.asarray(cls_lst.cpu() if hasattr(cls_lst, "cpu") else cls_lst), H, W, 0))
+
+    def close(self):
+        return self.writer.close()
 
 
 # ------------------------------------------------------------------ sharding + the one collective (SURVEY 8e)
@@ -172,34 +258,59 @@ def _check_present_classes(batches, smax):
 def build_validation(model=None, par=None, dataset=None, indices=None, device="cuda", args=None, pipe=None):
     """-> (hist [nc,nc] int64 on device, images processed, seconds).  Mirrors :63-128."""
     from ..pipeline import TrainingFreePipeline
-    from ..utils import evaluate
-    from ..utils.affutils import refine_cams_with_aff, refine_cams_with_bkg_weclip
-    from .. import ops
-    S = args.resize_size
-    on_gpu = torch.device(device).type == "cuda"
     if pipe is None:
         pipe = TrainingFreePipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
                                     caa_thre=0.79, smax=dataset.max_k())
     hist = torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device)
     t0 = time.time()
-    nimg = 0
     training_free = bool(getattr(args, "training_free", True))
     per_image = args.api_path or not training_free
-    if getattr(args, "ragged_batches", False) and not per_image:
+    ragged = bool(getattr(args, "ragged_batches", False)) and not per_image
+    save_cam = bool(getattr(args, "save_cam", False))
+    if save_cam and not (ragged or per_image):
+        raise ValueError("--save_cam needs the decoded images: ragged batches (--data_folder or --ragged true) or the per-image path "
+                         "(--api_path true / --training_free false)")
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
+    writers = default_cam_writers(local_world) if save_cam else 0
+    cam = _CamSaver(args, writers) if save_cam else None
+    try:
+        return _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers)
+    finally:
+        if cam is not None:
+            cam.close()
+
+
+def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers):
+    from ..utils import evaluate
+    from ..utils.affutils import refine_cams_with_aff, refine_cams_with_bkg_weclip
+    from .. import ops
+    S = args.resize_size
+    on_gpu = torch.device(device).type == "cuda"
+    nimg = 0
+    if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
         from ..datasets.loader import ragged_batches
         from ..utils import imutils
         pipe.hist = hist
         keep = bool(getattr(args, "crf_post", False))
         nw = int(getattr(args, "num_workers", -1))
-        if nw < 0:
-            nw = default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1))))
+        if nw < 0:                                           # the JPEG encoders of --save_cam share this rank's CPUs
+            nw = max(2, default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))) - writers)
         if getattr(args, "decode", "threads") == "processes" and nw > 0:    # the reference's mechanism (DataLoader worker processes, :167)
             batches = ragged_batches(dataset, indices, args.batch_size, num_workers=nw, pin_memory=False)
         else:                                                               # default: a thread pool (datasets/loader.threaded_batches)
             from ..datasets.loader import threaded_batches
             batches = threaded_batches(dataset, indices, args.batch_size, num_threads=max(nw, 1))
         batches = _check_present_classes(batches, pipe.smax)
+        if cam is not None:                                    # the host one-hot rows, in the feeder's order (it keeps the order)
+            from collections import deque
+            host_cls = deque()
+
+            def _tap(bs):
+                for rb in bs:
+                    host_cls.append(rb.cls.numpy().copy())
+                    yield rb
+            batches = _tap(batches)
         if on_gpu:
             from ..datasets.loader import DeviceFeeder
             feed = DeviceFeeder(batches, device)              # H2D on a copy stream, a few batches ahead
@@ -207,6 +318,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
             feed = ((rb.names, ops.RaggedPlan(rb.hw, None), rb.images, rb.cls, rb.labels) for rb in batches)
         for names, plan, images, cls_t, labels_t in feed:
             out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
+            if cam is not None:                                                             # :97-111, same stream, step's own cams
+                cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, host_cls.popleft())
             if keep:                                                                        # :116-119 record for the CRF stage
                 inter = out[1]
                 cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
@@ -222,6 +335,9 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     for s in range(0, len(indices), bs):
         names, imgs, gts, cls = dataset.batch(indices[s:s + bs])
         inputs = torch.from_numpy(imgs).to(device, non_blocking=True)
+        if cam is not None and inputs.dtype != torch.uint8:
+            raise ValueError("--save_cam needs the decoded uint8 images (--data_folder, --ragged true or --u8_input true)")
+        decoded = inputs
         if inputs.dtype == torch.uint8:                                                     # decoded images: normalise on the device
             inputs = ops.normalize_img_u8(inputs)                                           # datasets/voc.py:115-116
         if inputs.shape[-2:] != (S, S):
@@ -246,6 +362,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
                 if getattr(args, "crf_post", False):                                         # :116-119 record for the CRF stage
                     from ..utils import imutils
                     imutils.save_logits(args.logits_dir, str(names[i]), normed, cls_lst, run_token=getattr(args, "run_token", None))
+                if cam is not None:                                                         # :97-111
+                    cam.image(names[i], decoded[i], normed, cls_lst)
                 hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
         else:
             pipe.hist = hist

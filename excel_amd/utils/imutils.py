@@ -7,6 +7,9 @@ records tools/infer_lam.py exchanges with its CRF stage.
   crf_keys_to_labels       tools/infer_lam.py:225-227: keys = pad(keys_gt + 1, (1, 0)); label = keys[argmax]
   save_label_png           the colour-coded label image the reference writes with imageio (:228); PIL here
   voc_test_palette / convert_test_seg2RGB   utils/pyutils.py:183-217: the VOC test-server palette PNG (21 VOC colours, grey after)
+  jet_lut / denormalize_roundtrip_table / cam_overlay_tables / CamOverlayWriter
+                           tools/infer_lam.py:97-111 (--save_cam): the host half of the CAM overlay images (the blend itself is
+                           excel_cam_overlay_ragged, camviz.hip)
 
 Plain numpy / PIL on the host: these are file formats, not compute.  DenseCRF itself (utils/dcrf.py) is excel_amd/utils/dcrf.py over
 excel_dcrf_inference (crf.hip).
@@ -103,3 +106,109 @@ def convert_test_seg2RGB(label, path):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     im.save(path)
     return path
+
+
+# ------------------------------------------------------------------ CAM overlay images (tools/infer_lam.py:97-111)
+# matplotlib's "jet" (_cm.py _jet_data): (x, y0, y1) anchors per channel.  matplotlib is not a dependency: the table is restated here.
+JET_SEGMENTS = {
+    "red": ((0.00, 0, 0), (0.35, 0, 0), (0.66, 1, 1), (0.89, 1, 1), (1.00, 0.5, 0.5)),
+    "green": ((0.000, 0, 0), (0.125, 0, 0), (0.375, 1, 1), (0.640, 1, 1), (0.910, 0, 0), (1.000, 0, 0)),
+    "blue": ((0.00, 0.5, 0.5), (0.11, 1, 1), (0.34, 1, 1), (0.65, 0, 0), (1.00, 0, 0)),
+}
+CAM_ALPHA_MAX = 0.5          # :101, the max-over-classes overlay
+CAM_ALPHA_PER_CLASS = 0.6    # :108, one overlay per present class
+CAM_JPEG_QUALITY = 75        # imageio's Pillow writer (and Pillow) default
+
+
+def _segment_lut(N, data):
+    """LinearSegmentedColormap._create_lookup_table(N, data, gamma=1.0), float64 [N]."""
+    a = np.array(data, np.float64)
+    x, y0, y1 = a[:, 0] * (N - 1), a[:, 1], a[:, 2]
+    xind = (N - 1) * np.linspace(0, 1, N) ** 1.0
+    ind = np.searchsorted(x, xind)[1:-1]
+    distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+    lut = np.concatenate([[y1[0]], distance * (y0[ind] - y1[ind - 1]) + y1[ind - 1], [y0[-1]]])
+    return np.clip(lut, 0.0, 1.0)
+
+
+def jet_lut(N=256):
+    """matplotlib's jet colormap table, float64 [N,3] (RGB; what plt.get_cmap("jet")(x)[..., :3] reads for 0 <= x <= 1)."""
+    return np.stack([_segment_lut(N, JET_SEGMENTS[c]) for c in ("red", "green", "blue")], 1)
+
+
+def denormalize_roundtrip_table(mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375)):
+    """uint8 [3,256]: entry [c][v] = what the reference's overlay shows for a decoded byte v of channel c - datasets/transforms.normalize_img
+    (numpy: float64 arithmetic, stored as float32) followed by utils/imutils.denormalize_img (torch CPU, float32, .type(torch.uint8)
+    truncates).  Not the identity: 1 / 5 / 14 of the R / G / B values change."""
+    import torch
+    v = np.arange(256, dtype=np.uint8)
+    imgarr = np.stack([v, v, v], -1)[None]                           # [1,256,3] HWC, like a decoded image
+    proc = np.empty_like(imgarr, np.float32)
+    for c in range(3):
+        proc[..., c] = (imgarr[..., c] - mean[c]) / std[c]
+    imgs = torch.from_numpy(proc).permute(2, 0, 1)[None]             # [1,3,1,256], the harness' input tensor
+    out = torch.zeros_like(imgs)
+    for c in range(3):
+        out[:, c, :, :] = imgs[:, c, :, :] * std[c] + mean[c]
+    return out.type(torch.uint8)[0, :, 0, :].numpy().copy()
+
+
+def cam_overlay_tables(alpha, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375)):
+    """The two float64 tables excel_cam_overlay_ragged adds, [2,768]: [0] = alpha * (jet * 255) as [256][3]; [1] = (1 - alpha) * the
+    round-trip image value as [3][256] - both terms of `alpha*cam_rgb + (1-alpha)*img` (:101-102) computed as numpy computes them, so
+    the kernel's one add gives the reference's float64 sum."""
+    lut = alpha * (jet_lut() * 255)
+    img = (1 - alpha) * denormalize_roundtrip_table(mean, std).astype(np.float64)
+    return np.ascontiguousarray(np.stack([lut.reshape(-1), img.reshape(-1)]))
+
+
+def save_jpeg(path, rgb):
+    """imageio.imsave(path, uint8 [H,W,3]) for a .jpg: Pillow at quality 75."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(rgb, np.uint8)).save(path, format="JPEG", quality=CAM_JPEG_QUALITY)
+    return path
+
+
+class CamOverlayWriter:
+    """Device overlays -> JPEG files, off the launching thread.  submit() enqueues the D2H copy of a batch's overlay bytes into pinned
+    memory on the current stream and records an event; a small thread pool waits for the event and encodes the files (Pillow releases
+    the GIL), overlapping the next batches.  At most `max_pending` batches are in flight: submit() waits for the oldest beyond that
+    (host back-pressure on the encoders, never a wait for the GPU in the launching thread).  close() waits for all and re-raises the
+    first encoder error."""
+
+    def __init__(self, threads=2, max_pending=None):
+        import concurrent.futures as cf
+        self.threads = max(1, int(threads))
+        self._pool = cf.ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="cam_jpeg")
+        self._pending = []
+        self._max = max_pending or 2 * self.threads + 1
+        self.files = 0
+
+    @staticmethod
+    def _encode(ev, host, items):
+        ev.synchronize()
+        buf = host.numpy()
+        for path, off, H, W in items:
+            save_jpeg(path, buf[off:off + 3 * H * W].reshape(H, W, 3))
+        return len(items)
+
+    def submit(self, dev_u8, items):
+        """dev_u8: flat uint8 device tensor; items: [(path, byte offset, H, W)] of the overlays it holds."""
+        import torch
+        if not items:
+            return
+        host = torch.empty(dev_u8.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(dev_u8, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        while len(self._pending) >= self._max:
+            self.files += self._pending.pop(0).result()
+        self._pending.append(self._pool.submit(self._encode, ev, host, list(items)))
+
+    def close(self):
+        try:
+            while self._pending:
+                self.files += self._pending.pop(0).result()
+        finally:
+            self._pool.shutdown(wait=True)
+        return self.files

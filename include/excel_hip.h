@@ -431,6 +431,27 @@ int excel_seg_resize_argmax_ragged(const float* planes, const int32_t* src_table
  * excel_dcrf_inference takes.  (h, w) == (H, W) skips the resize. */
 int excel_seg_softmax_resize(const float* planes, int h, int w, int nc, int H, int W, float* prob, void* stream);
 
+/* ------------------------------------------------------------------ CAM overlay images (camviz.hip)
+ * tools/infer_lam.py:97-111 (--save_cam): the jet-coloured CAM blended over the photo, per image at its own size, for a ragged batch
+ * in one launch.  For every pixel and channel ch
+ *   out = (uint8) trunc(tables[0][idx][ch] + tables[1][ch][v])        (one float64 add)
+ * where v = the decoded image byte (hwc, tight, image b at byte 3 * loff_b), idx = matplotlib jet's index of the cam value x (float32):
+ * floor(x * 256), x == 1 -> 255, x < 0 -> 0 (under), x > 1 -> 255 (over), NaN -> the bad colour (RGB 0, contributes 0.0).
+ *   tables (device float64 [2][768]): [0] = alpha * jet_lut * 255 as [256][3]; [1] = (1 - alpha) * denormalize_img(normalize_img(v))
+ *   as [3][256] - both pre-scaled on the host exactly as the reference computes them (excel_amd/utils/imutils.py).
+ *   mode EXCEL_CAM_OVERLAY_MAX:       x = max over the planes 1..k_b (NaN propagates, torch.max); one tight [H_b,W_b,3] overlay per
+ *                                     image at byte 3 * loff_b; an image with k_b = 0 is not written.
+ *   mode EXCEL_CAM_OVERLAY_PER_CLASS: x = plane 1 + c for c < k_b; overlay c of image b at byte out_off[b] + 3 * c * H_b * W_b.
+ * cams = Cmax pitched planes per image (the excel_cam_upsample_bkg_ragged layout; plane 0 = background, never read).  Only x < W_b and
+ * planes 1..k_b are read (pad columns and unused planes of the pipeline's step buffers may hold anything).
+ * ncls (device int32 [B]) = k_b, which the caller guarantees to be <= Cmax - 1; out_off (device int64 [B]) is needed in per-class mode.
+ * excel_cam_overlay is the same for ONE image whose cams are tight [1+k, H, W] (the per-image path's normed maps): out at byte 0. */
+#define EXCEL_CAM_OVERLAY_MAX 0
+#define EXCEL_CAM_OVERLAY_PER_CLASS 1
+int excel_cam_overlay_ragged(const uint8_t* hwc, const float* cams, int Cmax, const int32_t* ncls, const int64_t* out_off,
+                             const int32_t* table, const excel_ragged_info* info, int mode, const double* tables, uint8_t* out, void* stream);
+int excel_cam_overlay(const uint8_t* hwc, const float* cams, int k, int H, int W, int mode, const double* tables, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation (aug.hip)
  * VOC12ClsDataset(aug=True)'s transform (datasets/voc.py:110-117 over datasets/transforms.py) for a ragged batch of decoded uint8
  * images and label maps on the device, in the reference's order:
