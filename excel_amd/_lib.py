@@ -98,6 +98,8 @@ SIGNATURES = {
     "excel_vit_forward_ex": (c_i, [C.c_void_p, c_f, c_i, c_i, c_f, c_sz, c_f, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_i, c_f]),
     "excel_feature_affinity_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "excel_feature_affinity": (c_i, [c_f, c_i, c_i, c_i, C.c_float, C.c_float, c_i, c_f, c_f, c_f]),
+    "excel_feature_affinity_grouped_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "excel_feature_affinity_grouped": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, C.c_float, c_i, c_f, c_f, c_f]),
     "excel_attn_select_workspace_bytes": (c_sz, [c_i, c_i]),
     "excel_attn_select_mean": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
     "excel_decoder_create": (c_i, [C.POINTER(DecoderConfig), C.POINTER(DecoderWeights), C.POINTER(C.c_void_p)]),
@@ -139,6 +141,7 @@ SIGNATURES = {
                                 C.c_float, C.c_float, c_f, c_f, c_i, c_f]),
     "excel_ragged_plan": (c_i, [C.POINTER(C.c_int32), c_i, C.POINTER(RaggedInfo), C.POINTER(C.c_int32)]),
     "excel_normalize_resize_u8_ragged": (c_i, [c_f, c_f, c_i, c_i, C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f]),
+    "excel_normalize_resize_u8_ragged_mirror": (c_i, [c_f, c_f, c_i, c_i, C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f]),
     "excel_cam_upsample_bkg_ragged": (c_i, [c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_i, c_f, c_f, c_i, c_f]),
     "excel_par_ragged_workspace_bytes": (c_sz, [c_ll, c_i]),
     "excel_par_forward_ragged": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, C.POINTER(C.c_int32), c_i, c_i,

@@ -501,6 +501,15 @@ extern "C" int excel_feature_affinity(const float* feats, int B, int C, int P, f
     return excel_launch_feature_affinity(feats, B, C, P, beta, gamma, mode, out, workspace, ST(stream));
 }
 
+extern "C" size_t excel_feature_affinity_grouped_workspace_bytes(int B, int C, int P, int group) {
+    return excel_feature_affinity_grouped_ws_bytes(B, C, P, group);
+}
+
+extern "C" int excel_feature_affinity_grouped(const float* feats, int B, int C, int P, int group, int member_stride, float beta, float gamma,
+                                              int mode, float* out, void* workspace, void* stream) {
+    return excel_launch_feature_affinity_grouped(feats, B, C, P, group, member_stride, beta, gamma, mode, out, workspace, ST(stream));
+}
+
 extern "C" size_t excel_attn_select_workspace_bytes(int B, int n_layers) { return excel_attn_select_ws_bytes(B, n_layers); }
 
 extern "C" int excel_attn_select_mean(const float* attn, int Lw, int B, int N, int first_layer, int n_layers, const float* seg_attn,
@@ -688,6 +697,12 @@ extern "C" int excel_normalize_resize_u8_ragged(const uint8_t* hwc, const int32_
                                                 float* out, void* stream) {
     EXCEL_CHECK_ARG(hwc && table && out && mean3 && std3 && B > 0 && S > 0, "normalize_resize_u8_ragged: bad argument");
     return excel_launch_normalize_resize_u8_ragged(hwc, out, ragged_geo(table, B), S, mean3, std3, ST(stream));
+}
+
+extern "C" int excel_normalize_resize_u8_ragged_mirror(const uint8_t* hwc, const int32_t* table, int B, int S, const double* mean3,
+                                                       const double* std3, float* out, void* stream) {
+    EXCEL_CHECK_ARG(hwc && table && out && mean3 && std3 && B > 0 && S > 0, "normalize_resize_u8_ragged_mirror: bad argument");
+    return excel_launch_normalize_resize_u8_ragged_mirror(hwc, out, ragged_geo(table, B), S, mean3, std3, ST(stream));
 }
 
 extern "C" int excel_cam_upsample_bkg_ragged(const float* refined, const int32_t* ncls, const int32_t* table, const excel_ragged_info* info, int g,

@@ -79,6 +79,9 @@ __global__ __launch_bounds__(256) void bilinear_resize_kernel(const float* __res
 // -> transforms.normalize_img (datasets/transforms.py:7-14, double intermediate) -> F.interpolate(bilinear, align_corners=False) to
 // S x S (tools/infer_lam.py:74) -> out [B,3,S,S].  The same operations as excel_normalize_img_u8 followed by excel_bilinear_resize
 // (same bits), without the full-size fp32 intermediate.  grid (cdiv(S*S,256), 3, B)
+// MIRROR: out is [2B,3,S,S] and image B + b is image b mirrored along W (utils/camutils.py:15 flips AFTER the resize): every value
+// is computed once and stored twice.
+template <bool MIRROR>
 __global__ __launch_bounds__(256) void normalize_resize_u8_ragged_kernel(const unsigned char* __restrict__ hwc, float* __restrict__ out,
                                                                          const int* __restrict__ tab, int S, double m0, double m1, double m2,
                                                                          double s0, double s1, double s2) {
@@ -91,7 +94,9 @@ __global__ __launch_bounds__(256) void normalize_resize_u8_ragged_kernel(const u
     const BilinearTap t = bilinear_tap(x, y, h, w, S, S, 0);
     const double m = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
     auto px = [&](int yy, int xx) { return (float)(((double)src[((long long)yy * w + xx) * 3] - m) / sd); };
-    out[((long long)b * 3 + c) * S * S + i] = bilinear_blend(t, px(t.y0, t.x0), px(t.y0, t.x1), px(t.y1, t.x0), px(t.y1, t.x1));
+    const float v = bilinear_blend(t, px(t.y0, t.x0), px(t.y0, t.x1), px(t.y1, t.x0), px(t.y1, t.x1));
+    out[((long long)b * 3 + c) * S * S + i] = v;
+    if (MIRROR) out[((long long)(gridDim.z + b) * 3 + c) * S * S + y * S + (S - 1 - x)] = v;
 }
 
 // attr [2B,P,F] (second half computed from horizontally flipped inputs) -> out [B,P,F]:
@@ -308,9 +313,18 @@ int excel_launch_bilinear_resize(const float* in, float* out, long long planes, 
 int excel_launch_normalize_resize_u8_ragged(const unsigned char* hwc, float* out, const TileGeo& geo, int S, const double* mean, const double* stdv,
                                             hipStream_t st) {
     ProfScope prof__(PROF_OTHER, st);
-    hipLaunchKernelGGL(normalize_resize_u8_ragged_kernel, dim3(cdiv(S * S, 256), 3, geo.B), dim3(256), 0, st, hwc, out, geo.tab, S, mean[0], mean[1],
-                       mean[2], stdv[0], stdv[1], stdv[2]);
+    hipLaunchKernelGGL(normalize_resize_u8_ragged_kernel<false>, dim3(cdiv(S * S, 256), 3, geo.B), dim3(256), 0, st, hwc, out, geo.tab, S, mean[0],
+                       mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
     EXCEL_CHECK_LAUNCH("normalize_resize_u8_ragged");
+    return EXCEL_OK;
+}
+
+int excel_launch_normalize_resize_u8_ragged_mirror(const unsigned char* hwc, float* out, const TileGeo& geo, int S, const double* mean,
+                                                   const double* stdv, hipStream_t st) {
+    ProfScope prof__(PROF_OTHER, st);
+    hipLaunchKernelGGL(normalize_resize_u8_ragged_kernel<true>, dim3(cdiv(S * S, 256), 3, geo.B), dim3(256), 0, st, hwc, out, geo.tab, S, mean[0],
+                       mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
+    EXCEL_CHECK_LAUNCH("normalize_resize_u8_ragged_mirror");
     return EXCEL_OK;
 }
 

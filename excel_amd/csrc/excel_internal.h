@@ -75,6 +75,8 @@ int excel_launch_cam_upsample_bkg_ragged(const float* r, const int* ncls, float*
                                          int total_tiles, int zero_unused, hipStream_t st);
 int excel_launch_normalize_resize_u8_ragged(const unsigned char* hwc, float* out, const TileGeo& geo, int S, const double* mean, const double* stdv,
                                             hipStream_t st);
+int excel_launch_normalize_resize_u8_ragged_mirror(const unsigned char* hwc, float* out, const TileGeo& geo, int S, const double* mean,
+                                                   const double* stdv, hipStream_t st);
 int excel_launch_bilinear_ac(const float* in, float* out, int planes, int h, int w, int H, int W, hipStream_t st);
 int excel_launch_argmax_label(const float* cams, const int* nchan, const int* cls_idx, int B, int Smax, int Cmax, long long HW,
                               unsigned char* lab8, long long* lab64, hipStream_t st);
@@ -103,6 +105,9 @@ int excel_launch_train_losses(const float* seg, const float* attn_pred, const un
 size_t excel_feature_affinity_ws_bytes(int B, int C, int P);
 int excel_launch_feature_affinity(const float* feats, int B, int C, int P, float beta, float gamma, int mode, float* out, void* ws,
                                   hipStream_t st);
+size_t excel_feature_affinity_grouped_ws_bytes(int B, int C, int P, int group);
+int excel_launch_feature_affinity_grouped(const float* feats, int B, int C, int P, int group, int member_stride, float beta, float gamma,
+                                          int mode, float* out, void* ws, hipStream_t st);
 size_t excel_attn_select_ws_bytes(int B, int n_layers);
 int excel_launch_attn_select_mean(const float* attn, int Lw, int B, int N, int first_layer, int n_layers, const float* seg_attn,
                                   float* out, void* ws, hipStream_t st);

@@ -1,7 +1,7 @@
 // LVC ("learned visual cue") side of the path, SURVEY 8(f) rank 1 -- the pieces around the decoder features:
 //   * feature affinity: channel-normalised token similarity, shifted by beta x its mean over the WHOLE batch tensor and
 //     scaled by gamma; then either sigmoid (attn_pred, model/model_excel.py:70-76) or "negatives -> -inf, row softmax"
-//     (ex_attn, clip/clip_surgery_model.py:128-137);
+//     (ex_attn, clip/clip_surgery_model.py:128-137); the grouped form takes each mean over one group of images instead;
 //   * seg_attn layer selection of refine_cams_with_aff (utils/affutils.py:182-195).
 // All reductions are fixed-order (no atomics): results are run-to-run identical.
 #include "common.h"
@@ -61,13 +61,8 @@ __global__ void lvc_final_mean_kernel(const double* __restrict__ partial, int n_
 }
 
 // one wave per row: z = (sim - mean*beta)*gamma ; mode 0: sigmoid(z) ; mode 1: z < 0 -> -inf, softmax over the row
-__global__ __launch_bounds__(256) void lvc_finish_kernel(float* __restrict__ sim, const float* __restrict__ mean, long long rows, int P,
-                                                         float beta, float gamma, int mode) {
-    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    float* r = sim + row * P;
-    const float shift = mean[0] * beta;
+// (shared by the whole-batch and the grouped entry: the same instructions, so a group's rows equal a standalone call's bit for bit)
+__device__ __forceinline__ void lvc_finish_row(float* __restrict__ r, float shift, int P, float gamma, int mode, int lane) {
     if (mode == 0) {
         for (int i = lane; i < P; i += 64) {
             const float z = (r[i] - shift) * gamma;
@@ -91,6 +86,14 @@ __global__ __launch_bounds__(256) void lvc_finish_kernel(float* __restrict__ sim
         const float z = (r[i] - shift) * gamma;
         r[i] = (z < 0.f) ? 0.f : expf(z - m) / s;       // a row of all -inf gives 0/0 = NaN like torch.softmax
     }
+}
+
+__global__ __launch_bounds__(256) void lvc_finish_kernel(float* __restrict__ sim, const float* __restrict__ mean, long long rows, int P,
+                                                         float beta, float gamma, int mode) {
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    lvc_finish_row(sim + row * P, mean[0] * beta, P, gamma, mode, lane);
 }
 
 size_t excel_feature_affinity_ws_bytes(int B, int C, int P) {
@@ -131,6 +134,109 @@ int excel_launch_feature_affinity(const float* feats, int B, int C, int P, float
     hipLaunchKernelGGL(lvc_finish_kernel, dim3((unsigned)cdivl((long long)B * P, 4)), dim3(256), 0, st, out, mean, (long long)B * P, P,
                        beta, gamma, mode);
     EXCEL_CHECK_LAUNCH("feature_affinity");
+    return EXCEL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- grouped feature affinity
+// Same affinity, but the mean of each GROUP of `group` images is taken over that group alone (include/excel_hip.h).  Member m of
+// group j is image first(j) + m * ms with first(j) = (j / ms) * group * ms + j % ms: ms = 1 -> consecutive images, ms = B / group ->
+// image j of every slice of B / group images (the (x, flip x) pairs of a [2B] stack).
+__device__ __forceinline__ long long lvc_group_first(int j, int group, int ms) {
+    return (long long)(j / ms) * group * ms + (j % ms);
+}
+
+// partial[j, i] = sum of chunk i of group j's concatenated sims (member order): the chunking and the order of the additions of
+// lvc_partial_sum_kernel over a [group,P,P] tensor, reading the members where they lie.  grid (nparts, ngroups)
+__global__ __launch_bounds__(256) void lvc_group_partial_sum_kernel(const float* __restrict__ x, long long PP, int group, int ms,
+                                                                    double* __restrict__ partial) {
+    const int j = blockIdx.y;
+    const long long n = PP * group;
+    const long long per = (n + gridDim.x - 1) / gridDim.x;
+    const long long lo = (long long)blockIdx.x * per, hi = min(lo + per, n);
+    const float* src = x + lvc_group_first(j, group, ms) * PP;
+    const long long mstride = (long long)ms * PP;
+    double s = 0.0;
+    long long i = lo + threadIdx.x;
+    long long m = i / PP, off = i - m * PP;
+    for (; i < hi; i += 256) {
+        s += (double)src[m * mstride + off];
+        off += 256;
+        while (off >= PP) { off -= PP; ++m; }
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(long long)j * gridDim.x + blockIdx.x] = red[0];
+}
+
+// mean[j] = (sum of group j's partials in order) / n          grid (ngroups)
+__global__ void lvc_group_final_mean_kernel(const double* __restrict__ partial, int n_partial, long long n, float* __restrict__ mean) {
+    if (threadIdx.x) return;
+    const int j = blockIdx.x;
+    double s = 0.0;
+    for (int i = 0; i < n_partial; ++i) s += partial[(long long)j * n_partial + i];
+    mean[j] = (float)(s / (double)n);
+}
+
+// row r of image b = r / P uses the mean of b's group
+__global__ __launch_bounds__(256) void lvc_group_finish_kernel(float* __restrict__ sim, const float* __restrict__ mean, long long rows, int P,
+                                                               int group, int ms, float beta, float gamma, int mode) {
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int b = (int)(row / P), slab = group * ms, r = b % slab;
+    const int j = (b / slab) * ms + r % ms;
+    lvc_finish_row(sim + row * P, mean[j] * beta, P, gamma, mode, lane);
+}
+
+static int lvc_group_nparts(long long n) { return (int)min((long long)1024, cdivl(n, 4096)); }
+
+size_t excel_feature_affinity_grouped_ws_bytes(int B, int C, int P, int group) {
+    const int Cp = (C + 3) / 4 * 4;
+    const int ngroups = group > 0 ? B / group : 0;
+    return align_up((size_t)B * P * sizeof(float), 256) + align_up((size_t)B * P * Cp * sizeof(float), 256) +
+           align_up((size_t)ngroups * 1024 * sizeof(double), 256) + align_up((size_t)ngroups * sizeof(float), 256);
+}
+
+int excel_launch_feature_affinity_grouped(const float* feats, int B, int C, int P, int group, int member_stride, float beta, float gamma,
+                                          int mode, float* out, void* ws, hipStream_t st) {
+    ProfScope prof__(PROF_OTHER, st);
+    EXCEL_CHECK_ARG(feats && out && ws && B > 0 && C > 0 && P > 0 && (mode == 0 || mode == 1), "feature_affinity_grouped: bad argument");
+    EXCEL_CHECK_ARG(group >= 1 && member_stride >= 1 && B % ((long long)group * member_stride) == 0,
+                    "feature_affinity_grouped: B=%d is not a multiple of group (%d) x member_stride (%d)", B, group, member_stride);
+    const int Cp = (C + 3) / 4 * 4;
+    const int ngroups = B / group;
+    char* base = (char*)ws;
+    float* inv = (float*)base;
+    base += align_up((size_t)B * P * sizeof(float), 256);
+    float* fn = (float*)base;
+    base += align_up((size_t)B * P * Cp * sizeof(float), 256);
+    double* partial = (double*)base;
+    base += align_up((size_t)ngroups * 1024 * sizeof(double), 256);
+    float* mean = (float*)base;
+    hipLaunchKernelGGL(lvc_col_invnorm_kernel, dim3(cdiv(P, 256), B), dim3(256), 0, st, feats, inv, C, P);
+    hipLaunchKernelGGL(lvc_transpose_scale_kernel, dim3(cdiv(P, 32), cdiv(Cp, 32), B), dim3(256), 0, st, feats, inv, fn, C, Cp, P);
+    EXCEL_CHECK_LAUNCH("feature_affinity_grouped/normalize");
+    // sim[b] = fn[b] . fn[b]^T for every image: the GEMM of excel_launch_feature_affinity (one image per batch entry)
+    GemmArgs g{};
+    g.A = fn; g.B = fn; g.C = out; g.bias = nullptr; g.res = nullptr;
+    g.M = P; g.N = P; g.K = Cp; g.Kld = Cp; g.lda = Cp; g.ldb = Cp; g.ldc = P; g.ldr = 0;
+    g.sA = g.sB = (long long)P * Cp; g.sC = (long long)P * P; g.sR = 0; g.sBias = 0;
+    g.zdiv = 1; g.sA2 = g.sB2 = g.sC2 = 0;
+    g.act = GEMM_ACT_NONE; g.out_mode = GEMM_OUT_PLAIN; g.tokN = g.heads = g.hd = 0; g.alpha = 1.f;
+    int rc = excel_launch_gemm(g, true, B, st);
+    if (rc) return rc;
+    const long long PP = (long long)P * P, n = PP * group;      // a standalone call on one group: n = group * P * P
+    const int nparts = lvc_group_nparts(n);
+    hipLaunchKernelGGL(lvc_group_partial_sum_kernel, dim3(nparts, ngroups), dim3(256), 0, st, out, PP, group, member_stride, partial);
+    hipLaunchKernelGGL(lvc_group_final_mean_kernel, dim3(ngroups), dim3(64), 0, st, partial, nparts, n, mean);
+    hipLaunchKernelGGL(lvc_group_finish_kernel, dim3((unsigned)cdivl((long long)B * P, 4)), dim3(256), 0, st, out, mean, (long long)B * P, P,
+                       group, member_stride, beta, gamma, mode);
+    EXCEL_CHECK_LAUNCH("feature_affinity_grouped");
     return EXCEL_OK;
 }
 

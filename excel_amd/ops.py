@@ -678,6 +678,22 @@ def feature_affinity(feats, mode, beta=1.0, gamma=3.0):
     return out
 
 
+def feature_affinity_grouped(feats, mode, group, member_stride=1, beta=1.0, gamma=3.0, out=None):
+    """feature_affinity with the mean taken per group of images (include/excel_hip.h): member m of group j is image
+    (j // member_stride) * group * member_stride + j % member_stride + m * member_stride.  group=1: per image (attn_pred of a batch);
+    group=2, member_stride=B over a [2B] stack [x; flip x]: per (x_j, flip x_j) pair (ex_attn).  Every group equals a standalone
+    feature_affinity call on its images bit for bit."""
+    feats = f32c(feats)
+    feats = feats.reshape(feats.shape[0], feats.shape[1], -1)
+    B, Cc, P = feats.shape
+    out = _out(out, (B, P, P), torch.float32, feats.device)
+    ws = _ws(lib().excel_feature_affinity_grouped_workspace_bytes(B, Cc, P, int(group)), feats.device)
+    check(lib().excel_feature_affinity_grouped(_p(feats), B, Cc, P, int(group), int(member_stride), float(beta), float(gamma),
+                                               {"sigmoid": 0, "mask_softmax": 1}[mode], _p(out), _p(ws, torch.uint8), _stream()),
+          "excel_feature_affinity_grouped")
+    return out
+
+
 def compute_trans_mat(w_aff):
     """[B,P,P] (or [P,P]) -> trans_mat, same shape (utils/affutils.py:8-24)."""
     single = w_aff.dim() == 2
@@ -812,6 +828,17 @@ def normalize_resize_u8_ragged(hwc_packed, plan, S, mean=(123.675, 116.28, 103.5
     m, s = (C.c_double * 3)(*mean), (C.c_double * 3)(*std)
     check(lib().excel_normalize_resize_u8_ragged(_p(hwc_packed, torch.uint8), _p(plan.table, torch.int32), plan.B, S, m, s, _p(out), _stream()),
           "excel_normalize_resize_u8_ragged")
+    return out
+
+
+def normalize_resize_u8_ragged_mirror(hwc_packed, plan, S, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), out=None):
+    """normalize_resize_u8_ragged and its mirror along W in one pass -> [2B,3,S,S] = [x; flip(x)] (utils/camutils.py:15)."""
+    if hwc_packed.dtype != torch.uint8 or hwc_packed.numel() != 3 * plan.total_label_pix:
+        raise ValueError(f"hwc_packed must hold {3 * plan.total_label_pix} uint8 values")
+    out = _out(out, (2 * plan.B, 3, S, S), torch.float32, hwc_packed.device)
+    m, s = (C.c_double * 3)(*mean), (C.c_double * 3)(*std)
+    check(lib().excel_normalize_resize_u8_ragged_mirror(_p(hwc_packed, torch.uint8), _p(plan.table, torch.int32), plan.B, S, m, s, _p(out),
+                                                        _stream()), "excel_normalize_resize_u8_ragged_mirror")
     return out
 
 

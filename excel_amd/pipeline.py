@@ -92,6 +92,13 @@ class TrainingFreePipeline:
         _, _, attr, attn_w, _ = self.model(inputs)                                                  # infer_lam.py:79
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
+        return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
+                                      dict(attr=attr, w_aff=attn_w.w_aff))
+
+    def _ragged_back_half(self, inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates, inter):
+        """Up-sampling + background, PAR, arg-max and confusion of a ragged step (tools/infer_lam.py:94), shared by every regime.
+        inputs [B,3,S,S] = the network input PAR reads; `inter` = the regime's own intermediates (attr, w_aff)."""
+        dev = inputs.device
         C = self.smax + 1
         keep = return_intermediates
         cams = ops.cam_upsample_bkg_ragged(refined, ncls, g, plan, zero_unused=keep,
@@ -104,8 +111,7 @@ class TrainingFreePipeline:
         if gts_packed is not None:
             self.hist = ops.confusion_accumulate(gts_packed, labels, self.num_classes, self.hist)   # evaluate.py:9-20
         if return_intermediates:
-            return labels, dict(inputs=inputs.clone(), attr=attr, w_aff=attn_w.w_aff, refined=refined, cams=cams, par_out=par_out,
-                                cls_idx=idx, ncls=ncls)
+            return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
         return labels
 
     # ------------------------------------------------------------------ concurrent sub-batches
@@ -197,3 +203,71 @@ class TrainingFreePipeline:
             if sub["hist"] is not None:
                 self.hist = sub["hist"] if self.hist is None else self.hist + sub["hist"]
                 sub["hist"] = None
+
+
+class OptimisedLamPipeline(TrainingFreePipeline):
+    """The optimised-LAM regime (tools/infer_lam.py:79-94 with training_free=False: flip-TTA LAMs through the LVC branch and a
+    seg_attn-gated affinity, both driven by the trained decoder head) for a ragged batch of B images at once, on the training-free
+    pipeline's ragged back half.  Per image, labels are bit-identical to the reference's per-image call sequence:
+
+        model(x, n_attn_out=6)                      -> per-layer maps of x, attn_fts(x), attn_pred = affinity over image x alone
+        cure_attr_map_flip(model, x)                -> ex_feats = attn_fts([x; flip x]), ex_attn = affinity over that pair,
+                                                       LVC-branch CAMs of [x; flip x], flip-max + min-max (camutils.py:8-30)
+        refine_cams_with_aff(seg_attn=attn_pred)    -> gated affinity (affutils.py:182-195), random walk at caa_thre
+        refine_cams_with_bkg_weclip                 -> up-sampling, PAR, arg-max at the image's own size
+
+    The per-image sequence runs 5 image-forwards (x with the maps; [x; flip x] for ex_feats; [x; flip x] through the LVC branch).
+    Here it is 4 full-batch forwards per image: attn_fts(x) of the first forward is reused as the x half of ex_feats (the tower's
+    flags are those of model(x) in both calls, the per-layer maps are side outputs: the decoder input is the same bits), the flipped
+    half comes from a feature-only forward of flip x.  The whole-batch means of excel_feature_affinity are replaced by the grouped
+    entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
+
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6):
+        if getattr(model, "_dec", None) is None:
+            raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
+                             "(--training_free false --model_path)")
+        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax)
+        self.attn_layers = attn_layers
+
+    def _tower(self, imgs, n_attn_out=0):
+        """model.forward's tower call (model_excel.py:55-58 flags with a decoder head): maps, aliased feats, w_aff and x_raw as there."""
+        return self.model.encoder.encode_image(imgs, True, None, want_w_aff=True, aff_layers=6, n_attn_out=n_attn_out, want_feats=True,
+                                               feats_as_reference=True, want_raw=True, want_features=False)
+
+    @torch.no_grad()
+    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=448, return_intermediates=False):
+        """Same contract as TrainingFreePipeline.run_batch_ragged (flat uint8 labels, self.hist, self.last_cams, intermediates);
+        `attr` of the intermediates is the flip-TTA LAM [B,P,F], `w_aff` the seg_attn-gated affinity [B,P,P]."""
+        dev = hwc_packed.device
+        B = plan.B
+        g = S // 16
+        model = self.model
+        dec = model._dec
+        inputs2 = ops.normalize_resize_u8_ragged_mirror(hwc_packed, plan, S,
+                                                        out=self._buf("inputs2", 2 * B * 3 * S * S, device=dev).view(2 * B, 3, S, S))  # camutils.py:15
+        inputs = inputs2[:B]
+        # x: per-layer maps + decoder features (infer_lam.py:79 with n_attn_out=6)
+        r = self._tower(inputs, n_attn_out=6)
+        fts_x, _ = dec.forward(r["feats"], want_seg=False)                                          # model_excel.py:60-68
+        attn_pred = ops.feature_affinity_grouped(fts_x, "sigmoid", group=1)                          # :70-76, batch 1 per image
+        w_aff = ops.attn_select_mean(r["attn"], attn_pred, self.attn_layers)                         # affutils.py:182-195
+        del r
+        # flip x: decoder features only (the flipped half of camutils.py:17)
+        r = self._tower(inputs2[B:])
+        fts_f, _ = dec.forward(r["feats"], want_seg=False)
+        del r
+        ex_feats = torch.cat([fts_x, fts_f], 0)
+        del fts_f
+        ex_attn = ops.feature_affinity_grouped(ex_feats, "mask_softmax", group=2, member_stride=B)   # clip_surgery_model.py:128-137 per pair
+        del ex_feats
+        h = model.encoder.visual.handle()
+        r = h.forward(inputs2, want_w_aff=False, want_raw=True, want_features=False, ex_attn=ex_attn)  # camutils.py:18
+        del ex_attn
+        maps = ops.patch_text_cam(r["x_raw"], model._text_rows, num_fg=model.num_classes - 1, mode=h.gemm_mode())[1]   # model_excel.py:52
+        del r
+        attr = ops.flip_max_normalize(maps, g)                                                      # camutils.py:21-26
+        del maps
+        idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
+        refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # infer_lam.py:93
+        return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
+                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred))

@@ -2,7 +2,8 @@
 
 Differences from the reference, all deliberate:
   * batches of B > 1 images run through the device-resident TrainingFreePipeline (the reference is batch 1 with
-    per-class host round trips); `--api_path` runs the reference's per-image call sequence instead.  Real data (`--data_folder`:
+    per-class host round trips) - with `--training_free false` on ragged batches through OptimisedLamPipeline (the decoder-driven
+    flip-TTA LAMs, labels bit-identical to the per-image sequence); `--api_path` runs the reference's per-image call sequence instead.  Real data (`--data_folder`:
     every image has its own size, and the path refines and scores at that size, :74,:94) and `--ragged true` synthetic data run
     as RAGGED batches: a background decode pool (`--num_workers` threads; `--decode processes` = the reference's DataLoader worker
     processes, :167) fills a pinned staging ring, a copy stream moves the batches to the device ahead of the compute stream, the device resizes every image to the network size and runs the size-dependent half (up-sampling, PAR, arg-max) over packed
@@ -251,21 +252,27 @@ def _check_present_classes(batches, smax):
         if int(k.max()) > smax:
             b = int(k.argmax())
             raise RuntimeError(f"{rb.names[b]}: {int(k[b])} present classes, the pipeline was built for at most {smax} (dataset.max_k()): "
-                               "build TrainingFreePipeline with a larger smax")
+                               "build the pipeline with a larger smax")
         yield rb
 
 
 def build_validation(model=None, par=None, dataset=None, indices=None, device="cuda", args=None, pipe=None):
     """-> (hist [nc,nc] int64 on device, images processed, seconds).  Mirrors :63-128."""
-    from ..pipeline import TrainingFreePipeline
+    from ..pipeline import OptimisedLamPipeline, TrainingFreePipeline
+    training_free = bool(getattr(args, "training_free", True))
+    ragged_batches = bool(getattr(args, "ragged_batches", False))
+    # the optimised-LAM regime runs batched on ragged batches; uniform synthetic batches keep its per-image call sequence
+    per_image = args.api_path or (not training_free and not ragged_batches)
+    ragged = ragged_batches and not per_image
     if pipe is None:
-        pipe = TrainingFreePipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
-                                    caa_thre=0.79, smax=dataset.max_k())
+        if training_free:
+            pipe = TrainingFreePipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
+                                        caa_thre=0.79, smax=dataset.max_k())
+        elif ragged:
+            pipe = OptimisedLamPipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
+                                        caa_thre=0.79, smax=dataset.max_k())
     hist = torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device)
     t0 = time.time()
-    training_free = bool(getattr(args, "training_free", True))
-    per_image = args.api_path or not training_free
-    ragged = bool(getattr(args, "ragged_batches", False)) and not per_image
     save_cam = bool(getattr(args, "save_cam", False))
     if save_cam and not (ragged or per_image):
         raise ValueError("--save_cam needs the decoded images: ragged batches (--data_folder or --ragged true) or the per-image path "

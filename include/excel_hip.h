@@ -158,6 +158,24 @@ size_t excel_feature_affinity_workspace_bytes(int B, int C, int P);
 int excel_feature_affinity(const float* feats, int B, int C, int P, float beta, float gamma, int mode, float* out,
                            void* workspace, void* stream);
 
+/* excel_feature_affinity with each mean taken over one GROUP of images instead of the whole batch.  The reference computes
+ * attn_pred on one image (tools/infer_lam.py:79, batch 1) and ex_attn on the pair (x, flip x) (utils/camutils.py:15-18): a batched
+ * step of many images needs those means per image / per pair.
+ *   feats [B,C,P]; `group` images per group, B / group groups.  Member m (0 <= m < group) of group j is image
+ *       first(j) + m * member_stride,   first(j) = (j / member_stride) * group * member_stride + j % member_stride
+ *   requires B % (group * member_stride) == 0.  The two layouts the optimised-LAM step uses:
+ *       group 1, member_stride 1                  one image per group (attn_pred);
+ *       group 2, member_stride B/2 over a [2B'] stack   the pair (image j, image B' + j) (ex_attn over [x; flip x], B' = B/2).
+ *   BIT CONTRACT: every group's rows are bit-identical to excel_feature_affinity called on that group's images alone, stacked in
+ *   member order.  The per-group mean reproduces that call's fixed-order double sum: n = group*P*P, nparts = min(1024,
+ *   ceil(n / 4096)) chunks of ceil(n / nparts) values in member order, each summed by 256 strided lanes and a tree, the chunk sums
+ *   added in order (mode 1 masks z < 0, so one last bit of the mean can change the mask).
+ * One launch sequence per call (normalise, one batched similarity GEMM, partial sums over a (chunk, group) grid, per-group mean,
+ * finish); workspace: excel_feature_affinity_grouped_workspace_bytes(B, C, P, group).                                     */
+size_t excel_feature_affinity_grouped_workspace_bytes(int B, int C, int P, int group);
+int excel_feature_affinity_grouped(const float* feats, int B, int C, int P, int group, int member_stride, float beta, float gamma,
+                                   int mode, float* out, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ decoder head
  * SegFormerHead fuse (model/segformer_head.py:47-77: per ViT layer Linear(D,E) -> ReLU -> Linear(E,E) on the patch
  * tokens, channel concat, 1x1 conv L*E -> E) and DecoderTransformer (model/decoder/TransDecoder.py:105-124: dec_layers
@@ -380,6 +398,12 @@ int excel_ragged_plan(const int32_t* hw /*host [B,2] = (H_b, W_b)*/, int B, exce
  * (image b at byte 3 * loff_b) -> out [B,3,S,S] f32.  Same operations (same bits) as excel_normalize_img_u8 + excel_bilinear_resize. */
 int excel_normalize_resize_u8_ragged(const uint8_t* hwc, const int32_t* table, int B, int S, const double* mean3 /*host*/,
                                      const double* std3 /*host*/, float* out, void* stream);
+
+/* excel_normalize_resize_u8_ragged plus its mirror, in one pass: out [2B,3,S,S], images 0..B-1 bit-identical to
+ * excel_normalize_resize_u8_ragged, image B + b = image b mirrored along W (the flip-TTA input [x; flip x] of utils/camutils.py:15,
+ * which flips after the resize: the mirrored half is a second store of the same values, not a second resize). */
+int excel_normalize_resize_u8_ragged_mirror(const uint8_t* hwc, const int32_t* table, int B, int S, const double* mean3 /*host*/,
+                                            const double* std3 /*host*/, float* out, void* stream);
 
 /* excel_cam_upsample_bkg for a ragged batch: refined [B,Smax,P] -> cams = (Smax+1) pitched planes per image. workspace: B*Smax*P floats. */
 int excel_cam_upsample_bkg_ragged(const float* refined, const int32_t* ncls, const int32_t* table, const excel_ragged_info* info, int g,
