@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the training-free CAM + affinity + PAR hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One step = one pass of the whole path over one resident batch of synthetic 448x448 images
@@ -11,6 +11,11 @@ configuration its metric "images/sec (CAM+PAR refine, 448x448)" is quoted on.  I
 resident in HBM before the timed region.  Images are sharded across ranks (independent images, weak scaling: fixed
 per-GPU batch); the only collective is one RCCL all-gather of the [21,21] int64 confusion matrix at the end
 (inside the timed region).  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.  --full adds
+what takes runs of its own after the timed steps: the per-kernel table and the rooflines (an untimed pass with every launch
+bracketed), the CPU baseline and the label check against it, the numerics check, and the power, checkpoint-like-weights and
+ragged-harness side-lines.  The timed steps are the same in both modes.
 """
 import argparse
 import json
@@ -413,13 +418,16 @@ def main(argv=None, hooks=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step (BASELINE configs[2]: 32)")
-    ap.add_argument("--cpu-images", type=int, default=64, help="upper bound of the CPU-baseline sample (stops after ~60 s of CPU work; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: per-kernel table and rooflines, CPU baseline "
+                         "and label check, numerics check, power / checkpoint-like-weights / ragged-harness side-lines")
+    ap.add_argument("--cpu-images", type=int, default=64, help="--full: upper bound of the CPU-baseline sample (stops after ~60 s of CPU work; 0 = skip)")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--no-rccl", action="store_true", help="bare N=1 launch: do not bring up the one-rank RCCL group (the matrix is then not gathered)")
-    ap.add_argument("--ragged-images", type=int, default=256, help="images of the harness_ragged side-line (0 = skip)")
-    ap.add_argument("--power-seconds", type=float, default=3.0, help="untimed loop of the step with rocm-smi power sampling (0 = skip)")
-    ap.add_argument("--fp16w-steps", type=int, default=10, help="steps of the checkpoint-like-weights side-line (weights rounded through fp16 like the "
-                    "published CLIP archive; 0 = skip; skipped with --cpu-images 0, i.e. in profiling / A-B passes)")
+    ap.add_argument("--ragged-images", type=int, default=256, help="--full: images of the harness_ragged side-line (0 = skip)")
+    ap.add_argument("--power-seconds", type=float, default=3.0, help="--full: untimed loop of the step with rocm-smi power sampling (0 = skip)")
+    ap.add_argument("--fp16w-steps", type=int, default=10, help="--full: steps of the checkpoint-like-weights side-line (weights rounded through fp16 like "
+                    "the published CLIP archive; 0 = skip; skipped with --cpu-images 0, i.e. in profiling / A-B passes)")
     ap.add_argument("--weights", choices=["seeded", "fp16"], default="seeded",
                     help="seeded (default, the headline: full-mantissa fp32 weights as in rounds 1-5) | fp16: the SAME weights rounded through IEEE "
                          "half like the published CLIP archive - the model then starts in f16x2; for profiling that path under rocprofv3 "
@@ -521,6 +529,7 @@ def main(argv=None, hooks=None):
     dom_cat = "gemm_bf16x3" if gmode in ("bf16x3", "f16x3", "f16x2") else "gemm_nt"
     if timing:
         # the warm-up runs with the same event bracketing as the timed region, so nothing is used for the first time inside it
+        # (a plain run brackets too and reports nothing from it: its timed steps are the same as those of a --full run)
         ops.prof_enable(True, categories=[dom_cat, "par_iterate"], every=PROF_EVERY)
     for i in range(args.warmup):
         pipe.run_batch(*batches[i % n_batches])
@@ -568,10 +577,11 @@ def main(argv=None, hooks=None):
         dumped = dump_outputs(args.dump_outputs, labels.cpu().numpy(), total.cpu().numpy())
     del labels
     host_steps = host_marks
-    prof = None
+    prof = prof_all = None
     if timing:
         ops.prof_enable(False)
         prof = ops.prof_collect()
+    if timing and args.full:
         # per-kernel time table: a second, untimed pass of the same steps with every category bracketed, on ONE stream
         # (whole batch per launch) so the per-kernel times are not inflated by a concurrently running sub-batch
         ops.prof_enable(True, every=1)
@@ -623,7 +633,7 @@ def main(argv=None, hooks=None):
         }
         if dumped:
             out["dump_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
-        if prof:
+        if prof_all is not None:
             steps = args.steps
             ms = {k: v["ms"] / steps for k, v in prof_all.items() if v["launches"]}
             mode, cat = gmode, dom_cat
@@ -748,7 +758,9 @@ def main(argv=None, hooks=None):
                     "note": "bound: 97 % of these flops are the projection GEMM (198 tiles on 256 CUs: 77 % of one round); the similarity part is HBM / "
                             "latency-bound (arithmetic intensity ~45 flop/B, SURVEY 8d; x_raw is read twice: norm pass + similarity pass); ln_post is timed under 'layernorm'"}
             out["kernel_ms_per_step"] = {k: round(v, 4) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])}
-        if on_gpu and world == 1 and args.cpu_images > 0:
+        # single-GPU side-lines and checks after the timed steps: --full only
+        sidelines = on_gpu and world == 1 and args.full
+        if sidelines and args.cpu_images > 0:
             ncpu = min(args.cpu_images, n_batches * B)
             sd_cpu = None
             if args.weights == "fp16":           # the checker runs on the weights the GPU ran on
@@ -768,17 +780,17 @@ def main(argv=None, hooks=None):
             out["verify"] = {"images": len(agree), "pixels": px, "label_agreement_mean": round(float(np.mean(agree)), 6),
                              "label_agreement_min": round(float(np.min(agree)), 6),
                              "checker": "oracle (CPU port) labels of the same images; bf16x3 vs exact fp32 differ only where a CAM lies on a uint8 / box threshold"}
-        if on_gpu and world == 1:
+        if sidelines:
             # the guard a user runs on his own weights (ExCEL_model.check_numerics): the default bf16x3 mode against exact fp32 on four of the
             # benchmark's images - CAM max-abs difference (gate 1e-3; infer_lam falls back to exact fp32 above 5e-4)
             out["numerics_check"] = model.check_numerics(batches[0][0][:4], fallback=False)
-        if on_gpu and world == 1 and args.power_seconds > 0:
+        if sidelines and args.power_seconds > 0:
             out["power"] = power_sideline(pipe, batches[0], args.power_seconds, B)
-        if on_gpu and world == 1 and args.fp16w_steps > 0 and args.cpu_images > 0:
+        if sidelines and args.fp16w_steps > 0 and args.cpu_images > 0:
             out["checkpoint_like_weights"] = fp16_valued_weights_sideline(args, device, batches, args.fp16w_steps,
                                                                           cpu_threads=out["cpu_baseline"]["threads_used"])
 
-        if on_gpu and world == 1 and args.ragged_images > 0:
+        if sidelines and args.ragged_images > 0:
             gc.collect()
             gc.freeze()                                             # as infer_lam.validate does: later collections skip the start-up heap
             out["harness_ragged"] = harness_ragged(model, device, n_images=args.ragged_images, batch=B)

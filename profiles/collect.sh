@@ -3,7 +3,7 @@
 # occupancy/busy PMC passes.  Usage: [BENCH_ARGS="--weights fp16"] bash profiles/collect.sh <tag> [git head]     -> gpurun_out/<tag>/...   (copy what should be judged to profiles/)
 # BENCH_ARGS: extra bench.py arguments of every pass (round 6: "--weights fp16" profiles the f16x2 step on checkpoint-like weights)
 set -u
-BENCH_ARGS=${BENCH_ARGS:-}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"      # every pass is the whole benchmark: the line with its rooflines and side-lines, the kernels they run
 TAG=${1:-prof}
 HEAD=${2:-unknown}
 OUT=$PWD/gpurun_out/$TAG

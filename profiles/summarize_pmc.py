@@ -37,7 +37,7 @@ def source_stamp(head):
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     from bench import csrc_sha16
     return {"head": head, "date": datetime.datetime.utcnow().strftime("%Y-%m-%dT%H:%MZ"), "csrc_sha16": csrc_sha16(),
-            "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python bench.py --steps 2 --warmup 1 --cpu-images 0 --ragged-images 0"}
+            "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python bench.py --full --steps 2 --warmup 1 --cpu-images 0 --ragged-images 0"}
 
 
 def main(fetch_csv, write_csv, head=None):

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 REPO=$PWD; OUT=$PWD/gpurun_out/pmc_$2; mkdir -p $OUT
 cd /tmp
-rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $OUT -o p -- python $REPO/bench.py --steps 2 --warmup 1 --cpu-images 0 --no-kernel-timing > /dev/null 2> $OUT/err.txt
+rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $OUT -o p -- python $REPO/bench.py --full --steps 2 --warmup 1 --cpu-images 0 --no-kernel-timing > /dev/null 2> $OUT/err.txt
 python - > $OUT/summary.txt <<PY
 import csv, collections, glob
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(collections.Counter)
