@@ -150,6 +150,7 @@ SIGNATURES = {
     "excel_seg_msc_fuse_ragged": (c_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i, c_i, c_f, C.POINTER(RaggedInfo),
                                         c_f, c_f, c_f]),
     "excel_seg_resize_argmax_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f]),
+    "excel_seg_resize_argmax_uniform": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_f, c_f]),
     "excel_seg_softmax_resize": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "excel_cam_overlay_ragged": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f, c_f]),
     "excel_cam_overlay": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f]),

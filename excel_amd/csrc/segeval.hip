@@ -6,6 +6,7 @@
 //                           result is the same bits; optional pitched logits planes and/or tight arg-max labels
 //   seg_resize_argmax_ragged pitched planes of one plan -> bilinear to the sizes of a second plan -> arg-max -> tight labels; the
 //                           resized nc-class logits never reach memory (bilinear_resize_kernel + argmax_key, same bits)
+//   seg_resize_argmax_uniform the same kernel with a tight uniform [B, nc, h, w] source (the decoder's seg logits of one batch)
 //   seg_softmax_resize      one image's pitched planes -> (bilinear to (H, W)) -> softmax over classes -> tight [nc,H,W]: the CRF's input
 //
 // All three are gather-bound: the sources are small (2B * nc * g^2 floats per scale, L2-resident) and each output pixel reads 4 (8 with
@@ -121,16 +122,26 @@ __global__ __launch_bounds__(256) void seg_msc_fuse_ragged_kernel(SegScales sc, 
 }
 
 // Tiles of the DESTINATION plan; one lane per column, four rows per lane (argmax_label_ragged_kernel's shape).  The source image b is
-// read through the source plan's record b.  Per pixel: bilinear_tap once, then bilinear_blend + running arg-max over the classes.
-__global__ __launch_bounds__(256) void seg_resize_argmax_ragged_kernel(const float* __restrict__ src, const int* __restrict__ src_tab, int nc,
+// read through `sg`: with a table, record b of the source plan (pitched planes); without one (sg.tab == nullptr), image b of a TIGHT
+// uniform [B, nc, sg.H, sg.W] tensor - the decoder's seg logits as they are, whatever g is (TileGeo's uniform convention, Wp = W).
+// Per pixel: bilinear_tap once, then bilinear_blend + running arg-max over the classes.
+__global__ __launch_bounds__(256) void seg_resize_argmax_ragged_kernel(const float* __restrict__ src, TileGeo sg, int nc,
                                                                        TileGeo dst, unsigned char* __restrict__ labels) {
     const Tile t = tile_of<true>(dst);
     const int x = t.x0 + (threadIdx.x & 63);
     if (x >= t.W) return;
-    const int* rec = src_tab + EXCEL_RAG_REC * t.b;
-    const int h = rec[0], w = rec[1], wp = (w + 3) & ~3;
+    int h, w, wp;
+    long long off;
+    if (sg.tab) {
+        const int* rec = sg.tab + EXCEL_RAG_REC * t.b;
+        h = rec[0]; w = rec[1]; wp = (w + 3) & ~3;
+        off = rec[2];
+    } else {
+        h = sg.H; w = sg.W; wp = w;
+        off = (long long)t.b * h * w;
+    }
     const long long hw = (long long)h * wp;
-    const float* base = src + (long long)nc * rec[2];
+    const float* base = src + (long long)nc * off;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int y = t.y0 + (threadIdx.x >> 6) + 4 * r;
@@ -214,8 +225,26 @@ extern "C" int excel_seg_resize_argmax_ragged(const float* planes, const int32_t
     if (dst_info->total_tiles == 0) return EXCEL_OK;
     TileGeo dst;
     dst.tab = dst_table; dst.B = dst_info->B; dst.H = dst.W = 0;
-    hipLaunchKernelGGL(seg_resize_argmax_ragged_kernel, dim3(dst_info->total_tiles), dim3(256), 0, ST(stream), planes, src_table, nc, dst, labels_u8);
+    TileGeo src;
+    src.tab = src_table; src.B = src_info->B; src.H = src.W = 0;
+    hipLaunchKernelGGL(seg_resize_argmax_ragged_kernel, dim3(dst_info->total_tiles), dim3(256), 0, ST(stream), planes, src, nc, dst, labels_u8);
     EXCEL_CHECK_LAUNCH("seg_resize_argmax_ragged");
+    return EXCEL_OK;
+}
+
+extern "C" int excel_seg_resize_argmax_uniform(const float* segs, int B, int h, int w, int nc, const int32_t* dst_table,
+                                               const excel_ragged_info* dst_info, uint8_t* labels_u8, void* stream) {
+    EXCEL_CHECK_ARG(segs && dst_table && dst_info && labels_u8, "seg_resize_argmax_uniform: null argument");
+    EXCEL_CHECK_ARG(nc >= 1 && nc <= 256, "seg_resize_argmax_uniform: need 1 <= nc <= 256 (nc = %d)", nc);
+    EXCEL_CHECK_ARG(h >= 1 && w >= 1, "seg_resize_argmax_uniform: source planes of %d x %d", h, w);
+    EXCEL_CHECK_ARG(B == dst_info->B && B >= 1, "seg_resize_argmax_uniform: %d source images, the plan holds %d", B, dst_info->B);
+    EXCEL_CHECK_ARG((long long)B * nc * h * w <= kI32, "seg_resize_argmax_uniform: B * nc * h * w must stay below 2^31");
+    if (dst_info->total_tiles == 0) return EXCEL_OK;
+    TileGeo src, dst;
+    src.tab = nullptr; src.B = B; src.H = h; src.W = w;
+    dst.tab = dst_table; dst.B = dst_info->B; dst.H = dst.W = 0;
+    hipLaunchKernelGGL(seg_resize_argmax_ragged_kernel, dim3(dst_info->total_tiles), dim3(256), 0, ST(stream), segs, src, nc, dst, labels_u8);
+    EXCEL_CHECK_LAUNCH("seg_resize_argmax_uniform");
     return EXCEL_OK;
 }
 

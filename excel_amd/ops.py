@@ -588,6 +588,20 @@ def seg_resize_argmax_ragged(planes, src_plan, dst_plan, nc):
     return lab
 
 
+def seg_resize_argmax_uniform(segs, dst_plan):
+    """engine/validatation_engine.py:27,37 for a ragged batch: the decoder's seg logits segs [B,nc,h,w] (tight, any h, w) -> bilinear to
+    every image's label size (dst_plan) -> arg-max -> tight uint8 labels, one launch (excel_seg_resize_argmax_uniform; the bits of
+    bilinear_resize + argmax_label per image)."""
+    segs = f32c(segs)
+    if segs.dim() != 4 or segs.shape[0] != dst_plan.B:
+        raise ValueError(f"seg_resize_argmax_uniform: segs must be [B={dst_plan.B}, nc, h, w], got {tuple(segs.shape)}")
+    B, nc, h, w = segs.shape
+    lab = torch.empty((dst_plan.total_label_pix,), dtype=torch.uint8, device=segs.device)
+    check(lib().excel_seg_resize_argmax_uniform(_p(segs), int(B), int(h), int(w), int(nc), _p(dst_plan.table, torch.int32),
+                                                C.byref(dst_plan.info), _p(lab, torch.uint8), _stream()), "excel_seg_resize_argmax_uniform")
+    return lab
+
+
 def seg_softmax_resize(planes, plan, b, nc, H, W):
     """The CRF's input for image b of a packed nc-plane pitched tensor (tools/infer_seg_voc.py:146-147, coco :144-145): bilinear to
     (H, W) (skipped at the same size), softmax over classes -> tight [nc, H, W] (excel_seg_softmax_resize)."""

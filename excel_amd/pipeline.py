@@ -271,3 +271,55 @@ class OptimisedLamPipeline(TrainingFreePipeline):
         refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # infer_lam.py:93
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
                                       dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred))
+
+
+class ValidationPipeline(TrainingFreePipeline):
+    """The in-training validation pass (engine/validatation_engine.py:19-37) for a ragged batch of B images at once, on the training-free
+    pipeline's ragged back half.  Per image, both confusion matrices equal the reference's per-image call sequence bit for bit:
+
+        model(x, n_attn_out=6)                      -> attr maps, per-layer maps, attn_fts, seg logits, attn_pred = affinity of x alone
+        refine_cams_with_aff(seg_attn=attn_pred)    -> gated affinity (affutils.py:182-195), random walk at caa_thre 0.75 (:33)
+        refine_cams_with_bkg_weclip                 -> up-sampling, PAR, arg-max at the image's own size   -> `self.hist`     (:34-36)
+        bilinear(seg, label size) + argmax(1)       -> seg prediction at the image's own size             -> `self.hist_seg` (:27, :37)
+
+    One tower forward per batch with model(x, n_attn_out=6)'s flags.  The model's own attn_pred takes its mean over the whole batch tensor
+    (= the reference only at batch 1); here it is the grouped entry with group 1, the per-image affinity.  The seg logits [B,nc,g,g] go to
+    every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
+
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6):
+        if getattr(model, "_dec", None) is None:
+            raise ValueError("ValidationPipeline needs the decoder head: build ExCEL_model(..., decoder_state_dict=)")
+        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax)
+        self.attn_layers = attn_layers
+        self.hist_seg = None
+
+    def reset(self):
+        super().reset()
+        self.hist_seg = None
+
+    @torch.no_grad()
+    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=320, return_intermediates=False):
+        """Same contract as TrainingFreePipeline.run_batch_ragged (flat uint8 pseudo labels, self.hist, self.last_cams, intermediates);
+        with ground truth it also accumulates the seg prediction's confusion matrix into self.hist_seg.  The intermediates add
+        attn_pred [B,P,P], seg [B,nc,g,g] and seg_labels (flat uint8, image b = plan.label(seg_labels, b))."""
+        dev = hwc_packed.device
+        B = plan.B
+        g = S // 16
+        model = self.model
+        h = model.encoder.visual.handle()
+        inputs = ops.normalize_resize_u8_ragged(hwc_packed, plan, S, out=self._buf("inputs", B * 3 * S * S, device=dev).view(B, 3, S, S))  # :20
+        r = model.encoder.encode_image(inputs, True, None, want_w_aff=True, aff_layers=6, n_attn_out=6, want_feats=True,
+                                       feats_as_reference=True, want_raw=True, want_features=False)                   # :25 (model_excel.py:55-58)
+        attr = ops.patch_text_cam(r["x_raw"], model._text_rows, num_fg=model.num_classes - 1, mode=h.gemm_mode())[1]  # model_excel.py:58
+        fts, seg = model._dec.forward(r["feats"])                                                   # model_excel.py:60-68
+        attn_pred = ops.feature_affinity_grouped(fts, "sigmoid", group=1)                            # :70-76, batch 1 per image
+        del fts
+        w_aff = ops.attn_select_mean(r["attn"], attn_pred, self.attn_layers)                         # affutils.py:182-195
+        del r
+        seg_labels = ops.seg_resize_argmax_uniform(seg, plan)                                        # :27, :37
+        if gts_packed is not None:
+            self.hist_seg = ops.confusion_accumulate(gts_packed, seg_labels, self.num_classes, self.hist_seg)
+        idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
+        refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # :33
+        return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
+                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred, seg=seg, seg_labels=seg_labels))   # :34-36

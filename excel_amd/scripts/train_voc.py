@@ -10,7 +10,9 @@ DecoderTrainer.train_step is one iteration, the loop body of :172-220:
 All tensor work runs in libexcel_hip.so; torch carries device memory and the one collective.  The data path of `train`: decode
 threads read the VOC tree (datasets/voc.VOC12ClsDataset) and draw each sample's augmentation parameters on the host, a copy stream
 stages the ragged batch and the transform's table (datasets/loader.DeviceFeeder), and ops.train_augment applies the reference's
-training transform on the device.  TensorBoard grids are not written.
+training transform on the device.  The validation pass every --eval_iters runs on ragged batches split across the ranks
+(engine/validatation_engine.build_validation_ragged: its own decode threads and copy stream, the same confusion matrices as the reference's
+per-image loop, which --val_api_path true runs instead).  TensorBoard grids are not written.
 
   python -m excel_amd.scripts.train_voc --data_folder VOC2012 --list_folder datasets/voc --model ViT-B-16.pt --bpe_path ... \
       [--crop_size 320 --spg 4 --max_iters 30000]
@@ -143,6 +145,10 @@ def get_parser():
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--num_workers", default=8, type=int, help="decode threads per rank")
     p.add_argument("--backend", default="nccl")
+    p.add_argument("--val_batch_size", default=16, type=int, help="images per ragged batch of the validation pass")
+    p.add_argument("--val_api_path", default=False, type=_bool,
+                   help="validate with the reference's per-image loop (build_validation) on every rank instead of the batched pass split "
+                        "across ranks (build_validation_ragged)")
     # model arguments of tools/infer_lam.py
     p.add_argument("--clip_root", default=None, type=str)
     p.add_argument("--bpe_path", default=None, type=str)
@@ -216,9 +222,9 @@ VOC = TrainVariant()
 def train(args, model=None, variant=VOC):
     """scripts/train_voc.py:train (scripts/train_coco.py:train with variant=train_coco.COCO).  `model`: an ExCEL_model with a decoder
     head (tests inject a small one); default: built from --model with the head at its initial weights.
-    -> dict(history=[per-iteration losses], tables=[validation tables], ckpts=[paths])."""
+    -> dict(history=[per-iteration losses], tables=[validation tables], ckpts=[paths], val_seconds=[wall seconds of each validation pass])."""
     from ..datasets import loader
-    from ..engine.validatation_engine import build_validation
+    from ..engine.validatation_engine import build_validation, build_validation_ragged
     from ..utils.PAR import PAR
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
@@ -243,7 +249,7 @@ def train(args, model=None, variant=VOC):
     feeder = loader.DeviceFeeder(batches, device, aug_crop_size=args.crop_size)
     class_list = variant.class_list(args)
     first_ckpt = variant.first_ckpt_iter(args)
-    history, tables, ckpts, meter = [], [], [], []
+    history, tables, ckpts, meter, val_seconds = [], [], [], [], []
     loss_log = open(os.path.join(args.work_dir, "losses.txt"), "w") if rank == 0 else None
     it = iter(feeder)
     try:
@@ -272,17 +278,27 @@ def train(args, model=None, variant=VOC):
                         torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
                         ckpts.append(path)
                 # the reference resizes to a fixed 320 (engine/validatation_engine.py:20) = its default crop; here: the crop size
-                table = build_validation(model=model, par=par, val_loader=_val_batches(val_dataset, device), device=device,
-                                         num_classes=args.num_classes, resize_size=args.crop_size, class_list=class_list)[0]
+                t_val = time.time()
+                if args.val_api_path:       # the reference's loop: every rank validates the whole list, one image at a time
+                    table = build_validation(model=model, par=par, val_loader=_val_batches(val_dataset, device), device=device,
+                                             num_classes=args.num_classes, resize_size=args.crop_size, class_list=class_list)[0]
+                else:                       # ragged batches, images r, r+R, ... on rank r, the matrices all-gathered once
+                    table = build_validation_ragged(model=model, par=par, dataset=val_dataset, device=device, num_classes=args.num_classes,
+                                                    resize_size=args.crop_size, class_list=class_list, batch_size=args.val_batch_size,
+                                                    num_workers=args.num_workers, rank=rank, world=world, group=None)[0]
+                torch.cuda.synchronize(device)
+                val_seconds.append(time.time() - t_val)
                 tables.append(table)
                 if rank == 0:
                     logging.info("\n" + table)
+                    logging.info("Validation: %d images in %.2f s (%s)" % (len(val_dataset), val_seconds[-1],
+                                                                           "per image" if args.val_api_path else f"{world} rank(s), batches of {args.val_batch_size}"))
     finally:
         it.close()                      # records the last batch's event, then DeviceFeeder.close waits for it and stops the stager
         feeder.close()
         if loss_log is not None:
             loss_log.close()
-    return dict(history=history, tables=tables, ckpts=ckpts)
+    return dict(history=history, tables=tables, ckpts=ckpts, val_seconds=val_seconds)
 
 
 if __name__ == "__main__":

@@ -450,6 +450,13 @@ int excel_seg_msc_fuse_ragged(const float* const* segs /*host [ns]*/, const int3
 int excel_seg_resize_argmax_ragged(const float* planes, const int32_t* src_table, const excel_ragged_info* src_info, const int32_t* dst_table,
                                    const excel_ragged_info* dst_info, int nc, uint8_t* labels_u8, void* stream);
 
+/* excel_seg_resize_argmax_ragged from a TIGHT uniform source: segs = [B, nc, h, w] f32 (the decoder's seg logits of one batch, any h, w;
+ * no row padding) -> tight uint8 arg-max labels at the sizes of (dst_table, dst_info), B images.  The in-training validation's seg
+ * prediction (engine/validatation_engine.py:27,37: F.interpolate to labels.shape, argmax(1)) for a ragged batch in one launch.  Same
+ * kernel, same bits as excel_bilinear_resize + excel_argmax_label per image. */
+int excel_seg_resize_argmax_uniform(const float* segs, int B, int h, int w, int nc, const int32_t* dst_table, const excel_ragged_info* dst_info,
+                                    uint8_t* labels_u8, void* stream);
+
 /* The DenseCRF's input for ONE image (tools/infer_seg_voc.py:146-147 softmax(logit); tools/infer_seg_coco.py:144-145 F.interpolate to
  * (H, W) then softmax): planes = nc pitched planes (row pitch w rounded up to 4 floats) at (h, w) -> prob tight [nc, H, W], the layout
  * excel_dcrf_inference takes.  (h, w) == (H, W) skips the resize. */
