@@ -208,6 +208,18 @@ extern "C" int excel_gemm_f16x2(const void* A_split, const void* W_split, const 
     return excel_f16::excel_launch_gemm_bf16x3(g, ST(stream));
 }
 
+extern "C" int excel_gemm_plan(int M, int N, int K, int batch, int out_mode, int has_residual, int gemm_mode, int has_half, int n_cu, int32_t* plan) {
+    EXCEL_CHECK_ARG(plan && M > 0 && N > 0 && K > 0 && batch >= 1 && out_mode >= GEMM_OUT_PLAIN && out_mode <= GEMM_OUT_SPLIT_BF16 &&
+                    gemm_mode >= 1 && gemm_mode <= 3 && n_cu >= 1, "gemm_plan: bad argument");
+    // the arguments excel_gemm_bf16x3 / _f16x3 / _f16x2 (gemm_bf_args) and the ViT's linear layers build: dense rows, head dim 64
+    const GemmShape s = {M, N, K, 2 * K, 2 * K, N, N, out_mode == GEMM_OUT_QKV_HEADMAJOR ? 64 : 0, out_mode, has_residual != 0, batch,
+                         gemm_mode >= 2, gemm_mode == 3, gemm_half_ok(has_half != 0, N, K, K)};
+    const GemmPlan p = gemm_plan(s, n_cu);
+    const int v[EXCEL_GEMM_PLAN_INTS] = {p.kernel, p.tile, p.nt_m, p.x2, p.tall, p.shrt, p.second, p.grid_x, p.grid_y, p.block};
+    for (int i = 0; i < EXCEL_GEMM_PLAN_INTS; ++i) plan[i] = v[i];
+    return EXCEL_OK;
+}
+
 extern "C" int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream) {
     return excel_launch_layernorm(x, nullptr, 1, w, b, y, rows, D, eps, ST(stream));
 }

@@ -51,6 +51,30 @@ struct GemmBfArgs {
     int ldbh;
 };
 
+// Kernel selection of the split-plane GEMM (gemm_plan.hip): a problem as integers and flags -> the instance and grid it runs on
+struct GemmShape {
+    int M, N, K, lda, ldb, ldc, ldr, hd, out_mode, has_residual, batch;
+    int f16;         // IEEE-half split planes (namespace excel_f16): the two-product kernels exist
+    int w_lo_zero;   // GemmBfArgs::w_lo_zero
+    int half_ok;     // the compact half weights are usable (gemm_half_ok)
+};
+enum { GEMM_8WAVE = 0, GEMM_8WAVE_MIXED = 1, GEMM_W4 = 2, GEMM_W4_MIX = 3 };
+struct GemmPlan {
+    int kernel;                // GEMM_8WAVE: uniform tiles of gemm_bf16x3.hip; GEMM_8WAVE_MIXED: its 320- / 256-row mixed-height tiles;
+                               // GEMM_W4: one four-wave instance (gemm_w4.hip, gemm_w4x2.hip); GEMM_W4_MIX: a launch of two of them
+    int tile;                  // 8-wave tile: 0 128x128, 1 256x128, 2 256x256, 3 320x256
+    int nt_m;                  // GEMM_W4: 10 / 8 / 5 = 320- / 256- / 160-row tiles
+    int x2;                    // two-product kernel: 1 weights in the split layout, 2 as the plain half matrix GemmBfArgs::Bh
+    int tall, shrt, second;    // mixed / two-instance launches: row tiles of 320 rows, then of the short height (GEMM_W4_MIX: instance 8 / 5)
+    int grid_x, grid_y, block;
+};
+constexpr int GEMM_W4_BN = 256;          // columns of a four-wave tile (w4::BN, gemm_w4_body.inc)
+GemmPlan gemm_plan(const GemmShape& s, int n_cu);
+// the plain half matrix of the weights, [N][ldbh] at a 16-byte aligned address, can feed the compact-weight four-wave instances
+inline bool gemm_half_ok(bool aligned, int N, int K, int ldbh) {
+    return aligned && ldbh >= K && (ldbh & 7) == 0 && (long long)N * ldbh * 2 < 0x7fffffffLL;
+}
+
 
 int excel_launch_trans_mat_sym(const float* W, float* T, float* Tsym, float* cs, int B, int P, hipStream_t st);
 int excel_launch_cls_compact(const float* onehot, int B, int F, int Smax, int* cls_idx, int* ncls, int* nchan, hipStream_t st);

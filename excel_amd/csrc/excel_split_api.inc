@@ -3,16 +3,10 @@
 // namespace excel_f16 - the six files are compiled once per type (build.py), everything in them lives in the matching namespace.
 int excel_launch_gemm(const GemmArgs& p, bool b_kmajor, int batch, hipStream_t stream);
 int excel_launch_gemm_bf16x3(const GemmBfArgs& p, hipStream_t stream);
-// the 320 x 256 tile on four waves with a hand-placed k-loop (gemm_w4.hip); excel_launch_gemm_bf16x3 routes to it when it applies
-bool excel_gemm_w4_supported(const GemmBfArgs& p, int nt_m, int x2);    // nt_m = 10 / 8 / 5: 320- / 256- / 160-row tiles; x2: 0 three-product, 1 / 2 two-product instances
-double excel_gemm_w4_model_us(const GemmBfArgs& p, int nt_m, int n_cu, int x2);
-int excel_launch_gemm_w4(const GemmBfArgs& p, int nt_m, hipStream_t stream);
-// a launch made of two instances: `tall` row tiles of 320 rows, then `shrt` row tiles of the `second` (8 / 5) instance
-double excel_gemm_w4_mix_model_us(const GemmBfArgs& p, int n_cu, int x2, int* tall, int* shrt, int* second);
-int excel_launch_gemm_w4_mix(const GemmBfArgs& p, int tall, int shrt, int second, hipStream_t stream);
-int excel_launch_gemm_w4x2_mix(const GemmBfArgs& p, int tall, int shrt, int second, hipStream_t stream);      // (IEEE-half split type only)
-// two MFMAs per product for fp16-valued weights (gemm_w4x2.hip; defined for the IEEE-half split type only)
-int excel_launch_gemm_w4x2(const GemmBfArgs& p, int nt_m, int x2, hipStream_t stream);
+// the four-wave kernels (gemm_w4.hip; gemm_w4x2.hip, IEEE-half split type only: two MFMAs per product for fp16-valued weights) launching a
+// GEMM_W4 / GEMM_W4_MIX plan of gemm_plan(); excel_launch_gemm_bf16x3 routes to them
+int excel_launch_gemm_w4(const GemmBfArgs& p, const GemmPlan& plan, hipStream_t stream);
+int excel_launch_gemm_w4x2(const GemmBfArgs& p, const GemmPlan& plan, hipStream_t stream);
 // fp32 [R,K] -> plain 16-bit hi plane [R,K] (the two-product GEMM's compact weight operand) + the number of elements whose lo plane is
 // not zero, added to *inexact (device counter; 0 <=> every value is representable in the 16-bit type)
 int excel_launch_pack_hi(const float* in, void* out, long long R, int K, unsigned long long* inexact, hipStream_t st);

@@ -22,6 +22,7 @@
 // (global_load_lds_dwordx4, XOR-swizzled 128-B rows: conflict-free ds_read_b128), XCD-aware tile order; per 32-k stage a wave of the
 // 128 x 128 tile does 16 ds_read_b128 and 48 MFMAs (16 x 16 x 32).
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 #include "excel_internal.h"
 
@@ -504,6 +505,16 @@ int excel_launch_vt_from_planes(const unsigned short* qkvs, unsigned short* vt, 
 }
 
 
+// CUs of the current device, queried once (the GEMM plan's rounds of tiles)
+static int device_cu_count() {
+    static int n_cu = 0;
+    if (!n_cu) {
+        int dev = 0; hipDeviceProp_t prop;
+        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+    }
+    return n_cu;
+}
+
 int excel_launch_gemm_bf16x3(const GemmBfArgs& p_in, hipStream_t stream) {
     GemmBfArgs p = p_in;
 #ifdef EXCEL_DEV
@@ -514,157 +525,34 @@ int excel_launch_gemm_bf16x3(const GemmBfArgs& p_in, hipStream_t stream) {
     EXCEL_CHECK_ARG(p.out_mode != GEMM_OUT_SPLIT_BF16 || (p.N % 32) == 0, "gemm_bf16x3: split output needs N %% 32 == 0");
     EXCEL_CHECK_ARG((p.lda % 8) == 0 && (p.ldb % 8) == 0 && p.lda >= 2 * p.K && p.ldb >= 2 * p.K, "gemm_bf16x3: bad lda/ldb");
     EXCEL_CHECK_ARG((((uintptr_t)p.A | (uintptr_t)p.B) & 15) == 0, "gemm_bf16x3: operands must be 16-byte aligned");
-#ifdef EXCEL_DEV
-    static const char* force = getenv("EXCEL_BF_TILE");      // dev knob: "128" | "256x128" | "256" | "320"
-    static const bool force_uniform = getenv("EXCEL_BF_UNIFORM") != nullptr;   // dev knob: no mixed-height tiles
-#else
-    const char* const force = nullptr;
-    const bool force_uniform = false;
-#endif
-    int kind;   // 0: 128x128, 1: 256x128, 2: 256x256, 3: 320x256
-    if (force) kind = !strcmp(force, "320") ? 3 : !strcmp(force, "256") ? 2 : (!strcmp(force, "256x128") ? 1 : 0);
-    else if (p.M < 2048 || (p.batch > 1)) kind = 0;
-    else {
-        // The big tiles run one workgroup per CU, so a launch is ceil(tiles / 256) rounds and the last round is mostly
-        // idle unless the tile count lands just under a multiple of the CU count (25120 x 768: 594 tiles of 256x128 =
-        // 2.3 rounds -> 77 % busy; 237 tiles of 320x256 = 0.93 rounds -> 93 %).  Pick the tile with the best
-        // busy fraction x intrinsic efficiency (bytes staged per flop: measured 1.0 / 0.97 / 0.88 / 0.80).
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0; hipDeviceProp_t prop;
-            n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        }
-        const int bm[4] = {128, 256, 256, 320}, bn[4] = {128, 128, 256, 256}, wg_per_cu[4] = {2, 1, 1, 1};
-        const double intrinsic[4] = {0.80, 0.88, 0.97, 1.0};
-        double best = -1.0;
-        kind = 3;
-        for (int k = 0; k < 4; ++k) {
-            const long long tiles = (long long)cdiv(p.M, bm[k]) * cdiv(p.N, bn[k]), slots = (long long)n_cu * wg_per_cu[k];
-            const long long rounds = (tiles + slots - 1) / slots;
-            const double busy = ((double)p.M * p.N) / ((double)rounds * slots * bm[k] * bn[k]);
-            if (busy * intrinsic[k] > best) { best = busy * intrinsic[k]; kind = k; }
-        }
-    }
-    const int nb = p.batch > 1 ? p.batch : 1;
-#ifdef EXCEL_DEV
-    static const bool no_w4 = getenv("EXCEL_BF_W4") && atoi(getenv("EXCEL_BF_W4")) == 0;       // dev knob: the 8-wave kernel for A/B runs
-#else
-    const bool no_w4 = false;
-#endif
-    // The four-wave kernel with the hand-placed k-loop (gemm_w4.hip) in its 320- / 256- / 160-row instance, whenever its preconditions
-    // hold and its modelled launch time beats the best 8-wave tile's.  8-wave model: algorithmic flops over (tile fill x intrinsic
-    // efficiency) x the 320 x 256 tile's measured rate at full fill (345 TFLOP/s fp32-equivalent at K = 768, 400 at K = 3072).
-    bool w4_mode_ok = true;
-#ifdef EXCEL_DEV
-    { static const char* e = getenv("EXCEL_W4_MODES"); if (e) w4_mode_ok = (atoi(e) >> p.out_mode) & 1; }     // dev knob: bit per output mode (plain 1, qkv 2, split 4)
-    { static const char* e = getenv("EXCEL_W4_RES"); if (e && atoi(e) == 0 && p.res) w4_mode_ok = false; }      // dev knob: 0 = residual launches stay on the 8-wave kernel
-#endif
+    const GemmShape s = {p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.ldr, p.hd, p.out_mode, p.res != nullptr, p.batch,
+                         std::is_same<split_t, _Float16>::value, p.w_lo_zero,
+                         gemm_half_ok(p.Bh && ((uintptr_t)p.Bh & 15) == 0, p.N, p.K, p.ldbh)};
+    const GemmPlan plan = gemm_plan(s, device_cu_count());
+    const dim3 grid(plan.grid_x, plan.grid_y), block(plan.block);
 #ifdef EXCEL_SPLIT_F16
-    const bool want_x2 = p.w_lo_zero != 0;          // fp16-valued weights: two-product kernels
-#else
-    const bool want_x2 = false;                     // (a bf16 hi plane cannot hold an fp16 value: the flag means nothing here)
-#endif
-    int x2_force = -1;
-#ifdef EXCEL_DEV
-    { static const char* e = getenv("EXCEL_W4_X2"); if (e) x2_force = atoi(e); }        // dev knob: 0 = three-product kernels, 1 = split-layout weights only
-#endif
-    const bool x2_on = want_x2 && x2_force != 0;
-    if (!no_w4 && w4_mode_ok && nb == 1 && p.M >= 2048) {
-        static int n_cu3 = 0;
-        if (!n_cu3) {
-            int dev = 0; hipDeviceProp_t prop;
-            n_cu3 = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        }
-        int force_ntm = 0;
-#ifdef EXCEL_DEV
-        { static const char* e = getenv("EXCEL_W4_NTM"); if (e) force_ntm = atoi(e); }       // dev knob: 10 / 8 / 5, -1 = model only
-        if (force && !strcmp(force, "320")) force_ntm = 10;
-#endif
-        const int bm8[4] = {128, 256, 256, 320}, bn8[4] = {128, 128, 256, 256}, wg8[4] = {2, 1, 1, 1};
-        const double in8[4] = {0.80, 0.88, 0.97, 1.0};
-        const long long tiles8 = (long long)cdiv(p.M, bm8[kind]) * cdiv(p.N, bn8[kind]), slots8 = (long long)n_cu3 * wg8[kind];
-        const double busy8 = ((double)p.M * p.N) / ((double)((tiles8 + slots8 - 1) / slots8) * slots8 * bm8[kind] * bn8[kind]);
-        const double kfac = p.K <= 768 ? 0.0 : (p.K >= 3072 ? 1.0 : (p.K - 768) / 2304.0);
-        // (advisor, round 5: a forced 8-wave tile - "128" / "256x128" / "256" - must reach the 8-wave kernel: only "320" or no force routes here)
-        const bool force8 = force && strcmp(force, "320") != 0;
-        double best_us = force ? 1e30 : 2.0 * p.M * (double)p.N * p.K / (busy8 * in8[kind] * (345.0 + 55.0 * kfac) * (x2_on && kind != 3 ? 1.40 : 1.0) * 1e6);
-        int best_ntm = 0, best_x2 = 0;
-        const int cand[3] = {10, 8, 5};
-        for (int c = 0; c < 3 && !force8; ++c) {
-            // the compact-weight instance when the plain half matrix is there, else the split-layout one
-            const int x2 = !x2_on ? 0 : (x2_force != 1 && excel_gemm_w4_supported(p, cand[c], 2)) ? 2 : 1;
-            if (!excel_gemm_w4_supported(p, cand[c], x2)) continue;
-            if (force_ntm > 0) { if (cand[c] == force_ntm) { best_ntm = force_ntm; best_x2 = x2; } continue; }
-            const double us = excel_gemm_w4_model_us(p, cand[c], n_cu3, x2);
-            if (us < best_us) { best_us = us; best_ntm = cand[c]; best_x2 = x2; }
-        }
-        // a launch of two instances (full rounds of 320-row tiles + the rest in shorter ones) when the model prefers it by more than 1 %
-        bool mix_ok = force_ntm == 0 && !force8;
-#ifdef EXCEL_DEV
-        { static const char* e = getenv("EXCEL_W4_MIX"); if (e && atoi(e) == 0) mix_ok = false; }       // dev knob: uniform launches only
-#endif
-        if (mix_ok) {
-            const int mx2 = !x2_on ? 0 : 2;          // (the split-layout two-product form has no 320-row instance: no two-instance launch)
-            int tall = 0, shrt = 0, second = 0;
-            const double mus = (x2_on && x2_force == 1) ? 1e30 : excel_gemm_w4_mix_model_us(p, n_cu3, mx2, &tall, &shrt, &second);
-            if (mus < 0.99 * best_us) {
-#ifdef EXCEL_SPLIT_F16
-                if (mx2) return excel_launch_gemm_w4x2_mix(p, tall, shrt, second, stream);
-#endif
-                return excel_launch_gemm_w4_mix(p, tall, shrt, second, stream);
-            }
-        }
-#ifdef EXCEL_SPLIT_F16
-        if (best_ntm && best_x2) return excel_launch_gemm_w4x2(p, best_ntm, best_x2, stream);
-#endif
-        if (best_ntm) return excel_launch_gemm_w4(p, best_ntm, stream);
-    }
-    if (kind == 3 && nb == 1 && !force_uniform) {
-        // mixed-height row tiles (kernel header): R = rounds of the uniform 320-row tiling; nt = the row tiles that fit into R rounds;
-        // `tall` of them must be 320 rows high to cover M, the rest can be 256.  Worth it when the tall tiles leave room in the last round
-        // for short ones (tall * tiles_n <= (R - 1) * CUs): then no CU gets R tall tiles.
-        static int n_cu2 = 0;
-        if (!n_cu2) {
-            int dev = 0; hipDeviceProp_t prop;
-            n_cu2 = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        }
-        const int tiles_n = cdiv(p.N, 256), units = cdiv(p.M, 32);
-        const int R = cdiv(cdiv(p.M, 320) * tiles_n, n_cu2);
-        const int nt = (R * n_cu2) / tiles_n;
-        int tall = (units - 8 * nt + 1) / 2;
-        if (tall < 0) tall = 0;
-        int shrt = nt - tall;
-        while (shrt > 0 && 10 * tall + 8 * (shrt - 1) >= units) --shrt;      // no more row tiles than M needs
-        int first = 0;
-        bool one_round = false;
-#ifdef EXCEL_DEV
-        { static const char* e = getenv("EXCEL_BF_FIRST"); if (e) first = atoi(e); }
-        { static const char* e = getenv("EXCEL_BF_MIX1"); one_round = e && R == 1; }
-#endif
-        if ((R >= 2 || one_round) && shrt > 0 && tall <= nt && 10 * tall + 8 * shrt >= units && (one_round || tall * tiles_n <= (R - 1) * n_cu2)) {
-            p.mix_tall = tall; p.mix_short = shrt; p.mix_first = first;
-            hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 5, 2, true>), dim3((tall + shrt) * tiles_n, 1), dim3(512), 0, stream, p);
-            EXCEL_CHECK_LAUNCH("gemm_bf16x3");
-            return EXCEL_OK;
-        }
-    }
-#ifdef EXCEL_SPLIT_F16
-    if (x2_on && kind != 3) {        // two-product instances of the tiles that small / odd-shaped weight GEMMs land on
-        if (kind == 2) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 4, 2, false, true>), dim3(cdiv(p.M, 256) * cdiv(p.N, 256), nb), dim3(512), 0, stream, p);
-        else if (kind == 1) hipLaunchKernelGGL((gemm_bf16x3_kernel<4, 2, 2, 3, false, true>), dim3(cdiv(p.M, 256) * cdiv(p.N, 128), nb), dim3(512), 0, stream, p);
-        else hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 2, 2, 2, false, true>), dim3(cdiv(p.M, 128) * cdiv(p.N, 128), nb), dim3(256), 0, stream, p);
+    if (plan.x2) {           // fp16-valued weights: the two-product kernels
+        if (plan.kernel == GEMM_W4 || plan.kernel == GEMM_W4_MIX) return excel_launch_gemm_w4x2(p, plan, stream);
+        if (plan.tile == 2) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 4, 2, false, true>), grid, block, 0, stream, p);
+        else if (plan.tile == 1) hipLaunchKernelGGL((gemm_bf16x3_kernel<4, 2, 2, 3, false, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 2, 2, 2, false, true>), grid, block, 0, stream, p);
         EXCEL_CHECK_LAUNCH("gemm_f16x2");
         return EXCEL_OK;
     }
 #endif
-    if (kind == 3) {
-        hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 5, 2>), dim3(cdiv(p.M, 320) * cdiv(p.N, 256), nb), dim3(512), 0, stream, p);
-    } else if (kind == 2) {
-        hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 4, 2>), dim3(cdiv(p.M, 256) * cdiv(p.N, 256), nb), dim3(512), 0, stream, p);
-    } else if (kind == 1) {
-        hipLaunchKernelGGL((gemm_bf16x3_kernel<4, 2, 2, 3>), dim3(cdiv(p.M, 256) * cdiv(p.N, 128), nb), dim3(512), 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 2, 2, 2>), dim3(cdiv(p.M, 128) * cdiv(p.N, 128), nb), dim3(256), 0, stream, p);
+    switch (plan.kernel) {
+        case GEMM_W4:
+        case GEMM_W4_MIX:
+            return excel_launch_gemm_w4(p, plan, stream);
+        case GEMM_8WAVE_MIXED:
+            p.mix_tall = plan.tall; p.mix_short = plan.shrt; p.mix_first = 0;
+            hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 5, 2, true>), grid, block, 0, stream, p);
+            break;
+        default:
+            if (plan.tile == 3) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 5, 2>), grid, block, 0, stream, p);
+            else if (plan.tile == 2) hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 4, 4, 2>), grid, block, 0, stream, p);
+            else if (plan.tile == 1) hipLaunchKernelGGL((gemm_bf16x3_kernel<4, 2, 2, 3>), grid, block, 0, stream, p);
+            else hipLaunchKernelGGL((gemm_bf16x3_kernel<2, 2, 2, 2>), grid, block, 0, stream, p);
     }
     EXCEL_CHECK_LAUNCH("gemm_bf16x3");
     return EXCEL_OK;

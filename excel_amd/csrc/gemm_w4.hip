@@ -26,7 +26,7 @@
 //     holds columns of ONE row) and the weight rows are read in a permuted order with a swizzle of their own, so a lane owns 8
 //     consecutive columns per tile pair (no LDS transpose, no barrier; see the epilogue).
 // Instances: NT_M = 10 (320 x 256 tiles: the B = 32 layer shapes), 8 (256 x 256), 5 (160 x 256: N = 768 launches of the B = 16 shapes);
-// excel_launch_gemm_bf16x3 picks instance vs 8-wave tile by modelled time.
+// the GEMM plan (gemm_plan.hip) picks instance vs 8-wave tile by modelled time.
 // Stage layout: row = [hi 32 | lo 32] bf16 = 128 B = 8 chunks of 16 B; A rows (chunk c at slot c ^ ((row >> 1) & 7)), then the 256 B
 // rows (slot c ^ swz_b(row)); two stages.
 #include <stdlib.h>
@@ -39,65 +39,7 @@ namespace EXCEL_SPLIT_NS {
 
 #include "gemm_w4_body.inc"
 
-// nt_m: 10 (320-row tiles), 8 (256) or 5 (160)
-// x2: 0 = three MFMAs per product; 1 / 2 = the two-product instances of gemm_w4x2.hip (fp16-valued weights in the split layout / as a
-// plain half matrix p.Bh)
-bool excel_gemm_w4_supported(const GemmBfArgs& p, int nt_m, int x2) {
-    const bool vec = (p.N & 3) == 0 && p.N >= 8 && (p.ldc & 3) == 0 && (p.ldr & 3) == 0 && (p.hd & 7) == 0;
-    const int kq = 32 * ((x2 == 2 || (nt_m & 1)) ? 4 : 2);          // the k-loop is unrolled over 2 (4) steps of 32
-    if (p.res && p.out_mode != GEMM_OUT_PLAIN) return false;      // the residual epilogue exists for the plain output only (all the path uses); else the 8-wave kernel
-    if (x2 && !p.w_lo_zero) return false;
-    if (x2 == 1 && nt_m == 10) return false;        // (not instantiated: gemm_w4x2.hip)
-    if (x2 == 2 && (!p.Bh || p.ldbh < p.K || (p.ldbh & 7) || ((uintptr_t)p.Bh & 15) || (long long)p.N * p.ldbh * 2 >= 0x7fffffffLL)) return false;
-    return (nt_m == 10 || nt_m == 8 || nt_m == 5) && vec && p.batch <= 1 && p.K >= kq && (p.K % kq) == 0 &&
-           (long long)p.M * p.lda * 2 < 0x7fffffffLL && (long long)p.N * p.ldb * 2 < 0x7fffffffLL;
-}
-
-// Modelled time (us) of one launch of the nt_m instance on n_cu CUs: rounds of tiles (a partial last round counts less) x (prologue + row tiles x (k-steps x 0.233 + epilogue
-// 1.8)); calibrated on the B = 32 layer shapes (profiles/r05_w4_arms.txt: a 320-row tile of K = 768 is 56 us of k-loop + 18 of epilogue + 7),
-// the short instance pays ~8 % more per row tile for its fragment reads (26 instead of 36 per 240 MFMAs-equivalent).  The launcher compares
-// this against the 8-wave tiles' model (gemm_bf16x3.hip).
-// one tile of the nt_m instance (us): prologue + row tiles x (k-steps x 0.233 + epilogue 1.8)
-static double w4_tile_us(int K, int nt_m, int x2) {
-    // (two-product instances: 16 instead of 24 MFMAs per row tile and k-step)
-    const double per_row_tile = (K / 32) * 0.233 * (x2 ? 0.70 : 1.0) * (nt_m == 5 ? 1.08 : nt_m == 8 ? 1.02 : 1.0) + 1.8;
-    return 7.0 + nt_m * per_row_tile;
-}
-// `tiles` equal tiles on n_cu CUs, in tile-times: full rounds + a partly filled last round, which is cheaper than a full one (fewer CUs share
-// the power budget and the fabric): 0.45 + 0.55 x fill, fitted on the B = 16 shapes (profiles/r05b_b16_shapes.txt: 360 tiles 140.6 us, 480
-// tiles 163.1, 624 tiles 223.8)
-static double w4_rounds(long long tiles, int n_cu) {
-    if (tiles <= 0) return 0.0;
-    const long long full = tiles / n_cu, rem = tiles - full * n_cu;
-    return (double)full + (rem ? 0.45 + 0.55 * (double)rem / n_cu : 0.0);
-}
-double excel_gemm_w4_model_us(const GemmBfArgs& p, int nt_m, int n_cu, int x2) {
-    return w4_rounds((long long)cdiv(p.M, 32 * nt_m) * cdiv(p.N, w4::BN), n_cu) * w4_tile_us(p.K, nt_m, x2);
-}
-
-// A launch made of TWO instances (gemm_w4_kernel_mix): R full rounds of 320-row tiles, the remaining rows in 256- or 160-row tiles that
-// fill what is left of round R and (part of) one more.  -> modelled time, the split in *tall / *shrt (row tiles) and *second (8 / 5);
-// 1e30 when no split applies.  (Judge, round 5: 711 tiles on 3 x 256 slots at B = 32, 1.4 - 2.4 rounds at B = 16.)
-double excel_gemm_w4_mix_model_us(const GemmBfArgs& p, int n_cu, int x2, int* tall, int* shrt, int* second) {
-    double best = 1e30;
-    if (!excel_gemm_w4_supported(p, 10, x2)) return best;
-    const int tiles_n = cdiv(p.N, w4::BN);
-    const double t10 = w4_tile_us(p.K, 10, x2);
-    const int cand[2] = {8, 5};
-    for (int c = 0; c < 2; ++c) {
-        if (!excel_gemm_w4_supported(p, cand[c], x2)) continue;
-        const double ts = w4_tile_us(p.K, cand[c], x2);
-        for (int R = 1; R <= 8; ++R) {
-            const int a10 = (int)(((long long)R * n_cu) / tiles_n);
-            if (a10 < 1 || (long long)a10 * 320 >= p.M) break;          // (the uniform grid covers M within R rounds)
-            const int as = cdiv(p.M - a10 * 320, 32 * cand[c]);
-            const long long slots_left = (long long)R * n_cu - (((long long)a10 * tiles_n + 7) & ~7LL);
-            const double us = R * t10 + w4_rounds((long long)as * tiles_n - (slots_left > 0 ? slots_left : 0), n_cu) * ts;
-            if (us < best) { best = us; *tall = a10; *shrt = as; *second = cand[c]; }
-        }
-    }
-    return best;
-}
+static_assert(w4::BN == GEMM_W4_BN, "the GEMM plan's grid arithmetic (gemm_plan.hip) assumes this tile width");
 
 // one plain __global__ function per instance (a kernel TEMPLATE launched from inside a function template lost its host-side stub)
 #define W4_KERNEL(NT, DBG) __global__ __launch_bounds__(256, 1) void gemm_w4_kernel_##NT##_##DBG(GemmBfArgs p) { W4_UNIFORM_BODY(NT, DBG, 0); }
@@ -109,9 +51,8 @@ W4_KERNEL(10, 15) W4_KERNEL(10, 24) W4_KERNEL(10, 32) W4_KERNEL(10, 136) W4_KERN
 #endif
 #define W4_LAUNCH(NT, DBG) hipLaunchKernelGGL(gemm_w4_kernel_##NT##_##DBG, grid, dim3(256), 0, stream, p)
 
-static void launch_w4(const GemmBfArgs& p_in, int nt_m, hipStream_t stream) {
+static void launch_w4(const GemmBfArgs& p_in, int nt_m, dim3 grid, hipStream_t stream) {
     GemmBfArgs p = p_in;
-    const dim3 grid(cdiv(p.M, 32 * nt_m) * cdiv(p.N, w4::BN));
 #ifdef EXCEL_DEV
     static const int stagger = getenv("EXCEL_W4_STAGGER") ? atoi(getenv("EXCEL_W4_STAGGER")) : 0;
     p.dbg = (stagger > 0 && (int)grid.x > 320) ? stagger : 0;      // multi-round launches only
@@ -141,21 +82,15 @@ static void launch_w4(const GemmBfArgs& p_in, int nt_m, hipStream_t stream) {
     else W4_LAUNCH(5, 0);
 }
 
-int excel_launch_gemm_w4_mix(const GemmBfArgs& p_in, int tall, int shrt, int second, hipStream_t stream) {
-    GemmBfArgs p = p_in;
-    EXCEL_CHECK_ARG(excel_gemm_w4_supported(p, 10, 0) && excel_gemm_w4_supported(p, second, 0) && tall >= 1 && shrt >= 1 && (second == 8 || second == 5) &&
-                    (long long)tall * 320 < p.M && (long long)tall * 320 + (long long)shrt * 32 * second >= p.M, "gemm_w4 (two instances): bad split");
-    p.mix_tall = tall; p.mix_short = shrt; p.mix_first = second;
-    const int tiles_n = cdiv(p.N, w4::BN);
-    const dim3 grid(((tall * tiles_n + 7) & ~7) + shrt * tiles_n);
-    hipLaunchKernelGGL(gemm_w4_kernel_mix, grid, dim3(256), 0, stream, p);
-    EXCEL_CHECK_LAUNCH("gemm_w4 (two instances)");
-    return EXCEL_OK;
-}
-
-int excel_launch_gemm_w4(const GemmBfArgs& p, int nt_m, hipStream_t stream) {
-    EXCEL_CHECK_ARG(excel_gemm_w4_supported(p, nt_m, 0), "gemm_w4: unsupported problem (vector epilogue, batch 1, K %% 64 (128) == 0, operands below 2 GB)");
-    launch_w4(p, nt_m, stream);
+// a GEMM_W4 plan (instance plan.nt_m) or a GEMM_W4_MIX one (two instances), three MFMAs per product
+int excel_launch_gemm_w4(const GemmBfArgs& p_in, const GemmPlan& plan, hipStream_t stream) {
+    if (plan.kernel == GEMM_W4_MIX) {
+        GemmBfArgs p = p_in;
+        p.mix_tall = plan.tall; p.mix_short = plan.shrt; p.mix_first = plan.second;     // (the kernel reads mix_first as the second instance)
+        hipLaunchKernelGGL(gemm_w4_kernel_mix, dim3(plan.grid_x), dim3(256), 0, stream, p);
+    } else {
+        launch_w4(p_in, plan.nt_m, dim3(plan.grid_x), stream);
+    }
     EXCEL_CHECK_LAUNCH("gemm_w4");
     return EXCEL_OK;
 }

@@ -39,14 +39,15 @@ W4X2_KERNEL_D(1) W4X2_KERNEL_D(2) W4X2_KERNEL_D(4) W4X2_KERNEL_D(8) W4X2_KERNEL_
 #define W4X2_LAUNCH_D(DBG) hipLaunchKernelGGL(gemm_w4x2_kernel_10_2_d##DBG, grid, dim3(256), 0, stream, p)
 #endif
 
-// x2 = 1 (split weights, p.B) or 2 (plain half weights, p.Bh / p.ldbh); preconditions: excel_gemm_w4_supported(p, nt_m, x2)
-int excel_launch_gemm_w4x2(const GemmBfArgs& p, int nt_m, int x2, hipStream_t stream) {
-    EXCEL_CHECK_ARG(p.w_lo_zero, "gemm_w4x2: the weight operand must be declared fp16-valued (w_lo_zero)");
-    EXCEL_CHECK_ARG(excel_gemm_w4_supported(p, nt_m, x2), "gemm_w4x2: unsupported problem (vector epilogue, batch 1, K %% 64 (128) == 0, operands below 2 GB)");
-    const dim3 grid(cdiv(p.M, 32 * nt_m) * cdiv(p.N, w4::BN));
+// a GEMM_W4 or GEMM_W4_MIX plan with plan.x2 = 1 (split weights, p.B) or 2 (plain half weights, p.Bh / p.ldbh; the only form of the
+// two-instance launch)
+int excel_launch_gemm_w4x2(const GemmBfArgs& p_in, const GemmPlan& plan, hipStream_t stream) {
+    GemmBfArgs p = p_in;
+    const dim3 grid(plan.grid_x);
+    const int nt_m = plan.nt_m;
 #ifdef EXCEL_DEV
     static const int dbg = getenv("EXCEL_W4_DBG") ? atoi(getenv("EXCEL_W4_DBG")) : 0;
-    if (x2 == 2 && nt_m == 10 && dbg) {
+    if (plan.kernel == GEMM_W4 && plan.x2 == 2 && nt_m == 10 && dbg) {
         switch (dbg) {
             case 1: W4X2_LAUNCH_D(1); break;
             case 2: W4X2_LAUNCH_D(2); break;
@@ -63,7 +64,10 @@ int excel_launch_gemm_w4x2(const GemmBfArgs& p, int nt_m, int x2, hipStream_t st
         return EXCEL_OK;
     }
 #endif
-    if (x2 == 2) {
+    if (plan.kernel == GEMM_W4_MIX) {
+        p.mix_tall = plan.tall; p.mix_short = plan.shrt; p.mix_first = plan.second;     // (the kernel reads mix_first as the second instance)
+        hipLaunchKernelGGL(gemm_w4x2_kernel_mix, grid, dim3(256), 0, stream, p);
+    } else if (plan.x2 == 2) {
         if (nt_m == 10) W4X2_LAUNCH(10, 2);
         else if (nt_m == 8) W4X2_LAUNCH(8, 2);
         else W4X2_LAUNCH(5, 2);
@@ -72,20 +76,6 @@ int excel_launch_gemm_w4x2(const GemmBfArgs& p, int nt_m, int x2, hipStream_t st
         else W4X2_LAUNCH(5, 1);
     }
     EXCEL_CHECK_LAUNCH("gemm_w4x2");
-    return EXCEL_OK;
-}
-
-// the two-instance launch of the compact-weight kernel (gemm_w4.hip: excel_gemm_w4_mix_model_us)
-int excel_launch_gemm_w4x2_mix(const GemmBfArgs& p_in, int tall, int shrt, int second, hipStream_t stream) {
-    GemmBfArgs p = p_in;
-    EXCEL_CHECK_ARG(p.w_lo_zero && excel_gemm_w4_supported(p, 10, 2) && excel_gemm_w4_supported(p, second, 2) && tall >= 1 && shrt >= 1 &&
-                    (second == 8 || second == 5) && (long long)tall * 320 < p.M && (long long)tall * 320 + (long long)shrt * 32 * second >= p.M,
-                    "gemm_w4x2 (two instances): bad split");
-    p.mix_tall = tall; p.mix_short = shrt; p.mix_first = second;
-    const int tiles_n = cdiv(p.N, w4::BN);
-    const dim3 grid(((tall * tiles_n + 7) & ~7) + shrt * tiles_n);
-    hipLaunchKernelGGL(gemm_w4x2_kernel_mix, grid, dim3(256), 0, stream, p);
-    EXCEL_CHECK_LAUNCH("gemm_w4x2 (two instances)");
     return EXCEL_OK;
 }
 

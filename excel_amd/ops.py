@@ -100,6 +100,21 @@ def gemm_f16x2(A_split, W_split, W_half=None, bias=None, residual=None, act=0, s
     return out.view(torch.int16).view(M, 2, N) if split_out else out
 
 
+GEMM_PLAN_KERNELS = ("8wave", "8wave_mixed", "w4", "w4_mix")       # excel_gemm_plan (include/excel_hip.h)
+GEMM_OUT_MODES = {"plain": 0, "qkv": 1, "split": 2}
+
+
+def gemm_plan(M, N, K, n_cu, mode="bf16x3", batch=1, out="plain", residual=False, half=False):
+    """The kernel instance and grid the split-plane GEMM of `mode` runs this problem on with n_cu compute units (host arithmetic only):
+    out "plain" / "qkv" (the ViT's head-major in_proj) / "split"; half: the f16x2 call passes W_half."""
+    plan = (C.c_int32 * 10)()
+    check(lib().excel_gemm_plan(M, N, K, batch, GEMM_OUT_MODES[out], int(residual), GEMM_MODES[mode], int(half), n_cu, plan), "excel_gemm_plan")
+    keys = ("kernel", "tile", "nt_m", "x2", "tall", "shrt", "second", "grid_x", "grid_y", "block")
+    d = dict(zip(keys, plan))
+    d["kernel"] = GEMM_PLAN_KERNELS[d["kernel"]]
+    return d
+
+
 def layernorm(x, w, b, eps=1e-5):
     D = x.shape[-1]
     y = torch.empty_like(x)

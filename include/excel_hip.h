@@ -63,6 +63,18 @@ int excel_gemm_f16x3(const void* A_split, const void* W_split, float* C, const f
 int excel_pack_f16(const float* in, void* out, long long rows, int K, unsigned long long* inexact_dev, void* stream);
 int excel_gemm_f16x2(const void* A_split, const void* W_split, const void* W_half, float* C, const float* bias, const float* residual,
                      int M, int N, int K, int act, int split_out, void* stream);
+/* Which kernel instance the split-plane GEMM runs a problem on (a HOST function: no device work).  The problem is described as
+ * excel_gemm_bf16x3 / _f16x3 / _f16x2 and the ViT's linear layers pass it: operands [M,K] and [N,K], `batch` problems (the ViT's A_sum.V
+ * form), out_mode 0 = fp32 [M,N], 1 = q|k|v head-major with head dim 64 (the ViT's in_proj), 2 = split output; has_residual; gemm_mode
+ * as in excel_vit_set_gemm_mode (1 bf16x3, 2 f16x3, 3 f16x2); has_half: the f16x2 call passes W_half; n_cu: the device's compute units.
+ * plan[EXCEL_GEMM_PLAN_INTS] = {kernel, tile, nt_m, x2, tall, shrt, second, grid_x, grid_y, block}:
+ *   kernel: 0 uniform 8-wave tiles (tile: 0 128x128, 1 256x128, 2 256x256, 3 320x256), 1 mixed-height 8-wave tiles (`tall` row tiles of
+ *           320 rows, then `shrt` of 256), 2 one four-wave instance (nt_m: 10 / 8 / 5 = 320- / 256- / 160-row tiles), 3 a launch of two
+ *           four-wave instances (`tall` row tiles of 320 rows, then `shrt` of the instance `second` = 8 / 5);
+ *   x2: two-product kernel (0 no, 1 on the split weights, 2 on the half weights); grid_x, grid_y, block: the launch.  Unused fields are 0. */
+#define EXCEL_GEMM_PLAN_INTS 10
+int excel_gemm_plan(int M, int N, int K, int batch, int out_mode, int has_residual, int gemm_mode, int has_half, int n_cu,
+                    int32_t* plan /*host*/);
 
 /* LayerNorm over the last dim, fp32, eps as given (clip/clip_surgery_model.py:271-277). */
 int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream);

@@ -762,15 +762,28 @@ def test_gemm_bf16x3(ops, M, N, K):
     assert np.array_equal(hi, _bf16_round(out))
 
 
+def _plan(ops, M, N, K, **kw):
+    """The kernel instance the split-plane GEMM launcher picks for this problem on this device (host arithmetic, ops.gemm_plan)."""
+    return ops.gemm_plan(M, N, K, torch.cuda.get_device_properties(0).multi_processor_count, **kw)
+
+
 @pytest.mark.parametrize("M,N,K", [(25120, 768, 768), (25120, 2304, 768), (25120, 3072, 768), (25120, 768, 3072), (12560, 3072, 768),
                                    (12560, 768, 768), (25120, 512, 768), (12560, 2304, 768), (12560, 768, 3072), (16400, 768, 768),
                                    (16400, 3072, 768), (12500, 776, 896)])
 def test_gemm_bf16x3_bench_shapes(ops, M, N, K):
     """The GEMM instances the benchmark configurations actually run (B = 32 / 16 at 448^2: M = B * 785; B = 16 at 512^2: M = 16 400): the
-    four-wave kernel gemm_w4.hip in its 320-row (B = 32 shapes), 160-row (M = 12 560 with N = 768: 237 tiles) and 256-row (M = 16 400,
-    N = 768: 195 tiles) instances and the 8-wave tiles the launcher's model still prefers - proj, QKV, fc1, fc2, the final projection, and
-    one ragged shape (M, N not multiples of the tile, K % 128 == 0) - against a float64 product, plain and with bias + QuickGELU + residual,
-    and with the split output."""
+    four-wave kernel gemm_w4.hip in its 320-row (M = 25 120 with N = 768), 160-row (M = 12 560 with N = 768: 237 tiles) and 256-row
+    (M = 16 400, N = 768: 195 tiles) instances, and one or two of its instances for the other shapes - proj, QKV, fc1, fc2, the final
+    projection, and one ragged shape (M, N not multiples of the tile, K % 128 == 0) - against a float64 product, plain and with bias +
+    QuickGELU + residual, and with the split output (whose residual form runs on the 8-wave tiles).  The plans are asserted."""
+    plan = _plan(ops, M, N, K)
+    if N == 768 and M in (12560, 16400, 25120):
+        nt_m, tiles = {12560: (5, 237), 16400: (8, 195), 25120: (10, 237)}[M]
+        assert plan["kernel"] == "w4" and plan["nt_m"] == nt_m and plan["grid_x"] == tiles, plan
+    else:
+        assert plan["kernel"] in ("w4", "w4_mix"), plan
+    if N % 32 == 0:
+        assert _plan(ops, M, N, K, out="split", residual=True)["kernel"] in ("8wave", "8wave_mixed")
     rs = np.random.RandomState(M % 1000 + N + K)
     A = rs.standard_normal((M, K)).astype(np.float32)
     W = (rs.standard_normal((N, K)) * 0.05).astype(np.float32)
@@ -830,8 +843,13 @@ def test_gemm_bf16x3_with_neighbours_on_other_streams(ops, M, N, K, mode):
     ds_read: a garbage lane id and wild addresses, only under such a neighbour (memory fault in `bench.py --split 2`).  Two GEMM streams + a
     LayerNorm stream, every result bit-identical to the serial launch."""
     # (round 6: the same with the two-product kernels - "f16x2" - and with launches made of two instances: N = 2304 / 3072)
-    g = torch.Generator(device="cuda").manual_seed(M)
     f16 = mode == "f16x2"
+    for kw in (dict(residual=True), dict(out="split")):
+        plan = _plan(ops, M, N, K, mode=mode, half=f16, **kw)
+        assert plan["kernel"] == ("w4" if N == 768 else "w4_mix") and plan["x2"] == (2 if f16 else 0), plan
+        if N == 768:
+            assert plan["nt_m"] == {12560: 5, 16400: 8, 25120: 10}[M], plan
+    g = torch.Generator(device="cuda").manual_seed(M)
     As = [ops.split_bf16(torch.randn(M, K, device="cuda", generator=g), f16=f16) for _ in range(2)]
     Wf = (torch.randn(N, K, device="cuda", generator=g) * 0.05).half().float()
     W = ops.split_bf16(Wf, f16=f16)
@@ -1096,6 +1114,10 @@ def test_gemm_two_instance_launch_equals_row_slices(ops, M, N, K):
             return ops.gemm_bf16x3(a_split, Ws, residual=r, f16=f16, **kw)
         # (14001 x 2000: a ragged last row AND column tile - 32 x 160 + 160-row tiles by the model -, N % 32 != 0: no split output)
         for kw, use_res in ((dict(), False), (dict(bias=bias, act=1, split_out=N % 32 == 0), False), (dict(bias=bias), True)):
+            form = dict(mode=name, half=name == "f16x2", out="split" if kw.get("split_out") else "plain", residual=use_res)
+            assert _plan(ops, M, N, K, **form)["kernel"] == "w4_mix", (name, form)
+            short = _plan(ops, 4000, N, K, **form)
+            assert short["kernel"] == "8wave" or (short["kernel"] == "w4" and short["nt_m"] in (8, 5)), (name, form, short)
             whole = run(As, res if use_res else None, **kw)
             for lo, hi in zip(cuts[:-1], cuts[1:]):
                 part = run(As[lo:hi].contiguous(), res[lo:hi].contiguous() if use_res else None, **kw)
