@@ -220,6 +220,16 @@ extern "C" int excel_gemm_plan(int M, int N, int K, int batch, int out_mode, int
     return EXCEL_OK;
 }
 
+extern "C" int excel_attn_plan(int B, int H, int N, int gemm_mode, int surgery, int want_w, int32_t* plan) {
+    EXCEL_CHECK_ARG(plan && B >= 1 && H >= 1 && N >= 1 && N <= (1 << 20) && (long long)B * H <= 65535 && gemm_mode >= 0 && gemm_mode <= 3 &&
+                    (surgery == 0 || surgery == 1) && (want_w == 0 || want_w == 1), "attn_plan: bad argument");
+    const AttnPlan p = attn_plan(B, H, N, gemm_mode, surgery, want_w);
+    const int v[EXCEL_ATTN_PLAN_INTS] = {p.path, p.ntiles, p.ntw, p.nw, p.nw_full, p.rp_ntypes, p.rp_grid[0], p.rp_grid[1], p.rp_grid[2],
+                                         p.grid[0], p.grid[1], p.grid[2], p.block, p.split_c};
+    for (int i = 0; i < EXCEL_ATTN_PLAN_INTS; ++i) plan[i] = v[i];
+    return EXCEL_OK;
+}
+
 extern "C" int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream) {
     return excel_launch_layernorm(x, nullptr, 1, w, b, y, rows, D, eps, ST(stream));
 }
@@ -539,7 +549,7 @@ static int vit_forward_f16(EXCEL_VIT_FWD_ARGS) {
     using excel_f16::excel_launch_gemm; using excel_f16::excel_launch_gemm_bf16x3; using excel_f16::excel_launch_split_bf16;
     using excel_f16::excel_launch_vt_from_planes; using excel_f16::excel_launch_layernorm; using excel_f16::excel_launch_assemble_ln_pre;
     using excel_f16::excel_launch_token_axis_normalize; using excel_f16::excel_launch_im2col; using excel_f16::excel_launch_attn_rowpass;
-    using excel_f16::excel_launch_attn_accum; using excel_f16::excel_attn_strip_supported; using excel_f16::excel_launch_attn_strip;
+    using excel_f16::excel_launch_attn_accum; using excel_f16::excel_launch_attn_strip;
 #include "vit_forward_body.inc"
 }
 static int vit_forward_impl(EXCEL_VIT_FWD_ARGS) {

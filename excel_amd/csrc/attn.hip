@@ -935,40 +935,41 @@ __global__ __launch_bounds__(512, 2) void attn_accum_bf_kernel(AccumArgs p) {
 }
 
 int excel_launch_attn_rowpass(const float* qkvh, float* out, float* stats, int B, int H, int N, int hd, float scale,
-                              int ntypes, hipStream_t st, int split_out, const unsigned short* qkvs, int flash_nq,
+                              const AttnPlan& pl, hipStream_t st, int split_out, const unsigned short* qkvs, int flash_nq,
                               const unsigned short* vt, int vt_kp) {
     ProfScope prof__(PROF_ATTN_ROWPASS, st);
     EXCEL_CHECK_ARG(hd == HD, "attention: head_dim must be 64 (got %d)", hd);
-    EXCEL_CHECK_ARG(ntypes == 1 || ntypes == 4, "attention: ntypes must be 1 or 4");
+    EXCEL_CHECK_ARG(pl.rp_ntypes == 1 || pl.rp_ntypes == 4, "attention: ntypes must be 1 or 4");
+    EXCEL_CHECK_ARG((pl.path == ATTN_TWOPASS_F32) == !split_out, "attention: the plan is of another mode");
     RowpassArgs a{qkvh, out, reinterpret_cast<float2*>(stats), B, H, N, scale, split_out, qkvs, flash_nq, vt, vt_kp, 1, 1 << 20};
 #ifdef EXCEL_DEV
     { static const int x = getenv("EXCEL_ROWPASS_XCD") ? atoi(getenv("EXCEL_ROWPASS_XCD")) : 1; a.xcd_local = x; }
     { static const int g = getenv("EXCEL_ROWPASS_GRP") ? atoi(getenv("EXCEL_ROWPASS_GRP")) : 0; if (g > 0) a.tail_grp = g; }
 #endif
-    hipLaunchKernelGGL(attn_rowpass_kernel, dim3(cdiv(N, 128), B * H, ntypes), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(attn_rowpass_kernel, dim3(pl.rp_grid[0], pl.rp_grid[1], pl.rp_grid[2]), dim3(256), 0, st, a);
     EXCEL_CHECK_LAUNCH("attn_rowpass");
     return EXCEL_OK;
 }
 
 int excel_launch_attn_accum(const float* qkvh, const float* stats, float* a_sum, float* w_aff, float* attn_out, int B, int H,
                             int N, int NP, int hd, float scale, int surgery, float w_scale, float aff_scale, int aff_init,
-                            hipStream_t st, const unsigned short* qkvs, int a_sum_split, const float* ex_attn) {
+                            const AttnPlan& pl, hipStream_t st, const unsigned short* qkvs, int a_sum_split, const float* ex_attn) {
     ProfScope prof__(PROF_ATTN_ACCUM, st);
     EXCEL_CHECK_ARG(hd == HD, "attention: head_dim must be 64 (got %d)", hd);
+    EXCEL_CHECK_ARG(pl.path == (qkvs ? ATTN_TWOPASS_SPLIT : ATTN_TWOPASS_F32) && pl.block > 0, "attn_accum: the plan names another path");
     EXCEL_CHECK_ARG(!surgery || (a_sum && NP >= N && NP <= cdiv(N, 64) * 64), "attn_accum: bad a_sum/NP");
     AccumArgs a{qkvh, reinterpret_cast<const float2*>(stats), a_sum, w_aff, attn_out, B, H, N, NP, scale, w_scale, aff_scale, aff_init, qkvs, 0, a_sum_split, surgery ? ex_attn : nullptr, (float)H};
-    dim3 grid(cdiv(N, 64), cdiv(N, 64), B);
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);       // 64 x 64 tiles, 256 threads; split modes: 128 x 64, 512
 #ifdef EXCEL_DEV
     { static const char* d = getenv("EXCEL_ACCUM_DBG"); if (d) a.dbg = atoi(d); }
 #endif
     if (qkvs) {            // bf16x3 mode beyond the strip kernel's reach (attn_strip.hip: N > 1280)
-        dim3 g2(cdiv(N, 64), cdiv(N, 128), B);
-        if (surgery) hipLaunchKernelGGL((attn_accum_bf_kernel<true>), g2, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((attn_accum_bf_kernel<false>), g2, dim3(512), 0, st, a);
+        if (surgery) hipLaunchKernelGGL((attn_accum_bf_kernel<true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((attn_accum_bf_kernel<false>), grid, block, 0, st, a);
     } else if (surgery)
-        hipLaunchKernelGGL((attn_accum_kernel<true, false>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((attn_accum_kernel<true, false>), grid, block, 0, st, a);
     else
-        hipLaunchKernelGGL((attn_accum_kernel<false, false>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((attn_accum_kernel<false, false>), grid, block, 0, st, a);
     EXCEL_CHECK_LAUNCH("attn_accum");
     return EXCEL_OK;
 }

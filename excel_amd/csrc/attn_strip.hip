@@ -514,29 +514,22 @@ __global__ __launch_bounds__(512) void attn_strip_kernel(StripArgs p) {
     }
 }
 
-// Strip-resident accumulate pass; returns EXCEL_ERR_ARG-free "not applicable" (1) when the shape does not fit (caller falls back).
-bool excel_attn_strip_supported(int N) { return cdiv(N, 32) <= 40; }       // 8 waves x 5 key tiles: beyond that the two-pass kernels run
-
+// Strip-resident accumulate pass (the shapes attn_plan() sends here: ATTN_STRIP, at most 8 waves x 5 key tiles).
 int excel_launch_attn_strip(const unsigned short* qkvs, unsigned short* a_sum, float* w_aff, float* attn_out, int B, int H, int N,
                             int KP, int hd, float scale, int surgery, float w_scale, float aff_scale, int aff_init, const float* ex_attn,
-                            hipStream_t st, const float* wstats) {
+                            const AttnPlan& pl, hipStream_t st, const float* wstats) {
     EXCEL_CHECK_ARG(hd == 64, "attention: head_dim must be 64 (got %d)", hd);
     EXCEL_CHECK_ARG(qkvs && (!surgery || (a_sum && KP == cdiv(N, 32) * 32)), "attn_strip: bad a_sum/KP");
-    const int ntiles = cdiv(N, 32);
     EXCEL_CHECK_ARG(wstats || !(w_aff || attn_out), "attn_strip: the W sweep needs the flash row pass's q.k row statistics (wstats)");
-    EXCEL_CHECK_ARG(excel_attn_strip_supported(N), "attn_strip: N=%d exceeds the strip-resident envelope (ask excel_attn_strip_supported)", N);
+    EXCEL_CHECK_ARG(pl.path == ATTN_STRIP && pl.block > 0, "attn_strip: N=%d exceeds the strip-resident envelope or the layer needs no sweep (ask attn_plan)", N);
+    EXCEL_CHECK_ARG(pl.ntiles == cdiv(N, 32) && (pl.split_c > 0) == (surgery && (w_aff || attn_out)), "attn_strip: the plan is of another problem");
     ProfScope prof__(PROF_ATTN_ACCUM, st);
-    const int ntw = cdiv(ntiles, 8);
-    const int nw = cdiv(ntiles, ntw);                          // 25 tiles: 7 waves x (4,4,4,4,3,3,3)
+    const int ntiles = pl.ntiles, ntw = pl.ntw, nw = pl.nw;
     EXCEL_CHECK_ARG(ntiles / nw >= ntw - 1 && (long long)3 * H * N * 256 < (1LL << 31), "attn_strip: unsupported shape");
     StripArgs a{qkvs, a_sum, w_aff, attn_out, surgery ? ex_attn : nullptr, B, H, N, KP, ntiles, cdiv(N, 32), scale, w_scale, aff_scale, (float)H,
                 aff_init, surgery, 0, reinterpret_cast<const float2*>(wstats)};
-    // Both sweeps wanted: one workgroup per (strip, sweep).  A strip workgroup fills a CU (148 KB LDS), so B x nstrips = 800 uniform
-    // workgroups on 256 CUs are 3.125 rounds = 4 rounds of 4H phases; split, the 3H-phase workgroups go first and the H-phase ones
-    // level the tail: 150-156 phase-times per CU instead of 192.
-    const bool split = surgery && (w_aff || attn_out);
-    if (split) a.split_c = cdiv(B * a.nstrips, 8);
-    const dim3 grid(split ? 8 * 2 * a.split_c : B * a.nstrips), block(nw * 64);
+    a.split_c = pl.split_c;            // both sweeps wanted: one workgroup per (strip, sweep), see attn_plan()
+    const dim3 grid(pl.grid[0]), block(pl.block);
 #ifdef EXCEL_DEV
     // dev build only: ablation variants (bit0 no MFMA, bit1 no DMA in the loop, bit2 no softmax, bit3 no schedule groups)
     static const int dbg = getenv("EXCEL_STRIP_DBG") ? atoi(getenv("EXCEL_STRIP_DBG")) : 0;

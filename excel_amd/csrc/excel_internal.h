@@ -70,6 +70,21 @@ struct GemmPlan {
 };
 constexpr int GEMM_W4_BN = 256;          // columns of a four-wave tile (w4::BN, gemm_w4_body.inc)
 GemmPlan gemm_plan(const GemmShape& s, int n_cu);
+// Kernel selection of the ViT attention (attn_plan.hip): which kernels one layer's attention runs on, with their grids.  Host arithmetic
+// on integers, shared by the launchers (attn.hip, attn_strip.hip), the ViT forward and the host query of the C ABI (excel_attn_plan).
+enum { ATTN_STRIP = 0, ATTN_TWOPASS_SPLIT = 1, ATTN_TWOPASS_F32 = 2 };
+constexpr int ATTN_STRIP_MAX_TILES = 40;   // the strip-resident kernel keeps 32 query rows x ALL keys in registers: 8 waves x 5 key tiles of 32
+struct AttnPlan {
+    int path;                  // ATTN_STRIP: flash row pass + attn_strip_kernel<ntw>; ATTN_TWOPASS_SPLIT: row pass + attn_accum_bf_kernel (split
+                               // modes beyond the strip envelope); ATTN_TWOPASS_F32: row pass + attn_accum_kernel (exact fp32)
+    int ntiles;                // key tiles of 32: cdiv(N, 32) (also the number of 32-row query strips)
+    int ntw, nw, nw_full;      // strip: tiles per wave (the instance), waves, waves that own ntw tiles (the others own ntw - 1)
+    int rp_ntypes;             // row pass: 1 = q.k alone, 4 = q.k, q.q, k.k, v.v (a surgery layer on a two-pass path)
+    int rp_grid[3];            // row pass grid (256 threads)
+    int grid[3], block;        // second kernel (strip / accumulate); all 0 when the layer needs none (no surgery, no weights wanted)
+    int split_c;               // strip with both sweeps: strips per XCD chunk (StripArgs::split_c), else 0
+};
+AttnPlan attn_plan(int B, int H, int N, int gemm_mode, int surgery, int want_w);
 // the plain half matrix of the weights, [N][ldbh] at a 16-byte aligned address, can feed the compact-weight four-wave instances
 inline bool gemm_half_ok(bool aligned, int N, int K, int ldbh) {
     return aligned && ldbh >= K && (ldbh & 7) == 0 && (long long)N * ldbh * 2 < 0x7fffffffLL;

@@ -19,16 +19,17 @@ int excel_launch_assemble_ln_pre(const float* patch, const float* cls_emb, const
 int excel_launch_token_axis_normalize(const float* f, float* ss, float* out, int B, int tokN, int C, hipStream_t st);
 int excel_launch_im2col(const float* img, float* col, int B, int S, int ps, hipStream_t st, int split_out = 0);
 int excel_launch_attn_rowpass(const float* qkvh, float* out, float* stats, int B, int H, int N, int hd, float scale,
-                              int ntypes, hipStream_t st, int split_out = 0, const unsigned short* qkvs = nullptr, int flash_nq = 1 << 30,
+                              const AttnPlan& plan, hipStream_t st, int split_out = 0, const unsigned short* qkvs = nullptr, int flash_nq = 1 << 30,
                               const unsigned short* vt = nullptr, int KP = 0);
 int excel_launch_attn_accum(const float* qkvh, const float* stats, float* a_sum, float* w_aff, float* attn_out, int B, int H,
                             int N, int NP, int hd, float scale, int surgery, float w_scale, float aff_scale, int aff_init,
-                            hipStream_t st, const unsigned short* qkvs = nullptr, int a_sum_split = 0, const float* ex_attn = nullptr);
-// the strip-resident kernel keeps 32 query rows x ALL keys of an image in registers: at most 8 waves x 5 key tiles of 32
-bool excel_attn_strip_supported(int N);
+                            const AttnPlan& plan, hipStream_t st, const unsigned short* qkvs = nullptr, int a_sum_split = 0,
+                            const float* ex_attn = nullptr);
+// `plan`: attn_plan() of this layer (excel_internal.h) - the path (strip-resident kernel up to 8 waves x 5 key tiles of 32, else the two-
+// pass kernels), the row pass's score types and every grid come from it; a launcher refuses a plan that names another path
 int excel_launch_attn_strip(const unsigned short* qkvs, unsigned short* a_sum, float* w_aff, float* attn_out, int B, int H, int N,
                             int KP, int hd, float scale, int surgery, float w_scale, float aff_scale, int aff_init, const float* ex_attn,
-                            hipStream_t st, const float* wstats);
+                            const AttnPlan& plan, hipStream_t st, const float* wstats);
 // wstats (no default: every caller states it): the {row max in LOG2 units, 1 / row sum} of q.k that excel_launch_attn_rowpass - the split-
 // plane ("bf") row pass of THIS layer, run on the SAME qkvs planes, launched earlier on the same stream - left in the type-0 slots of its
 // statistics buffer ([B,H,4,N] float2).  The W sweep exponentiates against them without a running maximum: statistics of another layer,

@@ -93,18 +93,19 @@
         float* attn_l = (n_attn_out && l >= L - n_attn_out) ? attn_out + (size_t)(l - (L - n_attn_out)) * B * N * N : nullptr;
         // bf16x3 mode: the strip-resident kernel (attn_strip.hip) owns the softmax statistics of q.q / k.k / v.v and of the
         // q.k weights, so the row pass only runs its flash part (attention output of the original path)
-        const bool strip = bf && excel_attn_strip_supported(N);
-        TRY(excel_launch_attn_rowpass(ws.qkvh, ws.ao, ws.stats, B, H, N, 64, scale, (surgery && !strip) ? 4 : 1, st, bf, qkvs,
+        const AttnPlan ap = attn_plan(B, H, N, h->gemm_mode, surgery ? 1 : 0, (in_aff || attn_l) ? 1 : 0);
+        const bool strip = ap.path == ATTN_STRIP;
+        TRY(excel_launch_attn_rowpass(ws.qkvh, ws.ao, ws.stats, B, H, N, 64, scale, ap, st, bf, qkvs,
                                       cls_only ? 1 : (1 << 30), bf ? (const unsigned short*)ws.vt : nullptr, ws.KP));
         if (surgery || in_aff || attn_l) {
             if (strip) {
                 TRY(excel_launch_attn_strip(qkvs, surgery ? (unsigned short*)ws.a_sum : nullptr, in_aff ? w_aff : nullptr, attn_l, B, H, N, ws.KP,
                                             64, scale, surgery ? 1 : 0, surgery ? 1.f : 1.f / (float)H, 1.f / (float)aff_layers,
-                                            (l == L - aff_layers) ? 1 : 0, ex_attn, st, ws.stats));   // (the row pass above left the q.k row statistics in ws.stats)
+                                            (l == L - aff_layers) ? 1 : 0, ex_attn, ap, st, ws.stats));   // (the row pass above left the q.k row statistics in ws.stats)
             } else {
                 TRY(excel_launch_attn_accum(ws.qkvh, ws.stats, surgery ? ws.a_sum : nullptr, in_aff ? w_aff : nullptr, attn_l, B, H, N,
                                             bf ? ws.KP : ws.NP, 64, scale, surgery ? 1 : 0, surgery ? 1.f : 1.f / (float)H,
-                                            1.f / (float)aff_layers, (l == L - aff_layers) ? 1 : 0, st, qkvs, bf ? 1 : 0, ex_attn));
+                                            1.f / (float)aff_layers, (l == L - aff_layers) ? 1 : 0, ap, st, qkvs, bf ? 1 : 0, ex_attn));
             }
         }
         if (!surgery) {

@@ -115,6 +115,20 @@ def gemm_plan(M, N, K, n_cu, mode="bf16x3", batch=1, out="plain", residual=False
     return d
 
 
+ATTN_PLAN_PATHS = ("strip", "twopass_split", "twopass_f32")       # excel_attn_plan (include/excel_hip.h)
+
+
+def attn_plan(B, H, N, mode="bf16x3", surgery=True, want_w=True):
+    """The kernels one ViT layer's attention runs on for B images of N tokens and H heads in `mode` (host arithmetic only): the path,
+    the strip kernel's instance (ntw key tiles per wave on `waves` waves, `waves_full` of them with ntw tiles), the row pass's score
+    types and the grids.  surgery: one of the last n_surgery layers; want_w: w_aff / attn_out cover the layer."""
+    plan = (C.c_int32 * 14)()
+    check(lib().excel_attn_plan(B, H, N, GEMM_MODES[mode], int(surgery), int(want_w), plan), "excel_attn_plan")
+    v = list(plan)
+    return dict(path=ATTN_PLAN_PATHS[v[0]], ntiles=v[1], ntw=v[2], waves=v[3], waves_full=v[4], rowpass_ntypes=v[5], rowpass_grid=tuple(v[6:9]),
+                grid=tuple(v[9:12]), block=v[12], split_c=v[13])
+
+
 def layernorm(x, w, b, eps=1e-5):
     D = x.shape[-1]
     y = torch.empty_like(x)

@@ -75,6 +75,18 @@ int excel_gemm_f16x2(const void* A_split, const void* W_split, const void* W_hal
 #define EXCEL_GEMM_PLAN_INTS 10
 int excel_gemm_plan(int M, int N, int K, int batch, int out_mode, int has_residual, int gemm_mode, int has_half, int n_cu,
                     int32_t* plan /*host*/);
+/* Which kernels one ViT layer's attention runs on for B images of N tokens and H heads of dim 64 (a HOST function: no device work).
+ * gemm_mode as in excel_vit_set_gemm_mode (0 f32, 1 bf16x3, 2 f16x3, 3 f16x2); surgery: the layer is one of the last n_surgery (q.q /
+ * k.k / v.v attention); want_w: the head-mean q.k weights are wanted (w_aff and / or attn_out cover this layer).
+ * plan[EXCEL_ATTN_PLAN_INTS] = {path, ntiles, ntw, waves, waves_full, rowpass_ntypes, rowpass_grid x, y, z, grid x, y, z, block, split_c}:
+ *   path: 0 flash row pass + strip-resident kernel (split modes, ntiles = cdiv(N, 32) <= 40: instance ntw = cdiv(ntiles, 8) key tiles per
+ *         wave on waves = cdiv(ntiles, ntw) waves, of which waves_full own ntw tiles and the others ntw - 1), 1 row pass + split-plane
+ *         accumulate kernel (split modes beyond that), 2 row pass + fp32 accumulate kernel (f32);
+ *   rowpass_ntypes: 4 on a surgery layer of a two-pass path (q.k, q.q, k.k, v.v statistics), else 1; rowpass_grid: 256 threads each;
+ *   grid, block: the second kernel's launch (all 0 when the layer needs none: no surgery, no weights wanted); split_c: strips per XCD
+ *   chunk when the strip kernel's two sweeps run as separate workgroups (surgery and want_w), else 0.  Unused fields are 0. */
+#define EXCEL_ATTN_PLAN_INTS 14
+int excel_attn_plan(int B, int H, int N, int gemm_mode, int surgery, int want_w, int32_t* plan /*host*/);
 
 /* LayerNorm over the last dim, fp32, eps as given (clip/clip_surgery_model.py:271-277). */
 int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream);

@@ -509,6 +509,47 @@ def test_multi_scale_lam_vs_oracle(gpu):
     assert got.shape == (2, 4, 64, 64) and maxabs(got, ref) < 5e-4
 
 
+_MS448_REF = {}
+
+
+@pytest.mark.parametrize("gemm_mode,tol", [("f32", 5e-4), ("bf16x3", 1e-3)])
+def test_multi_scale_lam_vs_oracle_448_base(gpu, gemm_mode, tol):
+    """The sizes BASELINE configs[4] runs on a 448 base: scales 1.0 / 0.5 / 0.75 / 1.5 = 448^2, 224^2, 336^2 (N = 442: the strip kernel's
+    2-tiles-per-wave instance) and 672^2 (N = 1765: past the strip envelope, so bf16x3 takes the row pass with 4 score types and
+    attn_accum_bf_kernel - the only reference comparison of a LAM that went through them; f32 never enters that path).  Same oracle loop
+    as the 64^2 test above.  f32 keeps that test's tolerance; bf16x3 is held to the CAM gate of 1e-3 on the min-max normalised LAM."""
+    from excel_amd import ops
+    from excel_amd.utils.camutils import multi_scale_lam
+    S = 448
+    scales = (1.0, 0.5, 0.75, 1.5)
+    if gemm_mode == "bf16x3":
+        assert [ops.attn_plan(4, TINY.heads, (int(s * S) // 16) ** 2 + 1, mode=gemm_mode)["path"] for s in scales] == \
+            ["strip", "strip", "strip", "twopass_split"]
+        assert ops.attn_plan(4, TINY.heads, 442, mode=gemm_mode)["ntw"] == 2
+    rs = np.random.RandomState(9)
+    text = rs.standard_normal((9, 64)).astype(np.float32)
+    text /= np.linalg.norm(text, axis=1, keepdims=True)
+    model, w = tiny_model(text.T.copy(), gemm_mode=gemm_mode, img_size=S)
+    x = rs.standard_normal((2, 3, S, S)).astype(np.float32)
+    got = host(multi_scale_lam(model, dev(x), scales))
+    if "ref" not in _MS448_REF:
+        wo = oracle.vit.reload_self_attn(w, TINY, S // 16, "train")
+        acc = 0
+        for s in scales:
+            hs = int(s * S) // 16 * 16
+            xs = x if hs == S else oracle.interp.bilinear_resize(x, hs, hs, align_corners=False)
+            m = _oracle_maps(np.concatenate([xs, xs[..., ::-1]], 0), wo, TINY, text.T.copy(), 4)
+            g = hs // 16
+            lam = oracle.interp.bilinear_resize(m.transpose(0, 2, 1).reshape(4, 4, g, g), S, S, align_corners=False)
+            acc = acc + np.maximum(lam[:2], lam[2:][..., ::-1])
+        acc = acc - acc.min(axis=(2, 3), keepdims=True)
+        _MS448_REF["ref"] = acc / (acc.max(axis=(2, 3), keepdims=True) + 1e-5)
+    ref = _MS448_REF["ref"]
+    err = maxabs(got, ref)
+    print(f"[multi-scale LAM 448 base] {gemm_mode}: max-abs error {err:.2e} (bound {tol:.0e})")
+    assert got.shape == (2, 4, S, S) and err < tol
+
+
 def test_split_batch_matches_single_stream(gpu, b16_model):
     """run_batch_split (concurrent sub-batches on separate streams, shared weights, per-stream workspaces) must give
     bit-identical labels and the same histogram as run_batch."""
