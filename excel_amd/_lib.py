@@ -156,6 +156,9 @@ SIGNATURES = {
     "excel_seg_softmax_resize": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "excel_cam_overlay_ragged": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f, c_f]),
     "excel_cam_overlay": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f]),
+    "excel_png_labels_bound_bytes": (c_sz, [c_i, c_i]),
+    "excel_png_labels_workspace_bytes": (c_sz, [c_i, c_i]),
+    "excel_png_encode_labels_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), C.POINTER(C.c_int32), c_f, c_f, c_sz, c_f, c_f, c_sz, c_f]),
     "excel_train_aug_plan": (c_i, [C.POINTER(C.c_int32), C.POINTER(AugParams), c_i, c_i, C.POINTER(TrainAugInfo), C.POINTER(C.c_int32)]),
     "excel_train_augment_workspace_bytes": (c_sz, [C.POINTER(TrainAugInfo)]),
     "excel_train_augment": (c_i, [c_f, c_f, c_f, C.POINTER(TrainAugInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f, c_f, c_f, c_f]),

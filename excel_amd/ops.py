@@ -971,6 +971,70 @@ def cam_overlay(hwc, cams, mode="max", alpha=None, mean=(123.675, 116.28, 103.53
     return out
 
 
+# ------------------------------------------------------------------ label PNG files (include/excel_hip.h, png.hip)
+_PNG_PALETTES = {}
+
+
+def png_labels_bound_bytes(H, W):
+    """Bytes that bound the PNG file of one H x W label map (excel_png_labels_bound_bytes); also the size of its slot in the arena."""
+    return int(lib().excel_png_labels_bound_bytes(int(H), int(W)))
+
+
+def png_labels_arena_bytes(hw):
+    """Arena bytes png_encode_labels_ragged needs for images of the sizes `hw` [(H, W)]: the sum of their bounds."""
+    return sum(png_labels_bound_bytes(h, w) for h, w in hw)
+
+
+def _png_palette(palette, device):
+    """uint8 [256,3] (None: utils.imutils.colormap(), the VOC colour map of SegmentationClassAug) -> flat device tensor, cached per device."""
+    import numpy as np
+    from .utils import imutils
+    pal = imutils.colormap() if palette is None else np.asarray(palette)
+    if pal.dtype != np.uint8 or pal.size != 768:
+        raise ValueError(f"palette must hold 256 RGB uint8 entries, got {pal.dtype} {pal.shape}")
+    key = (pal.tobytes(), str(device))
+    t = _PNG_PALETTES.get(key)
+    if t is None:
+        if len(_PNG_PALETTES) > 16:
+            _PNG_PALETTES.clear()
+        t = _PNG_PALETTES[key] = torch.from_numpy(np.ascontiguousarray(pal).reshape(-1).copy()).to(device)
+    return t
+
+
+def png_encode_labels_ragged(labels_flat, plan, palette=None, out=None, ws=None):
+    """tools/infer_lam.py:95 / tools/training_free_attr.py:225 for a ragged batch, on the device: the flat uint8 label maps
+    argmax_label_ragged writes (or a uniform [B,H,W] uint8 tensor with plan=None: the same entry over a plan of equal sizes) -> one
+    complete palette PNG file per image.  palette: uint8 [256,3], None = imutils.colormap() (the VOC colour map).
+    -> (bytes: flat uint8 device tensor, table: int64 device tensor [B,2] of (offset, size)); file b = bytes[off_b:off_b + size_b], and
+    off_b = the sum of png_labels_bound_bytes over the images in front, which the host knows without the table.
+    out: a flat uint8 device tensor of at least png_labels_arena_bytes(plan.hw) bytes to encode into (a view of it is returned);
+    ws: a uint8 device tensor for the row records (grown when too small is the caller's business: too small is an error)."""
+    import numpy as np
+    if plan is None:
+        if labels_flat.dim() != 3:
+            raise ValueError("plan=None needs a uniform [B,H,W] label tensor")
+        Bn, H, W = labels_flat.shape
+        plan = RaggedPlan([(H, W)] * Bn, labels_flat.device)
+    if labels_flat.dtype != torch.uint8 or labels_flat.numel() != plan.total_label_pix:
+        raise ValueError(f"labels must hold {plan.total_label_pix} uint8 values, got {labels_flat.dtype} x {labels_flat.numel()}")
+    dev = labels_flat.device
+    hw = np.ascontiguousarray(plan.hw, np.int32)
+    need = png_labels_arena_bytes(hw)
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+        raise ValueError("out= must be a flat contiguous uint8 tensor")
+    ws_need = int(lib().excel_png_labels_workspace_bytes(plan.B, int(hw[:, 0].max())))
+    if ws is None:
+        ws = _ws(ws_need, dev)
+    table = torch.empty((plan.B, 2), dtype=torch.int64, device=dev)
+    check(lib().excel_png_encode_labels_ragged(_p(labels_flat.contiguous().view(-1), torch.uint8), _p(plan.table, torch.int32), C.byref(plan.info),
+                                               hw.ctypes.data_as(C.POINTER(C.c_int32)), _p(_png_palette(palette, dev), torch.uint8),
+                                               _p(out, torch.uint8), out.numel(), _p(table, torch.int64), _p(ws, torch.uint8), ws.numel(),
+                                               _stream()), "excel_png_encode_labels_ragged")
+    return out[:need], table
+
+
 # ------------------------------------------------------------------ training augmentation (include/excel_hip.h, aug.hip)
 AUG_CANDIDATES = 10
 # one record per image, laid out like excel_aug_params (C alignment: 104 bytes)

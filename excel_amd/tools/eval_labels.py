@@ -1,0 +1,112 @@
+"""Score a directory of label PNGs against the ground truth - mirror of tools/infer_seg_coco_from_crf_pred.py:39-76 (validate_from_png).
+
+    python -m excel_amd.tools.eval_labels --pred_dir DIR --data_folder VOC2012/ --list_folder lists/ --infer_set train_aug
+
+reads `<pred_dir>/<name>.png` (what `infer_lam --save_label true` writes, or any palette / grey label PNG) and the ground truth
+(`<data_folder>/SegmentationClassAug/<name>.png`; with --dataset_name ms_coco `<data_folder>/SegmentationClass/<infer_set>/<name[13:]>.png`,
+:61), accumulates the [nc,nc] confusion matrix and prints the table infer_lam prints.  Differences from the reference, as in infer_lam:
+the files are decoded in a thread pool, the matrix is accumulated on the device (ops.confusion_accumulate), ranks take names r, r+R, ...
+and exchange their matrices once.  Without a GPU the matrix is computed with numpy (np.bincount, the arithmetic of utils/evaluate.py:9-20):
+file handling is the point of this program, not compute.  A missing prediction and a prediction whose size differs from the ground truth
+are errors that name the file.
+"""
+import argparse
+import concurrent.futures as cf
+import logging
+import os
+import time
+
+import numpy as np
+import torch
+
+from .infer_lam import VOC_CLASSES, format_scores_table, gather_hists, shard_indices
+
+
+def get_parser():
+    p = argparse.ArgumentParser()
+    p.add_argument("--pred_dir", required=True, type=str, help="directory of <name>.png label maps")
+    p.add_argument("--data_folder", required=True, type=str, help="VOC2012 root (SegmentationClassAug/) or COCO root (SegmentationClass/<split>/)")
+    p.add_argument("--list_folder", required=True, type=str, help="directory with <infer_set>.txt")
+    p.add_argument("--infer_set", default="train_aug", type=str)
+    p.add_argument("--dataset_name", default="pascal_voc", choices=["pascal_voc", "ms_coco"])
+    p.add_argument("--num_classes", default=None, type=int, help="default: 21 (pascal_voc) / 81 (ms_coco)")
+    p.add_argument("--num_workers", default=8, type=int, help="PNG decode threads")
+    p.add_argument("--batch_size", default=64, type=int, help="images decoded per device accumulation")
+    p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
+    p.add_argument("--backend", default="nccl")
+    return p
+
+
+def label_paths(args, name):
+    """(prediction, ground truth) of one list entry (infer_seg_coco_from_crf_pred.py:59-61)."""
+    if "coco" in args.dataset_name:
+        gt = os.path.join(args.data_folder, "SegmentationClass", args.infer_set, name[13:] + ".png")
+    else:
+        gt = os.path.join(args.data_folder, "SegmentationClassAug", name + ".png")
+    return os.path.join(args.pred_dir, name + ".png"), gt
+
+
+def _load_pair(args, name):
+    from PIL import Image
+    pred_path, gt_path = label_paths(args, name)
+    if not os.path.isfile(pred_path):
+        raise FileNotFoundError(f"eval_labels: no prediction for {name!r}: {pred_path} is missing")
+    gt = np.asarray(Image.open(gt_path))
+    pred = np.asarray(Image.open(pred_path))
+    if pred.shape != gt.shape or pred.ndim != 2:
+        raise ValueError(f"eval_labels: {pred_path} is {pred.shape}, the ground truth {gt_path} is {gt.shape}")
+    return np.ascontiguousarray(gt, np.uint8).reshape(-1), np.ascontiguousarray(pred, np.uint8).reshape(-1)
+
+
+def _hist_numpy(gt, pred, nc):
+    """_fast_hist (utils/evaluate.py:9-20): rows = ground truth, columns = prediction, labels >= nc (255 = ignore) dropped."""
+    gt, pred = gt.astype(np.int64), pred.astype(np.int64)
+    m = (gt < nc) & (pred < nc)
+    return np.bincount(nc * gt[m] + pred[m], minlength=nc * nc).reshape(nc, nc)
+
+
+def validate(args):
+    """-> {"score": scores_from_hist of the gathered matrix, "hist": [nc,nc] int64 (CPU tensor), "images": scored on this rank,
+    "seconds"}: the layout of infer_seg_voc.validate."""
+    from ..utils import evaluate
+    nc = args.num_classes or (81 if "coco" in args.dataset_name else 21)
+    world, rank = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0))
+    on_gpu = torch.cuda.is_available()
+    device = torch.device("cuda", args.local_rank) if on_gpu else torch.device("cpu")
+    if on_gpu:
+        torch.cuda.set_device(args.local_rank)
+    if world > 1 and not torch.distributed.is_initialized():
+        torch.distributed.init_process_group(backend=args.backend if on_gpu else "gloo")
+    with open(os.path.join(args.list_folder, args.infer_set) + ".txt") as f:
+        names = [x.split()[0] for x in f.read().split("\n") if x.strip()]
+    mine = [names[i] for i in shard_indices(len(names), rank, world)]
+    hist = torch.zeros((nc, nc), dtype=torch.int64, device=device)
+    t0 = time.time()
+    with cf.ThreadPoolExecutor(max_workers=max(1, int(args.num_workers))) as pool:
+        for s in range(0, len(mine), args.batch_size):
+            pairs = list(pool.map(lambda n: _load_pair(args, n), mine[s:s + args.batch_size]))       # raises the first error, in order
+            gt = np.concatenate([p[0] for p in pairs])
+            pred = np.concatenate([p[1] for p in pairs])
+            if on_gpu:
+                from .. import ops
+                hist = ops.confusion_accumulate(torch.from_numpy(gt).to(device), torch.from_numpy(pred).to(device), nc, hist)
+            else:
+                hist += torch.from_numpy(_hist_numpy(gt, pred, nc))
+    _, total = gather_hists(hist)
+    total = total.cpu()
+    score = evaluate.scores_from_hist(total)
+    secs = time.time() - t0
+    if rank == 0:
+        cats = VOC_CLASSES
+        if "coco" in args.dataset_name:
+            from ..datasets import coco
+            cats = coco.class_list
+        logging.info(f"label_score of {args.pred_dir}:")
+        logging.info("\n" + format_scores_table(score, cats))
+        logging.info(f"mIoU {score['miou'] * 100:.3f}  images {len(names)}  ({len(mine) / max(secs, 1e-9):.1f} img/s/rank)")
+    return {"score": score, "hist": total, "images": len(mine), "seconds": secs}
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    validate(get_parser().parse_args())

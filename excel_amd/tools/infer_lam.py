@@ -21,6 +21,10 @@ Differences from the reference, all deliberate:
     batches run.  Deliberate differences: per-class file names use the data set's own class list (the reference's voc.class_list[idx+1],
     :111, fails on COCO classes >= 20), and an image without a present class writes no max overlay (the reference's torch.max raises).
     Directories follow :242-267 (cam_output_dirs); --refine_with_aff only picks the aff_lam / seeds_lam tag there, as in the reference;
+  * `--save_label true` writes the pseudo-label map of every image as a palette PNG `<label_dir>/<name>.png` (the imsave of :95, commented
+    out in the reference; live at tools/training_free_attr.py:225): the labels the run scores, encoded on the device on the step's
+    stream (ops.png_encode_labels_ragged) with the VOC colour map, so the directory can stand in for a SegmentationClassAug directory
+    (255 = ignore) and `python -m excel_amd.tools.eval_labels` scores it.  Only file bytes come back; every rank writes its own shard;
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -60,6 +64,8 @@ def get_parser():
     p.add_argument("--save_cam", default=False, type=_bool, help="write the CAM overlay images (:97-111)")
     p.add_argument("--cam_dir", default=None, type=str, help="max-overlay directory (default: cam_output_dirs)")
     p.add_argument("--cs_cam_dir", default=None, type=str, help="per-class overlay directory (default: cam_output_dirs)")
+    p.add_argument("--save_label", default=False, type=_bool, help="write the pseudo-label maps as palette PNGs <label_dir>/<name>.png (:95)")
+    p.add_argument("--label_dir", default=None, type=str, help="label PNG directory (default: label_output_dir, next to the CAM directories)")
     p.add_argument("--data_folder", default=None, type=str, help="VOC2012 root (JPEGImages/, SegmentationClassAug/): real data instead of --synthetic")
     p.add_argument("--list_folder", default=None, type=str, help="directory with <infer_set>.txt and cls_labels_onehot.npy")
     p.add_argument("--u8_input", default=False, type=_bool, help="feed decoded uint8 HWC images and normalise on the device")
@@ -119,6 +125,14 @@ def cam_output_dirs(model_path, infer_set, training_free=True, refine_with_aff=T
             "cs_cam_dir": os.path.join(base, f"{infer_set}_{ckpt}_{tag}_class_specific_img")}
 
 
+def label_output_dir(model_path, infer_set, training_free=True, refine_with_aff=True):
+    """Where --save_label writes without --label_dir: next to cam_output_dirs' directories, <infer_set>_<ckpt>_<tag>_label."""
+    return cam_output_dirs(model_path, infer_set, training_free, refine_with_aff)["cam_dir"][:-len("_img")] + "_label"
+
+
+LABEL_WRITERS = 2        # threads that only open / write / close the device-encoded files
+
+
 def default_cam_writers(local_world=1):
     """JPEG encoder threads per rank: a quarter of this rank's CPU share (at least 1).  The decode pool gives these up (build_validation)."""
     return max(1, host_cpu_budget() // max(local_world, 1) // 4)
@@ -166,6 +180,43 @@ class _CamSaver:
         if out is not None:
             H, W = int(normed.shape[1]), int(normed.shape[2])
             self.writer.submit(out.view(-1), self._items(str(name), np.asarray(cls_lst.cpu() if hasattr(cls_lst, "cpu") else cls_lst), H, W, 0))
+
+    def close(self):
+        return self.writer.close()
+
+
+class _LabelSaver:
+    """--save_label: the step's labels -> PNG files, encoded on the device (ops.png_encode_labels_ragged), written by imutils.LabelPngWriter.
+    The arena and the row records live in grow-only buffers: the copy into the writer's pinned ring is queued on the same stream in
+    front of the next step's encoder, so one arena is enough."""
+
+    def __init__(self, args):
+        from ..utils import imutils
+        self.dir = getattr(args, "label_dir", None) or label_output_dir(getattr(args, "model_path", None), args.infer_set,
+                                                                         bool(getattr(args, "training_free", True)),
+                                                                         bool(getattr(args, "refine_with_aff", True)))
+        os.makedirs(self.dir, exist_ok=True)
+        self.writer = imutils.LabelPngWriter(LABEL_WRITERS)
+        self._arena = self._ws = None
+
+    def ragged(self, names, plan, labels_flat):
+        from .. import ops
+        if not labels_flat.is_cuda:
+            raise RuntimeError("--save_label encodes on the device: it needs GPU labels")
+        need = ops.png_labels_arena_bytes(plan.hw)
+        if self._arena is None or self._arena.numel() < need:
+            self._arena = torch.empty(need, dtype=torch.uint8, device=labels_flat.device)
+        ws_need = int(ops.lib().excel_png_labels_workspace_bytes(plan.B, int(plan.hw[:, 0].max())))
+        if self._ws is None or self._ws.numel() < ws_need:
+            self._ws = torch.empty(ws_need, dtype=torch.uint8, device=labels_flat.device)
+        data, table = ops.png_encode_labels_ragged(labels_flat, plan, out=self._arena, ws=self._ws)
+        self.writer.submit(data, table, [os.path.join(self.dir, str(n) + ".png") for n in names])
+
+    def uniform(self, names, labels):
+        """labels [B,H,W] uint8 (device): the same entry over a plan of equal sizes."""
+        from .. import ops
+        B, H, W = labels.shape
+        self.ragged(names, ops.RaggedPlan([(H, W)] * B, labels.device), labels.contiguous().view(-1))
 
     def close(self):
         return self.writer.close()
@@ -280,14 +331,25 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     writers = default_cam_writers(local_world) if save_cam else 0
     cam = _CamSaver(args, writers) if save_cam else None
+    lab = None
     try:
-        return _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers)
+        lab = _LabelSaver(args) if bool(getattr(args, "save_label", False)) else None
+        out = _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab)
+        if lab is not None:                                  # every file on disk (and a writer's error raised) before the scores are reported
+            lab, done = None, lab
+            done.close()
+        return out
     finally:
         if cam is not None:
             cam.close()
+        if lab is not None:                                  # on the way out of an exception: stop the writers, keep the first error
+            try:
+                lab.close()
+            except Exception:
+                pass
 
 
-def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers):
+def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab=None):
     from ..utils import evaluate
     from ..utils.affutils import refine_cams_with_aff, refine_cams_with_bkg_weclip
     from .. import ops
@@ -327,6 +389,8 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
             out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
             if cam is not None:                                                             # :97-111, same stream, step's own cams
                 cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, host_cls.popleft())
+            if lab is not None:                                                             # :95, same stream, the labels just scored
+                lab.ragged(names, plan, out[0] if keep else out)
             if keep:                                                                        # :116-119 record for the CRF stage
                 inter = out[1]
                 cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
@@ -372,10 +436,14 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
                 if cam is not None:                                                         # :97-111
                     cam.image(names[i], decoded[i], normed, cls_lst)
                 hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
+                if lab is not None:                                                         # :95 (uint8 as hist_from_labels scores them)
+                    lab.uniform([names[i]], labels[:1].to(torch.uint8))
         else:
             pipe.hist = hist
-            pipe.run_batch(inputs, cls_labels, gt_dev)
+            labels = pipe.run_batch(inputs, cls_labels, gt_dev)
             hist = pipe.hist
+            if lab is not None:                                                             # :95
+                lab.uniform(names, labels)
         nimg += len(imgs)
     torch.cuda.synchronize()
     return hist, nimg, time.time() - t0

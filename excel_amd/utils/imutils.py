@@ -10,6 +10,8 @@ records tools/infer_lam.py exchanges with its CRF stage.
   jet_lut / denormalize_roundtrip_table / cam_overlay_tables / CamOverlayWriter
                            tools/infer_lam.py:97-111 (--save_cam): the host half of the CAM overlay images (the blend itself is
                            excel_cam_overlay_ragged, camviz.hip)
+  LabelPngWriter           tools/infer_lam.py:95 / tools/training_free_attr.py:225 (--save_label): the host half of the label PNG files
+                           (the files themselves are encoded by excel_png_encode_labels_ragged, png.hip)
 
 Plain numpy / PIL on the host: these are file formats, not compute.  DenseCRF itself (utils/dcrf.py) is excel_amd/utils/dcrf.py over
 excel_dcrf_inference (crf.hip).
@@ -211,4 +213,102 @@ class CamOverlayWriter:
                 self.files += self._pending.pop(0).result()
         finally:
             self._pool.shutdown(wait=True)
+        return self.files
+
+
+# ------------------------------------------------------------------ label PNG files (tools/infer_lam.py:95, tools/training_free_attr.py:225)
+class LabelPngWriter:
+    """Device-encoded PNG files (ops.png_encode_labels_ragged) -> disk, off the launching thread.  submit() enqueues the D2H copy of a
+    batch's arena and its (offset, size) table into one of `slots` pinned buffers on the current stream and records an event; once the
+    event has completed the batch goes to a small thread pool that only does open / write / close.  Nothing on the host parses or patches
+    the bytes: the sizes come from the table.
+    The event discipline is DeviceFeeder's: every host-side look at an event (query, and the wait for the oldest one when the ring is
+    full, which with 4 slots is several steps old) happens in the thread that recorded it; the pool threads never touch the GPU.  A
+    pinned buffer is reused only after all its files are on disk; a writer's exception is raised by the next submit() or by close()."""
+
+    def __init__(self, threads=2, slots=4):
+        import concurrent.futures as cf
+        self.threads = max(1, int(threads))
+        self._pool = cf.ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="label_png")
+        self._slots = [dict(bytes=None, table=None, futures=[]) for _ in range(max(2, int(slots)))]
+        self._next = 0
+        self._copying = []           # [(event, slot, paths)] in submission order: copies the GPU may not have finished
+        self.files = 0
+        self.bytes = 0
+
+    @staticmethod
+    def _write(buf, table, paths, lo, hi):
+        n = 0
+        for b in range(lo, hi):
+            off, size = int(table[b, 0]), int(table[b, 1])
+            with open(paths[b], "wb") as f:
+                f.write(buf[off:off + size])
+            n += size
+        return hi - lo, n
+
+    def _collect(self, slot):
+        """Wait for the files of `slot` (re-raises a writer's exception)."""
+        futures, slot["futures"] = slot["futures"], []
+        err = None
+        for fu in futures:
+            try:
+                k, n = fu.result()
+                self.files += k
+                self.bytes += n
+            except BaseException as e:          # keep draining: the buffer must not be reused under a running writer
+                err = err or e
+        if err is not None:
+            raise err
+
+    def _dispatch(self, wait=False):
+        """Hand the batches whose copy has completed to the pool (in order); wait=True: wait for the oldest one first."""
+        while self._copying:
+            ev, slot, paths = self._copying[0]
+            if wait:
+                ev.synchronize()
+                wait = False
+            elif not ev.query():
+                return
+            self._copying.pop(0)
+            buf, table = memoryview(slot["bytes"].numpy()), slot["table"].numpy()
+            B = len(paths)
+            step = -(-B // self.threads)
+            slot["futures"] = [self._pool.submit(self._write, buf, table, paths, lo, min(B, lo + step)) for lo in range(0, B, step)]
+
+    def submit(self, dev_bytes, dev_table, paths):
+        """dev_bytes, dev_table: what ops.png_encode_labels_ragged returned (queued on the current stream); paths: one file name per image."""
+        import torch
+        if len(paths) != int(dev_table.shape[0]):
+            raise ValueError(f"{len(paths)} paths for {int(dev_table.shape[0])} images")
+        self._dispatch()
+        slot = self._slots[self._next]
+        self._next = (self._next + 1) % len(self._slots)
+        while any(s is slot for _, s, _ in self._copying):      # the ring went round: its copy must land and its files be written
+            self._dispatch(wait=True)
+        self._collect(slot)
+        if slot["bytes"] is None or slot["bytes"].numel() < dev_bytes.numel():
+            slot["bytes"] = torch.empty(dev_bytes.numel(), dtype=torch.uint8, pin_memory=True)
+        if slot["table"] is None or slot["table"].shape[0] < dev_table.shape[0]:
+            slot["table"] = torch.empty((int(dev_table.shape[0]), 2), dtype=torch.int64, pin_memory=True)
+        slot["bytes"][:dev_bytes.numel()].copy_(dev_bytes, non_blocking=True)
+        slot["table"][:dev_table.shape[0]].copy_(dev_table, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._copying.append((ev, slot, [str(p) for p in paths]))
+
+    def close(self):
+        """Wait for every file; -> the number of files written.  Re-raises the first writer's exception."""
+        err = None
+        try:
+            while self._copying:
+                self._dispatch(wait=True)
+            for slot in self._slots:
+                try:
+                    self._collect(slot)
+                except BaseException as e:
+                    err = err or e
+        finally:
+            self._pool.shutdown(wait=True)
+        if err is not None:
+            raise err
         return self.files

@@ -507,6 +507,29 @@ int excel_cam_overlay_ragged(const uint8_t* hwc, const float* cams, int Cmax, co
                              const int32_t* table, const excel_ragged_info* info, int mode, const double* tables, uint8_t* out, void* stream);
 int excel_cam_overlay(const uint8_t* hwc, const float* cams, int k, int H, int W, int mode, const double* tables, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ label PNG files (png.hip)
+ * The label image the reference saves per sample (tools/infer_lam.py:95, commented out there; tools/training_free_attr.py:225, live), for a
+ * ragged batch: labels = the tight uint8 label maps excel_argmax_label_ragged writes (image b at loff_b) -> one COMPLETE palette PNG file
+ * per image in `arena`, so that only file bytes cross to the host and nothing there parses or patches them.
+ *   file    signature; IHDR (W_b x H_b, 8 bit, colour type 3, no interlace); PLTE = the 256 RGB entries of `palette` (device, 768 bytes);
+ *           one IDAT; IEND - every chunk with its CRC-32.
+ *   IDAT    a zlib stream (0x78 0x01): ONE final deflate block with the fixed Huffman table (BTYPE = 01) that holds literals and matches
+ *           at distance 1 only (lengths 3..258; a run of L equal bytes = literal, (L-1)/258 matches of 258, then the remainder as one
+ *           match, or as literals when it is below 3), scanlines with filter type 0 coded independently and joined at bit granularity,
+ *           then the Adler-32 of the unfiltered scanlines.
+ *   layout  image b's file starts at the sum of excel_png_labels_bound_bytes(H_i, W_i) over i < b; out_table (device int64 [B][2]) receives
+ *           (offset, size) of every file.  The bytes are a pure function of the image's labels and the palette (no dependence on the
+ *           batch, the stream or the launch order); arena bytes outside the files are zero.
+ * excel_png_labels_bound_bytes = ceil(9 (W + 1) H / 8) + 880, rounded up to 16: every byte as a 9-bit literal is the worst case.
+ * hw (HOST int32 [B][2]) = the (H_b, W_b) the plan was built from: the sizes are checked against arena_bytes / workspace_bytes before any
+ * launch.  workspace: excel_png_labels_workspace_bytes(B, max H_b) bytes, 8-byte aligned; arena 4-byte aligned (it is cleared and the
+ * codes are OR-ed in with 32-bit atomics).  Limits: 9 (W_b + 1) H_b < 2^32 - 10, B <= 65535. */
+size_t excel_png_labels_bound_bytes(int H, int W);
+size_t excel_png_labels_workspace_bytes(int B, int max_h);
+int excel_png_encode_labels_ragged(const uint8_t* labels, const int32_t* table, const excel_ragged_info* info, const int32_t* hw /*host*/,
+                                   const uint8_t* palette, uint8_t* arena, size_t arena_bytes, int64_t* out_table, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation (aug.hip)
  * VOC12ClsDataset(aug=True)'s transform (datasets/voc.py:110-117 over datasets/transforms.py) for a ragged batch of decoded uint8
  * images and label maps on the device, in the reference's order:
