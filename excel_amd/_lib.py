@@ -130,6 +130,9 @@ SIGNATURES = {
     "excel_clip_feature_surgery": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, c_f, c_f, c_f, c_f]),
     "excel_dcrf_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "excel_dcrf_inference": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, c_f, c_f, c_f]),
+    "excel_dcrf_ragged_workspace_bytes": (c_i, [c_ll, c_i, C.POINTER(c_sz)]),
+    "excel_dcrf_inference_ragged": (c_i, [c_f, c_f, c_i, c_f, C.POINTER(RaggedInfo), c_i, c_i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          c_f, c_f, c_f, c_f]),
     "excel_attn_layer_mean": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "excel_trans_mat_workspace_bytes": (c_sz, [c_i, c_i]),
     "excel_compute_trans_mat": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f]),
@@ -154,6 +157,7 @@ SIGNATURES = {
     "excel_seg_resize_argmax_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f]),
     "excel_seg_resize_argmax_uniform": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_f, c_f]),
     "excel_seg_softmax_resize": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "excel_seg_softmax_resize_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f]),
     "excel_cam_overlay_ragged": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f, c_f]),
     "excel_cam_overlay": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f]),
     "excel_png_labels_bound_bytes": (c_sz, [c_i, c_i]),

@@ -142,6 +142,16 @@ __device__ __forceinline__ Tile tile_of(const TileGeo& g) {
     }
     return t;
 }
+// Kernels that walk the tight pixels of a ragged batch as ONE array (n in [0, total_label_pix)): the image that holds pixel n = the
+// last record whose loff <= n (binary search over the B records; every image has at least one pixel, so loff is strictly increasing).
+__device__ __forceinline__ int ragged_image_of_pixel(const int* __restrict__ tab, int B, long long n) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((long long)tab[EXCEL_RAG_REC * mid + 4] <= n) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
 
 // ---------------------------------------------------------------- optional per-category HIP-event profiling
 // (bench.py enables it to get live per-kernel durations on the launch stream; off by default: zero overhead)

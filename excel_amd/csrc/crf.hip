@@ -1,18 +1,25 @@
 // Fully-connected CRF post-processing (utils/dcrf.py:42-68 class DenseCRF, :7-40 crf_inference*; driven by tools/infer_lam.py:179-237):
 // mean-field inference with a Gaussian (x,y) and a bilateral (x,y,r,g,b) Potts term, message passing = high-dimensional Gaussian
 // filtering on the permutohedral lattice (Adams, Baek & Davis 2010), as Kraehenbuehl & Koltun's densecrf - the library behind the
-// reference's pydensecrf dependency - does it.  Everything on the device, one image per call:
+// reference's pydensecrf dependency - does it.  Everything on the device, for ONE image (excel_dcrf_inference) or for a GROUP of images
+// of a ragged batch in the same chain of launches (excel_dcrf_inference_ragged: the group is one array of sum H_b W_b pixels with
+// image-local (x, y); the image index rides in the spare short 7 of every lattice key, so one hash table per lattice kind serves the
+// group, no blur neighbour crosses an image, and every image gets the bits it gets alone):
 //   crf_lattice_kernel<D>   per pixel: feature -> elevate -> nearest 0-coloured lattice point -> rank -> barycentric weights + the D+1 vertex keys
 //   crf_hash_insert         open-addressing hash of vertex keys (atomicCAS claims a slot for the first vertex with a key; later ones compare)
 //   crf_offsets / crf_neighbors   vertex -> lattice point index; per lattice point and axis the two blur neighbours (key -+ 1, axis j: +- D)
-//   splat (64-bit fixed-point atomics: the sum is order independent, so results are bit-reproducible although lattice indices are
+//   crf_csr_*   per lattice point the list of its vertices (built in tables that are dead once the neighbours are found)
+//   splat (a segmented sum over those lists in 64-bit fixed point: the sum is order independent, so results are bit-reproducible although lattice indices are
 //   handed out by an atomic counter) -> D+1 blur passes -> slice, symmetric normalisation 1/sqrt(K 1)
 //   mean field: Q = softmax(-U); 10 x { Q = softmax(-U + w_g K_g Q + w_b K_b Q) }
+#include "../../include/excel_hip.h"
 #include "common.h"
 #include "excel_internal.h"
 
 #define TRY(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
-#define CRF_KS 8                 // shorts per stored key (D <= 7)
+#define CRF_KS 8                 // shorts per stored key (D <= 6: short 7 carries the image index of a group)
+#define CRF_IMG_SLOT 7
+#define CRF_MAX_IMAGES 32767
 #define CRF_FIX 1099511627776.0  // 2^40 fixed-point scale of the splat accumulators
 
 struct CrfKey { unsigned long long a, b; };   // 8 shorts
@@ -33,12 +40,21 @@ __device__ __forceinline__ int crf_getk(const CrfKey& k, int i) {
 }
 
 // feature layout of DenseCRF2D (densecrf.cpp addPairwiseGaussian / addPairwiseBilateral): (x/sxy, y/sxy[, r/srgb, g/srgb, b/srgb])
+// tab == nullptr: one image of H x W.  Otherwise pixel n of a group of B images (ragged table `tab`): image b = ragged_image_of_pixel,
+// (x, y) local to it, the key tagged with b.  rgb is packed like the pixels (image b at 3 * loff_b), so it is indexed by n either way.
 template <int D>
-__global__ __launch_bounds__(256) void crf_lattice_kernel(const unsigned char* __restrict__ rgb, int H, int W, float sxy, float srgb,
-                                                          CrfKey* __restrict__ keys, float* __restrict__ bary) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= H * W) return;
-    const int x = n % W, y = n / W;
+__global__ __launch_bounds__(256) void crf_lattice_kernel(const unsigned char* __restrict__ rgb, const int* __restrict__ tab, int B, long long N, int H,
+                                                          int W, float sxy, float srgb, CrfKey* __restrict__ keys, float* __restrict__ bary) {
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    int img = 0, loc = (int)n;
+    if (tab) {
+        img = ragged_image_of_pixel(tab, B, n);
+        const int* rec = tab + EXCEL_RAG_REC * img;
+        W = rec[1];
+        loc = (int)(n - rec[4]);
+    }
+    const int x = loc % W, y = loc / W;
     float f[D];
     f[0] = (float)x / sxy;
     f[1] = (float)y / sxy;
@@ -101,6 +117,7 @@ __global__ __launch_bounds__(256) void crf_lattice_kernel(const unsigned char* _
             const int can = (rank[i] <= D - r) ? r : r - (D + 1);
             crf_setk(k, i, rem0[i] + can);
         }
+        crf_setk(k, CRF_IMG_SLOT, img);
         keys[(long long)n * (D + 1) + r] = k;
         bary[(long long)n * (D + 1) + r] = bc[r];
     }
@@ -160,6 +177,9 @@ __global__ __launch_bounds__(256) void crf_neighbors_kernel(const CrfKey* __rest
         crf_setk(n1, c, (c == j) ? v + D : v - 1);
         crf_setk(n2, c, (c == j) ? v - D : v + 1);
     }
+    const int img = crf_getk(k, CRF_IMG_SLOT);                  // neighbours stay inside the image
+    crf_setk(n1, CRF_IMG_SLOT, img);
+    crf_setk(n2, CRF_IMG_SLOT, img);
     nbr[(long long)j * Mcap + i] = make_int2(crf_find(n1, keys, table, mask, latidx), crf_find(n2, keys, table, mask, latidx));
 }
 
@@ -178,24 +198,51 @@ struct CrfSide {                 // one lattice as the message-passing kernels s
     long long npv;
     int Dp1;
     float alpha;                 // 1 / (1 + 2^-D)
+    const int *seg_start, *seg_cnt, *seg_list;   // per lattice point: its vertices list[start .. start + cnt) (segmented splat)
 };
 
-// splat: acc[o][k] += w * (in[n][k] * norm[n]) in 2^-40 fixed point (integer sums commute: deterministic).  Grid-stride over one side.
+// splat: acc[o][k] = sum over the vertices of lattice point o of w * (in[n][k] * norm[n]), in 2^-40 fixed point (integer sums commute:
+// bit-reproducible whatever the order of a list).  No atomics: lattice point i adds up the vertices of its list (built once per lattice,
+// crf_csr_*), which gives the bits the earlier 64-bit atomicAdd splat gave and measured faster (EXPERIMENTS "Batched DenseCRF").  One
+// thread per (i, k), k fastest: the threads of a point walk the same list (broadcast loads) and read `in` along k.
 __device__ __forceinline__ void crf_splat_side(const float* __restrict__ in, int use_norm, const CrfSide& L, int C) {
-    const long long total = L.npv * C, stride = (long long)gridDim.x * 256;
+    const long long total = (long long)(*L.counter) * C, stride = (long long)gridDim.x * 256;
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
-        const long long pv = t / C;
-        const int k = (int)(t - pv * C);
-        const long long n = pv / L.Dp1;
-        float v = in[n * C + k];
-        if (use_norm) v = __fmul_rn(v, L.norm[n]);
-        const float wv = __fmul_rn(L.bary[pv], v);
-        atomicAdd(reinterpret_cast<unsigned long long*>(&L.acc[(long long)L.offset[pv] * C + k]), (unsigned long long)(long long)__double2ll_rn((double)wv * CRF_FIX));
+        const int i = (int)(t / C), k = (int)(t - (long long)i * C);
+        const int* lst = L.seg_list + L.seg_start[i];
+        const int cnt = L.seg_cnt[i];
+        long long sum = 0;
+        for (int e = 0; e < cnt; ++e) {
+            const long long pv = lst[e];
+            const long long n = pv / L.Dp1;
+            float v = in[n * C + k];
+            if (use_norm) v = __fmul_rn(v, L.norm[n]);
+            const float wv = __fmul_rn(L.bary[pv], v);
+            sum += (long long)__double2ll_rn((double)wv * CRF_FIX);
+        }
+        L.acc[t] = sum;
     }
 }
 __global__ __launch_bounds__(256) void crf_splat2_kernel(const float* __restrict__ in, int use_norm, CrfSide g, CrfSide b, int C) {
     crf_splat_side(in, use_norm, g, C);
     crf_splat_side(in, use_norm, b, C);
+}
+// vertex lists per lattice point: count, hand every point a segment (in any order: the sum does not care), fill
+__global__ __launch_bounds__(256) void crf_csr_count_kernel(const int* __restrict__ offset, long long npv, int* __restrict__ cnt) {
+    const long long pv = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pv < npv) atomicAdd(&cnt[offset[pv]], 1);
+}
+__global__ __launch_bounds__(256) void crf_csr_start_kernel(const int* __restrict__ cnt, const int* __restrict__ counter, int* __restrict__ cursor,
+                                                            int* __restrict__ start) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < *counter) start[i] = atomicAdd(cursor, cnt[i]);
+}
+__global__ __launch_bounds__(256) void crf_csr_fill_kernel(const int* __restrict__ offset, long long npv, const int* __restrict__ start,
+                                                           int* __restrict__ fill, int* __restrict__ list) {
+    const long long pv = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pv >= npv) return;
+    const int o = offset[pv];
+    list[start[o] + atomicAdd(&fill[o], 1)] = (int)pv;
 }
 __device__ __forceinline__ float crf_fix(long long a) { return (float)((double)a * (1.0 / CRF_FIX)); }
 // blur pass j of one lattice: grid-stride over its M lattice points (M is read on the device: the bilateral lattice of
@@ -258,11 +305,20 @@ __global__ __launch_bounds__(256) void crf_make_norm2_kernel(CrfSide g, CrfSide 
     norm_b[n] = 1.0f / sqrtf(vb.slice(crf_final_lat(b), 0, b.alpha) + 1e-20f);
 }
 // slice both messages + the mean-field update of one pixel:  Q = softmax(-U + w_g K_g Q + w_b K_b Q).  U [C,N] (plane-major, as
-// unary_from_softmax lays it out); Q [N,C].  have_msg = 0: the initial Q = softmax(-U).
-__global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict__ prob, int is_energy, long long N, int C, int have_msg, CrfSide g, float wg,
-                                                         CrfSide b, float wb, float* __restrict__ Q, float* __restrict__ out_cn) {
+// unary_from_softmax lays it out); Q [N,C].  have_msg = 0: the initial Q = softmax(-U).  With a ragged table U and out_cn are tight
+// [C, H_b, W_b] per image (image b at C * loff_b) and pixel n reads / writes the planes of its own image; lab (optional) = the arg-max
+// of the q values written, first maximum (excel_argmax_label's rule).
+__global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict__ prob, int is_energy, const int* __restrict__ tab, int B, long long N, int C,
+                                                         int have_msg, CrfSide g, float wg, CrfSide b, float wb, float* __restrict__ Q,
+                                                         float* __restrict__ out_cn, unsigned char* __restrict__ lab) {
     const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
+    long long ps = N, po = n;                                   // plane stride and offset of pixel n in U / out_cn
+    if (tab) {
+        const int* rec = tab + EXCEL_RAG_REC * ragged_image_of_pixel(tab, B, n);
+        ps = (long long)rec[0] * rec[1];
+        po = (long long)C * rec[4] + (n - rec[4]);
+    }
     CrfVerts<3> vg;
     CrfVerts<6> vb;
     float ng = 0.f, nb = 0.f;
@@ -270,7 +326,7 @@ __global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict
     if (have_msg) { vg.load(g, n, C); vb.load(b, n, C); ng = g.norm[n]; nb = b.norm[n]; }
     float mx = -INFINITY;
     for (int k = 0; k < C; ++k) {
-        const float pv = prob[(long long)k * N + n];
+        const float pv = prob[(long long)k * ps + po];
         const float u = is_energy ? pv : -logf(fminf(fmaxf(pv, 1e-5f), 1.0f));                  // unary_from_softmax (clip 1e-5)
         float t = -u;
         if (have_msg) {
@@ -282,11 +338,15 @@ __global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict
     }
     float sum = 0.f;
     for (int k = 0; k < C; ++k) { const float e = expf(Q[n * C + k] - mx); Q[n * C + k] = e; sum += e; }
+    float best = 0.f;
+    int bi = 0;
     for (int k = 0; k < C; ++k) {
         const float q = Q[n * C + k] / sum;
         Q[n * C + k] = q;
-        if (out_cn) out_cn[(long long)k * N + n] = q;
+        if (out_cn) out_cn[(long long)k * ps + po] = q;
+        if (k == 0 || q > best) { best = q; bi = k; }
     }
+    if (lab) lab[n] = (unsigned char)bi;
 }
 
 struct CrfLattice {
@@ -323,24 +383,53 @@ static CrfLattice crf_lattice_layout(char*& p, long long N, int D) {
     return L;
 }
 
-extern "C" size_t excel_dcrf_workspace_bytes(int H, int W, int C) {
-    const long long N = (long long)H * W;
-    // per lattice: build tables + fixed-point accumulators [npv*C] + two float lattices [npv*C]; Q [N,C]; ones [N]
+// per lattice: build tables + fixed-point accumulators [npv*C] + two float lattices [npv*C]; Q [N,C]; ones [N].  N = the pixels of the
+// image, or of the whole group: the group shares one set of tables, so a group of one costs what the image costs alone.
+static size_t crf_workspace_bytes(long long N, int C) {
     return crf_lattice_bytes(N, 2, nullptr) + crf_lattice_bytes(N, 5, nullptr) + crf_al(8 * (N * 3) * C) + 2 * crf_al(4 * (N * 3) * C) +
            crf_al(8 * (N * 6) * C) + 2 * crf_al(4 * (N * 6) * C) + crf_al(4 * N * C) + crf_al(4 * N);
 }
+// vertex indices (6 per pixel on the bilateral lattice) are ints and the hash table holds 2x as many slots, counted in 32 bits
+static bool crf_fits(long long N) { return N >= 1 && N * 6 <= (1ll << 30); }
+
+extern "C" size_t excel_dcrf_workspace_bytes(int H, int W, int C) {
+    return crf_workspace_bytes((long long)H * W, C);
+}
+
+extern "C" int excel_dcrf_ragged_workspace_bytes(long long total_label_pix, int C, size_t* bytes) {
+    EXCEL_CHECK_ARG(bytes && C >= 1 && total_label_pix >= 1, "dcrf_ragged_workspace_bytes: bad argument");
+    EXCEL_CHECK_ARG(crf_fits(total_label_pix), "dcrf_ragged_workspace_bytes: a group of %lld pixels has more lattice vertices (6 per pixel) than "
+                    "the 32-bit vertex indices hold: split it (ops.dcrf_groups)", total_label_pix);
+    *bytes = crf_workspace_bytes(total_label_pix, C);
+    return EXCEL_OK;
+}
 
 template <int D>
-static int crf_build(const CrfLattice& L, const unsigned char* rgb, int H, int W, float sxy, float srgb, hipStream_t st) {
-    const long long N = (long long)H * W;
+static int crf_build(const CrfLattice& L, const unsigned char* rgb, const int* tab, int B, long long N, int H, int W, float sxy, float srgb,
+                     hipStream_t st) {
     hipMemsetAsync(L.table, 0xFF, 4ull * (L.mask + 1), st);
     hipMemsetAsync(L.counter, 0, 4, st);
-    hipLaunchKernelGGL(crf_lattice_kernel<D>, dim3((unsigned)cdivl(N, 256)), dim3(256), 0, st, rgb, H, W, sxy, srgb, L.keys, L.bary);
+    hipLaunchKernelGGL(crf_lattice_kernel<D>, dim3((unsigned)cdivl(N, 256)), dim3(256), 0, st, rgb, tab, B, N, H, W, sxy, srgb, L.keys, L.bary);
     hipLaunchKernelGGL(crf_hash_insert_kernel, dim3((unsigned)cdivl(L.npv, 256)), dim3(256), 0, st, L.keys, L.npv, L.table, L.mask, L.rep, L.latidx, L.counter, L.lkeys);
     hipLaunchKernelGGL(crf_offsets_kernel, dim3((unsigned)cdivl(L.npv, 256)), dim3(256), 0, st, L.rep, L.latidx, L.npv, L.offset);
     hipLaunchKernelGGL(crf_neighbors_kernel<D>, dim3((unsigned)cdivl(L.npv * (D + 1), 256)), dim3(256), 0, st, L.lkeys, L.counter, L.keys, L.table, L.mask,
                        L.latidx, L.nbr, L.npv);
     EXCEL_CHECK_LAUNCH("dcrf lattice build");
+    return EXCEL_OK;
+}
+
+// The vertex lists live in tables that are dead once the neighbours are found: cnt / fill in lkeys (4 ints per vertex), start in latidx,
+// the list in keys, the segment cursor in table[0].  No workspace of their own.
+static int crf_csr_build(const CrfLattice& L, CrfSide& s, hipStream_t st) {
+    int *cnt = (int*)L.lkeys, *fill = cnt + L.npv, *start = L.latidx, *list = (int*)L.keys, *cursor = L.table;
+    hipMemsetAsync(cnt, 0, 8ull * L.npv, st);
+    hipMemsetAsync(cursor, 0, 4, st);
+    const unsigned gv = (unsigned)cdivl(L.npv, 256);
+    hipLaunchKernelGGL(crf_csr_count_kernel, dim3(gv), dim3(256), 0, st, L.offset, L.npv, cnt);
+    hipLaunchKernelGGL(crf_csr_start_kernel, dim3(gv), dim3(256), 0, st, cnt, L.counter, cursor, start);
+    hipLaunchKernelGGL(crf_csr_fill_kernel, dim3(gv), dim3(256), 0, st, L.offset, L.npv, start, fill, list);
+    EXCEL_CHECK_LAUNCH("dcrf vertex lists");
+    s.seg_start = start; s.seg_cnt = cnt; s.seg_list = list;
     return EXCEL_OK;
 }
 
@@ -355,19 +444,20 @@ static int crf_pass(const CrfSide& g, const CrfSide& b, const float* in, int use
     return EXCEL_OK;
 }
 
-extern "C" int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* prob, int prob_is_energy, int H, int W, int C, int iters, float pos_w,
-                                    float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q_out, void* workspace, void* stream) {
-    EXCEL_CHECK_ARG(rgb_hwc && prob && q_out && workspace && H > 0 && W > 0 && C >= 1 && iters >= 0, "dcrf_inference: bad argument");
+struct CrfParams { int iters; float pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std; };
+
+// The one chain of launches behind both entries: N pixels = one image (tab == nullptr, H x W) or a group of B images (tab).
+static int crf_run(const unsigned char* rgb_hwc, const float* prob, int prob_is_energy, const int* tab, int B, long long N, int H, int W, int C,
+                   const CrfParams& P, float* q_out, unsigned char* labels, void* workspace, hipStream_t st) {
     static_assert(true, "the message-passing kernels are written for the D = 2 (Gaussian) and D = 5 (bilateral) lattices of DenseCRF2D");
-    EXCEL_CHECK_ARG(pos_xy_std > 0.f && bi_xy_std > 0.f && bi_rgb_std > 0.f, "dcrf_inference: standard deviations must be positive");
-    hipStream_t st = (hipStream_t)stream;
-    const long long N = (long long)H * W;
+    const int iters = P.iters;
     char* p = (char*)workspace;
     CrfLattice Lg = crf_lattice_layout(p, N, 2), Lb = crf_lattice_layout(p, N, 5);
     CrfSide sg, sb;
     auto side = [&](CrfSide& s, const CrfLattice& L) {
         s.offset = L.offset; s.bary = L.bary; s.norm = L.norm; s.nbr = L.nbr; s.counter = L.counter; s.npv = L.npv; s.Dp1 = L.D + 1;
         s.alpha = 1.0f / (1.0f + powf(2.0f, (float)-L.D));
+        s.seg_start = s.seg_cnt = s.seg_list = nullptr;
         s.acc = (long long*)p; p += crf_al(8 * L.npv * C);
         s.lat0 = (float*)p; p += crf_al(4 * L.npv * C);
         s.lat1 = (float*)p; p += crf_al(4 * L.npv * C);
@@ -376,8 +466,10 @@ extern "C" int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* p
     side(sb, Lb);
     float* Q = (float*)p; p += crf_al(4 * N * C);
     float* ones = (float*)p; p += crf_al(4 * N);
-    TRY(crf_build<2>(Lg, rgb_hwc, H, W, pos_xy_std, 1.f, st));
-    TRY(crf_build<5>(Lb, rgb_hwc, H, W, bi_xy_std, bi_rgb_std, st));
+    TRY(crf_build<2>(Lg, rgb_hwc, tab, B, N, H, W, P.pos_xy_std, 1.f, st));
+    TRY(crf_build<5>(Lb, rgb_hwc, tab, B, N, H, W, P.bi_xy_std, P.bi_rgb_std, st));
+    TRY(crf_csr_build(Lg, sg, st));
+    TRY(crf_csr_build(Lb, sb, st));
     // the accumulators are cleared once; every message pass leaves them cleared (blur pass 1)
     hipMemsetAsync(sg.acc, 0, 8ull * Lg.npv * C, st);
     hipMemsetAsync(sb.acc, 0, 8ull * Lb.npv * C, st);
@@ -391,11 +483,38 @@ extern "C" int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* p
     // normalisers: norm = 1 / sqrt(K 1 + 1e-20)
     TRY(crf_pass(sg, sb, ones, 0, 1, st));
     hipLaunchKernelGGL(crf_make_norm2_kernel, dim3(gn), dim3(256), 0, st, sg, sb, N, Lg.norm, Lb.norm);
-    hipLaunchKernelGGL(crf_update_kernel, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, N, C, 0, sg, 0.f, sb, 0.f, Q, iters == 0 ? q_out : nullptr);
+    hipLaunchKernelGGL(crf_update_kernel, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, tab, B, N, C, 0, sg, 0.f, sb, 0.f, Q,
+                       iters == 0 ? q_out : nullptr, iters == 0 ? labels : nullptr);
     for (int it = 0; it < iters; ++it) {
         TRY(crf_pass(sg, sb, Q, 1, C, st));
-        hipLaunchKernelGGL(crf_update_kernel, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, N, C, 1, sg, pos_w, sb, bi_w, Q, it == iters - 1 ? q_out : nullptr);
+        const bool last = it == iters - 1;
+        hipLaunchKernelGGL(crf_update_kernel, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, tab, B, N, C, 1, sg, P.pos_w, sb, P.bi_w, Q,
+                           last ? q_out : nullptr, last ? labels : nullptr);
     }
     EXCEL_CHECK_LAUNCH("dcrf mean field");
     return EXCEL_OK;
+}
+
+extern "C" int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* prob, int prob_is_energy, int H, int W, int C, int iters, float pos_w,
+                                    float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q_out, void* workspace, void* stream) {
+    EXCEL_CHECK_ARG(rgb_hwc && prob && q_out && workspace && H > 0 && W > 0 && C >= 1 && iters >= 0, "dcrf_inference: bad argument");
+    EXCEL_CHECK_ARG(pos_xy_std > 0.f && bi_xy_std > 0.f && bi_rgb_std > 0.f, "dcrf_inference: standard deviations must be positive");
+    const CrfParams P{iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std};
+    return crf_run(rgb_hwc, prob, prob_is_energy, nullptr, 1, (long long)H * W, H, W, C, P, q_out, nullptr, workspace, (hipStream_t)stream);
+}
+
+// tools/infer_seg_voc.py:103-174 (crf_proc), tools/infer_seg_coco.py:144-145 and utils/dcrf.py:42-68 for a group of images at once
+extern "C" int excel_dcrf_inference_ragged(const uint8_t* hwc, const float* unary, int unary_is_energy, const int32_t* table,
+                                           const excel_ragged_info* info, int C, int iters, float pos_w, float pos_xy_std, float bi_w,
+                                           float bi_xy_std, float bi_rgb_std, uint8_t* labels_u8, float* q_out, void* workspace, void* stream) {
+    EXCEL_CHECK_ARG(hwc && unary && table && info && workspace, "dcrf_inference_ragged: null argument");
+    EXCEL_CHECK_ARG(labels_u8 || q_out, "dcrf_inference_ragged: ask for labels, Q or both");
+    EXCEL_CHECK_ARG(info->B > 0 && info->B <= CRF_MAX_IMAGES, "dcrf_inference_ragged: %d images, need 1..%d", info->B, CRF_MAX_IMAGES);
+    EXCEL_CHECK_ARG(C >= 1 && iters >= 0, "dcrf_inference_ragged: need C >= 1 and iters >= 0");
+    EXCEL_CHECK_ARG(!labels_u8 || C <= 256, "dcrf_inference_ragged: uint8 labels need C <= 256 (C = %d)", C);
+    EXCEL_CHECK_ARG(pos_xy_std > 0.f && bi_xy_std > 0.f && bi_rgb_std > 0.f, "dcrf_inference_ragged: standard deviations must be positive");
+    EXCEL_CHECK_ARG(crf_fits(info->total_label_pix), "dcrf_inference_ragged: a group of %lld pixels has more lattice vertices (6 per pixel) than "
+                    "the 32-bit vertex indices hold: split it (ops.dcrf_groups)", (long long)info->total_label_pix);
+    const CrfParams P{iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std};
+    return crf_run(hwc, unary, unary_is_energy, table, info->B, info->total_label_pix, 0, 0, C, P, q_out, labels_u8, workspace, (hipStream_t)stream);
 }

@@ -8,6 +8,7 @@
 //                           resized nc-class logits never reach memory (bilinear_resize_kernel + argmax_key, same bits)
 //   seg_resize_argmax_uniform the same kernel with a tight uniform [B, nc, h, w] source (the decoder's seg logits of one batch)
 //   seg_softmax_resize      one image's pitched planes -> (bilinear to (H, W)) -> softmax over classes -> tight [nc,H,W]: the CRF's input
+//   seg_softmax_resize_ragged  the same kernel over every image of a batch in one launch (source and target sizes from two plans)
 //
 // All three are gather-bound: the sources are small (2B * nc * g^2 floats per scale, L2-resident) and each output pixel reads 4 (8 with
 // the flip) of them per class and scale.  Tiles are the 64 x 16 pixel tiles of the ragged plan (common.h).
@@ -160,12 +161,23 @@ __global__ __launch_bounds__(256) void seg_resize_argmax_ragged_kernel(const flo
 }
 
 // One lane per output pixel; three passes over the classes (max, sum of exp, store) re-gather the (L2-resident) source instead of
-// holding nc values in registers.
-__global__ __launch_bounds__(256) void seg_softmax_resize_kernel(const float* __restrict__ src, int h, int w, int nc, int H, int W,
-                                                                 float* __restrict__ prob) {
+// holding nc values in registers.  dtab == nullptr: one image, (h, w) -> (H, W).  Otherwise pixel i of the tight pixels of the target
+// plan `dtab` (B images): its image's sizes and offsets come from record b of the two plans (source planes at nc * poff_b, target
+// [nc, H_b, W_b] at nc * loff_b).
+__global__ __launch_bounds__(256) void seg_softmax_resize_kernel(const float* __restrict__ src, const int* __restrict__ stab,
+                                                                 const int* __restrict__ dtab, int B, long long total, int h, int w, int nc, int H,
+                                                                 int W, float* __restrict__ prob) {
+    long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    if (dtab) {
+        const int b = ragged_image_of_pixel(dtab, B, i);
+        const int *sr = stab + EXCEL_RAG_REC * b, *dr = dtab + EXCEL_RAG_REC * b;
+        h = sr[0]; w = sr[1]; H = dr[0]; W = dr[1];
+        src += (long long)nc * sr[2];
+        prob += (long long)nc * dr[4];
+        i -= dr[4];
+    }
     const long long HW = (long long)H * W;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= HW) return;
     const int x = (int)(i % W), y = (int)(i / W);
     const int wp = (w + 3) & ~3;
     const long long hw = (long long)h * wp;
@@ -254,7 +266,22 @@ extern "C" int excel_seg_softmax_resize(const float* planes, int h, int w, int n
     EXCEL_CHECK_ARG((long long)nc * h * ((w + 3) & ~3) <= kI32 && (long long)nc * H * W <= kI32,
                     "seg_softmax_resize: nc * h * Wp and nc * H * W must stay below 2^31");
     const long long n = (long long)H * W;
-    hipLaunchKernelGGL(seg_softmax_resize_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST(stream), planes, h, w, nc, H, W, prob);
+    hipLaunchKernelGGL(seg_softmax_resize_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST(stream), planes, (const int*)nullptr,
+                       (const int*)nullptr, 1, n, h, w, nc, H, W, prob);
     EXCEL_CHECK_LAUNCH("seg_softmax_resize");
+    return EXCEL_OK;
+}
+
+extern "C" int excel_seg_softmax_resize_ragged(const float* planes, const int32_t* src_table, const excel_ragged_info* src_info,
+                                               const int32_t* dst_table, const excel_ragged_info* dst_info, int nc, float* prob, void* stream) {
+    EXCEL_CHECK_ARG(planes && src_table && src_info && dst_table && dst_info && prob, "seg_softmax_resize_ragged: null argument");
+    EXCEL_CHECK_ARG(nc >= 1, "seg_softmax_resize_ragged: nc >= 1");
+    EXCEL_CHECK_ARG(src_info->B == dst_info->B && src_info->B >= 1, "seg_softmax_resize_ragged: the two plans hold %d and %d images",
+                    src_info->B, dst_info->B);
+    EXCEL_CHECK_ARG((long long)nc * src_info->total_pix <= kI32, "seg_softmax_resize_ragged: nc * total_pix must stay below 2^31");
+    const long long n = dst_info->total_label_pix;
+    hipLaunchKernelGGL(seg_softmax_resize_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST(stream), planes, src_table, dst_table,
+                       dst_info->B, n, 0, 0, nc, 0, 0, prob);
+    EXCEL_CHECK_LAUNCH("seg_softmax_resize_ragged");
     return EXCEL_OK;
 }

@@ -645,6 +645,19 @@ def seg_softmax_resize(planes, plan, b, nc, H, W):
     return prob
 
 
+def seg_softmax_resize_ragged(planes, src_plan, dst_plan, nc):
+    """seg_softmax_resize for every image of a ragged batch in one launch (excel_seg_softmax_resize_ragged): nc pitched planes per
+    image at src_plan's sizes -> tight [nc, H_b, W_b] probabilities per image at dst_plan's sizes, image b at nc * loff_b (flat)."""
+    if src_plan.B != dst_plan.B:
+        raise ValueError(f"seg_softmax_resize_ragged: plans of {src_plan.B} and {dst_plan.B} images")
+    if planes.numel() != nc * src_plan.total_pix:
+        raise ValueError(f"seg_softmax_resize_ragged: planes must hold nc * total_pix = {nc * src_plan.total_pix} floats")
+    prob = torch.empty((nc * dst_plan.total_label_pix,), dtype=torch.float32, device=planes.device)
+    check(lib().excel_seg_softmax_resize_ragged(_p(planes), _p(src_plan.table, torch.int32), C.byref(src_plan.info), _p(dst_plan.table, torch.int32),
+                                                C.byref(dst_plan.info), int(nc), _p(prob), _stream()), "excel_seg_softmax_resize_ragged")
+    return prob
+
+
 # ------------------------------------------------------------------ CAM
 def clip_feature_surgery(image_features, text_features, num_fg=None, t=2.0, want_full=True):
     """image_features [B,N,C], text_features [T,C] -> (full [B,N,T] | None, slice [B,N-1,F] | None)."""
@@ -1281,6 +1294,77 @@ def dcrf_inference(image_u8, prob, iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi
     check(lib().excel_dcrf_inference(_p(image_u8, torch.uint8), _p(prob), 1 if is_energy else 0, H, W, Cn, int(iters), float(pos_w), float(pos_xy_std),
                                      float(bi_w), float(bi_xy_std), float(bi_rgb_std), _p(out), _p(ws, torch.uint8), _stream()), "excel_dcrf_inference")
     return out
+
+
+_dcrf_budget_warned = False
+
+
+def dcrf_ragged_workspace_bytes(hw, C_):
+    """Workspace of excel_dcrf_inference_ragged for a group of images of sizes hw = [(H, W), ...] and C_ classes (host only).
+    RuntimeError where the library refuses the group (more lattice vertices than its 32-bit indices hold)."""
+    total = sum(int(h) * int(w) for h, w in hw)
+    out = C.c_size_t(0)
+    check(lib().excel_dcrf_ragged_workspace_bytes(total, int(C_), C.byref(out)), "excel_dcrf_ragged_workspace_bytes")
+    return int(out.value)
+
+
+def dcrf_groups(hw, C_, budget_bytes):
+    """Split a batch into consecutive runs [(start, stop), ...] for excel_dcrf_inference_ragged (host only): images are added to a run
+    while its workspace stays within budget_bytes (and the library accepts it); an image that alone exceeds the budget is a run of its
+    own.  Every image is in exactly one run, in order."""
+    sizes = [(int(h), int(w)) for h, w in hw]
+    runs, start = [], 0
+    for b in range(1, len(sizes) + 1):
+        if b == len(sizes):
+            runs.append((start, b))
+            break
+        try:
+            fits = dcrf_ragged_workspace_bytes(sizes[start:b + 1], C_) <= budget_bytes
+        except RuntimeError:
+            fits = False
+        if not fits:
+            runs.append((start, b))
+            start = b
+    return runs
+
+
+def dcrf_inference_ragged(images_u8, plan, unary, C_, iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std, is_energy=False, want_labels=True,
+                          want_q=False, budget_bytes=None):
+    """dcrf_inference (+ argmax_label) for a ragged batch, a group of images per chain of launches (excel_dcrf_inference_ragged).
+    images_u8: the packed uint8 HWC images (image b at 3 * loff_b); unary: flat, tight [C_, H_b, W_b] per image at C_ * loff_b
+    (seg_softmax_resize_ragged's output; energies when is_energy).  budget_bytes caps the workspace: the batch is cut into
+    dcrf_groups and the groups run one after another in one workspace (None: the whole batch is one group).
+    -> (labels, q): tight uint8 labels [total_label_pix] and flat marginals (layout of `unary`), None where not wanted.  Every image
+    has the bits of dcrf_inference / argmax_label on it alone, whatever the grouping."""
+    if not (want_labels or want_q):
+        raise ValueError("dcrf_inference_ragged: ask for labels, q or both")
+    n = plan.total_label_pix
+    if images_u8.dtype != torch.uint8 or images_u8.numel() != 3 * n:
+        raise ValueError(f"dcrf_inference_ragged: images_u8 must hold {3 * n} uint8 values")
+    if unary.dtype != torch.float32 or unary.numel() != C_ * n:
+        raise ValueError(f"dcrf_inference_ragged: unary must hold C * total_label_pix = {C_ * n} float32 values")
+    images_u8, unary = images_u8.view(-1), unary.view(-1)
+    dev = unary.device
+    labels = torch.empty((n,), dtype=torch.uint8, device=dev) if want_labels else None
+    q = torch.empty((C_ * n,), dtype=torch.float32, device=dev) if want_q else None
+    groups = [(0, plan.B)] if budget_bytes is None else dcrf_groups(plan.hw, C_, budget_bytes)
+    need = max(dcrf_ragged_workspace_bytes(plan.hw[s:e], C_) for s, e in groups)
+    global _dcrf_budget_warned
+    if budget_bytes is not None and need > budget_bytes and not _dcrf_budget_warned:
+        _dcrf_budget_warned = True
+        import warnings
+        warnings.warn(f"dcrf_inference_ragged: one image alone needs a workspace of {need} bytes, over the budget of {budget_bytes}; "
+                      "it runs as a group of its own (said once)")
+    ws = _ws(need, dev)
+    for s, e in groups:
+        sub = plan if (s, e) == (0, plan.B) else RaggedPlan(plan.hw[s:e], dev)
+        lo, hi = int(plan.loff[s]), int(plan.loff[e])
+        check(lib().excel_dcrf_inference_ragged(_p(images_u8[3 * lo:3 * hi], torch.uint8), _p(unary[C_ * lo:C_ * hi]), 1 if is_energy else 0,
+                                                _p(sub.table, torch.int32), C.byref(sub.info), int(C_), int(iters), float(pos_w), float(pos_xy_std),
+                                                float(bi_w), float(bi_xy_std), float(bi_rgb_std),
+                                                _p(labels[lo:hi], torch.uint8) if want_labels else None, _p(q[C_ * lo:C_ * hi]) if want_q else None,
+                                                _p(ws, torch.uint8), _stream()), "excel_dcrf_inference_ragged")
+    return labels, q
 
 
 def prof_collect():

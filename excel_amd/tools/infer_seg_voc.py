@@ -14,9 +14,12 @@ COCO: excel_seg_resize_argmax_ragged after a fuse at 0.2x).  The confusion matri
 and all-gather it once.  `--batch_size 1` runs the same code with the reference's batch of one.
 
 Deliberate differences from the reference:
-  * the DenseCRF stage (crf_proc, :103-174) runs INLINE on the fused logits that are still on the device (excel_seg_softmax_resize +
-    excel_dcrf_inference per image): no `{"msc_seg": ...}` records are written and no `logits/` directory is created (the reference
-    writes ~15 MB per VOC image and reads them back);
+  * the DenseCRF stage (crf_proc, :103-174) runs INLINE on the fused logits that are still on the device, for the whole batch at once
+    (--crf_batched true, the default: excel_seg_softmax_resize_ragged + excel_dcrf_inference_ragged over groups of images that fit
+    --crf_ws_gb of workspace, one confusion update and one device-to-host copy of the batch's labels, the PNGs written by a small
+    thread pool while the next batch runs) or image by image (--crf_batched false: excel_seg_softmax_resize + excel_dcrf_inference
+    per image); both give the same files and histograms, bit for bit.  No `{"msc_seg": ...}` records are written and no `logits/`
+    directory is created (the reference writes ~15 MB per VOC image and reads them back);
   * output paths follow :223-240 (`<model_path before "checkpoints/">/<infer_set>/<infer_set>_<ckpt>_segs/...`); a --model_path
     without a `checkpoints/` component uses the checkpoint's own directory in place of the part before it;
   * --scales takes a comma-separated list ("0.7,1.0,1.2,1.5").
@@ -108,6 +111,8 @@ def get_parser():
     p.add_argument("--gemm_mode", default=None, type=str)
     p.add_argument("--gemm_check", default=True, type=_bool)
     p.add_argument("--gemm_check_tol", default=5e-4, type=float)
+    p.add_argument("--crf_batched", default=True, type=_bool, help="run the DenseCRF stage over the whole batch (false: image by image)")
+    p.add_argument("--crf_ws_gb", default=16.0, type=float, help="workspace budget of the batched DenseCRF stage; a batch is cut into groups that fit")
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -170,56 +175,98 @@ log = logging.getLogger("excel_amd.infer_seg")        # results.log receives thi
 log.setLevel(logging.INFO)
 
 CRF_PARAMS = dict(iter_max=10, pos_xy_std=1, pos_w=3, bi_xy_std=67, bi_rgb_std=3, bi_w=4)      # :112-119
+CRF_WRITERS = 4                  # threads that encode the batched CRF stage's PNGs
+
+
+def _write_crf_files(dirs, name, lab_np, test):
+    """The files crf_proc writes for one image (:153-162)."""
+    from ..utils import imutils
+    _save_png(os.path.join(dirs["seg_preds"], name + ".png"), lab_np)
+    _save_png(os.path.join(dirs["seg_preds_rgb"], name + ".png"), imutils.encode_cmap(lab_np).astype(np.uint8))
+    if test:
+        imutils.convert_test_seg2RGB(lab_np, os.path.join(dirs["test"], name + ".png"))
+
+
+def _crf_batch(post, images, plan, planes, fplan, nc, budget):
+    """crf_proc :134-152 for a whole ragged batch: softmax of the fused logits at every image's size, mean field, arg-max ->
+    tight uint8 labels on the device (ops.dcrf_inference_ragged; the bits of the per-image chain)."""
+    prob = ops.seg_softmax_resize_ragged(planes, fplan, plan, nc)
+    lab, _ = ops.dcrf_inference_ragged(images, plan, prob, nc, post.iter_max, post.pos_w, post.pos_xy_std, post.bi_w, post.bi_xy_std,
+                                       post.bi_rgb_std, want_labels=True, budget_bytes=budget)
+    return lab
 
 
 @torch.no_grad()
 def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None):
     """The loop of _validate (:58-91) and crf_proc (:103-174) over ragged batches `feed` = (names, plan, images u8, cls, labels u8)
-    device tuples (datasets/loader.DeviceFeeder).  -> dict(hist, hist_crf (None without --crf_post), images)."""
+    device tuples (datasets/loader.DeviceFeeder).  -> dict(hist, hist_crf (None without --crf_post), images).  With --crf_batched the
+    CRF files of a batch are written by a thread pool while the next batch runs; it is joined, and a failed write raised, before this
+    returns."""
+    from concurrent.futures import ThreadPoolExecutor
     from ..utils import imutils
     from ..utils.dcrf import DenseCRF
     nc = int(args.num_classes)
     crf = bool(args.crf_post)
+    batched = crf and bool(getattr(args, "crf_batched", True))
+    budget = int(float(getattr(args, "crf_ws_gb", 16.0)) * 2 ** 30)
     sizes = scale_sizes(args.resize_size, parse_scales(args.scales))
     flips = [s != 1.0 or variant.flip_first for _, s in sizes]
     post = DenseCRF(**CRF_PARAMS) if crf else None
     hist = hist_crf = None
     nimg = 0
-    for names, plan, images, _cls, labels in feed:
-        dev = images.device
-        if hist is None:
-            hist = torch.zeros((nc, nc), dtype=torch.int64, device=dev)
-            hist_crf = torch.zeros((nc, nc), dtype=torch.int64, device=dev) if crf else None
-        segs = []
-        for S, _ in sizes:                                                                   # :63-80
-            x = ops.normalize_resize_u8_ragged(images, plan, S)
-            segs.append(model.seg_logits(torch.cat([x, x.flip(-1)], dim=0)))
-        if variant.fuse_factor is None:                                                       # VOC: fuse at the label size
-            fplan = plan
-            planes, pred = ops.seg_msc_fuse_ragged(segs, flips, plan, want_planes=crf, want_labels=True, label_hw=plan.hw)
-        else:                                                                                 # COCO: fuse small, arg-max at the label size
-            fplan = ops.RaggedPlan([variant.fuse_size(h, w) for h, w in plan.hw], dev)
-            planes, _ = ops.seg_msc_fuse_ragged(segs, flips, fplan, want_planes=True)
-            pred = ops.seg_resize_argmax_ragged(planes, fplan, plan, nc)
-        if not test:
-            hist = ops.confusion_accumulate(labels, pred, nc, hist)                          # :86-87, :97
-        for b, name in enumerate(names):
-            H, W = int(plan.hw[b, 0]), int(plan.hw[b, 1])
-            if crf:                                                                           # crf_proc :134-152, inline
-                prob = ops.seg_softmax_resize(planes, fplan, b, nc, H, W)
-                lo = int(plan.loff[b])
-                q = post(images[3 * lo:3 * (lo + H * W)].view(H, W, 3), prob)
-                lab = ops.argmax_label(q[None])[0]
+    writers = ThreadPoolExecutor(max_workers=CRF_WRITERS) if batched else None
+    pending = []
+    try:
+        for names, plan, images, _cls, labels in feed:
+            dev = images.device
+            if hist is None:
+                hist = torch.zeros((nc, nc), dtype=torch.int64, device=dev)
+                hist_crf = torch.zeros((nc, nc), dtype=torch.int64, device=dev) if crf else None
+            segs = []
+            for S, _ in sizes:                                                                   # :63-80
+                x = ops.normalize_resize_u8_ragged(images, plan, S)
+                segs.append(model.seg_logits(torch.cat([x, x.flip(-1)], dim=0)))
+            if variant.fuse_factor is None:                                                       # VOC: fuse at the label size
+                fplan = plan
+                planes, pred = ops.seg_msc_fuse_ragged(segs, flips, plan, want_planes=crf, want_labels=True, label_hw=plan.hw)
+            else:                                                                                 # COCO: fuse small, arg-max at the label size
+                fplan = ops.RaggedPlan([variant.fuse_size(h, w) for h, w in plan.hw], dev)
+                planes, _ = ops.seg_msc_fuse_ragged(segs, flips, fplan, want_planes=True)
+                pred = ops.seg_resize_argmax_ragged(planes, fplan, plan, nc)
+            if not test:
+                hist = ops.confusion_accumulate(labels, pred, nc, hist)                          # :86-87, :97
+            if batched:
+                lab = _crf_batch(post, images, plan, planes, fplan, nc, budget)
                 if not test:
-                    hist_crf = ops.confusion_accumulate(plan.label(labels, b), lab, nc, hist_crf)
-                lab_np = lab.cpu().numpy()
-                _save_png(os.path.join(dirs["seg_preds"], name + ".png"), lab_np)
-                _save_png(os.path.join(dirs["seg_preds_rgb"], name + ".png"), imutils.encode_cmap(lab_np).astype(np.uint8))
-                if test:
-                    imutils.convert_test_seg2RGB(lab_np, os.path.join(dirs["test"], name + ".png"))
-            elif test:                                                                        # :92-95
-                imutils.convert_test_seg2RGB(plan.label(pred, b).cpu().numpy(), os.path.join(dirs["test"], name + ".png"))
-        nimg += len(names)
+                    hist_crf = ops.confusion_accumulate(labels, lab, nc, hist_crf)
+                lab_host = lab.cpu().numpy()                                                      # the batch's one device-to-host copy
+            for b, name in enumerate(names):
+                H, W = int(plan.hw[b, 0]), int(plan.hw[b, 1])
+                if batched:
+                    lo = int(plan.loff[b])
+                    pending.append(writers.submit(_write_crf_files, dirs, name, lab_host[lo:lo + H * W].reshape(H, W), test))
+                elif crf:                                                                         # crf_proc :134-152, inline
+                    prob = ops.seg_softmax_resize(planes, fplan, b, nc, H, W)
+                    lo = int(plan.loff[b])
+                    q = post(images[3 * lo:3 * (lo + H * W)].view(H, W, 3), prob)
+                    lab = ops.argmax_label(q[None])[0]
+                    if not test:
+                        hist_crf = ops.confusion_accumulate(plan.label(labels, b), lab, nc, hist_crf)
+                    lab_np = lab.cpu().numpy()
+                    _save_png(os.path.join(dirs["seg_preds"], name + ".png"), lab_np)
+                    _save_png(os.path.join(dirs["seg_preds_rgb"], name + ".png"), imutils.encode_cmap(lab_np).astype(np.uint8))
+                    if test:
+                        imutils.convert_test_seg2RGB(lab_np, os.path.join(dirs["test"], name + ".png"))
+                elif test:                                                                        # :92-95
+                    imutils.convert_test_seg2RGB(plan.label(pred, b).cpu().numpy(), os.path.join(dirs["test"], name + ".png"))
+            while len(pending) > 8 * CRF_WRITERS:                                                 # bounds the label maps waiting on the host
+                pending.pop(0).result()
+            nimg += len(names)
+        for f in pending:
+            f.result()
+    finally:
+        if writers is not None:
+            writers.shutdown(wait=True)
     return {"hist": hist, "hist_crf": hist_crf, "images": nimg}
 
 

@@ -333,6 +333,8 @@ size_t excel_dcrf_workspace_bytes(int H, int W, int C);
 int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* prob, int prob_is_energy, int H, int W, int C, int iters, float pos_w,
                          float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q_out, void* workspace, void* stream);
 
+/* A group of images of a ragged batch in one chain of launches: excel_dcrf_inference_ragged, below ("segmentation evaluation"). */
+
 /* ------------------------------------------------------------------ affinity random walk */
 
 /* mean over layers of attn[l, 1:, 1:] for one stacked tensor [Lw,B,N,N] -> [B,P,P] (utils/affutils.py:180,197). */
@@ -485,6 +487,31 @@ int excel_seg_resize_argmax_uniform(const float* segs, int B, int h, int w, int 
  * (H, W) then softmax): planes = nc pitched planes (row pitch w rounded up to 4 floats) at (h, w) -> prob tight [nc, H, W], the layout
  * excel_dcrf_inference takes.  (h, w) == (H, W) skips the resize. */
 int excel_seg_softmax_resize(const float* planes, int h, int w, int nc, int H, int W, float* prob, void* stream);
+
+/* excel_seg_softmax_resize for every image of a ragged batch in one launch (tools/infer_seg_voc.py:146-147 with dst = src sizes,
+ * tools/infer_seg_coco.py:144-145 with the 0.2x fuse sizes as src): planes = nc pitched planes per image at the sizes of
+ * (src_table, src_info) -> prob tight [nc, H_b, W_b] per image at the sizes of (dst_table, dst_info), image b at element nc * loff_b:
+ * the unary excel_dcrf_inference_ragged takes.  Same kernel, same bits as excel_seg_softmax_resize per image. */
+int excel_seg_softmax_resize_ragged(const float* planes, const int32_t* src_table, const excel_ragged_info* src_info, const int32_t* dst_table,
+                                    const excel_ragged_info* dst_info, int nc, float* prob, void* stream);
+
+/* excel_dcrf_inference for a GROUP of images of a ragged batch in one chain of launches (lattice build, normalisers, mean-field steps
+ * run once for the group, not once per image): what tools/infer_seg_voc.py:103-174 (crf_proc), tools/infer_seg_coco.py:144-145 and
+ * utils/dcrf.py:42-68 do per image.  (table, info) = the excel_ragged_plan of the group (see "ragged batches" below).
+ *   hwc     the decoded uint8 [H_b,W_b,3] images back to back (image b at byte 3 * loff_b)
+ *   unary   tight [C, H_b, W_b] per image, image b at element C * loff_b: probabilities (unary_is_energy = 0) or energies (1); the
+ *           layout excel_seg_softmax_resize_ragged writes
+ *   labels_u8 (optional) tight arg-max of Q over the classes, image b at loff_b, first maximum (excel_argmax_label's rule; C <= 256)
+ *   q_out     (optional) the marginals, tight [C, H_b, W_b] per image at C * loff_b
+ * Every image gets the bits excel_dcrf_inference (+ excel_argmax_label) gives it alone, whatever else is in the group: the image index
+ * is part of every lattice key, so no lattice point is shared and no blur neighbour crosses an image, and the splat sums in fixed point.
+ * Refused: B <= 0 or B > 32767, null pointers, neither output, and a group of more than 2^30 / 6 pixels (vertex indices are 32-bit).
+ * The workspace depends on the group's pixel count alone; for one image it is exactly excel_dcrf_workspace_bytes(H, W, C).  Callers
+ * with a memory budget split a batch into consecutive groups (excel_amd.ops.dcrf_groups); the results do not depend on the split. */
+int excel_dcrf_ragged_workspace_bytes(long long total_label_pix, int C, size_t* bytes /*host, out*/);
+int excel_dcrf_inference_ragged(const uint8_t* hwc, const float* unary, int unary_is_energy, const int32_t* table,
+                                const excel_ragged_info* info, int C, int iters, float pos_w, float pos_xy_std, float bi_w,
+                                float bi_xy_std, float bi_rgb_std, uint8_t* labels_u8, float* q_out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------ CAM overlay images (camviz.hip)
  * tools/infer_lam.py:97-111 (--save_cam): the jet-coloured CAM blended over the photo, per image at its own size, for a ragged batch
