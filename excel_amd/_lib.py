@@ -133,6 +133,9 @@ SIGNATURES = {
     "excel_dcrf_ragged_workspace_bytes": (c_i, [c_ll, c_i, C.POINTER(c_sz)]),
     "excel_dcrf_inference_ragged": (c_i, [c_f, c_f, c_i, c_f, C.POINTER(RaggedInfo), c_i, c_i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                           c_f, c_f, c_f, c_f]),
+    "excel_dcrf_lam_ragged_workspace_bytes": (c_i, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i, C.POINTER(c_sz)]),
+    "excel_dcrf_lam_ragged": (c_i, [c_f, c_f, c_f, C.POINTER(C.c_int32), c_f, c_f, C.POINTER(RaggedInfo), c_i, c_i, c_i, C.c_float, C.c_float,
+                                    C.c_float, C.c_float, C.c_float, c_f, c_f, c_f, c_f]),
     "excel_attn_layer_mean": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "excel_trans_mat_workspace_bytes": (c_sz, [c_i, c_i]),
     "excel_compute_trans_mat": (c_i, [c_f, c_i, c_i, c_f, c_f, c_f]),

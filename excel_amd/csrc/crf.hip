@@ -12,6 +12,13 @@
 //   splat (a segmented sum over those lists in 64-bit fixed point: the sum is order independent, so results are bit-reproducible although lattice indices are
 //   handed out by an atomic counter) -> D+1 blur passes -> slice, symmetric normalisation 1/sqrt(K 1)
 //   mean field: Q = softmax(-U); 10 x { Q = softmax(-U + w_g K_g Q + w_b K_b Q) }
+// excel_dcrf_lam_ragged is the group form for LAMs (tools/infer_lam.py:179-237 inline): every image b of the group has its OWN class count
+// nchan[b] (its k_b + 1 planes) and reads the pipeline's pitched step cams in place.  The value rows of pixels and lattice points keep ONE
+// stride per group, Cg = max nchan; a work item (point, k) with k >= the class count of the point's image returns, so rows of an image
+// with fewer classes are partly unused (memory, idle lanes) but never read or written past its count.  A lattice point's image is
+// short 7 of its key; the CSR build reuses the key table, so the per-point class counts are written to workspace of their own before
+// it (crf_point_classes_kernel).  The per-class arithmetic and the order of the softmax sum are those of the uniform path, so every image
+// gets, bit for bit, the Q and labels excel_dcrf_inference gives it alone with C = nchan[b] on its tight planes.
 #include "../../include/excel_hip.h"
 #include "common.h"
 #include "excel_internal.h"
@@ -199,16 +206,20 @@ struct CrfSide {                 // one lattice as the message-passing kernels s
     int Dp1;
     float alpha;                 // 1 / (1 + 2^-D)
     const int *seg_start, *seg_cnt, *seg_list;   // per lattice point: its vertices list[start .. start + cnt) (segmented splat)
+    const int* ncls;             // LAM groups: class count of every lattice point's image (<= the row stride C); null otherwise
 };
 
 // splat: acc[o][k] = sum over the vertices of lattice point o of w * (in[n][k] * norm[n]), in 2^-40 fixed point (integer sums commute:
 // bit-reproducible whatever the order of a list).  No atomics: lattice point i adds up the vertices of its list (built once per lattice,
 // crf_csr_*), which gives the bits the earlier 64-bit atomicAdd splat gave and measured faster (EXPERIMENTS "Batched DenseCRF").  One
 // thread per (i, k), k fastest: the threads of a point walk the same list (broadcast loads) and read `in` along k.
+// LAM: rows have stride C = the group's largest class count; item (i, k) beyond the class count of point i's image has no work.
+template <bool LAM>
 __device__ __forceinline__ void crf_splat_side(const float* __restrict__ in, int use_norm, const CrfSide& L, int C) {
     const long long total = (long long)(*L.counter) * C, stride = (long long)gridDim.x * 256;
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
         const int i = (int)(t / C), k = (int)(t - (long long)i * C);
+        if (LAM && k >= L.ncls[i]) continue;
         const int* lst = L.seg_list + L.seg_start[i];
         const int cnt = L.seg_cnt[i];
         long long sum = 0;
@@ -223,9 +234,10 @@ __device__ __forceinline__ void crf_splat_side(const float* __restrict__ in, int
         L.acc[t] = sum;
     }
 }
+template <bool LAM>
 __global__ __launch_bounds__(256) void crf_splat2_kernel(const float* __restrict__ in, int use_norm, CrfSide g, CrfSide b, int C) {
-    crf_splat_side(in, use_norm, g, C);
-    crf_splat_side(in, use_norm, b, C);
+    crf_splat_side<LAM>(in, use_norm, g, C);
+    crf_splat_side<LAM>(in, use_norm, b, C);
 }
 // vertex lists per lattice point: count, hand every point a segment (in any order: the sum does not care), fill
 __global__ __launch_bounds__(256) void crf_csr_count_kernel(const int* __restrict__ offset, long long npv, int* __restrict__ cnt) {
@@ -248,6 +260,7 @@ __device__ __forceinline__ float crf_fix(long long a) { return (float)((double)a
 // blur pass j of one lattice: grid-stride over its M lattice points (M is read on the device: the bilateral lattice of
 // tools/infer_lam.py's parameters (sxy 67) has a few thousand points, the launch capacity would be 6 N).  Pass 0 converts the
 // accumulators on the fly, pass 1 clears them (nobody reads them after pass 0).
+template <bool LAM>
 __device__ __forceinline__ void crf_blur_side(const CrfSide& L, int j, int C) {
     if (j >= L.Dp1) return;
     const long long total = (long long)(*L.counter) * C, stride = (long long)gridDim.x * 256;
@@ -256,6 +269,7 @@ __device__ __forceinline__ void crf_blur_side(const CrfSide& L, int j, int C) {
     const int2* nbr = L.nbr + (long long)j * L.npv;
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
         const int i = (int)(t / C), k = (int)(t - (long long)i * C);
+        if (LAM && k >= L.ncls[i]) continue;                   // (the neighbours are points of the same image: same count)
         const int2 nb = nbr[i];
         if (j == 0) {
             const float a = nb.x >= 0 ? crf_fix(L.acc[(long long)nb.x * C + k]) : 0.f, c = nb.y >= 0 ? crf_fix(L.acc[(long long)nb.y * C + k]) : 0.f;
@@ -267,9 +281,19 @@ __device__ __forceinline__ void crf_blur_side(const CrfSide& L, int j, int C) {
         }
     }
 }
+template <bool LAM>
 __global__ __launch_bounds__(256) void crf_blur2_kernel(CrfSide g, CrfSide b, int j, int C) {
-    crf_blur_side(g, j, C);
-    crf_blur_side(b, j, C);
+    crf_blur_side<LAM>(g, j, C);
+    crf_blur_side<LAM>(b, j, C);
+}
+// LAM groups: the class count of every lattice point = that of its image (short 7 of its key), clamped to the row stride.  Runs before
+// crf_csr_build, which reuses lkeys.
+__global__ __launch_bounds__(256) void crf_point_classes_kernel(const CrfKey* __restrict__ lkeys, const int* __restrict__ counter,
+                                                                const int* __restrict__ nchan, int B, int Cg, int* __restrict__ ncls) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= *counter) return;
+    const int img = min(max(crf_getk(lkeys[i], CRF_IMG_SLOT), 0), B - 1);
+    ncls[i] = min(max(nchan[img], 1), Cg);
 }
 // the Dp1 vertices of pixel n (lattice point, barycentric weight x alpha... kept separate: same roundings as the per-kernel form) in
 // registers: a pixel's C classes reuse them
@@ -308,13 +332,32 @@ __global__ __launch_bounds__(256) void crf_make_norm2_kernel(CrfSide g, CrfSide 
 // unary_from_softmax lays it out); Q [N,C].  have_msg = 0: the initial Q = softmax(-U).  With a ragged table U and out_cn are tight
 // [C, H_b, W_b] per image (image b at C * loff_b) and pixel n reads / writes the planes of its own image; lab (optional) = the arg-max
 // of the q values written, first maximum (excel_argmax_label's rule).
+// LAM: U and out_cn are Cmax PITCHED planes per image (image b at Cmax * poff_b, rows of Wp_b floats: the pipeline's step cams), pixel n
+// runs over the first nc = nchan[image] planes only (clamped to 1..C; C = the stride of the Q rows), pad columns and planes >= nc are
+// neither read nor written, and lab = the key of the arg-max (channel 0 -> 0, c -> cls_idx[b, c-1] + 1: excel_argmax_label_ragged's map).
+struct CrfLam {
+    const int* nchan;            // device [B]
+    const int* cls_idx;          // device [B, smax] or null
+    int smax, Cmax;
+};
+template <bool LAM>
 __global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict__ prob, int is_energy, const int* __restrict__ tab, int B, long long N, int C,
                                                          int have_msg, CrfSide g, float wg, CrfSide b, float wb, float* __restrict__ Q,
-                                                         float* __restrict__ out_cn, unsigned char* __restrict__ lab) {
+                                                         float* __restrict__ out_cn, unsigned char* __restrict__ lab, CrfLam lam) {
     const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
     long long ps = N, po = n;                                   // plane stride and offset of pixel n in U / out_cn
-    if (tab) {
+    int nc = C;
+    const int* cls_row = nullptr;
+    if (LAM) {
+        const int img = ragged_image_of_pixel(tab, B, n);
+        const int* rec = tab + EXCEL_RAG_REC * img;
+        const int W = rec[1], Wp = (W + 3) & ~3, loc = (int)(n - rec[4]), y = loc / W;
+        ps = (long long)rec[0] * Wp;
+        po = (long long)lam.Cmax * rec[2] + (long long)y * Wp + (loc - y * W);
+        nc = min(max(lam.nchan[img], 1), C);
+        if (lam.cls_idx) cls_row = lam.cls_idx + (long long)img * lam.smax;
+    } else if (tab) {
         const int* rec = tab + EXCEL_RAG_REC * ragged_image_of_pixel(tab, B, n);
         ps = (long long)rec[0] * rec[1];
         po = (long long)C * rec[4] + (n - rec[4]);
@@ -325,7 +368,7 @@ __global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict
     const float *lg = crf_final_lat(g), *lb = crf_final_lat(b);
     if (have_msg) { vg.load(g, n, C); vb.load(b, n, C); ng = g.norm[n]; nb = b.norm[n]; }
     float mx = -INFINITY;
-    for (int k = 0; k < C; ++k) {
+    for (int k = 0; k < nc; ++k) {
         const float pv = prob[(long long)k * ps + po];
         const float u = is_energy ? pv : -logf(fminf(fmaxf(pv, 1e-5f), 1.0f));                  // unary_from_softmax (clip 1e-5)
         float t = -u;
@@ -337,15 +380,16 @@ __global__ __launch_bounds__(256) void crf_update_kernel(const float* __restrict
         mx = fmaxf(mx, t);
     }
     float sum = 0.f;
-    for (int k = 0; k < C; ++k) { const float e = expf(Q[n * C + k] - mx); Q[n * C + k] = e; sum += e; }
+    for (int k = 0; k < nc; ++k) { const float e = expf(Q[n * C + k] - mx); Q[n * C + k] = e; sum += e; }
     float best = 0.f;
     int bi = 0;
-    for (int k = 0; k < C; ++k) {
+    for (int k = 0; k < nc; ++k) {
         const float q = Q[n * C + k] / sum;
         Q[n * C + k] = q;
         if (out_cn) out_cn[(long long)k * ps + po] = q;
         if (k == 0 || q > best) { best = q; bi = k; }
     }
+    if (LAM && bi > 0 && cls_row) bi = cls_row[bi - 1] + 1;     // valid_key = [0, cls + 1 ...] (tools/infer_lam.py:225-226)
     if (lab) lab[n] = (unsigned char)bi;
 }
 
@@ -389,6 +433,8 @@ static size_t crf_workspace_bytes(long long N, int C) {
     return crf_lattice_bytes(N, 2, nullptr) + crf_lattice_bytes(N, 5, nullptr) + crf_al(8 * (N * 3) * C) + 2 * crf_al(4 * (N * 3) * C) +
            crf_al(8 * (N * 6) * C) + 2 * crf_al(4 * (N * 6) * C) + crf_al(4 * N * C) + crf_al(4 * N);
 }
+// LAM groups: + one class count per lattice point (capacity: one per vertex) of both lattices
+static size_t crf_lam_workspace_bytes(long long N, int Cg) { return crf_workspace_bytes(N, Cg) + crf_al(4 * (N * 3)) + crf_al(4 * (N * 6)); }
 // vertex indices (6 per pixel on the bilateral lattice) are ints and the hash table holds 2x as many slots, counted in 32 bits
 static bool crf_fits(long long N) { return N >= 1 && N * 6 <= (1ll << 30); }
 
@@ -434,21 +480,24 @@ static int crf_csr_build(const CrfLattice& L, CrfSide& s, hipStream_t st) {
 }
 
 // messages of BOTH kernels for `in` [N,C]: splat, blur passes; the caller slices (crf_make_norm2 / crf_update)
+template <bool LAM>
 static int crf_pass(const CrfSide& g, const CrfSide& b, const float* in, int use_norm, int C, hipStream_t st) {
     const long long work = (g.npv + b.npv) * C;
     const unsigned gm = (unsigned)(cdivl(work, 256) < 4096 ? cdivl(work, 256) : 4096);      // grid-stride kernels
-    hipLaunchKernelGGL(crf_splat2_kernel, dim3(gm), dim3(256), 0, st, in, use_norm, g, b, C);
+    hipLaunchKernelGGL(crf_splat2_kernel<LAM>, dim3(gm), dim3(256), 0, st, in, use_norm, g, b, C);
     const int passes = g.Dp1 > b.Dp1 ? g.Dp1 : b.Dp1;
-    for (int j = 0; j < passes; ++j) hipLaunchKernelGGL(crf_blur2_kernel, dim3(gm), dim3(256), 0, st, g, b, j, C);
+    for (int j = 0; j < passes; ++j) hipLaunchKernelGGL(crf_blur2_kernel<LAM>, dim3(gm), dim3(256), 0, st, g, b, j, C);
     EXCEL_CHECK_LAUNCH("dcrf message passing");
     return EXCEL_OK;
 }
 
 struct CrfParams { int iters; float pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std; };
 
-// The one chain of launches behind both entries: N pixels = one image (tab == nullptr, H x W) or a group of B images (tab).
+// The one chain of launches behind all entries: N pixels = one image (tab == nullptr, H x W) or a group of B images (tab).  LAM: the
+// group's images have their own class counts (lam.nchan), C = the group's largest = the stride of the value rows.
+template <bool LAM>
 static int crf_run(const unsigned char* rgb_hwc, const float* prob, int prob_is_energy, const int* tab, int B, long long N, int H, int W, int C,
-                   const CrfParams& P, float* q_out, unsigned char* labels, void* workspace, hipStream_t st) {
+                   const CrfParams& P, float* q_out, unsigned char* labels, void* workspace, hipStream_t st, const CrfLam& lam = CrfLam{}) {
     static_assert(true, "the message-passing kernels are written for the D = 2 (Gaussian) and D = 5 (bilateral) lattices of DenseCRF2D");
     const int iters = P.iters;
     char* p = (char*)workspace;
@@ -458,6 +507,7 @@ static int crf_run(const unsigned char* rgb_hwc, const float* prob, int prob_is_
         s.offset = L.offset; s.bary = L.bary; s.norm = L.norm; s.nbr = L.nbr; s.counter = L.counter; s.npv = L.npv; s.Dp1 = L.D + 1;
         s.alpha = 1.0f / (1.0f + powf(2.0f, (float)-L.D));
         s.seg_start = s.seg_cnt = s.seg_list = nullptr;
+        s.ncls = nullptr;
         s.acc = (long long*)p; p += crf_al(8 * L.npv * C);
         s.lat0 = (float*)p; p += crf_al(4 * L.npv * C);
         s.lat1 = (float*)p; p += crf_al(4 * L.npv * C);
@@ -468,6 +518,14 @@ static int crf_run(const unsigned char* rgb_hwc, const float* prob, int prob_is_
     float* ones = (float*)p; p += crf_al(4 * N);
     TRY(crf_build<2>(Lg, rgb_hwc, tab, B, N, H, W, P.pos_xy_std, 1.f, st));
     TRY(crf_build<5>(Lb, rgb_hwc, tab, B, N, H, W, P.bi_xy_std, P.bi_rgb_std, st));
+    if (LAM) {                                                  // before the CSR build takes lkeys over
+        int* cg = (int*)p; p += crf_al(4 * Lg.npv);
+        int* cb = (int*)p; p += crf_al(4 * Lb.npv);
+        hipLaunchKernelGGL(crf_point_classes_kernel, dim3((unsigned)cdivl(Lg.npv, 256)), dim3(256), 0, st, Lg.lkeys, Lg.counter, lam.nchan, B, C, cg);
+        hipLaunchKernelGGL(crf_point_classes_kernel, dim3((unsigned)cdivl(Lb.npv, 256)), dim3(256), 0, st, Lb.lkeys, Lb.counter, lam.nchan, B, C, cb);
+        EXCEL_CHECK_LAUNCH("dcrf point classes");
+        sg.ncls = cg; sb.ncls = cb;
+    }
     TRY(crf_csr_build(Lg, sg, st));
     TRY(crf_csr_build(Lb, sb, st));
     // the accumulators are cleared once; every message pass leaves them cleared (blur pass 1)
@@ -481,15 +539,15 @@ static int crf_run(const unsigned char* rgb_hwc, const float* prob, int prob_is_
     }
     const unsigned gn = (unsigned)cdivl(N, 256);
     // normalisers: norm = 1 / sqrt(K 1 + 1e-20)
-    TRY(crf_pass(sg, sb, ones, 0, 1, st));
+    TRY(crf_pass<false>(sg, sb, ones, 0, 1, st));               // (one value per point: every image has it)
     hipLaunchKernelGGL(crf_make_norm2_kernel, dim3(gn), dim3(256), 0, st, sg, sb, N, Lg.norm, Lb.norm);
-    hipLaunchKernelGGL(crf_update_kernel, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, tab, B, N, C, 0, sg, 0.f, sb, 0.f, Q,
-                       iters == 0 ? q_out : nullptr, iters == 0 ? labels : nullptr);
+    hipLaunchKernelGGL(crf_update_kernel<LAM>, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, tab, B, N, C, 0, sg, 0.f, sb, 0.f, Q,
+                       iters == 0 ? q_out : nullptr, iters == 0 ? labels : nullptr, lam);
     for (int it = 0; it < iters; ++it) {
-        TRY(crf_pass(sg, sb, Q, 1, C, st));
+        TRY(crf_pass<LAM>(sg, sb, Q, 1, C, st));
         const bool last = it == iters - 1;
-        hipLaunchKernelGGL(crf_update_kernel, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, tab, B, N, C, 1, sg, P.pos_w, sb, P.bi_w, Q,
-                           last ? q_out : nullptr, last ? labels : nullptr);
+        hipLaunchKernelGGL(crf_update_kernel<LAM>, dim3(gn), dim3(256), 0, st, prob, prob_is_energy, tab, B, N, C, 1, sg, P.pos_w, sb, P.bi_w, Q,
+                           last ? q_out : nullptr, last ? labels : nullptr, lam);
     }
     EXCEL_CHECK_LAUNCH("dcrf mean field");
     return EXCEL_OK;
@@ -500,7 +558,7 @@ extern "C" int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* p
     EXCEL_CHECK_ARG(rgb_hwc && prob && q_out && workspace && H > 0 && W > 0 && C >= 1 && iters >= 0, "dcrf_inference: bad argument");
     EXCEL_CHECK_ARG(pos_xy_std > 0.f && bi_xy_std > 0.f && bi_rgb_std > 0.f, "dcrf_inference: standard deviations must be positive");
     const CrfParams P{iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std};
-    return crf_run(rgb_hwc, prob, prob_is_energy, nullptr, 1, (long long)H * W, H, W, C, P, q_out, nullptr, workspace, (hipStream_t)stream);
+    return crf_run<false>(rgb_hwc, prob, prob_is_energy, nullptr, 1, (long long)H * W, H, W, C, P, q_out, nullptr, workspace, (hipStream_t)stream);
 }
 
 // tools/infer_seg_voc.py:103-174 (crf_proc), tools/infer_seg_coco.py:144-145 and utils/dcrf.py:42-68 for a group of images at once
@@ -516,5 +574,52 @@ extern "C" int excel_dcrf_inference_ragged(const uint8_t* hwc, const float* unar
     EXCEL_CHECK_ARG(crf_fits(info->total_label_pix), "dcrf_inference_ragged: a group of %lld pixels has more lattice vertices (6 per pixel) than "
                     "the 32-bit vertex indices hold: split it (ops.dcrf_groups)", (long long)info->total_label_pix);
     const CrfParams P{iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std};
-    return crf_run(hwc, unary, unary_is_energy, table, info->B, info->total_label_pix, 0, 0, C, P, q_out, labels_u8, workspace, (hipStream_t)stream);
+    return crf_run<false>(hwc, unary, unary_is_energy, table, info->B, info->total_label_pix, 0, 0, C, P, q_out, labels_u8, workspace, (hipStream_t)stream);
+}
+
+// tools/infer_lam.py:179-237 (crf_proc) for a group of LAMs with their own class counts, on the step's cams where they lie
+static int crf_lam_counts(const int32_t* nchan_host, int B, int Cmax, const char* who, int* Cg) {
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        EXCEL_CHECK_ARG(nchan_host[b] >= 1 && (Cmax <= 0 || nchan_host[b] <= Cmax), "%s: image %d has %d classes, need 1..%d", who, b,
+                        (int)nchan_host[b], Cmax > 0 ? Cmax : 2147483647);
+        if (nchan_host[b] > mx) mx = nchan_host[b];
+    }
+    *Cg = mx;
+    return EXCEL_OK;
+}
+
+extern "C" int excel_dcrf_lam_ragged_workspace_bytes(const int32_t* hw, const int32_t* nchan, int B, size_t* bytes) {
+    EXCEL_CHECK_ARG(hw && nchan && bytes && B >= 1 && B <= CRF_MAX_IMAGES, "dcrf_lam_ragged_workspace_bytes: bad argument");
+    long long N = 0;
+    for (int b = 0; b < B; ++b) {
+        EXCEL_CHECK_ARG(hw[2 * b] >= 1 && hw[2 * b + 1] >= 1, "dcrf_lam_ragged_workspace_bytes: image %d has size %d x %d", b, (int)hw[2 * b], (int)hw[2 * b + 1]);
+        N += (long long)hw[2 * b] * hw[2 * b + 1];
+    }
+    int Cg = 0;
+    TRY(crf_lam_counts(nchan, B, 0, "dcrf_lam_ragged_workspace_bytes", &Cg));
+    EXCEL_CHECK_ARG(crf_fits(N), "dcrf_lam_ragged_workspace_bytes: a group of %lld pixels has more lattice vertices (6 per pixel) than "
+                    "the 32-bit vertex indices hold: split it (ops.dcrf_lam_groups)", N);
+    *bytes = crf_lam_workspace_bytes(N, Cg);
+    return EXCEL_OK;
+}
+
+extern "C" int excel_dcrf_lam_ragged(const uint8_t* hwc, const float* cams, const int32_t* nchan, const int32_t* nchan_host, const int32_t* cls_idx,
+                                     const int32_t* table, const excel_ragged_info* info, int smax, int Cmax, int iters, float pos_w,
+                                     float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, uint8_t* labels_u8, float* q_out,
+                                     void* workspace, void* stream) {
+    EXCEL_CHECK_ARG(hwc && cams && nchan && nchan_host && table && info && workspace, "dcrf_lam_ragged: null argument");
+    EXCEL_CHECK_ARG(labels_u8 || q_out, "dcrf_lam_ragged: ask for labels, Q or both");
+    EXCEL_CHECK_ARG(info->B > 0 && info->B <= CRF_MAX_IMAGES, "dcrf_lam_ragged: %d images, need 1..%d", info->B, CRF_MAX_IMAGES);
+    EXCEL_CHECK_ARG(Cmax >= 1 && iters >= 0, "dcrf_lam_ragged: need Cmax >= 1 and iters >= 0");
+    EXCEL_CHECK_ARG(!cls_idx || (smax >= 1 && Cmax <= smax + 1), "dcrf_lam_ragged: cls_idx rows of %d entries cannot map %d channels", smax, Cmax);
+    EXCEL_CHECK_ARG(!labels_u8 || Cmax <= 256, "dcrf_lam_ragged: uint8 labels need Cmax <= 256 (Cmax = %d)", Cmax);
+    EXCEL_CHECK_ARG(pos_xy_std > 0.f && bi_xy_std > 0.f && bi_rgb_std > 0.f, "dcrf_lam_ragged: standard deviations must be positive");
+    EXCEL_CHECK_ARG(crf_fits(info->total_label_pix), "dcrf_lam_ragged: a group of %lld pixels has more lattice vertices (6 per pixel) than "
+                    "the 32-bit vertex indices hold: split it (ops.dcrf_lam_groups)", (long long)info->total_label_pix);
+    int Cg = 0;
+    TRY(crf_lam_counts(nchan_host, info->B, Cmax, "dcrf_lam_ragged", &Cg));
+    const CrfParams P{iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std};
+    const CrfLam lam{nchan, cls_idx, smax, Cmax};
+    return crf_run<true>(hwc, cams, 0, table, info->B, info->total_label_pix, 0, 0, Cg, P, q_out, labels_u8, workspace, (hipStream_t)stream, lam);
 }

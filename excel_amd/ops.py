@@ -1367,6 +1367,102 @@ def dcrf_inference_ragged(images_u8, plan, unary, C_, iters, pos_w, pos_xy_std, 
     return labels, q
 
 
+def _lam_counts(hw, nchan):
+    import numpy as np
+    hw = np.ascontiguousarray(np.asarray(hw, np.int32).reshape(-1, 2))
+    nchan = np.ascontiguousarray(np.asarray(nchan, np.int32).reshape(-1))
+    if len(hw) != len(nchan):
+        raise ValueError(f"{len(hw)} sizes but {len(nchan)} class counts")
+    return hw, nchan
+
+
+def dcrf_lam_ragged_workspace_bytes(hw, nchan):
+    """Workspace of excel_dcrf_lam_ragged for a group of images of sizes hw = [(H, W), ...] with nchan[b] classes each (host only):
+    that of dcrf_ragged_workspace_bytes(hw, max(nchan)) plus one int32 per lattice vertex (9 per pixel; two arrays, each rounded up to
+    256 bytes).  RuntimeError where the library refuses the group."""
+    hw, nchan = _lam_counts(hw, nchan)
+    out = C.c_size_t(0)
+    i32 = C.POINTER(C.c_int32)
+    check(lib().excel_dcrf_lam_ragged_workspace_bytes(hw.ctypes.data_as(i32), nchan.ctypes.data_as(i32), len(nchan), C.byref(out)),
+          "excel_dcrf_lam_ragged_workspace_bytes")
+    return int(out.value)
+
+
+def dcrf_lam_groups(hw, nchan, budget_bytes):
+    """dcrf_groups for excel_dcrf_lam_ragged (host only): consecutive runs [(start, stop), ...] whose workspace stays within
+    budget_bytes; an image that alone exceeds the budget is a run of its own.  Every image is in exactly one run, in order."""
+    hw, nchan = _lam_counts(hw, nchan)
+    runs, start = [], 0
+    for b in range(1, len(nchan) + 1):
+        if b == len(nchan):
+            runs.append((start, b))
+            break
+        try:
+            fits = dcrf_lam_ragged_workspace_bytes(hw[start:b + 1], nchan[start:b + 1]) <= budget_bytes
+        except RuntimeError:
+            fits = False
+        if not fits:
+            runs.append((start, b))
+            start = b
+    return runs
+
+
+def dcrf_lam_ragged(images_u8, plan, cams, Cmax, nchan, nchan_host, cls_idx, iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std,
+                    want_labels=True, want_q=False, budget_bytes=None):
+    """The DenseCRF stage of tools/infer_lam.py:179-237 for a ragged batch of LAMs with their own class counts (excel_dcrf_lam_ragged).
+    images_u8: the packed uint8 HWC images; cams: Cmax pitched planes per image (image b at Cmax * poff_b: pipeline.last_cams), read
+    in place (planes >= nchan[b] and pad columns are never touched); nchan (device int32 [B]) / nchan_host (host, same values) = the
+    class counts; cls_idx (device int32 [B, smax] or None) maps the arg-max to the labels (0, cls_idx + 1).  budget_bytes caps the
+    workspace: the batch is cut into dcrf_lam_groups, which run one after another in one workspace (None: one group).
+    -> (labels, q): tight uint8 labels [total_label_pix] and marginals in the layout of `cams` (torch.empty: only planes < nchan[b] and
+    columns < W_b are written), None where not wanted.  Every image has the bits of dcrf_inference on its own planes + argmax_label."""
+    import numpy as np
+    if not (want_labels or want_q):
+        raise ValueError("dcrf_lam_ragged: ask for labels, q or both")
+    Cmax = int(Cmax)
+    n = plan.total_label_pix
+    hw, nchan_host = _lam_counts(plan.hw, nchan_host)
+    if images_u8.dtype != torch.uint8 or images_u8.numel() != 3 * n:
+        raise ValueError(f"dcrf_lam_ragged: images_u8 must hold {3 * n} uint8 values")
+    if cams.dtype != torch.float32 or cams.numel() != Cmax * plan.total_pix:
+        raise ValueError(f"dcrf_lam_ragged: cams must hold Cmax * total_pix = {Cmax * plan.total_pix} float32 values")
+    if nchan.dtype != torch.int32 or nchan.numel() != plan.B:
+        raise ValueError(f"dcrf_lam_ragged: nchan must be int32 [{plan.B}]")
+    smax = Cmax - 1
+    if cls_idx is not None:
+        if cls_idx.dtype != torch.int32 or cls_idx.dim() != 2 or cls_idx.shape[0] != plan.B or not cls_idx.is_contiguous():
+            raise ValueError(f"dcrf_lam_ragged: cls_idx must be contiguous int32 [{plan.B}, smax]")
+        smax = int(cls_idx.shape[1])
+    images_u8, cams, nchan = images_u8.view(-1), cams.view(-1), nchan.view(-1)
+    dev = cams.device
+    labels = torch.empty((n,), dtype=torch.uint8, device=dev) if want_labels else None
+    q = torch.empty((Cmax * plan.total_pix,), dtype=torch.float32, device=dev) if want_q else None
+    groups = [(0, plan.B)] if budget_bytes is None else dcrf_lam_groups(hw, nchan_host, budget_bytes)
+    sizes = [dcrf_lam_ragged_workspace_bytes(hw[s:e], nchan_host[s:e]) for s, e in groups]
+    need = max(sizes)
+    global _dcrf_budget_warned
+    if budget_bytes is not None and need > budget_bytes and not _dcrf_budget_warned:
+        _dcrf_budget_warned = True
+        import warnings
+        warnings.warn(f"dcrf_lam_ragged: one image alone needs a workspace of {need} bytes, over the budget of {budget_bytes}; "
+                      "it runs as a group of its own (said once)")
+    dcrf_lam_ragged.last_groups, dcrf_lam_ragged.last_workspace_bytes = len(groups), need
+    ws = _ws(need, dev)
+    i32 = C.POINTER(C.c_int32)
+    for s, e in groups:
+        sub = plan if (s, e) == (0, plan.B) else RaggedPlan(hw[s:e], dev)
+        lo, hi = int(plan.loff[s]), int(plan.loff[e])
+        po, pe = Cmax * int(plan.poff[s]), Cmax * int(plan.poff[e])
+        host = np.ascontiguousarray(nchan_host[s:e])
+        check(lib().excel_dcrf_lam_ragged(_p(images_u8[3 * lo:3 * hi], torch.uint8), _p(cams[po:pe]), _p(nchan[s:e], torch.int32),
+                                          host.ctypes.data_as(i32), _p(cls_idx[s:e], torch.int32) if cls_idx is not None else None,
+                                          _p(sub.table, torch.int32), C.byref(sub.info), smax, Cmax, int(iters), float(pos_w),
+                                          float(pos_xy_std), float(bi_w), float(bi_xy_std), float(bi_rgb_std),
+                                          _p(labels[lo:hi], torch.uint8) if want_labels else None, _p(q[po:pe]) if want_q else None,
+                                          _p(ws, torch.uint8), _stream()), "excel_dcrf_lam_ragged")
+    return labels, q
+
+
 def prof_collect():
     """-> {category: dict(ms=summed elapsed, launches=count, work=algorithmic FLOPs or 0)} and clears the log."""
     n = lib().excel_prof_num_categories()

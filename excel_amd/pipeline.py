@@ -104,6 +104,7 @@ class TrainingFreePipeline:
         cams = ops.cam_upsample_bkg_ragged(refined, ncls, g, plan, zero_unused=keep,
                                            out=None if keep else self._buf("cams", C * plan.total_pix, device=dev))   # affutils.py:164-166
         self.last_cams = cams
+        self.last_nchan, self.last_cls_idx = nchan, idx       # the step's class counts (k_b + 1) and compacted class lists, for the same consumers
         ws = self._buf("par_ws", ops.lib().excel_par_ragged_workspace_bytes(plan.total_pix, C), torch.uint8, dev)
         par_out = ops.par_forward_ragged(inputs, cams, plan, C, self.dilations, self.num_iter, nchan=nchan, ws=ws,
                                          out=None if keep else self._buf("par_out", C * plan.total_pix, device=dev))   # affutils.py:84

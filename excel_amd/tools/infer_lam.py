@@ -25,6 +25,13 @@ Differences from the reference, all deliberate:
     out in the reference; live at tools/training_free_attr.py:225): the labels the run scores, encoded on the device on the step's
     stream (ops.png_encode_labels_ragged) with the VOC colour map, so the directory can stand in for a SegmentationClassAug directory
     (255 = ignore) and `python -m excel_amd.tools.eval_labels` scores it.  Only file bytes come back; every rank writes its own shard;
+  * `--crf_post true --crf_inline true` runs the DenseCRF stage (:179-237) inside the main loop instead of over logits records: right
+    after each ragged step, on its stream, ops.dcrf_lam_ragged refines the step's cams where they lie - every image over its own k + 1
+    planes, the whole batch in one chain of launches per --crf_ws_gb group - and the labels go into a device-side confusion matrix
+    that is gathered once like the main one.  No records, no second decode, no crf_proc pass; labels bit-identical to the record path.
+    `--crf_label_dir DIR` writes the CRF labels as palette PNGs through the device encoder (like --save_label);
+    --segs_crf_rgb_dir keeps its colour-coded files.  `--infer_set` names with "test" keep the record path (the reference scores
+    against image[:,:,0] there, :213-214);
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -72,6 +79,10 @@ def get_parser():
     p.add_argument("--crf_post", default=False, type=_bool, help="write the per-image logits records (:116-119, api path) and run the DenseCRF stage over them (:179-237)")
     p.add_argument("--logits_dir", default="./logits", type=str)
     p.add_argument("--segs_crf_rgb_dir", default=None, type=str, help="colour-coded CRF label images (tools/infer_lam.py:228); default: not written")
+    p.add_argument("--crf_inline", default=False, type=_bool,
+                   help="with --crf_post: run the DenseCRF stage inside the main loop on the step's cams (no logits records, no crf_proc pass)")
+    p.add_argument("--crf_ws_gb", default=16.0, type=float, help="--crf_inline: workspace budget of the DenseCRF stage in GiB; a batch is cut into groups that fit")
+    p.add_argument("--crf_label_dir", default=None, type=str, help="--crf_inline: write the CRF labels as palette PNGs <dir>/<name>.png (device encoder)")
     p.add_argument("--num_classes", default=21, type=int)
     p.add_argument("--ignore_index", default=255, type=int)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
@@ -190,9 +201,9 @@ class _LabelSaver:
     The arena and the row records live in grow-only buffers: the copy into the writer's pinned ring is queued on the same stream in
     front of the next step's encoder, so one arena is enough."""
 
-    def __init__(self, args):
+    def __init__(self, args, directory=None):
         from ..utils import imutils
-        self.dir = getattr(args, "label_dir", None) or label_output_dir(getattr(args, "model_path", None), args.infer_set,
+        self.dir = directory or getattr(args, "label_dir", None) or label_output_dir(getattr(args, "model_path", None), args.infer_set,
                                                                          bool(getattr(args, "training_free", True)),
                                                                          bool(getattr(args, "refine_with_aff", True)))
         os.makedirs(self.dir, exist_ok=True)
@@ -220,6 +231,98 @@ class _LabelSaver:
 
     def close(self):
         return self.writer.close()
+
+
+CRF_PARAMS = dict(iter_max=10, pos_w=3, pos_xy_std=1, bi_w=4, bi_xy_std=67, bi_rgb_std=3)     # tools/infer_lam.py:191-198
+CRF_RGB_WRITERS = 2      # threads that colour-code and save the --segs_crf_rgb_dir images
+
+
+def crf_inline_wanted(args):
+    """--crf_post true --crf_inline true, except for a test split (the reference scores against image[:,:,0] there, :213-214)."""
+    return bool(getattr(args, "crf_post", False)) and bool(getattr(args, "crf_inline", False)) and "test" not in str(args.infer_set)
+
+
+def _save_crf_rgb(path, lab):
+    from PIL import Image
+    from ..utils import imutils
+    Image.fromarray(imutils.encode_cmap(lab)).save(path)                                    # :228
+
+
+class _CrfInline:
+    """--crf_inline: the DenseCRF stage of :179-237 on the step's own cams, right after the step and on its stream.  Labels go into a
+    device-side confusion matrix (`hist`), into palette PNGs (--crf_label_dir, device encoder) and, from one device-to-host copy of the
+    batch's labels made only then, into the colour-coded files of --segs_crf_rgb_dir (a small thread pool)."""
+
+    def __init__(self, args, device):
+        self.nc = args.num_classes
+        self.hist = torch.zeros((self.nc, self.nc), dtype=torch.int64, device=device)
+        self.budget = int(float(getattr(args, "crf_ws_gb", 16.0)) * 2 ** 30)
+        self.groups, self.calls, self.peak_ws = 0, 0, 0
+        self.lab = self.pool = None
+        self.futures = []
+        if getattr(args, "crf_label_dir", None):
+            self.lab = _LabelSaver(args, args.crf_label_dir)
+        self.rgb_dir = getattr(args, "segs_crf_rgb_dir", None)
+        if self.rgb_dir:
+            from concurrent.futures import ThreadPoolExecutor
+            os.makedirs(self.rgb_dir, exist_ok=True)
+            self.pool = ThreadPoolExecutor(CRF_RGB_WRITERS)
+
+    def _rgb(self, names, plan, labels_flat):
+        host = labels_flat.cpu().numpy()                                                    # the one copy, only when the files are asked for
+        self.futures = [f for f in self.futures if not f.done() or f.result() is not None]  # (a finished writer's error is raised here)
+        for b, name in enumerate(names):
+            H, W, o = int(plan.hw[b, 0]), int(plan.hw[b, 1]), int(plan.loff[b])
+            self.futures.append(self.pool.submit(_save_crf_rgb, os.path.join(self.rgb_dir, str(name) + ".png"), host[o:o + H * W].reshape(H, W)))
+
+    def ragged(self, names, plan, images, cams, Cmax, nchan, nchan_host, cls_idx, gts_packed):
+        from .. import ops
+        P = CRF_PARAMS
+        labels, _ = ops.dcrf_lam_ragged(images, plan, cams, Cmax, nchan, nchan_host, cls_idx, P["iter_max"], P["pos_w"], P["pos_xy_std"],
+                                        P["bi_w"], P["bi_xy_std"], P["bi_rgb_std"], want_labels=True, want_q=False, budget_bytes=self.budget)
+        self.calls += 1
+        self.groups += int(getattr(ops.dcrf_lam_ragged, "last_groups", 1))
+        self.peak_ws = max(self.peak_ws, int(getattr(ops.dcrf_lam_ragged, "last_workspace_bytes", 0)))
+        if gts_packed is not None:
+            self.hist = ops.confusion_accumulate(gts_packed, labels, self.nc, self.hist)    # :233
+        if self.lab is not None:
+            self.lab.ragged(names, plan, labels)
+        if self.pool is not None:
+            self._rgb(names, plan, labels)
+        return labels
+
+    def image(self, name, hwc, normed, cls_lst, gt):
+        """The per-image path (--api_path true): :221-226 on the image's own normed maps, without a record."""
+        from .. import ops
+        P = CRF_PARAMS
+        if hwc.dtype != torch.uint8:
+            raise ValueError("--crf_inline needs the decoded uint8 images (--data_folder, --ragged true or --u8_input true)")
+        q = ops.dcrf_inference(hwc, normed, P["iter_max"], P["pos_w"], P["pos_xy_std"], P["bi_w"], P["bi_xy_std"], P["bi_rgb_std"])   # :221
+        keys = torch.nn.functional.pad(torch.as_tensor(cls_lst, device=q.device).to(torch.int64).view(-1) + 1, (1, 0))     # :225
+        labels = keys[q.argmax(0)].to(torch.uint8)                                          # :222, :226
+        self.calls += 1
+        self.groups += 1
+        self.hist = ops.confusion_accumulate(gt.to(torch.uint8), labels, self.nc, self.hist)                                  # :233
+        plan = None
+        if self.lab is not None:
+            self.lab.uniform([name], labels[None])
+        if self.pool is not None:
+            plan = ops.RaggedPlan([tuple(labels.shape)], None)
+            self._rgb([name], plan, labels.view(-1))
+        return labels
+
+    def close(self):
+        err = None
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+            for f in self.futures:
+                err = err or f.exception()
+            self.pool = None
+        if self.lab is not None:
+            lab, self.lab = self.lab, None
+            lab.close()
+        if err is not None:
+            raise err
 
 
 # ------------------------------------------------------------------ sharding + the one collective (SURVEY 8e)
@@ -331,17 +434,32 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     writers = default_cam_writers(local_world) if save_cam else 0
     cam = _CamSaver(args, writers) if save_cam else None
-    lab = None
+    lab = crf = None
+    build_validation.last_crf_hist = build_validation.last_crf_stats = None
+    if crf_inline_wanted(args) and not (ragged or per_image):
+        raise ValueError("--crf_inline needs the decoded images: ragged batches (--data_folder or --ragged true) or the per-image path "
+                         "(--api_path true / --training_free false)")
     try:
         lab = _LabelSaver(args) if bool(getattr(args, "save_label", False)) else None
-        out = _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab)
+        crf = _CrfInline(args, device) if crf_inline_wanted(args) else None
+        out = _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab, crf)
         if lab is not None:                                  # every file on disk (and a writer's error raised) before the scores are reported
             lab, done = None, lab
             done.close()
+        if crf is not None:
+            crf, done = None, crf
+            done.close()
+            build_validation.last_crf_hist = done.hist
+            build_validation.last_crf_stats = dict(calls=done.calls, groups=done.groups, peak_workspace_bytes=done.peak_ws)
         return out
     finally:
         if cam is not None:
             cam.close()
+        if crf is not None:
+            try:
+                crf.close()
+            except Exception:
+                pass
         if lab is not None:                                  # on the way out of an exception: stop the writers, keep the first error
             try:
                 lab.close()
@@ -349,7 +467,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
                 pass
 
 
-def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab=None):
+def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab=None,
+                      crf=None):
     from ..utils import evaluate
     from ..utils.affutils import refine_cams_with_aff, refine_cams_with_bkg_weclip
     from .. import ops
@@ -361,7 +480,7 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
         from ..datasets.loader import ragged_batches
         from ..utils import imutils
         pipe.hist = hist
-        keep = bool(getattr(args, "crf_post", False))
+        keep = bool(getattr(args, "crf_post", False)) and crf is None      # the record path of the CRF stage; --crf_inline needs no copies
         nw = int(getattr(args, "num_workers", -1))
         if nw < 0:                                           # the JPEG encoders of --save_cam share this rank's CPUs
             nw = max(2, default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))) - writers)
@@ -371,7 +490,7 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
             from ..datasets.loader import threaded_batches
             batches = threaded_batches(dataset, indices, args.batch_size, num_threads=max(nw, 1))
         batches = _check_present_classes(batches, pipe.smax)
-        if cam is not None:                                    # the host one-hot rows, in the feeder's order (it keeps the order)
+        if cam is not None or crf is not None:                 # the host one-hot rows, in the feeder's order (it keeps the order)
             from collections import deque
             host_cls = deque()
 
@@ -387,8 +506,12 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
             feed = ((rb.names, ops.RaggedPlan(rb.hw, None), rb.images, rb.cls, rb.labels) for rb in batches)
         for names, plan, images, cls_t, labels_t in feed:
             out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
+            cls_host = host_cls.popleft() if (cam is not None or crf is not None) else None
             if cam is not None:                                                             # :97-111, same stream, step's own cams
-                cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, host_cls.popleft())
+                cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, cls_host)
+            if crf is not None:                                                             # :179-237, same stream, step's own cams
+                nchan_host = np.minimum((cls_host != 0).sum(1), pipe.smax).astype(np.int32) + 1
+                crf.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, pipe.last_nchan, nchan_host, pipe.last_cls_idx, labels_t)
             if lab is not None:                                                             # :95, same stream, the labels just scored
                 lab.ragged(names, plan, out[0] if keep else out)
             if keep:                                                                        # :116-119 record for the CRF stage
@@ -430,7 +553,9 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
                 refined, cls_lst = refine_cams_with_aff(attr_map, attn_weights[:, i], cls_labels[i], size=inputs.shape[2:],
                                                         seg_attn=seg_attn, caa_thre=0.79)   # :93
                 labels, normed = refine_cams_with_bkg_weclip(refined, inputs[i], cls_lst, par, gts.shape[-2:])   # :94
-                if getattr(args, "crf_post", False):                                         # :116-119 record for the CRF stage
+                if crf is not None:                                                         # :179-237 without a record
+                    crf.image(str(names[i]), decoded[i], normed, cls_lst, gt_dev[i])
+                elif getattr(args, "crf_post", False):                                      # :116-119 record for the CRF stage
                     from ..utils import imutils
                     imutils.save_logits(args.logits_dir, str(names[i]), normed, cls_lst, run_token=getattr(args, "run_token", None))
                 if cam is not None:                                                         # :97-111
@@ -660,8 +785,18 @@ def validate(args=None, dataset=None, pipe=None):
                            "per_rank_hist_mass": [int(x) for x in per_rank.reshape(per_rank.shape[0], -1).sum(1).tolist()],
                            "hist_total": [[int(v) for v in row] for row in total.cpu().tolist()],       # the gathered confusion matrix itself
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size}, f)
-    if getattr(args, "crf_post", False) and getattr(args, "data_folder", None):             # :173-174
-        crf_score, crf_total = crf_proc(args, rank, world, device)
+    inline_hist = getattr(build_validation, "last_crf_hist", None)
+    if getattr(args, "crf_post", False) and getattr(args, "crf_inline", False) and inline_hist is None and rank == 0:
+        logging.info(f"--crf_inline: the {args.infer_set} split keeps the record path of the CRF stage (scored against image[:,:,0], :213-214)")
+    if inline_hist is not None or (getattr(args, "crf_post", False) and getattr(args, "data_folder", None)):     # :173-174
+        if inline_hist is not None:                                                         # scored in the loop: one gather, like the main histogram
+            _, crf_total = gather_hists(inline_hist)
+            crf_score = evaluate.scores_from_hist(crf_total)
+            st = build_validation.last_crf_stats
+            if rank == 0:
+                logging.info(f"crf inline: {st['groups']} groups over {st['calls']} batches, peak workspace {st['peak_workspace_bytes'] / 2 ** 20:.1f} MiB")
+        else:
+            crf_score, crf_total = crf_proc(args, rank, world, device)
         validate.last_crf = (crf_score, crf_total)
         if rank == 0:
             logging.info("crf_seg_score:")

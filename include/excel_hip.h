@@ -513,6 +513,37 @@ int excel_dcrf_inference_ragged(const uint8_t* hwc, const float* unary, int unar
                                 const excel_ragged_info* info, int C, int iters, float pos_w, float pos_xy_std, float bi_w,
                                 float bi_xy_std, float bi_rgb_std, uint8_t* labels_u8, float* q_out, void* workspace, void* stream);
 
+/* The DenseCRF stage of tools/infer_lam.py:179-237 (crf_proc) for a GROUP of LAMs of a ragged batch, in one chain of launches and on the
+ * step's cams where they lie: a LAM has k_b + 1 planes and k_b differs per image, so every image runs the mean field over its OWN
+ * number of classes.  (table, info) = the excel_ragged_plan of the group.
+ *   hwc        the decoded uint8 [H_b,W_b,3] images back to back (image b at byte 3 * loff_b)
+ *   cams       Cmax PITCHED planes per image (image b at element Cmax * poff_b, rows of Wp_b floats: the excel_cam_upsample_bkg_ragged
+ *              layout, i.e. the pipeline's step cams).  Probabilities: the unary is -log(clip(p, 1e-5, 1)) (utils/dcrf.py
+ *              unary_from_softmax; :221 passes the LAM as the probability map).  Only planes c < nchan[b] and columns x < W_b are read
+ *              (the rest of a step buffer is uninitialised).
+ *   nchan      device int32 [B]: image b runs softmax, splat, blur, slice and arg-max over its first nchan[b] planes, 1 <= nchan[b] <= Cmax
+ *   nchan_host host int32 [B], the same values: they size the value rows (one stride per group, Cg = max nchan_host) and are validated
+ *              (EXCEL_ERR_ARG outside 1..Cmax).  The kernels clamp the device values to 1..Cg, so a device array that disagrees
+ *              cannot make them read or write out of bounds.
+ *   cls_idx    device int32 [B, smax] or NULL (then Cmax <= smax + 1 is not required)
+ *   labels_u8  (optional) tight, image b at loff_b: the first-maximum arg-max of the final Q mapped like excel_argmax_label_ragged maps
+ *              it: channel 0 -> 0, channel c -> cls_idx[b, c-1] + 1 (:225-226 keys = pad(keys_gt + 1, (1, 0)); keys[argmax]); with
+ *              cls_idx == NULL the raw channel
+ *   q_out      (optional) the marginals in the layout of cams; only planes < nchan[b] and columns < W_b are written
+ * Every image gets, BIT FOR BIT, the Q and labels excel_dcrf_inference gives it alone with C = nchan[b] on its tight planes, whatever
+ * its batch neighbours and their class counts: the image index is part of every lattice key, the splat sums in fixed point, and the
+ * per-class arithmetic and the order of the softmax sum are those of the uniform entries (which keep their own code path and bits).
+ * Rows of pixels and lattice points have the stride Cg; a work item (point, k) with k >= the count of the point's image returns: an
+ * image with fewer classes costs memory and idle lanes, not memory traffic.  Workspace = that of excel_dcrf_ragged_workspace_bytes at
+ * C = Cg plus one int32 per lattice vertex (9 per pixel, each array rounded up to 256 bytes): the class count of every lattice point.
+ * Refused: null pointers, neither output, B outside 1..32767, non-positive standard deviations, a group of more than 2^30 / 6 pixels.
+ * No host synchronisation; everything on `stream`. */
+int excel_dcrf_lam_ragged_workspace_bytes(const int32_t* hw /*host [B,2]*/, const int32_t* nchan /*host [B]*/, int B, size_t* bytes /*host, out*/);
+int excel_dcrf_lam_ragged(const uint8_t* hwc, const float* cams, const int32_t* nchan /*device [B]*/, const int32_t* nchan_host /*host [B]*/,
+                          const int32_t* cls_idx /*device [B,smax] or NULL*/, const int32_t* table, const excel_ragged_info* info, int smax,
+                          int Cmax, int iters, float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std,
+                          uint8_t* labels_u8, float* q_out, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ CAM overlay images (camviz.hip)
  * tools/infer_lam.py:97-111 (--save_cam): the jet-coloured CAM blended over the photo, per image at its own size, for a ragged batch
  * in one launch.  For every pixel and channel ch
