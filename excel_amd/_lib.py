@@ -163,6 +163,9 @@ SIGNATURES = {
     "excel_seg_softmax_resize_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f]),
     "excel_cam_overlay_ragged": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f, c_f]),
     "excel_cam_overlay": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f]),
+    "excel_train_panels_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_int64)]),
+    "excel_train_panels": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                 c_f, c_f, c_f, c_sz, c_f]),
     "excel_png_labels_bound_bytes": (c_sz, [c_i, c_i]),
     "excel_png_labels_workspace_bytes": (c_sz, [c_i, c_i]),
     "excel_png_encode_labels_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), C.POINTER(C.c_int32), c_f, c_f, c_sz, c_f, c_f, c_sz, c_f]),

@@ -12,9 +12,7 @@
 #include "../../include/excel_hip.h"
 #include "common.h"
 #include "excel_internal.h"
-
-#define CAMVIZ_LUT 256
-#define CAMVIZ_BAD CAMVIZ_LUT          // LDS entry 256 of the jet table: the "bad" colour (NaN), RGB 0
+#include "jet.h"
 
 // Tile `tile` of the ragged plan, or of one tight H x W image (geo.tab == nullptr: b = 0, Wp = W, no offsets).
 __device__ __forceinline__ Tile camviz_tile(const TileGeo& g, int tile) {
@@ -27,15 +25,6 @@ __device__ __forceinline__ Tile camviz_tile(const TileGeo& g, int tile) {
     t.HW = (long long)g.H * g.W;
     t.base = 0; t.lab = 0;
     return t;
-}
-
-// matplotlib Colormap.__call__ for N = 256 and a float32 value: floor(x * 256) (exact), x == 1 -> 255, under (x < 0) -> 0,
-// over (x > 1) -> 255, NaN -> the bad entry.
-__device__ __forceinline__ int jet_index(float x) {
-    if (isnan(x)) return CAMVIZ_BAD;
-    if (x < 0.f) return 0;
-    if (x >= 1.f) return CAMVIZ_LUT - 1;
-    return (int)(x * 256.f);
 }
 
 // One lane per column, four rows per lane (argmax_label_ragged_kernel's shape): cam loads are 64 consecutive floats per wave, image

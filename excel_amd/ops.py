@@ -984,6 +984,101 @@ def cam_overlay(hwc, cams, mode="max", alpha=None, mean=(123.675, 116.28, 103.53
     return out
 
 
+# ------------------------------------------------------------------ training-progress panels (include/excel_hip.h, trainviz.hip)
+TRAIN_PANELS = ("img1", "cam1", "pseu_aff", "pseu_mid", "seg_gt", "seg_pred")     # bit k of the C ABI's panel_mask; the reference's tag order
+TB_MEAN, TB_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)                     # utils/tbutils.py:28
+_PANEL_TABLES = {}
+
+
+def train_panels_plan(B, S, g, panels=TRAIN_PANELS, nrow=2):
+    """excel_train_panels_plan (host only) -> ({name: (Hg, Wg, byte offset)} of the requested panels in panel order, total bytes)."""
+    unknown = [n for n in panels if n not in TRAIN_PANELS]
+    if unknown:
+        raise ValueError(f"unknown panels {unknown}; known: {list(TRAIN_PANELS)}")
+    mask = sum(1 << TRAIN_PANELS.index(n) for n in set(panels))
+    out = (C.c_int64 * (3 * len(TRAIN_PANELS) + 1))()
+    check(lib().excel_train_panels_plan(int(B), int(nrow), int(S), int(g), mask, out), "excel_train_panels_plan")
+    plan = {n: (int(out[3 * k]), int(out[3 * k + 1]), int(out[3 * k + 2])) for k, n in enumerate(TRAIN_PANELS) if (mask >> k) & 1}
+    return plan, int(out[3 * len(TRAIN_PANELS)])
+
+
+class TrainPanels(dict):
+    """panel name -> uint8 [Hg,Wg,3] device view; `buffer` is the one flat uint8 tensor the views share and `plan` their
+    (Hg, Wg, byte offset), so a caller that wants the panels on the host makes ONE copy (host())."""
+    buffer = None
+    plan = None
+
+    def host(self):
+        """-> {name: numpy uint8 [Hg,Wg,3]} from one device-to-host copy of the shared buffer"""
+        buf = self.buffer.cpu().numpy()
+        return {n: buf[off:off + 3 * Hg * Wg].reshape(Hg, Wg, 3) for n, (Hg, Wg, off) in self.plan.items()}
+
+
+def _panel_tables(device):
+    """(0.5 * (jet * 255) as float64 [256,3], the VOC palette uint8 [256,3]) on the device, built once per device"""
+    t = _PANEL_TABLES.get(str(device))
+    if t is None:
+        from .utils import imutils
+        t = _PANEL_TABLES[str(device)] = (torch.from_numpy(imutils.jet_lut() * 255 * 0.5).contiguous().to(device),
+                                          torch.from_numpy(imutils.colormap()).contiguous().to(device))
+    return t
+
+
+def train_panels(inputs=None, attr_maps_raw=None, cls_label=None, pseu_aff=None, pseu_mid=None, seg_gt=None, seg_pred=None, nrow=2,
+                 panels=None, S=None, g=None):
+    """The image grids of scripts/train_voc.py:233-246 (utils/tbutils.py make_grid_image / make_grid_label) for one training batch in
+    one launch: inputs f32 [B,3,S,S] normalised, attr_maps_raw f32 [B,P,F] (P = g*g), cls_label [B,F], label maps uint8 [B,S,S]
+    (pseu_mid: [B,g,g]).  `panels` defaults to every panel whose inputs were given (img1 needs inputs; cam1 inputs, attr_maps_raw and
+    cls_label).  S / g are taken from the tensors.  -> TrainPanels: name -> uint8 [Hg,Wg,3] views of one device buffer."""
+    given = dict(pseu_aff=pseu_aff, pseu_mid=pseu_mid, seg_gt=seg_gt, seg_pred=seg_pred)
+    if panels is None:
+        panels = [n for n in TRAIN_PANELS if (n == "img1" and inputs is not None)
+                  or (n == "cam1" and inputs is not None and attr_maps_raw is not None and cls_label is not None)
+                  or given.get(n) is not None]
+    if not panels:
+        raise ValueError("train_panels: nothing to render")
+    ref = inputs if inputs is not None else next((t for n, t in given.items() if n != "pseu_mid" and t is not None), None)
+    B = int((ref if ref is not None else pseu_mid).shape[0])
+    S = int(ref.shape[-1]) if ref is not None else int(S or 1)
+    if ref is not None and tuple(ref.shape[-2:]) != (S, S):
+        raise ValueError(f"train_panels needs square crops, got {tuple(ref.shape[-2:])}")
+    F_ = P = 0
+    if attr_maps_raw is not None:
+        attr_maps_raw = f32c(attr_maps_raw)
+        P, F_ = int(attr_maps_raw.shape[1]), int(attr_maps_raw.shape[2])
+        g = int(round(P ** 0.5)) if g is None else int(g)
+        cls_label = f32c(cls_label) if cls_label is not None else None
+        if cls_label is not None and tuple(cls_label.shape) != (B, F_):
+            raise ValueError(f"cls_label must be [{B},{F_}], got {tuple(cls_label.shape)}")
+    elif pseu_mid is not None:
+        g = int(pseu_mid.shape[-1])
+    g = int(g or 1)
+    dev = (ref if ref is not None else pseu_mid).device
+    labs = []
+    for n, side in (("pseu_aff", S), ("pseu_mid", g), ("seg_gt", S), ("seg_pred", S)):
+        t = given[n]
+        if t is not None:
+            if t.dtype != torch.uint8 or tuple(t.shape) != (B, side, side):
+                raise ValueError(f"{n} must be uint8 [{B},{side},{side}], got {t.dtype} {tuple(t.shape)}")
+            t = t.contiguous()
+        labs.append(t)
+    if inputs is not None:
+        inputs = f32c(inputs)
+        if tuple(inputs.shape) != (B, 3, S, S):
+            raise ValueError(f"inputs must be [B,3,S,S], got {tuple(inputs.shape)}")
+    plan, total = train_panels_plan(B, S, g, panels, nrow)
+    mask = sum(1 << TRAIN_PANELS.index(n) for n in plan)
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    jet, pal = _panel_tables(dev)
+    m, s = (C.c_float * 3)(*TB_MEAN), (C.c_float * 3)(*TB_STD)
+    check(lib().excel_train_panels(_p(inputs), _p(attr_maps_raw), _p(cls_label), *[_p(t, torch.uint8) for t in labs], B, F_, P, g, S, int(nrow),
+                                   mask, m, s, _p(jet, torch.float64), _p(pal, torch.uint8), _p(out, torch.uint8), total, _stream()),
+          "excel_train_panels")
+    res = TrainPanels((n, out[off:off + 3 * Hg * Wg].view(Hg, Wg, 3)) for n, (Hg, Wg, off) in plan.items())
+    res.buffer, res.plan = out, plan
+    return res
+
+
 # ------------------------------------------------------------------ label PNG files (include/excel_hip.h, png.hip)
 _PNG_PALETTES = {}
 

@@ -8,7 +8,8 @@ What differs from VOC, all taken from the reference's two files (`diff scripts/t
   * loop: caa_thre 0.88 (:193), the LVC switch (cure_attr_map on the head's features + seg_attn) at n_iter >= 30000 (:184-192), the
     affinity target is always the pseudo labels (:206, no switch to the seg arg-max);
   * checkpoints only from iteration 40000 on (:249), lowered with --save_ckpt_from;
-  * validation with 81 classes and COCO's class names (:251).
+  * validation with 81 classes and COCO's class names (:251);
+  * --save_visual / tb_writer: five progress panels, no seg_gt (:229-242); seg_pred has the crop's size as in VOC (:199, :235).
 Checkpoints are model_iter_N.pth with the head's keys, for `python -m excel_amd.tools.infer_seg_coco --model_path ...`.
 
   python -m excel_amd.scripts.train_coco --data_folder MSCOCO2014 --list_folder datasets/coco --model ViT-B-16.pt --bpe_path ...
@@ -42,6 +43,11 @@ class CocoVariant(TrainVariant):
         return ops.train_augment_image(images, plan, None, args.crop_size, aug_plan=plan.aug)[0]
 
     @staticmethod
+    def augment_with_gt(images, plan, labels, args):
+        """no label map in this data: the progress panels have no seg_gt (scripts/train_coco.py:234, :241)"""
+        return CocoVariant.augment(images, plan, labels, args), None
+
+    @staticmethod
     def class_list(args):
         from ..datasets import coco
         return coco.class_list if args.num_classes == 81 else None
@@ -64,8 +70,8 @@ def get_parser():
     return p
 
 
-def train(args, model=None):
-    return train_voc.train(args, model=model, variant=COCO)
+def train(args, model=None, tb_writer=None):
+    return train_voc.train(args, model=model, variant=COCO, tb_writer=tb_writer)
 
 
 if __name__ == "__main__":

@@ -565,6 +565,38 @@ int excel_cam_overlay_ragged(const uint8_t* hwc, const float* cams, int Cmax, co
                              const int32_t* table, const excel_ragged_info* info, int mode, const double* tables, uint8_t* out, void* stream);
 int excel_cam_overlay(const uint8_t* hwc, const float* cams, int k, int H, int W, int mode, const double* tables, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ training-progress panels (trainviz.hip)
+ * The image grids scripts/train_voc.py:233-246 (scripts/train_coco.py:229-242) renders every --log_iters iterations, for one training
+ * batch in one launch.  Panel k (EXCEL_TRAIN_PANEL_*, the order of the reference's add_image calls) is a tight uint8 [Hg,Wg,3] RGB grid in
+ * torchvision.utils.make_grid's default layout (utils/tbutils.py:46, :59, :92): xmaps = min(nrow, B), ymaps = ceil(B / xmaps), a cell is
+ * (h+2) x (w+2), the grid (h+2)*ymaps + 2 by (w+2)*xmaps + 2, image k at row (k / xmaps)*(h+2) + 2, column (k % xmaps)*(w+2) + 2, everything
+ * else 0 (the cells past B too); B == 1 is the bare image.  Every byte of a requested panel is written.
+ *   IMG1      utils/tbutils.py:28-33 (denormalize_img): (uint8) (((x * std_c) + mean_c) * 255) in float32, truncated, clamped to [0, 255]
+ *             (the reference's conversion is undefined outside); img f32 [B,3,S,S], mean / std HOST float[3] (0.485.. / 0.229..)
+ *   CAM1      utils/tbutils.py:39, :52-58: attr f32 [B,P,F] read as [B,F,g,g] (P == g*g), every class plane sampled bilinearly
+ *             (align_corners = False) at the pixel, times cls_label[b,f] (f32 [B,F]), max over f (NaN propagates, torch.max), jet index
+ *             as in excel_cam_overlay, out = (uint8) trunc(jet[idx][ch] + 0.5 * img1 byte) in float64; jet (device float64 [256][3]) =
+ *             0.5 * (jet_lut * 255), pre-scaled on the host as the reference computes it
+ *   PSEU_AFF, SEG_GT, SEG_PRED   utils/tbutils.py:88-93: uint8 [B,S,S] label maps through `palette` (device uint8 [256][3])
+ *   PSEU_MID  the same for a uint8 [B,g,g] label map: a grid of g x g cells
+ * excel_train_panels_plan (a HOST function: no device work) -> out[3*k .. 3*k+2] = (Hg, Wg, byte offset) of panel k (0, 0, 0 when bit k of
+ * panel_mask is clear), out[3 * EXCEL_TRAIN_PANELS] = total bytes; the requested panels follow each other tightly in panel order.
+ * excel_train_panels renders them into `out` (out_bytes >= the plan's total).  Inputs of panels that are not requested may be NULL; a
+ * requested panel without its input, a size at or above 2^31 (3*B*S*S, B*P*F, the total bytes) and P != g*g are argument errors. */
+#define EXCEL_TRAIN_PANELS 6
+#define EXCEL_TRAIN_PANEL_IMG1 0
+#define EXCEL_TRAIN_PANEL_CAM1 1
+#define EXCEL_TRAIN_PANEL_PSEU_AFF 2
+#define EXCEL_TRAIN_PANEL_PSEU_MID 3
+#define EXCEL_TRAIN_PANEL_SEG_GT 4
+#define EXCEL_TRAIN_PANEL_SEG_PRED 5
+#define EXCEL_TRAIN_PANELS_PLAN_INTS (3 * EXCEL_TRAIN_PANELS + 1)
+int excel_train_panels_plan(int B, int nrow, int S, int g, int panel_mask, int64_t* out /*host*/);
+int excel_train_panels(const float* img, const float* attr, const float* cls_label, const uint8_t* pseu_aff, const uint8_t* pseu_mid,
+                       const uint8_t* seg_gt, const uint8_t* seg_pred, int B, int F, int P, int g, int S, int nrow, int panel_mask,
+                       const float* mean /*host*/, const float* std /*host*/, const double* jet, const uint8_t* palette, uint8_t* out,
+                       size_t out_bytes, void* stream);
+
 /* ------------------------------------------------------------------ label PNG files (png.hip)
  * The label image the reference saves per sample (tools/infer_lam.py:95, commented out there; tools/training_free_attr.py:225, live), for a
  * ragged batch: labels = the tight uint8 label maps excel_argmax_label_ragged writes (image b at loff_b) -> one COMPLETE palette PNG file
