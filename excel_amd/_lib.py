@@ -169,6 +169,9 @@ SIGNATURES = {
     "excel_png_labels_bound_bytes": (c_sz, [c_i, c_i]),
     "excel_png_labels_workspace_bytes": (c_sz, [c_i, c_i]),
     "excel_png_encode_labels_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), C.POINTER(C.c_int32), c_f, c_f, c_sz, c_f, c_f, c_sz, c_f]),
+    "excel_jpeg_rgb_arena_bytes": (c_sz, [C.POINTER(C.c_int32), c_i]),
+    "excel_jpeg_rgb_workspace_bytes": (c_sz, [C.POINTER(C.c_int32), c_i]),
+    "excel_jpeg_encode_rgb_ragged": (c_i, [c_f, C.POINTER(C.c_int64), C.POINTER(C.c_int32), c_i, c_i, c_f, c_sz, c_f, c_f, c_sz, c_f]),
     "excel_train_aug_plan": (c_i, [C.POINTER(C.c_int32), C.POINTER(AugParams), c_i, c_i, C.POINTER(TrainAugInfo), C.POINTER(C.c_int32)]),
     "excel_train_augment_workspace_bytes": (c_sz, [C.POINTER(TrainAugInfo)]),
     "excel_train_augment": (c_i, [c_f, c_f, c_f, C.POINTER(TrainAugInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f, c_f, c_f, c_f]),

@@ -1143,6 +1143,60 @@ def png_encode_labels_ragged(labels_flat, plan, palette=None, out=None, ws=None)
     return out[:need], table
 
 
+# ------------------------------------------------------------------ CAM overlay JPEG files (include/excel_hip.h, jpeg.hip)
+JPEG_HEADER_BYTES = 623          # SOI .. SOS; a file is this, the entropy-coded segment and the 2 bytes of EOI
+
+
+def _jpeg_items(items):
+    import numpy as np
+    it = np.asarray(items, np.int64).reshape(-1, 3)
+    if it.shape[0] < 1:
+        raise ValueError("jpeg_encode_rgb_ragged needs at least one image")
+    return np.ascontiguousarray(it[:, 0]), np.ascontiguousarray(it[:, 1:].astype(np.int32))
+
+
+def jpeg_rgb_arena_bytes(hw):
+    """Arena bytes that bound the files of RGB images of the sizes `hw` [(H, W)]: 625 + 3 H W each (excel_jpeg_rgb_arena_bytes)."""
+    import numpy as np
+    hw = np.ascontiguousarray(np.asarray(hw, np.int32).reshape(-1, 2))
+    return int(lib().excel_jpeg_rgb_arena_bytes(hw.ctypes.data_as(C.POINTER(C.c_int32)), hw.shape[0]))
+
+
+def jpeg_rgb_workspace_bytes(hw):
+    """Workspace bytes of jpeg_encode_rgb_ragged for images of the sizes `hw` [(H, W)] (excel_jpeg_rgb_workspace_bytes)."""
+    import numpy as np
+    hw = np.ascontiguousarray(np.asarray(hw, np.int32).reshape(-1, 2))
+    return int(lib().excel_jpeg_rgb_workspace_bytes(hw.ctypes.data_as(C.POINTER(C.c_int32)), hw.shape[0]))
+
+
+def jpeg_encode_rgb_ragged(rgb_flat, items, quality=75, out=None, ws=None):
+    """tools/infer_lam.py:104,111 for a ragged batch, on the device: rgb_flat = the flat uint8 buffer cam_overlay_ragged writes, items =
+    [(byte offset, H, W)] of the tight [H,W,3] images in it -> one complete baseline JPEG file per image, the bytes Pillow writes at
+    `quality`.  -> (bytes: flat uint8 device tensor, table: int64 device tensor [n,2] of (offset, size)); the files lie back to back,
+    file i = bytes[off_i:off_i + size_i].  size -1: the file would have ended behind the arena and was not written (encode that image
+    on the host).  out: a flat uint8 device tensor to encode into, of any size (None: jpeg_rgb_arena_bytes, which the files are
+    expected to stay below); ws: a uint8 device tensor of at least jpeg_rgb_workspace_bytes (too small is an error)."""
+    off, hw = _jpeg_items(items)
+    if rgb_flat.dtype != torch.uint8 or rgb_flat.dim() != 1 or not rgb_flat.is_contiguous():
+        raise ValueError("rgb_flat must be a flat contiguous uint8 tensor")
+    ends = off + 3 * hw[:, 0].astype("int64") * hw[:, 1].astype("int64")
+    if (off < 0).any() or int(ends.max()) > rgb_flat.numel():
+        raise ValueError(f"items reach byte {int(ends.max())} of a buffer of {rgb_flat.numel()} bytes (or hold a negative offset)")
+    dev = rgb_flat.device
+    n = int(hw.shape[0])
+    hw_p, off_p = hw.ctypes.data_as(C.POINTER(C.c_int32)), off.ctypes.data_as(C.POINTER(C.c_int64))
+    if out is None:
+        out = torch.empty(max(int(lib().excel_jpeg_rgb_arena_bytes(hw_p, n)), 1), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
+        raise ValueError("out= must be a flat contiguous uint8 tensor")
+    if ws is None:
+        ws = _ws(max(int(lib().excel_jpeg_rgb_workspace_bytes(hw_p, n)), 1), dev)
+    table = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    check(lib().excel_jpeg_encode_rgb_ragged(_p(rgb_flat, torch.uint8), off_p, hw_p, n, int(quality), _p(out, torch.uint8), out.numel(),
+                                             _p(table, torch.int64), _p(ws, torch.uint8), ws.numel(), _stream()), "excel_jpeg_encode_rgb_ragged")
+    return out, table
+
+
 # ------------------------------------------------------------------ training augmentation (include/excel_hip.h, aug.hip)
 AUG_CANDIDATES = 10
 # one record per image, laid out like excel_aug_params (C alignment: 104 bytes)

@@ -69,6 +69,8 @@ def get_parser():
     p.add_argument("--refine_with_aff", default=True, type=_bool, help="only names the output tag (aff_lam / seeds_lam, :242-246)")
     p.add_argument("--save_cls_specific_cam", default=True, type=_bool, help="with --save_cam: one overlay per present class (:104-111)")
     p.add_argument("--save_cam", default=False, type=_bool, help="write the CAM overlay images (:97-111)")
+    p.add_argument("--cam_device_jpeg", default=False, type=_bool,
+                   help="with --save_cam on the batched path: encode the overlay JPEGs on the device (the same bytes; --api_path true keeps the host encoder)")
     p.add_argument("--cam_dir", default=None, type=str, help="max-overlay directory (default: cam_output_dirs)")
     p.add_argument("--cs_cam_dir", default=None, type=str, help="per-class overlay directory (default: cam_output_dirs)")
     p.add_argument("--save_label", default=False, type=_bool, help="write the pseudo-label maps as palette PNGs <label_dir>/<name>.png (:95)")
@@ -158,9 +160,13 @@ def class_names(args):
 
 
 class _CamSaver:
-    """--save_cam: device overlays of a batch / an image -> JPEG files through imutils.CamOverlayWriter."""
+    """--save_cam: device overlays of a batch / an image -> JPEG files through imutils.CamOverlayWriter (host encoder), or with
+    device_jpeg=True through ops.jpeg_encode_rgb_ragged and imutils.CamJpegWriter: the files are encoded on the device into a grow-only
+    arena, only its bytes cross, threads only write.  The first arena has the raw size of the overlays (the bound); once a batch has
+    landed, the arena is budgeted by the largest file / raw ratio seen (plus a quarter), and an overlay that does not fit is encoded on
+    the host by the writer - the same bytes either way."""
 
-    def __init__(self, args, writers):
+    def __init__(self, args, writers, device_jpeg=False):
         from ..utils import imutils
         self.per_class = bool(getattr(args, "save_cls_specific_cam", True))
         self.mode = "per_class" if self.per_class else "max"
@@ -169,7 +175,27 @@ class _CamSaver:
         self.dir = (getattr(args, "cs_cam_dir", None) or dirs["cs_cam_dir"]) if self.per_class else (getattr(args, "cam_dir", None) or dirs["cam_dir"])
         os.makedirs(self.dir, exist_ok=True)
         self.names = class_names(args)
-        self.writer = imutils.CamOverlayWriter(writers)
+        self.device_jpeg = bool(device_jpeg)
+        self.writer = imutils.CamJpegWriter(LABEL_WRITERS) if self.device_jpeg else imutils.CamOverlayWriter(writers)
+        self._arena = self._ws = None
+        self.batches = self.copied = 0       # batches with overlays; bytes they sent to the host
+
+    def _encode(self, out, items):
+        from .. import ops
+        paths, geo = [it[0] for it in items], [it[1:] for it in items]
+        hw = [(H, W) for _, H, W in geo]
+        budget = ops.jpeg_rgb_arena_bytes(hw)
+        if self.writer.ratio is not None:
+            raw = sum(3 * H * W for H, W in hw)
+            budget = min(budget, len(hw) * (ops.JPEG_HEADER_BYTES + 2) + int(raw * min(1.0, 1.25 * self.writer.ratio + 0.02)))
+        if self._arena is None or self._arena.numel() < budget:
+            self._arena = torch.empty(budget, dtype=torch.uint8, device=out.device)
+        ws_need = ops.jpeg_rgb_workspace_bytes(hw)
+        if self._ws is None or self._ws.numel() < ws_need:
+            self._ws = torch.empty(ws_need, dtype=torch.uint8, device=out.device)
+        from ..utils import imutils
+        data, table = ops.jpeg_encode_rgb_ragged(out, geo, imutils.CAM_JPEG_QUALITY, out=self._arena[:budget], ws=self._ws)
+        self.writer.submit(data, table, paths, geo, out)
 
     def _items(self, name, present, H, W, off):
         if not self.per_class:
@@ -183,7 +209,15 @@ class _CamSaver:
         items = []
         for b, name in enumerate(names):
             items += self._items(str(name), present[b], int(plan.hw[b, 0]), int(plan.hw[b, 1]), off[b])
-        self.writer.submit(out, items)
+        if not items:
+            return
+        self.batches += 1
+        if self.device_jpeg:
+            self._encode(out, items)
+            self.copied = self.writer.copied
+        else:
+            self.writer.submit(out, items)
+            self.copied += int(out.numel())
 
     def image(self, name, hwc, normed, cls_lst):
         from .. import ops
@@ -433,9 +467,9 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
                          "(--api_path true / --training_free false)")
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     writers = default_cam_writers(local_world) if save_cam else 0
-    cam = _CamSaver(args, writers) if save_cam else None
+    cam = _CamSaver(args, writers, device_jpeg=bool(getattr(args, "cam_device_jpeg", False)) and ragged) if save_cam else None
     lab = crf = None
-    build_validation.last_crf_hist = build_validation.last_crf_stats = None
+    build_validation.last_crf_hist = build_validation.last_crf_stats = build_validation.last_cam_stats = None
     if crf_inline_wanted(args) and not (ragged or per_image):
         raise ValueError("--crf_inline needs the decoded images: ragged batches (--data_folder or --ragged true) or the per-image path "
                          "(--api_path true / --training_free false)")
@@ -454,7 +488,11 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         return out
     finally:
         if cam is not None:
-            cam.close()
+            try:
+                files = cam.close()
+            finally:
+                build_validation.last_cam_stats = dict(device_jpeg=cam.device_jpeg, files=getattr(cam.writer, "files", 0), batches=cam.batches,
+                                                       bytes_to_host=cam.copied, host_fallbacks=getattr(cam.writer, "fallbacks", 0))
         if crf is not None:
             try:
                 crf.close()

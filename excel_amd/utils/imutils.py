@@ -10,6 +10,8 @@ records tools/infer_lam.py exchanges with its CRF stage.
   jet_lut / denormalize_roundtrip_table / cam_overlay_tables / CamOverlayWriter
                            tools/infer_lam.py:97-111 (--save_cam): the host half of the CAM overlay images (the blend itself is
                            excel_cam_overlay_ragged, camviz.hip)
+  CamJpegWriter            tools/infer_lam.py:104,111 (--save_cam --cam_device_jpeg true): the host half of the device-encoded overlay files
+                           (excel_jpeg_encode_rgb_ragged, jpeg.hip)
   LabelPngWriter           tools/infer_lam.py:95 / tools/training_free_attr.py:225 (--save_label): the host half of the label PNG files
                            (the files themselves are encoded by excel_png_encode_labels_ragged, png.hip)
 
@@ -312,3 +314,81 @@ class LabelPngWriter:
         if err is not None:
             raise err
         return self.files
+
+
+# ------------------------------------------------------------------ device-encoded CAM overlay files (tools/infer_lam.py:104,111)
+class CamJpegWriter(LabelPngWriter):
+    """Device-encoded JPEG files (ops.jpeg_encode_rgb_ragged) -> disk: LabelPngWriter's ring of pinned buffers and its event discipline
+    (every event wait in the launching thread, the pool threads only open / write / close).  A table entry of size -1 is a file that did
+    not fit into the arena: when the batch is handed to the pool, the launching thread copies that one overlay's raw bytes from `rgb`
+    and a pool thread encodes it with save_jpeg, which writes the same bytes.  `ratio` is the largest (file bytes / raw bytes) of a
+    batch seen so far (None before the first batch has landed): what a caller sizes the next arena by."""
+
+    def __init__(self, threads=2, slots=4):
+        super().__init__(threads, slots)
+        self.fallbacks = 0          # overlays encoded on the host (size -1 in the table)
+        self.copied = 0             # bytes copied to the host
+        self.ratio = None
+
+    @staticmethod
+    def _write(buf, table, paths, raw, lo, hi):
+        n = 0
+        for b in range(lo, hi):
+            if b in raw:
+                save_jpeg(paths[b], raw[b])
+                continue
+            off, size = int(table[b, 0]), int(table[b, 1])
+            with open(paths[b], "wb") as f:
+                f.write(buf[off:off + size])
+            n += size
+        return hi - lo, n
+
+    def _hand_over(self, slot, paths, items, rgb):
+        """The copy of `slot` has landed: its files -> the pool.  items: [(byte offset, H, W)] of the overlays in `rgb` (a flat uint8
+        tensor, device or host)."""
+        buf, table = memoryview(slot["bytes"].numpy()), slot["table"].numpy()
+        B = len(paths)
+        raw = {}
+        for b, (off, H, W) in enumerate(items):
+            if table[b, 1] < 0:
+                raw[b] = rgb[int(off):int(off) + 3 * H * W].cpu().numpy().reshape(H, W, 3)
+        self.fallbacks += len(raw)
+        if not raw:
+            r = float(table[:B, 1].sum()) / max(1, sum(3 * H * W for _, H, W in items))
+            self.ratio = r if self.ratio is None else max(self.ratio, r)
+        step = -(-B // self.threads)
+        slot["futures"] = [self._pool.submit(self._write, buf, table, paths, raw, lo, min(B, lo + step)) for lo in range(0, B, step)]
+
+    def _dispatch(self, wait=False):
+        while self._copying:
+            ev, slot, paths, items, rgb = self._copying[0]
+            if wait:
+                ev.synchronize()
+                wait = False
+            elif not ev.query():
+                return
+            self._copying.pop(0)
+            self._hand_over(slot, paths, items, rgb)
+
+    def submit(self, dev_bytes, dev_table, paths, items, rgb):
+        """dev_bytes, dev_table: what ops.jpeg_encode_rgb_ragged returned (queued on the current stream); paths: one file name per image;
+        items, rgb: what the encoder was given (rgb is kept alive until the batch has been handed to the pool)."""
+        import torch
+        if not (len(paths) == len(items) == int(dev_table.shape[0])):
+            raise ValueError(f"{len(paths)} paths and {len(items)} items for {int(dev_table.shape[0])} images")
+        self._dispatch()
+        slot = self._slots[self._next]
+        self._next = (self._next + 1) % len(self._slots)
+        while any(c[1] is slot for c in self._copying):
+            self._dispatch(wait=True)
+        self._collect(slot)
+        if slot["bytes"] is None or slot["bytes"].numel() < dev_bytes.numel():
+            slot["bytes"] = torch.empty(dev_bytes.numel(), dtype=torch.uint8, pin_memory=True)
+        if slot["table"] is None or slot["table"].shape[0] < dev_table.shape[0]:
+            slot["table"] = torch.empty((int(dev_table.shape[0]), 2), dtype=torch.int64, pin_memory=True)
+        slot["bytes"][:dev_bytes.numel()].copy_(dev_bytes, non_blocking=True)
+        slot["table"][:dev_table.shape[0]].copy_(dev_table, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.copied += int(dev_bytes.numel()) + 16 * int(dev_table.shape[0])
+        self._copying.append((ev, slot, [str(p) for p in paths], [(int(o), int(h), int(w)) for o, h, w in items], rgb))

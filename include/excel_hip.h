@@ -620,6 +620,34 @@ int excel_png_encode_labels_ragged(const uint8_t* labels, const int32_t* table, 
                                    const uint8_t* palette, uint8_t* arena, size_t arena_bytes, int64_t* out_table, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ CAM overlay JPEG files (jpeg.hip)
+ * The overlay images the reference saves per sample (tools/infer_lam.py:104,111: imageio.imsave of a uint8 [H,W,3] array to a .jpg, which
+ * is Pillow at quality 75), for a ragged batch: rgb = the flat uint8 buffer excel_cam_overlay_ragged writes (tight [H_i,W_i,3] images,
+ * image i at byte off_i; any offsets, odd ones included) -> one COMPLETE baseline JFIF file per image in `arena`, so that only file bytes
+ * cross to the host.  The bytes are the ones PIL.Image.fromarray(rgb_i).save(f, format="JPEG", quality=quality) writes (Pillow 12 over
+ * libjpeg-turbo 3): every stage is libjpeg's integer arithmetic.
+ *   file    SOI; APP0 (JFIF 1.01, no units, 1 x 1); two DQT (the Annex K tables at libjpeg's quality scaling, zig-zag order); SOF0 (8 bit,
+ *           Y 2x2 with table 0, Cb / Cr 1x1 with table 1); four DHT (DC0, AC0, DC1, AC1: the Annex K tables); one interleaved SOS; the
+ *           entropy-coded segment (no restart markers, 0x00 behind every 0xFF, last byte filled with 1-bits); EOI.  623 bytes in front of
+ *           the segment, 2 behind it.
+ *   pixels  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb / Cr likewise with offset (128 << 16) + 32767; chroma = the mean of 2 x 2
+ *           converted pixels with bias 1, 2, 1, 2 ... along a row; level shift 128; "islow" DCT; division by 8 q rounding half away from
+ *           zero.  Padding as libjpeg pads (see jpeg.hip): replicated edges, and luma blocks wholly outside the image repeat the DC value
+ *           of the block in front of them.
+ *   layout  the files lie back to back from arena[0] in the order of the images; out_table (device int64 [n][2]) receives (offset, size)
+ *           of every file.  A file that would end behind arena_bytes gets size -1 and none of its bytes is written (so does every file
+ *           behind it: the offsets are the running sum of the sizes); arena bytes outside the files are never touched.  The bytes of a
+ *           file are a pure function of its pixels and the quality (no dependence on the batch, the stream or the launch order).
+ * excel_jpeg_rgb_arena_bytes = the sum of 625 + 3 H_i W_i: the raw size plus the header, which a quality-75 file of an overlay is expected
+ * (not proven) to stay below - hence the -1; tiny images do exceed it (the file of a 1 x 1 image has 631 bytes, its bound 628).  excel_jpeg_rgb_workspace_bytes: coefficients, block start bits and the unstuffed stream at
+ * its worst case of 208 bytes per 8 x 8 block.  Both return 0 for sizes out of range.
+ * off (HOST int64 [n]) and hw (HOST int32 [n][2] = H_i, W_i) are read before the call returns (they travel as kernel arguments).
+ * workspace 16-byte aligned.  Limits: 1 <= n <= 65535, 1 <= H_i, W_i <= 65535, 3 H_i W_i < 2^31, 1 <= quality <= 100. */
+size_t excel_jpeg_rgb_arena_bytes(const int32_t* hw /*host*/, int n);
+size_t excel_jpeg_rgb_workspace_bytes(const int32_t* hw /*host*/, int n);
+int excel_jpeg_encode_rgb_ragged(const uint8_t* rgb, const int64_t* off /*host*/, const int32_t* hw /*host*/, int n, int quality, uint8_t* arena,
+                                 size_t arena_bytes, int64_t* out_table, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation (aug.hip)
  * VOC12ClsDataset(aug=True)'s transform (datasets/voc.py:110-117 over datasets/transforms.py) for a ragged batch of decoded uint8
  * images and label maps on the device, in the reference's order:
