@@ -82,9 +82,12 @@ __device__ __forceinline__ void lvc_finish_row(float* __restrict__ r, float shif
         if (!(z < 0.f)) s += expf(z - m);
     }
     s = wave_sum(s);
+    // a row whose every entry is masked is softmax over all -inf: NaN in every position, like torch.softmax (a row with one entry
+    // left has s >= 1, and its masked entries are exp(-inf) / s = 0)
+    const float masked = s > 0.f ? 0.f : NAN;
     for (int i = lane; i < P; i += 64) {
         const float z = (r[i] - shift) * gamma;
-        r[i] = (z < 0.f) ? 0.f : expf(z - m) / s;       // a row of all -inf gives 0/0 = NaN like torch.softmax
+        r[i] = (z < 0.f) ? masked : expf(z - m) / s;
     }
 }
 

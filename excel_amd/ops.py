@@ -1296,7 +1296,8 @@ def train_augment_image(images_u8, plan, params, crop_size, aug_plan=None, mean=
 
 
 def cam_upsample_bkg_ragged(refined, ncls, g, plan, out=None, zero_unused=True):
-    """refined [B,Smax,P] -> packed cams: (Smax+1) pitched planes per image at its own (H_b, W_b)."""
+    """refined [B,Smax,P] -> packed cams: (Smax+1) pitched planes per image at its own (H_b, W_b).  The pad columns (x >= W_b) of the
+    pitched rows are not written, and with zero_unused=False neither are the planes > ncls[b]: every consumer stops at W_b and nchan[b]."""
     refined = f32c(refined)
     B, smax, P = refined.shape
     assert B == plan.B
