@@ -546,7 +546,7 @@ static int vit_forward_bf16(EXCEL_VIT_FWD_ARGS) {
 }
 static int vit_forward_f16(EXCEL_VIT_FWD_ARGS) {
     // IEEE-half split planes ("f16x3"): every split-type dependent launcher of the body comes from namespace excel_f16
-    using excel_f16::excel_launch_gemm; using excel_f16::excel_launch_gemm_bf16x3; using excel_f16::excel_launch_split_bf16;
+    using excel_f16::excel_launch_gemm_bf16x3; using excel_f16::excel_launch_split_bf16;
     using excel_f16::excel_launch_vt_from_planes; using excel_f16::excel_launch_layernorm; using excel_f16::excel_launch_assemble_ln_pre;
     using excel_f16::excel_launch_token_axis_normalize; using excel_f16::excel_launch_im2col; using excel_f16::excel_launch_attn_rowpass;
     using excel_f16::excel_launch_attn_accum; using excel_f16::excel_launch_attn_strip;

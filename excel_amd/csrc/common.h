@@ -91,6 +91,35 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
     return base + loc;
 }
 
+// Workgroup -> ((image, head) bh, q-block qb) of the attention row pass kernels (attn.hip, attn_f32.hip; grid = q-blocks x (image, head)
+// x score types).  xcd_local = 0: the launch order.
+__device__ __forceinline__ void rowpass_block_map(int N, int xcd_local, int tail_grp, int& bh, int& qb) {
+    bh = blockIdx.y, qb = blockIdx.x;
+    if (xcd_local) {
+        // the q-blocks of one (image, head) share its K / V^T tiles: keep them on one XCD (consecutive logical ids) so the tiles are
+        // fetched from the fabric once, not once per XCD (measured fabric traffic of this kernel: 2.6x its algorithmic bytes)
+        const int nq = gridDim.x, nbh = gridDim.y, lin = blockIdx.x + nq * blockIdx.y;
+        if ((nbh & 7) == 0 && nq > 1 && (N & 127) != 0) {
+            // ... and, inside an XCD's chunk, the full q-blocks first and the partial last q-block of every (image, head) at the end:
+            // 384 x 7 workgroups on 768 slots are 3.5 rounds; 384 x 6 full ones are exactly 3, and the tail round is then made of the
+            // short blocks (17 of 128 rows at N = 785: one active wave) instead of a half-empty round of full ones
+            // Round 4: not ONE tail per XCD but one per chunk of `tail_grp` groups: the partial block of a group then runs while the
+            // group's K / V tiles (400 KB per (image, head)) are still in the XCD's 4-MB L2 - at the very end every partial block
+            // re-fetched them from the fabric (PMC: 463 MB per launch against 312 MB before the tail order, ~308 MB algorithmic).
+            const int x = lin & 7, loc = lin >> 3, per = nbh >> 3;
+            const int grp = min(max(tail_grp, 1), per), cs = grp * nq;
+            const int c = loc / cs, within = loc - c * cs;
+            const int g0 = c * grp, gcount = min(grp, per - g0), nfull = gcount * (nq - 1);
+            if (within < nfull) { bh = x * per + g0 + within / (nq - 1); qb = within % (nq - 1); }
+            else { bh = x * per + g0 + (within - nfull); qb = nq - 1; }
+        } else {
+            const int id = xcd_remap(lin, nq * nbh);
+            qb = id % nq;
+            bh = id / nq;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- launch geometry: uniform batch or ragged batch (tile map)
 // Ragged batches (include/excel_hip.h, "ragged batches"): B images of different sizes in one launch.  Planes are PITCHED (row pitch
 // Wp = W rounded up to 4 floats, so every row and plane starts 16-byte aligned), image b of a K-plane tensor starts at element

@@ -71,7 +71,7 @@ struct GemmPlan {
 constexpr int GEMM_W4_BN = 256;          // columns of a four-wave tile (w4::BN, gemm_w4_body.inc)
 GemmPlan gemm_plan(const GemmShape& s, int n_cu);
 // Kernel selection of the ViT attention (attn_plan.hip): which kernels one layer's attention runs on, with their grids.  Host arithmetic
-// on integers, shared by the launchers (attn.hip, attn_strip.hip), the ViT forward and the host query of the C ABI (excel_attn_plan).
+// on integers, shared by the launchers (attn.hip, attn_f32.hip, attn_strip.hip), the ViT forward and the host query of the C ABI (excel_attn_plan).
 enum { ATTN_STRIP = 0, ATTN_TWOPASS_SPLIT = 1, ATTN_TWOPASS_F32 = 2 };
 constexpr int ATTN_STRIP_MAX_TILES = 40;   // the strip-resident kernel keeps 32 query rows x ALL keys in registers: 8 waves x 5 key tiles of 32
 struct AttnPlan {
@@ -90,6 +90,13 @@ inline bool gemm_half_ok(bool aligned, int N, int K, int ldbh) {
     return aligned && ldbh >= K && (ldbh & 7) == 0 && (long long)N * ldbh * 2 < 0x7fffffffLL;
 }
 
+// exact-fp32 GEMM (gemm.hip) and the exact-fp32 attention of an ATTN_TWOPASS_F32 plan (attn_f32.hip)
+int excel_launch_gemm(const GemmArgs& p, bool b_kmajor, int batch, hipStream_t stream);
+int excel_launch_attn_rowpass_f32(const float* qkvh, float* out, float* stats, int B, int H, int N, int hd, float scale,
+                                  const AttnPlan& plan, hipStream_t st, int flash_nq);
+int excel_launch_attn_accum_f32(const float* qkvh, const float* stats, float* a_sum, float* w_aff, float* attn_out, int B, int H,
+                                int N, int NP, int hd, float scale, int surgery, float w_scale, float aff_scale, int aff_init,
+                                const AttnPlan& plan, hipStream_t st, const float* ex_attn);
 
 int excel_launch_trans_mat_sym(const float* W, float* T, float* Tsym, float* cs, int B, int P, hipStream_t st);
 int excel_launch_cls_compact(const float* onehot, int B, int F, int Smax, int* cls_idx, int* ncls, int* nchan, hipStream_t st);

@@ -1,7 +1,6 @@
-// Launch interfaces of the translation units that depend on the 16-bit type of the split operand planes (gemm.hip, gemm_bf16x3.hip,
+// Launch interfaces of the translation units that depend on the 16-bit type of the split operand planes (gemm_bf16x3.hip, gemm_w4.hip,
 // norm.hip, attn.hip, attn_strip.hip, cam.hip).  Included twice by excel_internal.h: inside namespace excel_bf16 and inside
 // namespace excel_f16 - the six files are compiled once per type (build.py), everything in them lives in the matching namespace.
-int excel_launch_gemm(const GemmArgs& p, bool b_kmajor, int batch, hipStream_t stream);
 int excel_launch_gemm_bf16x3(const GemmBfArgs& p, hipStream_t stream);
 // the four-wave kernels (gemm_w4.hip; gemm_w4x2.hip, IEEE-half split type only: two MFMAs per product for fp16-valued weights) launching a
 // GEMM_W4 / GEMM_W4_MIX plan of gemm_plan(); excel_launch_gemm_bf16x3 routes to them
@@ -18,15 +17,15 @@ int excel_launch_assemble_ln_pre(const float* patch, const float* cls_emb, const
                                  float* x, int B, int tokN, int D, float eps, hipStream_t st);
 int excel_launch_token_axis_normalize(const float* f, float* ss, float* out, int B, int tokN, int C, hipStream_t st);
 int excel_launch_im2col(const float* img, float* col, int B, int S, int ps, hipStream_t st, int split_out = 0);
-int excel_launch_attn_rowpass(const float* qkvh, float* out, float* stats, int B, int H, int N, int hd, float scale,
-                              const AttnPlan& plan, hipStream_t st, int split_out = 0, const unsigned short* qkvs = nullptr, int flash_nq = 1 << 30,
-                              const unsigned short* vt = nullptr, int KP = 0);
-int excel_launch_attn_accum(const float* qkvh, const float* stats, float* a_sum, float* w_aff, float* attn_out, int B, int H,
+// the split-plane row pass and accumulate pass (attn.hip): qkvs = the q|k|v planes, `out` and `a_sum` are written as split tensors
+int excel_launch_attn_rowpass(const unsigned short* qkvs, float* out, float* stats, int B, int H, int N, int hd, float scale,
+                              const AttnPlan& plan, hipStream_t st, int flash_nq);
+int excel_launch_attn_accum(const unsigned short* qkvs, const float* stats, float* a_sum, float* w_aff, float* attn_out, int B, int H,
                             int N, int NP, int hd, float scale, int surgery, float w_scale, float aff_scale, int aff_init,
-                            const AttnPlan& plan, hipStream_t st, const unsigned short* qkvs = nullptr, int a_sum_split = 0,
-                            const float* ex_attn = nullptr);
+                            const AttnPlan& plan, hipStream_t st, const float* ex_attn);
 // `plan`: attn_plan() of this layer (excel_internal.h) - the path (strip-resident kernel up to 8 waves x 5 key tiles of 32, else the two-
-// pass kernels), the row pass's score types and every grid come from it; a launcher refuses a plan that names another path
+// pass kernels), the row pass's score types and every grid come from it; a launcher refuses a plan that names another path (the exact-
+// fp32 path has launchers of its own: excel_internal.h)
 int excel_launch_attn_strip(const unsigned short* qkvs, unsigned short* a_sum, float* w_aff, float* attn_out, int B, int H, int N,
                             int KP, int hd, float scale, int surgery, float w_scale, float aff_scale, int aff_init, const float* ex_attn,
                             const AttnPlan& plan, hipStream_t st, const float* wstats);

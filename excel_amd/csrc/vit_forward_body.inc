@@ -83,7 +83,7 @@
         float* src = (surgery && l > first_surgery) ? ws.xo : ws.x;   // :315 vs :323
         TRY(excel_launch_layernorm(src, nullptr, 1, bw.ln1_w, bw.ln1_b, ws.y, M, D, eps, st, bf));
         TRY(linear(ws.y, bw.in_proj_w, sw.in_proj, sw.h_in_proj, bw.in_proj_b, nullptr, ws.qkvh, 3 * D, D, GEMM_ACT_NONE, GEMM_OUT_QKV_HEADMAJOR));
-        const unsigned short* qkvs = bf ? (const unsigned short*)ws.qkvs : nullptr;
+        const unsigned short* qkvs = (const unsigned short*)ws.qkvs;    // split modes: the q|k|v planes the in-proj GEMM just wrote
         // last block: its original-path output feeds only x[0] = x_ori[0] (:442) -> attention output, out-proj and MLP are
         // needed for the cls rows alone (the reference computes all rows; all_feats consumers still get them on request)
         const bool cls_only = surgery && l == L - 1 && !feats_out;
@@ -94,18 +94,23 @@
         // bf16x3 mode: the strip-resident kernel (attn_strip.hip) owns the softmax statistics of q.q / k.k / v.v and of the
         // q.k weights, so the row pass only runs its flash part (attention output of the original path)
         const AttnPlan ap = attn_plan(B, H, N, h->gemm_mode, surgery ? 1 : 0, (in_aff || attn_l) ? 1 : 0);
-        const bool strip = ap.path == ATTN_STRIP;
-        TRY(excel_launch_attn_rowpass(ws.qkvh, ws.ao, ws.stats, B, H, N, 64, scale, ap, st, bf, qkvs,
-                                      cls_only ? 1 : (1 << 30), bf ? (const unsigned short*)ws.vt : nullptr, ws.KP));
+        const bool f32 = ap.path == ATTN_TWOPASS_F32;
+        const int flash_nq = cls_only ? 1 : (1 << 30);
+        if (f32) TRY(excel_launch_attn_rowpass_f32(ws.qkvh, ws.ao, ws.stats, B, H, N, 64, scale, ap, st, flash_nq));
+        else TRY(excel_launch_attn_rowpass(qkvs, ws.ao, ws.stats, B, H, N, 64, scale, ap, st, flash_nq));
         if (surgery || in_aff || attn_l) {
-            if (strip) {
+            if (ap.path == ATTN_STRIP) {
                 TRY(excel_launch_attn_strip(qkvs, surgery ? (unsigned short*)ws.a_sum : nullptr, in_aff ? w_aff : nullptr, attn_l, B, H, N, ws.KP,
                                             64, scale, surgery ? 1 : 0, surgery ? 1.f : 1.f / (float)H, 1.f / (float)aff_layers,
                                             (l == L - aff_layers) ? 1 : 0, ex_attn, ap, st, ws.stats));   // (the row pass above left the q.k row statistics in ws.stats)
+            } else if (f32) {
+                TRY(excel_launch_attn_accum_f32(ws.qkvh, ws.stats, surgery ? ws.a_sum : nullptr, in_aff ? w_aff : nullptr, attn_l, B, H, N,
+                                                ws.NP, 64, scale, surgery ? 1 : 0, surgery ? 1.f : 1.f / (float)H,
+                                                1.f / (float)aff_layers, (l == L - aff_layers) ? 1 : 0, ap, st, ex_attn));
             } else {
-                TRY(excel_launch_attn_accum(ws.qkvh, ws.stats, surgery ? ws.a_sum : nullptr, in_aff ? w_aff : nullptr, attn_l, B, H, N,
-                                            bf ? ws.KP : ws.NP, 64, scale, surgery ? 1 : 0, surgery ? 1.f : 1.f / (float)H,
-                                            1.f / (float)aff_layers, (l == L - aff_layers) ? 1 : 0, ap, st, qkvs, bf ? 1 : 0, ex_attn));
+                TRY(excel_launch_attn_accum(qkvs, ws.stats, surgery ? ws.a_sum : nullptr, in_aff ? w_aff : nullptr, attn_l, B, H, N,
+                                            ws.KP, 64, scale, surgery ? 1 : 0, surgery ? 1.f : 1.f / (float)H,
+                                            1.f / (float)aff_layers, (l == L - aff_layers) ? 1 : 0, ap, st, ex_attn));
             }
         }
         if (!surgery) {

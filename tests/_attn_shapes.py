@@ -6,7 +6,8 @@ Dispatch (attn_plan.hip), for N = g*g + 1 tokens, cdiv(a, b) = ceil(a / b):
     last  = N - 32 * (tiles - 1)                valid keys in the last tile
     split modes, tiles <= 40: strip kernel, instance ntw = cdiv(tiles, 8), waves nw = cdiv(tiles, ntw),
                               full = tiles - nw * (ntw - 1) waves own ntw tiles, the other nw - full own ntw - 1
-    split modes, tiles  > 40: row pass with 4 score types + attn_accum_bf_kernel; f32: row pass + attn_accum_kernel, whatever N
+    split modes, tiles  > 40: row pass with 4 score types + attn_accum_bf_kernel (attn.hip, one binary per split type)
+    f32, whatever N:          attn_rowpass_f32_kernel + attn_accum_kernel (attn_f32.hip, one binary)
 """
 import numpy as np
 

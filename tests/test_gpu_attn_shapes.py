@@ -23,8 +23,8 @@ The launchers pick a kernel instance per range of N = g*g + 1 (excel_attn_plan; 
 (the LVC cue also runs at g = 28, instance <4>; the size-reuse test adds g = 14 and 28)
 
 B = 3 makes B x strips no multiple of 8 for the strip kernel's split grid and gives blockIdx.z > 0 in the two-pass kernels.  bf16x3 and
-f16x3 run everywhere (the two namespaces are different binaries); f32 - always attn_accum_kernel - on one shape per row, for the row
-pass's 128-row query-block edges.
+f16x3 run everywhere (the two namespaces are different binaries); f32 - always attn_rowpass_f32_kernel + attn_accum_kernel, attn_f32.hip -
+on one shape per row, for the row pass's 128-row query-block edges.
 
 Two nets (TINY, seed 31), each through reload_self_attn(feat_size=g, "train"):
   flat    attn_gain 0.25: nearly uniform rows, every valid key holds >= 0.3 of a uniform share.  One wrongly admitted or dropped key
