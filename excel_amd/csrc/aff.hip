@@ -93,7 +93,7 @@ __global__ void cls_compact_kernel(const float* __restrict__ onehot, int B, int 
             ++n;
         }
     for (int s = min(n, Smax); s < Smax; ++s) cls_idx[(long long)b * Smax + s] = -1;
-    ncls[b] = n;   // caller checks n <= Smax
+    ncls[b] = n;   // the true count: caller checks n <= Smax, consumers clamp (include/excel_hip.h, excel_cls_compact)
     if (nchan) nchan[b] = min(n, Smax) + 1;   // + background channel
 }
 

@@ -13,7 +13,9 @@ from . import ops
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
-        image-level labels; VOC train_aug: 6)."""
+        image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
+        its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
+        tests/test_gpu_many_classes.py) - a caller that must not lose classes checks the one-hot rows itself, like tools/infer_lam."""
         self.model = model
         self.num_classes = num_classes
         self.dilations = tuple(dilations)

@@ -353,7 +353,12 @@ size_t excel_trans_mat_workspace_bytes(int B, int P);
 int excel_compute_trans_mat(const float* w_aff, int B, int P, float* trans_out, void* workspace, void* stream);
 
 /* present-class compaction of one-hot labels [B,F] -> cls_idx [B,Smax] (-1 padded), ncls [B], and optionally
- * nchan [B] = min(ncls,Smax)+1 (channels incl. background)  (cls_lst = torch.where(cls_label)[0], utils/affutils.py:203). */
+ * nchan [B] = min(ncls,Smax)+1 (channels incl. background)  (cls_lst = torch.where(cls_label)[0], utils/affutils.py:203).
+ * More present classes than Smax: ncls[b] is the TRUE count (it may exceed Smax: that is how a caller sees the overflow), cls_idx
+ * holds the first Smax present class indices in ascending order, and nchan[b] = Smax + 1.  Every consumer of ncls below clamps it
+ * with min(ncls, Smax) and touches rows / channels < Smax (+ 1) only, so such an image is processed as if only its first Smax
+ * classes were marked present - same bits, nothing written behind [B,Smax,..] - and the classes beyond are silently dropped.
+ * Nothing in the library refuses it: a caller that must not lose classes compares ncls with Smax itself (tools/infer_lam does). */
 int excel_cls_compact(const float* onehot, int B, int F, int Smax, int32_t* cls_idx, int32_t* ncls, int32_t* nchan, void* stream);
 
 /* scoremap2bbox + box mask (utils/affutils.py:26-53, :208-214) for every (image, present class):

@@ -3,7 +3,8 @@
 One entry per op (or small family of ops): build(ops) -> Case(fn, defined, holes, n_ws; n_ws > 0: the ops allocate through ops._ws).  fn() calls the op(s) on seeded inputs and returns
 the outputs as a tree; it is run twice, on scratch / output memory of 0x00 and of 0xFF bytes, and the two trees must be bit-identical.
 Shapes are the smallest that still have padding in every buffer that can have it (P = 25 -> Pp = 28, nc = 21 -> ncp = 24, C = 30 ->
-Cp = 32, W % 4 != 0 in every pitched plane).
+Cp = 32, W % 4 != 0 in every pitched plane).  The *_many cases run the class-count dependent ops again at the COCO counts (Smax = 18, Cmax = 19,
+images of 18, 9 and 1 present classes): the Smax- / Cmax-sized regions of their workspaces at the size production gives them.
 
 What each workspace holds, and the invariant that keeps an unwritten byte from reaching a result:
   DecoderHandle.forward      dec_ws_layout: nine float regions, no integer table.  Score rows have pitch Pp; dec_row_softmax_kernel zeroes
@@ -48,13 +49,13 @@ COVERS = {
     "feature_affinity_grouped": ["feature_affinity_grouped"],
     "attn_select_mean": ["attn_means"],
     "compute_trans_mat": ["trans_mat"],
-    "refine_cams_with_aff_batched": ["refine"],
-    "cam_upsample_bkg": ["cam_upsample"],
-    "cam_upsample_bkg_ragged": ["cam_upsample_ragged"],
+    "refine_cams_with_aff_batched": ["refine", "refine_many"],
+    "cam_upsample_bkg": ["cam_upsample", "cam_upsample_many"],
+    "cam_upsample_bkg_ragged": ["cam_upsample_ragged", "cam_upsample_ragged_many"],
     "clip_feature_surgery": ["clip_feature_surgery"],
     "patch_text_cam": ["patch_text_cam"],
-    "par_forward": ["par_forward"],
-    "par_forward_ragged": ["par_forward_ragged"],
+    "par_forward": ["par_forward", "par_forward_many"],
+    "par_forward_ragged": ["par_forward_ragged", "par_forward_ragged_many"],
     "dcrf_inference": ["dcrf"],
     "dcrf_inference_ragged": ["dcrf_ragged"],
     "dcrf_lam_ragged": ["dcrf_lam"],
@@ -239,53 +240,63 @@ def _trans_mat(ops):
     return Case(fn, n_ws=3)
 
 
-def _cam_inputs(ops, seed, g=5, F=6, smax=3):
+def _cam_inputs(ops, seed, many=False):
+    """-> (rs, cls_idx, ncls, nchan, host counts, F, smax).  many: the COCO class counts (datasets/coco.py: max_k() == 18) - F = 80,
+    smax = 18, images of 9, 1 and 18 present classes (the first and the last class among them): the Smax- / Cmax-dependent regions
+    of the workspaces at the size production runs them with, next to an image that uses one row of them."""
     rs = np.random.RandomState(seed)
+    F, smax = (80, 18) if many else (6, 3)
     onehot = np.zeros((3, F), np.float32)
-    onehot[0, [1, 4]] = 1
-    onehot[1, [2]] = 1                                                          # one class
-    onehot[2, [0, 3, 5]] = 1
+    if many:
+        onehot[0, rs.choice(F, 9, replace=False)] = 1
+        onehot[1, [41]] = 1
+        onehot[2, np.concatenate([[0, F - 1], 1 + rs.choice(F - 2, 16, replace=False)])] = 1
+    else:
+        onehot[0, [1, 4]] = 1
+        onehot[1, [2]] = 1                                                      # one class
+        onehot[2, [0, 3, 5]] = 1
     idx, ncls, nchan = ops.cls_compact(dev(onehot), smax, want_nchan=True)
-    return rs, idx, ncls, nchan, np.array([2, 1, 3])
+    return rs, idx, ncls, nchan, onehot.sum(1).astype(np.int64), F, smax
 
 
-def _refine(ops):
-    rs, idx, ncls, _, _ = _cam_inputs(ops, 7)
-    attr = dev(rs.rand(3, 25, 6).astype(np.float32))
+def _refine(ops, many=False):
+    rs, idx, ncls, _, _, F, _ = _cam_inputs(ops, 7, many)
+    attr = dev(rs.rand(3, 25, F).astype(np.float32))
     w_aff = dev(rs.rand(3, 25, 25).astype(np.float32) ** 6 + 1e-4)
     return Case(lambda: ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, 5), n_ws=1)
 
 
-def _cam_upsample(ops):
+def _cam_upsample(ops, many=False):
     """zero_unused=False: "channels > ncls[b] are zero unless zero_unused=False: nothing on the path reads them" (ops.cam_upsample_bkg):
     those channels are the documented hole."""
     torch = _torch()
-    rs, _, ncls, _, n = _cam_inputs(ops, 8)
-    refined = dev(rs.rand(3, 3, 25).astype(np.float32))
+    rs, _, ncls, _, n, _, smax = _cam_inputs(ops, 8, many)
+    refined = dev(rs.rand(3, smax, 25).astype(np.float32))
     H, W = 17, 29
 
     def fn():
-        own = torch.empty((3, 4, H, W), dtype=torch.float32, device="cuda")
+        own = torch.empty((3, smax + 1, H, W), dtype=torch.float32, device="cuda")
         return dict(zeroed=ops.cam_upsample_bkg(refined, ncls, 5, H, W), own=ops.cam_upsample_bkg(refined, ncls, 5, H, W, out=own),
                     unused=ops.cam_upsample_bkg(refined, ncls, 5, H, W, zero_unused=False))
 
     def defined(path, t):
         return torch.cat([t[b, :n[b] + 1].reshape(-1) for b in range(3)]) if "unused" in path else t
-    return Case(fn, defined, lambda r: [r["unused"][b, n[b] + 1:] for b in range(3) if n[b] < 3], n_ws=3)
+    return Case(fn, defined, lambda r: [r["unused"][b, n[b] + 1:] for b in range(3) if n[b] < smax], n_ws=3)
 
 
-def _cam_upsample_ragged(ops):
+def _cam_upsample_ragged(ops, many=False):
     """Pitched planes: "the pad columns (x >= W_b) of the pitched rows are not written" (ops.cam_upsample_bkg_ragged), and with
     zero_unused=False neither are the planes > ncls[b]."""
     torch = _torch()
-    rs, _, ncls, _, n = _cam_inputs(ops, 9)
+    rs, _, ncls, _, n, _, smax = _cam_inputs(ops, 9, many)
     sizes = SIZES + [(9, 6)]
     plan = ops.RaggedPlan(sizes, "cuda")
-    refined = dev(rs.rand(3, 3, 25).astype(np.float32))
-    m_all, m_used = dev(pitched_mask(plan, 4)), dev(pitched_mask(plan, 4, n + 1))
+    refined = dev(rs.rand(3, smax, 25).astype(np.float32))
+    C = smax + 1
+    m_all, m_used = dev(pitched_mask(plan, C)), dev(pitched_mask(plan, C, n + 1))
 
     def fn():
-        own = torch.empty((4 * plan.total_pix,), dtype=torch.float32, device="cuda")
+        own = torch.empty((C * plan.total_pix,), dtype=torch.float32, device="cuda")
         return dict(zeroed=ops.cam_upsample_bkg_ragged(refined, ncls, 5, plan, out=own),
                     unused=ops.cam_upsample_bkg_ragged(refined, ncls, 5, plan, zero_unused=False))
     return Case(fn, lambda path, t: t[m_used if "unused" in path else m_all], lambda r: [r["zeroed"][~m_all], r["unused"][~m_used]], n_ws=2)
@@ -318,49 +329,52 @@ def _patch_text_cam(ops):
     return Case(fn, n_ws=6)
 
 
-def _par_forward(ops):
+def _par_forward(ops, many=False):
     """"Channels >= nchan[b] of `out` are not written" (ops.par_forward): the hole of a caller's out=.  Recomputing kernel at W % 4 == 0
-    (with a guide that is resized, so the guide region of the workspace is in use), streamed planes on request and at W % 4 != 0."""
+    (with a guide that is resized, so the guide region of the workspace is in use), streamed planes on request and at W % 4 != 0.
+    many: Cmax = 19 (18 classes + background), an image of 2 channels (one class) next to one of 19."""
     torch = _torch()
     rs = np.random.RandomState(12)
+    C, lo = (19, 2) if many else (3, 1)
     imgs = dev(rs.standard_normal((2, 3, 12, 20)).astype(np.float32))
-    m32 = dev(rs.rand(2, 3, 17, 32).astype(np.float32))
-    m29 = dev(rs.rand(2, 3, 17, 29).astype(np.float32))
-    nchan = dev(np.array([1, 3], np.int32))
+    m32 = dev(rs.rand(2, C, 17, 32).astype(np.float32))
+    m29 = dev(rs.rand(2, C, 17, 29).astype(np.float32))
+    nchan = dev(np.array([lo, C], np.int32))
 
     def fn():
         r = dict(recompute=ops.par_forward(imgs, m32, num_iter=2), streamed=ops.par_forward(imgs, m32, num_iter=2, stream_affinities=True),
                  odd=ops.par_forward(imgs, m29, num_iter=2), nchan=ops.par_forward(imgs, m32, num_iter=2, nchan=nchan),
                  nchan_streamed=ops.par_forward(imgs, m29, num_iter=2, nchan=nchan))
         assert torch.equal(r["recompute"], r["streamed"])
-        need = ops.lib().excel_par_workspace_bytes(2, 3, 17, 32, len(ops.PAR_DILATIONS))
+        need = ops.lib().excel_par_workspace_bytes(2, C, 17, 32, len(ops.PAR_DILATIONS))
         own, ws = torch.empty(m32.shape, dtype=torch.float32, device="cuda"), torch.empty(need, dtype=torch.uint8, device="cuda")
         r["own"] = ops.par_forward(imgs, m32, num_iter=2, nchan=nchan, out=own, ws=ws)
         return r
 
     def defined(path, t):
-        return torch.cat([t[0, :1].reshape(-1), t[1].reshape(-1)]) if "own" in path else t
-    return Case(fn, defined, lambda r: [r["own"][0, 1:]], n_ws=5)
+        return torch.cat([t[0, :lo].reshape(-1), t[1].reshape(-1)]) if "own" in path else t
+    return Case(fn, defined, lambda r: [r["own"][0, lo:]], n_ws=5)
 
 
-def _par_forward_ragged(ops):
+def _par_forward_ragged(ops, many=False):
     """"The pad columns (W_b <= x < Wp_b) of `out` and its planes c >= nchan[b] are UNDEFINED on return" (include/excel_hip.h,
     excel_par_forward_ragged): undefined, not unwritten (the pixel-pair store of an odd W writes its pad lane), so they are masked
     and not required to keep the poison."""
     torch = _torch()
     rs = np.random.RandomState(13)
     plan = ops.RaggedPlan(SIZES, "cuda")
+    C, lo = (19, 2) if many else (3, 1)                                            # many: 18 classes + background next to one class
     imgs = dev(rs.standard_normal((2, 3, 16, 16)).astype(np.float32))
-    masks = dev(pitched(rs, plan, 3))
-    nch = np.array([1, 3])
+    masks = dev(pitched(rs, plan, C))
+    nch = np.array([lo, C])
     nchan = dev(nch.astype(np.int32))
-    m_all, m_used = dev(pitched_mask(plan, 3)), dev(pitched_mask(plan, 3, nch))
+    m_all, m_used = dev(pitched_mask(plan, C)), dev(pitched_mask(plan, C, nch))
 
     def fn():
-        need = ops.lib().excel_par_ragged_workspace_bytes(plan.total_pix, 3)
+        need = ops.lib().excel_par_ragged_workspace_bytes(plan.total_pix, C)
         own, ws = torch.empty(masks.shape, dtype=torch.float32, device="cuda"), torch.empty(need, dtype=torch.uint8, device="cuda")
-        return dict(all=ops.par_forward_ragged(imgs, masks, plan, 3, num_iter=2), nchan=ops.par_forward_ragged(imgs, masks, plan, 3, num_iter=2, nchan=nchan),
-                    own=ops.par_forward_ragged(imgs, masks, plan, 3, num_iter=2, nchan=nchan, out=own, ws=ws))
+        return dict(all=ops.par_forward_ragged(imgs, masks, plan, C, num_iter=2), nchan=ops.par_forward_ragged(imgs, masks, plan, C, num_iter=2, nchan=nchan),
+                    own=ops.par_forward_ragged(imgs, masks, plan, C, num_iter=2, nchan=nchan, out=own, ws=ws))
     return Case(fn, lambda path, t: t[m_all if "all" in path else m_used], n_ws=2)
 
 
@@ -571,6 +585,10 @@ CASES = {
     "cam_upsample_ragged": _cam_upsample_ragged, "clip_feature_surgery": _clip_feature_surgery, "patch_text_cam": _patch_text_cam,
     "par_forward": _par_forward, "par_forward_ragged": _par_forward_ragged, "dcrf": _dcrf, "dcrf_ragged": _dcrf_ragged, "dcrf_lam": _dcrf_lam,
     "train_augment": _train_augment, "png": _png, "jpeg": _jpeg, "vit_f32": _vit_f32,
+    # the same ops at the COCO class counts (Smax = 18, Cmax = 19; mixed counts with 18 and 1)
+    "refine_many": lambda ops: _refine(ops, many=True), "cam_upsample_many": lambda ops: _cam_upsample(ops, many=True),
+    "cam_upsample_ragged_many": lambda ops: _cam_upsample_ragged(ops, many=True), "par_forward_many": lambda ops: _par_forward(ops, many=True),
+    "par_forward_ragged_many": lambda ops: _par_forward_ragged(ops, many=True),
     # no workspace: outputs only
     "seg_ops": _seg_ops, "input_ops": _input_ops, "label_ops": _label_ops, "train_panels": _train_panels,
 }
