@@ -178,6 +178,8 @@ SIGNATURES = {
     "excel_train_augment_image": (c_i, [c_f, c_f, C.POINTER(TrainAugInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f, c_f, c_f]),
     "excel_argmax_label": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_ll, c_f, c_f, c_f]),
     "excel_confusion_accumulate": (c_i, [c_f, c_f, c_ll, c_i, c_f, c_f]),
+    "excel_nonfinite_count": (c_i, [c_f, c_i, c_ll, c_f, c_i, c_f]),
+    "excel_confusion_accumulate_masked": (c_i, [c_f, c_f, c_i, c_ll, c_f, C.POINTER(RaggedInfo), c_f, c_i, c_f, c_f]),
     "excel_attr_aggregate": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, C.c_double, c_f, c_f]),
     "excel_bilinear_resize": (c_i, [c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_f]),
     "excel_pos_embed_resize": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f]),

@@ -191,6 +191,9 @@ class VitHandle:
             # results, ~2.5 % slower), "f16x2" (f16x3 with two MFMAs per product in the nn.Linear GEMMs - needs fp16-VALUED weights, which
             # every published CLIP archive has: bit-identical to f16x3 there and faster than bf16x3) or "f32" (exact fp32 MFMA).
             # Default ("auto"): f16x2 when the weights allow it, else bf16x3.  EXCEL_GEMM_MODE overrides.
+            # The f16 modes hold activations (LayerNorm / QuickGELU outputs, q|k|v) in IEEE half: beyond 65 504 they turn into NaNs on
+            # purpose.  Nothing in the forward pass looks for them; the overflow guard (nonfinite_count + confusion_accumulate_masked,
+            # pipeline guard=, infer_lam --overflow_guard) is what catches such an image and re-runs it in "f32".
             mode = gemm_mode or os.environ.get("EXCEL_GEMM_MODE", "auto")
             if mode != "f32" and (width % 32 or (3 * patch * patch) % 32):
                 mode = "f32"
@@ -1353,6 +1356,41 @@ def confusion_accumulate(gt_u8, pred_u8, num_classes, hist=None):
         hist = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=gt.device)
     check(lib().excel_confusion_accumulate(_p(gt, torch.uint8), _p(pr, torch.uint8), gt.numel(), num_classes,
                                            _p(hist, torch.int64), _stream()), "excel_confusion_accumulate")
+    return hist
+
+
+# ------------------------------------------------------------------ overflow guard of the f16 modes (include/excel_hip.h, "overflow guard")
+def nonfinite_count(x, out=None, init=True):
+    """x: float32 [B, ...] (first dimension = the image; contiguous, 4-byte aligned is enough) -> int32 [B]: per image the number of
+    +-inf / NaN values.  init=False ADDS to `out`, so the tensors of one step share one counter.  No workspace, no synchronisation."""
+    B = int(x.shape[0])
+    if out is None:
+        if not init:
+            raise ValueError("nonfinite_count: init=False adds to an existing counter: pass out=")
+        out = torch.empty((B,), dtype=torch.int32, device=x.device)
+    if out.numel() != B:
+        raise ValueError(f"nonfinite_count: out holds {out.numel()} counters for {B} images")
+    check(lib().excel_nonfinite_count(_p(x), B, x.numel() // B, _p(out, torch.int32), 1 if init else 0, _stream()), "excel_nonfinite_count")
+    return out
+
+
+def confusion_accumulate_masked(gt_u8, pred_u8, num_classes, skip, hist=None, plan=None):
+    """confusion_accumulate over the images with skip[b] == 0 (skip: int32 [B], device - e.g. nonfinite_count's counters).
+    plan=None: gt / pred are uniform [B,H,W] maps; with a RaggedPlan they are its tight label maps back to back."""
+    gt = gt_u8.contiguous()
+    pr = pred_u8.contiguous()
+    assert gt.numel() == pr.numel()
+    B = plan.B if plan is not None else int(gt.shape[0])
+    if skip.numel() != B:
+        raise ValueError(f"confusion_accumulate_masked: skip holds {skip.numel()} flags for {B} images")
+    if plan is not None and gt.numel() != plan.total_label_pix:
+        raise ValueError(f"confusion_accumulate_masked: {gt.numel()} pixels, the plan holds {plan.total_label_pix}")
+    if hist is None:
+        hist = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=gt.device)
+    check(lib().excel_confusion_accumulate_masked(_p(gt, torch.uint8), _p(pr, torch.uint8), B, gt.numel() // B,
+                                                  _p(plan.table, torch.int32) if plan is not None else None,
+                                                  C.byref(plan.info) if plan is not None else None, _p(skip, torch.int32), num_classes,
+                                                  _p(hist, torch.int64), _stream()), "excel_confusion_accumulate_masked")
     return hist
 
 

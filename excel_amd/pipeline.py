@@ -5,17 +5,46 @@ One `run_batch` = tools/infer_lam.py:74-114 for B images at once:
     -> min-max + cv2-style up-sampling + background -> PAR x20 -> arg-max -> confusion accumulate.
 No host round trip happens inside a step (the reference makes ~2k+5 per image).
 """
+import contextlib
+
 import torch
 
 from . import ops
 
+GUARD_MODES = (None, "skip", "observe")
+
+
+class GuardTicket:
+    """The per-image non-finite counts of one guarded step on their way to the host: a pinned int32 [B] the step's stream copies
+    into, and the event recorded behind that copy.  ready() never blocks; flags() waits for the event."""
+
+    def __init__(self, host, event):
+        self._host, self._event = host, event
+
+    def ready(self):
+        return self._event.query()
+
+    def flags(self):
+        self._event.synchronize()
+        return self._host.numpy()
+
 
 class TrainingFreePipeline:
-    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6):
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
-        tests/test_gpu_many_classes.py) - a caller that must not lose classes checks the one-hot rows itself, like tools/infer_lam."""
+        tests/test_gpu_many_classes.py) - a caller that must not lose classes checks the one-hot rows itself, like tools/infer_lam.
+        `guard` = the overflow guard of the f16 GEMM modes (an activation beyond 65 504 turns an image's maps into NaNs there):
+          None       today's step, launch for launch;
+          "skip"     run_batch / run_batch_ragged count the non-finite values per image in what they hand to the random walk (attr, the
+                     affinity) and in its result, score only the images without one (ops.confusion_accumulate_masked) and leave the
+                     counts in `last_flags` (device int32 [B], until the next step on the stream) and `last_guard` (a GuardTicket);
+          "observe"  the same counts and ticket, every image scored (the exact-fp32 second pass, see exact_mode)."""
+        if guard not in GUARD_MODES:
+            raise ValueError(f"guard must be one of {GUARD_MODES} (got {guard!r})")
+        self.guard = guard
+        self.last_flags = self.last_guard = None
         self.model = model
         self.num_classes = num_classes
         self.dilations = tuple(dilations)
@@ -24,6 +53,11 @@ class TrainingFreePipeline:
         self.smax = smax
         self.hist = None
         self._bufs = {}
+
+    @property
+    def device(self):
+        """Where the model lives (tools/infer_lam.validate reads it from a caller-supplied pipeline)."""
+        return torch.device(getattr(self.model, "device", "cuda"))
 
     def reset(self):
         self.drain()
@@ -44,6 +78,45 @@ class TrainingFreePipeline:
             b = self._bufs[key] = torch.empty(int(numel), dtype=dtype, device=device)
         return b[:int(numel)]
 
+    # ------------------------------------------------------------------ overflow guard
+    def _guard_count(self, *tensors):
+        """guard set: per-image non-finite counts over `tensors` ([B, ...] each; the first launch writes, the rest add), then the copy to
+        pinned memory and the event of the step's ticket - all on the step's stream, no synchronisation.  -> the device counts or None."""
+        if self.guard is None:
+            return None
+        B = tensors[0].shape[0]
+        flags = self._buf("guard", B, torch.int32, tensors[0].device)
+        for i, t in enumerate(tensors):
+            ops.nonfinite_count(t, out=flags, init=(i == 0))
+        host = torch.empty((B,), dtype=torch.int32, pin_memory=True)
+        host.copy_(flags, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.last_flags, self.last_guard = flags, GuardTicket(host, ev)
+        return flags
+
+    def _score(self, gts, labels, flags, plan=None):
+        if self.guard == "skip":
+            return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, self.hist, plan=plan)
+        return ops.confusion_accumulate(gts, labels, self.num_classes, self.hist)                  # evaluate.py:9-20
+
+    def _no_guard(self, what):
+        if self.guard is not None:
+            raise ValueError(f"{what} has no overflow guard (guard={self.guard!r}): it is a bench / training path - use run_batch or "
+                             "run_batch_ragged, or build the pipeline with guard=None")
+
+    @contextlib.contextmanager
+    def exact_mode(self):
+        """Switch the model's ViT handle to exact fp32 ("f32") for the block and restore the mode it found (the second pass over the
+        images the guard flagged).  Switching re-splits the weights and synchronises the device: not for use inside a timed loop."""
+        h = self.model.encoder.visual.handle()
+        before = h.gemm_mode()
+        h.set_gemm_mode("f32")
+        try:
+            yield self
+        finally:
+            h.set_gemm_mode(before)
+
     @torch.no_grad()
     def run_batch(self, inputs, cls_labels, gts=None, label_hw=None, return_intermediates=False):
         """inputs [B,3,S,S] f32 (normalised, already at the network size), cls_labels [B,F] f32 one-hot,
@@ -54,6 +127,7 @@ class TrainingFreePipeline:
         _, _, attr, attn_w, _ = self.model(inputs)                                                  # infer_lam.py:79
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
+        flags = self._guard_count(attr, attn_w.w_aff, refined)
         C = self.smax + 1
         if return_intermediates:            # the caller keeps these: fresh tensors, unused channels zeroed
             cams = ops.cam_upsample_bkg(refined, ncls, g, H, W)                                     # affutils.py:164-166
@@ -67,7 +141,7 @@ class TrainingFreePipeline:
                                       out=self._buf("par_out", B * C * H * W, device=dev).view(B, C, H, W))
         labels = ops.argmax_label(par_out, nchan, idx)                                              # affutils.py:86-87
         if gts is not None:
-            self.hist = ops.confusion_accumulate(gts, labels, self.num_classes, self.hist)          # evaluate.py:9-20
+            self.hist = self._score(gts, labels, flags)
         if return_intermediates:
             return labels, dict(attr=attr, w_aff=attn_w.w_aff, refined=refined, cams=cams, par_out=par_out,
                                 cls_idx=idx, ncls=ncls)
@@ -94,12 +168,14 @@ class TrainingFreePipeline:
         _, _, attr, attn_w, _ = self.model(inputs)                                                  # infer_lam.py:79
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
+        flags = self._guard_count(attr, attn_w.w_aff, refined)
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=attn_w.w_aff))
+                                      dict(attr=attr, w_aff=attn_w.w_aff), flags)
 
-    def _ragged_back_half(self, inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates, inter):
+    def _ragged_back_half(self, inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates, inter, flags=None):
         """Up-sampling + background, PAR, arg-max and confusion of a ragged step (tools/infer_lam.py:94), shared by every regime.
-        inputs [B,3,S,S] = the network input PAR reads; `inter` = the regime's own intermediates (attr, w_aff)."""
+        inputs [B,3,S,S] = the network input PAR reads; `inter` = the regime's own intermediates (attr, w_aff); `flags` = the guard's
+        per-image counts (None without a guard)."""
         dev = inputs.device
         C = self.smax + 1
         keep = return_intermediates
@@ -112,7 +188,7 @@ class TrainingFreePipeline:
                                          out=None if keep else self._buf("par_out", C * plan.total_pix, device=dev))   # affutils.py:84
         labels = ops.argmax_label_ragged(par_out, plan, C, nchan, idx)                              # affutils.py:86-87
         if gts_packed is not None:
-            self.hist = ops.confusion_accumulate(gts_packed, labels, self.num_classes, self.hist)   # evaluate.py:9-20
+            self.hist = self._score(gts_packed, labels, flags, plan=plan)
         if return_intermediates:
             return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
         return labels
@@ -126,6 +202,7 @@ class TrainingFreePipeline:
     @torch.no_grad()
     def run_batch_split(self, inputs, cls_labels, gts=None, label_hw=None, nsplit=2):
         """Same contract as run_batch; the returned labels and self.hist are complete only after drain()."""
+        self._no_guard("run_batch_split")
         B, _, S, _ = inputs.shape
         nsplit = max(1, min(nsplit, B))
         if nsplit == 1:
@@ -168,6 +245,7 @@ class TrainingFreePipeline:
 
     @torch.no_grad()
     def run_batch_overlapped(self, inputs, cls_labels, gts=None, label_hw=None):
+        self._no_guard("run_batch_overlapped")
         sa, sb = self._streams()
         cur = torch.cuda.current_stream()
         B, _, S, _ = inputs.shape
@@ -225,11 +303,11 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     half comes from a feature-only forward of flip x.  The whole-batch means of excel_feature_affinity are replaced by the grouped
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
-    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6):
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None):
         if getattr(model, "_dec", None) is None:
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
-        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax)
+        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -272,8 +350,9 @@ class OptimisedLamPipeline(TrainingFreePipeline):
         del maps
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # infer_lam.py:93
+        flags = self._guard_count(attr, w_aff, refined)
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred))
+                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred), flags)
 
 
 class ValidationPipeline(TrainingFreePipeline):
@@ -289,9 +368,12 @@ class ValidationPipeline(TrainingFreePipeline):
     (= the reference only at batch 1); here it is the grouped entry with group 1, the per-image affinity.  The seg logits [B,nc,g,g] go to
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
-    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6):
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None):
         if getattr(model, "_dec", None) is None:
             raise ValueError("ValidationPipeline needs the decoder head: build ExCEL_model(..., decoder_state_dict=)")
+        if guard is not None:
+            raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
+                             "histograms per step and is out of the guard's scope")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax)
         self.attn_layers = attn_layers
         self.hist_seg = None

@@ -32,6 +32,12 @@ Differences from the reference, all deliberate:
     `--crf_label_dir DIR` writes the CRF labels as palette PNGs through the device encoder (like --save_label);
     --segs_crf_rgb_dir keeps its colour-coded files.  `--infer_set` names with "test" keep the record path (the reference scores
     against image[:,:,0] there, :213-214);
+  * `--overflow_guard` (default auto = rerun on the batched GPU loop when the run's GEMM mode is f16x2 / f16x3, else off): those modes
+    hold activations in IEEE half and turn a value beyond 65 504 into NaNs on purpose.  Every batched step counts the non-finite
+    values of its attribute maps, affinity and random-walk result per image on the device (pipeline guard="skip"; no host wait in the
+    loop), keeps flagged images out of the confusion matrices, and after the loop exactly those images run once more in exact fp32
+    through the same consumers - their files are overwritten by name.  `raise` stops at the first flagged image instead; `off` is the
+    unguarded loop.  The second pass is rank-local (no collective); the report is validate.last_guard;
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -51,6 +57,32 @@ VOC_CLASSES = ["_background_", "aeroplane", "bicycle", "bird", "boat", "bottle",
 
 def _bool(x):
     return x.lower() in ["true", "1", "yes"]
+
+
+OVERFLOW_GUARD_POLICIES = ("auto", "off", "raise", "rerun")
+F16_GEMM_MODES = ("f16x2", "f16x3")          # activations in IEEE half: range 65 504, overflow -> NaN (include/excel_hip.h, modes 2 and 3)
+
+
+def resolve_overflow_guard(policy, gemm_mode, on_gpu, batched):
+    """--overflow_guard -> the policy the loop runs with ("off" | "raise" | "rerun").  auto = rerun when the loop is the batched one on
+    a GPU and the handle's mode (after the start-up check) is an f16 mode, else off: bf16x3 has the fp32 exponent range, f32 is exact.
+    An explicit raise / rerun on the per-image loop is an error: that loop has no guard."""
+    if policy not in OVERFLOW_GUARD_POLICIES:
+        raise ValueError(f"--overflow_guard must be one of {OVERFLOW_GUARD_POLICIES} (got {policy!r})")
+    if policy == "auto":
+        return "rerun" if (batched and on_gpu and gemm_mode in F16_GEMM_MODES) else "off"
+    if policy != "off" and not batched:
+        raise ValueError(f"--overflow_guard {policy} needs the batched loop: the per-image loop (--api_path true, or --training_free false "
+                         "on uniform synthetic batches) has no overflow guard - use --overflow_guard off or auto there")
+    return policy
+
+
+def _handle_gemm_mode(model):
+    """The GEMM mode of the model's ViT handle, or None (no model: a stub pipeline)."""
+    try:
+        return model.encoder.visual.handle().gemm_mode()
+    except AttributeError:
+        return None
 
 
 def get_parser():
@@ -110,6 +142,11 @@ def get_parser():
                         "--gemm_check_tol the run moves down the ladder bf16x3 -> f16x3 (f16x2 on fp16-valued weights) -> f32 (ill-conditioned weights; "
                         "ExCEL_model.check_numerics)")
     p.add_argument("--gemm_check_tol", default=5e-4, type=float)
+    p.add_argument("--overflow_guard", default="auto", choices=list(OVERFLOW_GUARD_POLICIES),
+                   help="the f16 GEMM modes (f16x2 / f16x3) turn an activation beyond 65 504 into NaNs: rerun = count the non-finite values "
+                        "per image on the device in every batched step, keep flagged images out of the scores and run exactly those again in "
+                        "exact fp32 after the loop; raise = stop at the first flagged image; off = no check; auto = rerun on the batched GPU "
+                        "loop in an f16 mode, else off (bf16x3 has the fp32 exponent range, f32 is exact)")
     p.add_argument("--cpu_affinity", default="auto", choices=["auto", "off"],
                    help="auto: with several ranks on the node every rank pins itself (decode pool included) to its own share of the host cores")
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
@@ -226,6 +263,9 @@ class _CamSaver:
             H, W = int(normed.shape[1]), int(normed.shape[2])
             self.writer.submit(out.view(-1), self._items(str(name), np.asarray(cls_lst.cpu() if hasattr(cls_lst, "cpu") else cls_lst), H, W, 0))
 
+    def barrier(self):
+        self.writer.barrier()
+
     def close(self):
         return self.writer.close()
 
@@ -262,6 +302,9 @@ class _LabelSaver:
         from .. import ops
         B, H, W = labels.shape
         self.ragged(names, ops.RaggedPlan([(H, W)] * B, labels.device), labels.contiguous().view(-1))
+
+    def barrier(self):
+        self.writer.barrier()
 
     def close(self):
         return self.writer.close()
@@ -309,7 +352,8 @@ class _CrfInline:
             H, W, o = int(plan.hw[b, 0]), int(plan.hw[b, 1]), int(plan.loff[b])
             self.futures.append(self.pool.submit(_save_crf_rgb, os.path.join(self.rgb_dir, str(name) + ".png"), host[o:o + H * W].reshape(H, W)))
 
-    def ragged(self, names, plan, images, cams, Cmax, nchan, nchan_host, cls_idx, gts_packed):
+    def ragged(self, names, plan, images, cams, Cmax, nchan, nchan_host, cls_idx, gts_packed, skip=None):
+        """`skip`: the step's per-image overflow flags (device int32 [B]) - flagged images stay out of `hist` - or None."""
         from .. import ops
         P = CRF_PARAMS
         labels, _ = ops.dcrf_lam_ragged(images, plan, cams, Cmax, nchan, nchan_host, cls_idx, P["iter_max"], P["pos_w"], P["pos_xy_std"],
@@ -317,7 +361,9 @@ class _CrfInline:
         self.calls += 1
         self.groups += int(getattr(ops.dcrf_lam_ragged, "last_groups", 1))
         self.peak_ws = max(self.peak_ws, int(getattr(ops.dcrf_lam_ragged, "last_workspace_bytes", 0)))
-        if gts_packed is not None:
+        if gts_packed is not None and skip is not None:
+            self.hist = ops.confusion_accumulate_masked(gts_packed, labels, self.nc, skip, self.hist, plan=plan)
+        elif gts_packed is not None:
             self.hist = ops.confusion_accumulate(gts_packed, labels, self.nc, self.hist)    # :233
         if self.lab is not None:
             self.lab.ragged(names, plan, labels)
@@ -344,6 +390,14 @@ class _CrfInline:
             plan = ops.RaggedPlan([tuple(labels.shape)], None)
             self._rgb([name], plan, labels.view(-1))
         return labels
+
+    def barrier(self):
+        """Every file queued so far is on disk (a writer's error is raised)."""
+        for f in self.futures:
+            f.result()
+        self.futures = []
+        if self.lab is not None:
+            self.lab.barrier()
 
     def close(self):
         err = None
@@ -452,13 +506,22 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     # the optimised-LAM regime runs batched on ragged batches; uniform synthetic batches keep its per-image call sequence
     per_image = args.api_path or (not training_free and not ragged_batches)
     ragged = ragged_batches and not per_image
+    # the overflow guard of the f16 modes: resolved from the mode the handle is in NOW (after the start-up check)
+    mode = _handle_gemm_mode(model if pipe is None else getattr(pipe, "model", None))
+    policy = resolve_overflow_guard(getattr(args, "overflow_guard", "auto"), mode, torch.device(device).type == "cuda", not per_image)
     if pipe is None:
+        guard = "skip" if policy in ("raise", "rerun") else None
         if training_free:
             pipe = TrainingFreePipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
-                                        caa_thre=0.79, smax=dataset.max_k())
+                                        caa_thre=0.79, smax=dataset.max_k(), guard=guard)
         elif ragged:
             pipe = OptimisedLamPipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
-                                        caa_thre=0.79, smax=dataset.max_k())
+                                        caa_thre=0.79, smax=dataset.max_k(), guard=guard)
+    elif policy != "off" and getattr(pipe, "guard", None) is None:
+        # a caller's pipeline keeps the guard it was built with: without one there are no flags to act on
+        logging.warning(f"--overflow_guard {policy}: the supplied pipeline was built without a guard - running unguarded")
+        policy = "off"
+    build_validation.last_guard = {"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []}
     hist = torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device)
     t0 = time.time()
     save_cam = bool(getattr(args, "save_cam", False))
@@ -476,7 +539,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     try:
         lab = _LabelSaver(args) if bool(getattr(args, "save_label", False)) else None
         crf = _CrfInline(args, device) if crf_inline_wanted(args) else None
-        out = _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab, crf)
+        out = _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab, crf,
+                                build_validation.last_guard)
         if lab is not None:                                  # every file on disk (and a writer's error raised) before the scores are reported
             lab, done = None, lab
             done.close()
@@ -506,66 +570,17 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
 
 
 def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab=None,
-                      crf=None):
+                      crf=None, guard=None):
     from ..utils import evaluate
     from ..utils.affutils import refine_cams_with_aff, refine_cams_with_bkg_weclip
     from .. import ops
     S = args.resize_size
     on_gpu = torch.device(device).type == "cuda"
     nimg = 0
-    if ragged:
-        # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
-        from ..datasets.loader import ragged_batches
-        from ..utils import imutils
-        pipe.hist = hist
-        keep = bool(getattr(args, "crf_post", False)) and crf is None      # the record path of the CRF stage; --crf_inline needs no copies
-        nw = int(getattr(args, "num_workers", -1))
-        if nw < 0:                                           # the JPEG encoders of --save_cam share this rank's CPUs
-            nw = max(2, default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))) - writers)
-        if getattr(args, "decode", "threads") == "processes" and nw > 0:    # the reference's mechanism (DataLoader worker processes, :167)
-            batches = ragged_batches(dataset, indices, args.batch_size, num_workers=nw, pin_memory=False)
-        else:                                                               # default: a thread pool (datasets/loader.threaded_batches)
-            from ..datasets.loader import threaded_batches
-            batches = threaded_batches(dataset, indices, args.batch_size, num_threads=max(nw, 1))
-        batches = _check_present_classes(batches, pipe.smax)
-        if cam is not None or crf is not None:                 # the host one-hot rows, in the feeder's order (it keeps the order)
-            from collections import deque
-            host_cls = deque()
-
-            def _tap(bs):
-                for rb in bs:
-                    host_cls.append(rb.cls.numpy().copy())
-                    yield rb
-            batches = _tap(batches)
-        if on_gpu:
-            from ..datasets.loader import DeviceFeeder
-            feed = DeviceFeeder(batches, device)              # H2D on a copy stream, a few batches ahead
-        else:                                                  # (control-flow tests: a stub pipeline on CPU tensors)
-            feed = ((rb.names, ops.RaggedPlan(rb.hw, None), rb.images, rb.cls, rb.labels) for rb in batches)
-        for names, plan, images, cls_t, labels_t in feed:
-            out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
-            cls_host = host_cls.popleft() if (cam is not None or crf is not None) else None
-            if cam is not None:                                                             # :97-111, same stream, step's own cams
-                cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, cls_host)
-            if crf is not None:                                                             # :179-237, same stream, step's own cams
-                nchan_host = np.minimum((cls_host != 0).sum(1), pipe.smax).astype(np.int32) + 1
-                crf.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, pipe.last_nchan, nchan_host, pipe.last_cls_idx, labels_t)
-            if lab is not None:                                                             # :95, same stream, the labels just scored
-                lab.ragged(names, plan, out[0] if keep else out)
-            if keep:                                                                        # :116-119 record for the CRF stage
-                inter = out[1]
-                cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
-                for b, name in enumerate(names):
-                    k = min(int(ncls[b]), pipe.smax)            # (ncls <= smax is enforced below; the record stays consistent anyway)
-                    imutils.save_logits(args.logits_dir, name, plan.planes(inter["cams"], b, pipe.smax + 1)[:k + 1], cls_idx[b, :k].astype(np.int64),
-                                        run_token=getattr(args, "run_token", None))
-            nimg += len(names)
-        if on_gpu:
-            torch.cuda.synchronize()
-        return pipe.hist, nimg, time.time() - t0
-    bs = 1 if per_image else args.batch_size
-    for s in range(0, len(indices), bs):
-        names, imgs, gts, cls = dataset.batch(indices[s:s + bs])
+    if not per_image:
+        return _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu)
+    for s in range(0, len(indices)):
+        names, imgs, gts, cls = dataset.batch(indices[s:s + 1])
         inputs = torch.from_numpy(imgs).to(device, non_blocking=True)
         if cam is not None and inputs.dtype != torch.uint8:
             raise ValueError("--save_cam needs the decoded uint8 images (--data_folder, --ragged true or --u8_input true)")
@@ -576,40 +591,177 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
             inputs = ops.bilinear_resize(inputs, S, S, align_corners=False)                 # :74
         cls_labels = torch.from_numpy(cls).to(device, non_blocking=True)
         gt_dev = torch.from_numpy(gts).to(device, non_blocking=True)
-        if per_image:
-            if training_free:
-                _, _, attr_maps_raw, attn_weights, attn_pred = model(inputs)                # :79
-            else:
-                # optimised-LAM regime (:84-85, :91): needs the caller's decoder as model.feature_head
-                from ..utils.camutils import cure_attr_map_flip
-                _, _, _, attn_weights, attn_pred = model(inputs, n_attn_out=6)              # :79
-                if attn_pred is None:
-                    raise RuntimeError("--training_free false needs model.feature_head (the learned decoder, SURVEY 8f #2)")
-                attr_maps_raw = cure_attr_map_flip(model, inputs)                           # :85
-            for i, attr_map in enumerate(attr_maps_raw):                                    # :88
-                seg_attn = None if training_free else attn_pred[i][None]                    # :91-92
-                refined, cls_lst = refine_cams_with_aff(attr_map, attn_weights[:, i], cls_labels[i], size=inputs.shape[2:],
-                                                        seg_attn=seg_attn, caa_thre=0.79)   # :93
-                labels, normed = refine_cams_with_bkg_weclip(refined, inputs[i], cls_lst, par, gts.shape[-2:])   # :94
-                if crf is not None:                                                         # :179-237 without a record
-                    crf.image(str(names[i]), decoded[i], normed, cls_lst, gt_dev[i])
-                elif getattr(args, "crf_post", False):                                      # :116-119 record for the CRF stage
-                    from ..utils import imutils
-                    imutils.save_logits(args.logits_dir, str(names[i]), normed, cls_lst, run_token=getattr(args, "run_token", None))
-                if cam is not None:                                                         # :97-111
-                    cam.image(names[i], decoded[i], normed, cls_lst)
-                hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
-                if lab is not None:                                                         # :95 (uint8 as hist_from_labels scores them)
-                    lab.uniform([names[i]], labels[:1].to(torch.uint8))
+        if training_free:
+            _, _, attr_maps_raw, attn_weights, attn_pred = model(inputs)                    # :79
         else:
-            pipe.hist = hist
-            labels = pipe.run_batch(inputs, cls_labels, gt_dev)
-            hist = pipe.hist
-            if lab is not None:                                                             # :95
-                lab.uniform(names, labels)
+            # optimised-LAM regime (:84-85, :91): needs the caller's decoder as model.feature_head
+            from ..utils.camutils import cure_attr_map_flip
+            _, _, _, attn_weights, attn_pred = model(inputs, n_attn_out=6)                  # :79
+            if attn_pred is None:
+                raise RuntimeError("--training_free false needs model.feature_head (the learned decoder, SURVEY 8f #2)")
+            attr_maps_raw = cure_attr_map_flip(model, inputs)                               # :85
+        for i, attr_map in enumerate(attr_maps_raw):                                        # :88
+            seg_attn = None if training_free else attn_pred[i][None]                        # :91-92
+            refined, cls_lst = refine_cams_with_aff(attr_map, attn_weights[:, i], cls_labels[i], size=inputs.shape[2:],
+                                                    seg_attn=seg_attn, caa_thre=0.79)       # :93
+            labels, normed = refine_cams_with_bkg_weclip(refined, inputs[i], cls_lst, par, gts.shape[-2:])   # :94
+            if crf is not None:                                                             # :179-237 without a record
+                crf.image(str(names[i]), decoded[i], normed, cls_lst, gt_dev[i])
+            elif getattr(args, "crf_post", False):                                          # :116-119 record for the CRF stage
+                from ..utils import imutils
+                imutils.save_logits(args.logits_dir, str(names[i]), normed, cls_lst, run_token=getattr(args, "run_token", None))
+            if cam is not None:                                                             # :97-111
+                cam.image(names[i], decoded[i], normed, cls_lst)
+            hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
+            if lab is not None:                                                             # :95 (uint8 as hist_from_labels scores them)
+                lab.uniform([names[i]], labels[:1].to(torch.uint8))
         nimg += len(imgs)
     torch.cuda.synchronize()
     return hist, nimg, time.time() - t0
+
+
+def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu):
+    """The batched loop of build_validation: one pass over `indices`, and with the overflow guard's `rerun` policy a second pass in exact
+    fp32 over the images the first one flagged - the same loop body (`steps`) and the same consumers both times."""
+    from collections import deque
+    from .. import ops
+    S = args.resize_size
+    policy = guard["policy"] if guard else "off"
+    pipe.hist = hist
+    host_cls = deque()          # the host one-hot rows, in the feeder's order (it keeps the order)
+    if ragged:
+        # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
+        from ..datasets.loader import ragged_batches
+        from ..utils import imutils
+        keep = bool(getattr(args, "crf_post", False)) and crf is None      # the record path of the CRF stage; --crf_inline needs no copies
+        nw = int(getattr(args, "num_workers", -1))
+        if nw < 0:                                           # the JPEG encoders of --save_cam share this rank's CPUs
+            nw = max(2, default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))) - writers)
+
+    def feed_of(idxs):
+        if getattr(args, "decode", "threads") == "processes" and nw > 0:    # the reference's mechanism (DataLoader worker processes, :167)
+            batches = ragged_batches(dataset, idxs, args.batch_size, num_workers=nw, pin_memory=False)
+        else:                                                               # default: a thread pool (datasets/loader.threaded_batches)
+            from ..datasets.loader import threaded_batches
+            batches = threaded_batches(dataset, idxs, args.batch_size, num_threads=max(nw, 1))
+        batches = _check_present_classes(batches, pipe.smax)
+        if cam is not None or crf is not None:
+
+            def _tap(bs):
+                for rb in bs:
+                    host_cls.append(rb.cls.numpy().copy())
+                    yield rb
+            batches = _tap(batches)
+        if on_gpu:
+            from ..datasets.loader import DeviceFeeder
+            return DeviceFeeder(batches, device)              # H2D on a copy stream, a few batches ahead
+        # (control-flow tests: a stub pipeline on CPU tensors)
+        return ((rb.names, ops.RaggedPlan(rb.hw, None), rb.images, rb.cls, rb.labels) for rb in batches)
+
+    def ragged_step(names, plan, images, cls_t, labels_t):
+        out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
+        cls_host = host_cls.popleft() if (cam is not None or crf is not None) else None
+        if cam is not None:                                                             # :97-111, same stream, step's own cams
+            cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, cls_host)
+        if crf is not None:                                                             # :179-237, same stream, step's own cams
+            nchan_host = np.minimum((cls_host != 0).sum(1), pipe.smax).astype(np.int32) + 1
+            skip = pipe.last_flags if getattr(pipe, "guard", None) == "skip" else None  # flagged images stay out of the CRF scores too
+            crf.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, pipe.last_nchan, nchan_host, pipe.last_cls_idx, labels_t, skip)
+        if lab is not None:                                                             # :95, same stream, the labels just scored
+            lab.ragged(names, plan, out[0] if keep else out)
+        if keep:                                                                        # :116-119 record for the CRF stage
+            inter = out[1]
+            cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
+            for b, name in enumerate(names):
+                k = min(int(ncls[b]), pipe.smax)            # (ncls <= smax is enforced below; the record stays consistent anyway)
+                imutils.save_logits(args.logits_dir, name, plan.planes(inter["cams"], b, pipe.smax + 1)[:k + 1], cls_idx[b, :k].astype(np.int64),
+                                    run_token=getattr(args, "run_token", None))
+
+    def uniform_step(idxs):
+        names, imgs, gts, cls = dataset.batch(idxs)
+        inputs = torch.from_numpy(imgs).to(device, non_blocking=True)
+        if inputs.dtype == torch.uint8:                                                     # decoded images: normalise on the device
+            inputs = ops.normalize_img_u8(inputs)                                           # datasets/voc.py:115-116
+        if inputs.shape[-2:] != (S, S):
+            inputs = ops.bilinear_resize(inputs, S, S, align_corners=False)                 # :74
+        cls_labels = torch.from_numpy(cls).to(device, non_blocking=True)
+        gt_dev = torch.from_numpy(gts).to(device, non_blocking=True)
+        labels = pipe.run_batch(inputs, cls_labels, gt_dev)
+        if lab is not None:                                                                 # :95
+            lab.uniform(names, labels)
+        return names
+
+    def steps(idxs):
+        """One pass over `idxs`: every step is enqueued, then its names are yielded."""
+        if ragged:
+            for names, plan, images, cls_t, labels_t in feed_of(idxs):
+                ragged_step(names, plan, images, cls_t, labels_t)
+                yield names
+        else:
+            for s in range(0, len(idxs), args.batch_size):
+                yield uniform_step(idxs[s:s + args.batch_size])
+
+    pending = deque()           # (ticket, names, dataset indices) of the steps whose flags have not been read
+
+    def enqueue(names, idxs):
+        pending.append((pipe.last_guard, [str(n) for n in names], [int(i) for i in idxs]))
+
+    def take(wait, found, first_pass=True):
+        """Read the tickets that are ready (all of them with `wait`), oldest first: flagged images -> found[dataset index] = name."""
+        while pending and (wait or pending[0][0].ready()):
+            ticket, names, idxs = pending.popleft()
+            flags = np.asarray(ticket.flags()).reshape(-1)
+            bad = [b for b in range(len(names)) if flags[b] != 0]
+            for b in bad:
+                found[idxs[b]] = names[b]
+            if first_pass:
+                guard["checked"] += len(names)
+                guard["flagged"] = [found[i] for i in sorted(found)]
+                if bad and policy == "raise":
+                    raise RuntimeError(f"--overflow_guard raise: non-finite attribute maps / affinity in GEMM mode {guard['mode']} (an activation "
+                                       f"beyond the IEEE-half range 65 504) for {', '.join(names[b] for b in bad)}: run these images in f32 "
+                                       "(--overflow_guard rerun, or --gemm_mode f32)")
+
+    nimg, pos, flagged = 0, 0, {}
+    for names in steps(indices):
+        if policy != "off":
+            enqueue(names, indices[pos:pos + len(names)])
+            take(False, flagged)                              # never a wait inside the loop
+        pos += len(names)
+        nimg += len(names)
+    if policy != "off":
+        take(True, flagged)
+    if flagged:
+        logging.warning(f"overflow guard ({guard['mode']}): {len(flagged)} of {guard['checked']} images left the IEEE-half range (non-finite "
+                        f"maps): {', '.join(guard['flagged'])}" + (" - running them again in exact fp32" if policy == "rerun" else ""))
+    if policy == "rerun" and flagged:
+        # every file of the first pass on disk before a flagged image's file is written again: the good one must be the last
+        if on_gpu:
+            torch.cuda.synchronize()
+        for w in (cam, lab, crf):
+            if w is not None:
+                w.barrier()
+        order, still = sorted(flagged), {}
+        found_guard, pipe.guard = pipe.guard, "observe"       # count again, score everything: fp32's own result is final
+        try:
+            with pipe.exact_mode():
+                pos = 0
+                for names in steps(np.asarray(order, dtype=np.asarray(indices).dtype)):
+                    enqueue(names, order[pos:pos + len(names)])
+                    pos += len(names)
+                    guard["rerun"] += len(names)
+                take(True, still, first_pass=False)           # (also: the fp32 forwards are done before the mode goes back)
+                if on_gpu:
+                    torch.cuda.synchronize()
+        finally:
+            pipe.guard = found_guard
+        guard["nonfinite_in_f32"] = [still[i] for i in sorted(still)]
+        if still:
+            logging.warning(f"overflow guard: {len(still)} images are non-finite in exact fp32 too (kept as fp32 computes them): "
+                            f"{', '.join(guard['nonfinite_in_f32'])}")
+    if on_gpu:
+        torch.cuda.synchronize()
+    return pipe.hist, nimg, time.time() - t0
 
 
 def resolve_model_inputs(args):
@@ -802,6 +954,7 @@ def validate(args=None, dataset=None, pipe=None):
         validate.last_gemm_check = _gemm_self_check(model, dataset, idx, args, device, world)
     hist, nimg, secs = build_validation(model, par, dataset, idx, device, args, pipe=pipe)
     validate.last_model = model                                                             # handle for callers / tests
+    validate.last_guard = build_validation.last_guard                                       # the overflow guard's report (rank-local)
     per_rank, total = gather_hists(hist)
     validate.last_per_rank = per_rank
     score = evaluate.scores_from_hist(total)

@@ -209,10 +209,14 @@ class CamOverlayWriter:
             self.files += self._pending.pop(0).result()
         self._pending.append(self._pool.submit(self._encode, ev, host, list(items)))
 
+    def barrier(self):
+        """Wait until every file submitted so far is on disk (re-raises the first encoder error); the writer stays usable."""
+        while self._pending:
+            self.files += self._pending.pop(0).result()
+
     def close(self):
         try:
-            while self._pending:
-                self.files += self._pending.pop(0).result()
+            self.barrier()
         finally:
             self._pool.shutdown(wait=True)
         return self.files
@@ -298,21 +302,26 @@ class LabelPngWriter:
         ev.record()
         self._copying.append((ev, slot, [str(p) for p in paths]))
 
-    def close(self):
-        """Wait for every file; -> the number of files written.  Re-raises the first writer's exception."""
+    def barrier(self):
+        """Wait until every file submitted so far is on disk (re-raises the first writer's exception); the writer stays usable: a file
+        submitted afterwards under the same name replaces the earlier one, never the other way round."""
         err = None
-        try:
-            while self._copying:
-                self._dispatch(wait=True)
-            for slot in self._slots:
-                try:
-                    self._collect(slot)
-                except BaseException as e:
-                    err = err or e
-        finally:
-            self._pool.shutdown(wait=True)
+        while self._copying:
+            self._dispatch(wait=True)
+        for slot in self._slots:
+            try:
+                self._collect(slot)
+            except BaseException as e:
+                err = err or e
         if err is not None:
             raise err
+
+    def close(self):
+        """Wait for every file; -> the number of files written.  Re-raises the first writer's exception."""
+        try:
+            self.barrier()
+        finally:
+            self._pool.shutdown(wait=True)
         return self.files
 
 

@@ -132,11 +132,15 @@ void excel_vit_destroy(excel_vit_t h);
  *       the fastest mode; its CAM error is ~12x that of fp32 arithmetic (1e-5 on well-conditioned weights);
  *   2 = "f16x3": the same scheme on IEEE-half planes (22 mantissa bits where lo stays normal): fp32-grade results (within 1.4x of fp32
  *       arithmetic's own error on every network measured), ~2.5 % slower than mode 1 (the part is power-limited), values beyond 65 504
- *       overflow LOUDLY (hi = inf, lo = -inf: every product they enter is a NaN, never a finite wrong number);
+ *       (the largest finite IEEE half) overflow LOUDLY (hi = inf, lo = -inf: every product they enter is a NaN, never a finite wrong
+ *       number).  Nothing inside the forward pass looks for that NaN: the overflow guard below (excel_nonfinite_count over the
+ *       tensors a step hands on, excel_confusion_accumulate_masked) is what catches it per image, and the caller re-runs the
+ *       flagged images in mode 0;
  *   3 = "f16x2": mode 2 with the nn.Linear GEMMs on two MFMAs per product (excel_gemm_f16x2 above) - available when every weight
  *       matrix of the handle is fp16-valued (excel_vit_weights_fp16_exact; true for every published CLIP archive), refused with
  *       EXCEL_ERR_ARG otherwise.  Bit-identical to mode 2 on such weights, and the fastest mode: a third of the GEMMs' matrix-core
- *       work is gone.  The attention products (activation x activation) stay three-product.
+ *       work is gone.  The attention products (activation x activation) stay three-product.  Same 65 504 range and the same loud
+ *       overflow as mode 2; the same guard catches it.
  * Default 0, or the mode named by the environment variable EXCEL_GEMM_MODE (bf16x3 | f16x3 | f16x2) at create time.  Switching between
  * 1 and 2/3 re-splits the weights (synchronises the device). */
 int excel_vit_set_gemm_mode(excel_vit_t h, int mode);
@@ -423,6 +427,24 @@ typedef struct {
     int64_t table_ints;
 } excel_ragged_info;
 int excel_ragged_plan(const int32_t* hw /*host [B,2] = (H_b, W_b)*/, int B, excel_ragged_info* info /*host*/, int32_t* table /*host or NULL*/);
+
+/* ------------------------------------------------------------------ overflow guard of the f16 modes
+ * Modes 2 and 3 of excel_vit_set_gemm_mode turn an activation beyond 65 504 into NaNs.  These two entries let a batched step see that per
+ * image and keep such an image out of its scores without a host synchronisation; the caller re-runs the flagged images in mode 0.
+ *
+ * excel_nonfinite_count: x = B images of per_image fp32 values each, back to back; count[b] receives (init != 0) or is increased by
+ * (init == 0) the number of values of image b whose exponent field is all ones (+-inf and every NaN; an integer test on the bits), so the
+ * tensors of one step can share one counter.  x need only be 4-byte aligned, per_image is any value in [1, 2^31).  A streaming read: no
+ * workspace, and a tensor without such a value issues no atomic. */
+int excel_nonfinite_count(const float* x, int B, long long per_image, int32_t* count /*device [B]*/, int init, void* stream);
+
+/* excel_confusion_accumulate restricted to the images with skip[b] == 0 (skip: e.g. the counts above).  table == NULL: B uniform images
+ * of per_image pixels each (info unused); otherwise the tight label maps of the ragged plan (image b at loff_b; per_image ignored,
+ * info->B == B).  Integer counts: with nothing skipped the result equals excel_confusion_accumulate over the whole array bit for bit,
+ * otherwise excel_confusion_accumulate over the concatenation of the kept images. */
+int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_t* pred, int B, long long per_image, const int32_t* table,
+                                      const excel_ragged_info* info, const int32_t* skip /*device [B]*/, int num_classes, int64_t* hist,
+                                      void* stream);
 
 /* datasets/transforms.normalize_img + HWC->CHW + the harness' input resize (tools/infer_lam.py:74: F.interpolate bilinear,
  * align_corners=False, no antialias) for decoded images of different sizes: hwc = the uint8 [H_b,W_b,3] images back to back
