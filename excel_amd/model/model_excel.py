@@ -126,6 +126,14 @@ class ExCEL_model:
                                       want_raw=True, want_features=False)
         return self._dec.forward(r["feats"])[1]
 
+    def attr_maps(self, img):
+        """model(img)[2] alone - what the extra passes of the flip / multi-scale fuse need (pipeline tta_scales / tta_flip; any input
+        size the tower takes).  The tower is asked for x_raw only: no last-layers affinity (w_aff = NULL), no per-layer attention
+        (n_attn_out = 0), no decoder features.  Same bits as forward's attr_maps_raw (side outputs do not change the tokens)."""
+        r = self.encoder.encode_image(img, True, None, want_w_aff=False, n_attn_out=0, want_raw=True, want_features=False)
+        return ops.patch_text_cam(r["x_raw"], self._text_rows, num_fg=self.num_classes - 1,
+                                  mode=self.encoder.visual.handle().gemm_mode())[1]
+
     def check_numerics(self, img, tol=5e-4, fallback=True, reduce=None):
         """Guard of the fast matrix-core modes on the caller's OWN weights and images.  "bf16x3" carries 16 mantissa bits per operand:
         measured against a float64 run of the oracle its CAM error is ~12x that of fp32 arithmetic - 1e-5 on well-conditioned networks

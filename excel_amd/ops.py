@@ -1455,6 +1455,49 @@ def plane_minmax_normalize_(lam):
     return lam
 
 
+TTA_MAX_SCALES = 8
+TTA_MAX_GRID = 48
+
+
+def lam_tta_fuse(maps, grids, g_out, flip, out=None):
+    """Flip and multi-scale LAM fuse at the patch grid (excel_lam_tta_fuse; utils/camutils.py:8-63).
+    maps: per scale the model's attribute maps [2B if flip else B, g_s*g_s, F] (image B + b = the mirrored input of image b), in the
+    order they are summed; grids: the g_s -> [B, g_out*g_out, F], what refine_cams_with_aff_batched reads: per (b, f) plane the
+    bilinear resize to the g_out grid, the max with the mirrored half (flip), the sum over scales, min-max normalised.  Bit-equal to
+    lam_scale_accumulate per scale + plane_minmax_normalize_ (flip) for finite inputs; a plane that a non-finite value reaches is NaN
+    as a whole.  Two launches; `out` holds the sums in between, so nothing else is allocated."""
+    maps = [f32c(m) for m in maps]
+    grids = [int(g) for g in grids]
+    ns = len(maps)
+    if not 1 <= ns <= TTA_MAX_SCALES:
+        raise ValueError(f"lam_tta_fuse: {ns} scales, need 1..{TTA_MAX_SCALES}")
+    if len(grids) != ns:
+        raise ValueError("lam_tta_fuse: one grid size per scale")
+    g_out = int(g_out)
+    if not 1 <= g_out <= TTA_MAX_GRID:
+        raise ValueError(f"lam_tta_fuse: g_out = {g_out} outside [1, {TTA_MAX_GRID}]")
+    nb = int(maps[0].shape[0]) if maps[0].dim() == 3 else 0
+    F_ = int(maps[0].shape[2]) if maps[0].dim() == 3 else 0
+    if flip and nb % 2:
+        raise ValueError(f"lam_tta_fuse: flip needs [2B, P, F] maps (image, then mirrored image), got {nb} images")
+    B = nb // 2 if flip else nb
+    if B < 1 or F_ < 1:
+        raise ValueError(f"lam_tta_fuse: need B >= 1 and F >= 1, got maps of shape {tuple(maps[0].shape)}")
+    for m, g in zip(maps, grids):
+        if not 1 <= g <= TTA_MAX_GRID:
+            raise ValueError(f"lam_tta_fuse: grid {g} outside [1, {TTA_MAX_GRID}]")
+        if tuple(m.shape) != (nb, g * g, F_):
+            raise ValueError(f"lam_tta_fuse: the maps of grid {g} must be [{nb}, {g * g}, {F_}], got {tuple(m.shape)}")
+    if out is None:
+        out = torch.empty((B, g_out * g_out, F_), dtype=torch.float32, device=maps[0].device)
+    elif tuple(out.shape) != (B, g_out * g_out, F_):
+        raise ValueError(f"lam_tta_fuse: out must be [{B}, {g_out * g_out}, {F_}], got {tuple(out.shape)}")
+    ptrs = (C.c_void_p * ns)(*[_p(m).value for m in maps])
+    gs = (C.c_int32 * ns)(*grids)
+    check(lib().excel_lam_tta_fuse(ptrs, gs, ns, 1 if flip else 0, B, F_, g_out, _p(out), _stream()), "excel_lam_tta_fuse")
+    return out
+
+
 # ------------------------------------------------------------------ live kernel timing (HIP events on the launch stream)
 def prof_enable(on=True, categories=None, every=1):
     """categories: iterable of category names to bracket (None = all); every: bracket every n-th launch of a category

@@ -12,6 +12,43 @@ import torch
 from . import ops
 
 GUARD_MODES = (None, "skip", "observe")
+TTA_MAX_SCALES = ops.TTA_MAX_SCALES
+TTA_MAX_GRID = ops.TTA_MAX_GRID
+
+
+def _check_tta_scales(scales):
+    scales = [float(s) for s in scales]
+    if 1.0 not in scales:
+        raise ValueError(f"cam scales {scales}: scale 1.0 must be one of them (it supplies the affinity of the random walk)")
+    if len(scales) > TTA_MAX_SCALES:
+        raise ValueError(f"cam scales {scales}: {len(scales)} scales, at most {TTA_MAX_SCALES}")
+    return scales
+
+
+def tta_sizes(S, scales):
+    """The network sizes of a multi-scale pass at resize size S -> [(S_s, g_s), ...], scale 1.0 FIRST wherever the caller listed it (its
+    un-flipped half supplies the affinity and the image PAR reads), the others in the caller's order.  S_s = S for 1.0, else
+    int(s * S) // 16 * 16 (camutils.multi_scale_lam's rule); g_s = S_s // 16.  Refused, naming the scale: a list without 1.0, more than
+    8 scales, S_s < 16, g_s > 48 (the largest grid the ViT's attention kernels are tested at) and two scales with the same S_s."""
+    scales = _check_tta_scales(scales)
+    out, seen = [], {}
+    for s in [1.0] + [s for s in scales if s != 1.0] + [1.0] * (scales.count(1.0) - 1):
+        S_s = int(S) if s == 1.0 else int(s * S) // 16 * 16
+        if S_s < 16:
+            raise ValueError(f"cam scale {s}: network size {S_s} at resize size {S} is below one 16-pixel patch")
+        if S_s // 16 > TTA_MAX_GRID:
+            raise ValueError(f"cam scale {s}: grid {S_s // 16} at resize size {S} is above {TTA_MAX_GRID}")
+        if S_s in seen:
+            raise ValueError(f"cam scale {s}: rounds to the same network size {S_s} as scale {seen[S_s]} at resize size {S}")
+        seen[S_s] = s
+        out.append((S_s, S_s // 16))
+    return out
+
+
+def _refuse_tta(who, tta_scales, tta_flip):
+    if tta_flip or (tta_scales is not None and tuple(float(x) for x in tta_scales) != (1.0,)):
+        raise ValueError(f"{who} has no flip / multi-scale fuse (tta_scales={tta_scales}, tta_flip={tta_flip}): the option belongs to the "
+                         "training-free regime (TrainingFreePipeline.run_batch / run_batch_ragged)")
 
 
 class GuardTicket:
@@ -30,7 +67,8 @@ class GuardTicket:
 
 
 class TrainingFreePipeline:
-    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None):
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
+                 tta_scales=None, tta_flip=False):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -40,11 +78,20 @@ class TrainingFreePipeline:
           "skip"     run_batch / run_batch_ragged count the non-finite values per image in what they hand to the random walk (attr, the
                      affinity) and in its result, score only the images without one (ops.confusion_accumulate_masked) and leave the
                      counts in `last_flags` (device int32 [B], until the next step on the stream) and `last_guard` (a GuardTicket);
-          "observe"  the same counts and ticket, every image scored (the exact-fp32 second pass, see exact_mode)."""
+          "observe"  the same counts and ticket, every image scored (the exact-fp32 second pass, see exact_mode).
+        `tta_scales` / `tta_flip` = test-time augmentation of the LAMs (utils/camutils.py:8-63), off by default (None / False, also for
+        the single scale (1.0,) without flip: today's step, launch for launch).  With it, run_batch / run_batch_ragged run the model once
+        per scale of `tta_scales` (tta_sizes: 1.0 must be among them) on [x; mirror x] (tta_flip) and ops.lam_tta_fuse fuses the maps at
+        the patch grid of scale 1.0 into the `attr` the random walk reads; the affinity is that of the un-mirrored scale-1.0 pass."""
         if guard not in GUARD_MODES:
             raise ValueError(f"guard must be one of {GUARD_MODES} (got {guard!r})")
         self.guard = guard
         self.last_flags = self.last_guard = None
+        self.tta_flip = bool(tta_flip)
+        self.tta_scales = tuple(float(x) for x in tta_scales) if tta_scales is not None else (1.0,)
+        self.tta = self.tta_flip or self.tta_scales != (1.0,)
+        if self.tta:
+            _check_tta_scales(self.tta_scales)
         self.model = model
         self.num_classes = num_classes
         self.dilations = tuple(dilations)
@@ -117,6 +164,58 @@ class TrainingFreePipeline:
         finally:
             h.set_gemm_mode(before)
 
+    # ------------------------------------------------------------------ flip / multi-scale LAMs (utils/camutils.py:8-63)
+    # The step's own `attr` is the model's maps of one pass.  With tta_scales / tta_flip it is the fuse of one pass per scale over
+    # [x; mirror x]: every scale's maps go to the patch grid of scale 1.0, max with the mirrored half, sum, min-max - one op
+    # (ops.lam_tta_fuse) whose output is the [B,P,F] the random walk and the box mask read.  The reference's own fuse resizes to
+    # pixel size (camutils.multi_scale_lam); the step fuses at the grid because everything downstream of `attr` works there and
+    # cam_upsample_bkg does the one up-sampling to the label size afterwards.
+    def _no_tta(self, what):
+        if self.tta:
+            raise ValueError(f"{what} has no flip / multi-scale fuse (tta_scales={self.tta_scales}, tta_flip={self.tta_flip}): use "
+                             "run_batch or run_batch_ragged, or build the pipeline without tta_scales / tta_flip")
+
+    def _tta_uniform_input(self, inputs, S_s):
+        """[B,3,S,S] f32 -> the network input of one scale, [x_s; mirror x_s] with tta_flip (camutils.py:50-51)."""
+        x = inputs if S_s == inputs.shape[-1] else ops.bilinear_resize(inputs, S_s, S_s, align_corners=False)
+        return torch.cat([x, x.flip(-1)], 0) if self.tta_flip else x
+
+    def _tta_ragged_input(self, hwc_packed, plan, S_s, name):
+        """The packed uint8 images -> the network input of one scale, straight from the decoded pixels (no float image is resized twice)."""
+        nb = plan.B * (2 if self.tta_flip else 1)
+        out = self._buf(name, nb * 3 * S_s * S_s, device=hwc_packed.device).view(nb, 3, S_s, S_s)
+        if self.tta_flip:
+            return ops.normalize_resize_u8_ragged_mirror(hwc_packed, plan, S_s, out=out)           # camutils.py:15
+        return ops.normalize_resize_u8_ragged(hwc_packed, plan, S_s, out=out)
+
+    def _tta_maps(self, x, P1):
+        """model.attr_maps over x [n,3,S_s,S_s], cut into image groups of about the token count of the scale-1.0 pass (a 1.5x scale has
+        2.25x the tokens and 5x the attention scores per image).  The ViT is batch-invariant bit for bit: the grouping changes nothing."""
+        n, P_s = x.shape[0], (x.shape[-1] // 16) ** 2
+        step = max(1, min(n, n * P1 // P_s))
+        if step >= n:
+            return self.model.attr_maps(x)
+        return torch.cat([self.model.attr_maps(x[lo:lo + step]) for lo in range(0, n, step)], 0)
+
+    def _tta_attr(self, S, make_input):
+        """One model pass per scale (tta_sizes(S, tta_scales): 1.0 first) over make_input(S_s) = [B or 2B, 3, S_s, S_s], then the fuse.
+        Scale 1.0's un-mirrored half runs as the plain step does and supplies the affinity (tools/infer_lam.py:79 before :82); every
+        other pass asks the tower for the maps alone.  -> (attr [B,P,F], attn_weights of scale 1.0)"""
+        g = S // 16
+        maps, grids, attn_w = [], [], None
+        for S_s, g_s in tta_sizes(S, self.tta_scales):
+            x = make_input(S_s)
+            B = x.shape[0] // 2 if self.tta_flip else x.shape[0]
+            if attn_w is None:
+                _, _, m, attn_w, _ = self.model(x[:B])                                              # infer_lam.py:79
+                if self.tta_flip:
+                    m = torch.cat([m, self._tta_maps(x[B:], g * g)], 0)
+            else:
+                m = self._tta_maps(x, g * g)
+            maps.append(m)
+            grids.append(g_s)
+        return ops.lam_tta_fuse(maps, grids, g, self.tta_flip), attn_w
+
     @torch.no_grad()
     def run_batch(self, inputs, cls_labels, gts=None, label_hw=None, return_intermediates=False):
         """inputs [B,3,S,S] f32 (normalised, already at the network size), cls_labels [B,F] f32 one-hot,
@@ -124,7 +223,10 @@ class TrainingFreePipeline:
         B, _, S, _ = inputs.shape
         g = S // 16
         H, W = (gts.shape[-2:] if gts is not None else (label_hw or (S, S)))
-        _, _, attr, attn_w, _ = self.model(inputs)                                                  # infer_lam.py:79
+        if self.tta:
+            attr, attn_w = self._tta_attr(S, lambda S_s: self._tta_uniform_input(inputs, S_s))
+        else:
+            _, _, attr, attn_w, _ = self.model(inputs)                                              # infer_lam.py:79
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
         flags = self._guard_count(attr, attn_w.w_aff, refined)
@@ -164,8 +266,18 @@ class TrainingFreePipeline:
         dev = hwc_packed.device
         B = plan.B
         g = S // 16
-        inputs = ops.normalize_resize_u8_ragged(hwc_packed, plan, S, out=self._buf("inputs", B * 3 * S * S, device=dev).view(B, 3, S, S))  # voc.py:115, infer_lam.py:74
-        _, _, attr, attn_w, _ = self.model(inputs)                                                  # infer_lam.py:79
+        if self.tta:
+            first = []                      # the scale-1.0 input: its un-mirrored half is what PAR reads
+
+            def make(S_s):
+                x = self._tta_ragged_input(hwc_packed, plan, S_s, "inputs" if not first else "tta_inputs")
+                first.append(x)
+                return x
+            attr, attn_w = self._tta_attr(S, make)
+            inputs = first[0][:B]
+        else:
+            inputs = ops.normalize_resize_u8_ragged(hwc_packed, plan, S, out=self._buf("inputs", B * 3 * S * S, device=dev).view(B, 3, S, S))  # voc.py:115, infer_lam.py:74
+            _, _, attr, attn_w, _ = self.model(inputs)                                              # infer_lam.py:79
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
         flags = self._guard_count(attr, attn_w.w_aff, refined)
@@ -203,6 +315,7 @@ class TrainingFreePipeline:
     def run_batch_split(self, inputs, cls_labels, gts=None, label_hw=None, nsplit=2):
         """Same contract as run_batch; the returned labels and self.hist are complete only after drain()."""
         self._no_guard("run_batch_split")
+        self._no_tta("run_batch_split")
         B, _, S, _ = inputs.shape
         nsplit = max(1, min(nsplit, B))
         if nsplit == 1:
@@ -246,6 +359,7 @@ class TrainingFreePipeline:
     @torch.no_grad()
     def run_batch_overlapped(self, inputs, cls_labels, gts=None, label_hw=None):
         self._no_guard("run_batch_overlapped")
+        self._no_tta("run_batch_overlapped")
         sa, sb = self._streams()
         cur = torch.cuda.current_stream()
         B, _, S, _ = inputs.shape
@@ -303,7 +417,9 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     half comes from a feature-only forward of flip x.  The whole-batch means of excel_feature_affinity are replaced by the grouped
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
-    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None):
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
+                 tta_scales=None, tta_flip=False):
+        _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         if getattr(model, "_dec", None) is None:
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
@@ -368,7 +484,9 @@ class ValidationPipeline(TrainingFreePipeline):
     (= the reference only at batch 1); here it is the grouped entry with group 1, the per-image affinity.  The seg logits [B,nc,g,g] go to
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
-    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None):
+    def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
+                 tta_scales=None, tta_flip=False):
+        _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         if getattr(model, "_dec", None) is None:
             raise ValueError("ValidationPipeline needs the decoder head: build ExCEL_model(..., decoder_state_dict=)")
         if guard is not None:

@@ -38,6 +38,12 @@ Differences from the reference, all deliberate:
     loop), keeps flagged images out of the confusion matrices, and after the loop exactly those images run once more in exact fp32
     through the same consumers - their files are overwritten by name.  `raise` stops at the first flagged image instead; `off` is the
     unguarded loop.  The second pass is rank-local (no collective); the report is validate.last_guard;
+  * `--cam_scales "1.0,0.5,0.75,1.5"` and `--cam_flip true` (training-free regime; defaults "1.0" / false = the plain step): the flip and
+    multi-scale LAM fuse of utils/camutils.py:8-63 and the switched-off :82.  One model pass per scale over [x; mirror x], each network
+    input made straight from the decoded pixels; ops.lam_tta_fuse brings every scale's maps to the patch grid of --resize_size, takes
+    the maximum with the mirrored half, sums and min-max normalises - the `attr` the random walk reads.  The affinity is that of the
+    plain scale-1.0 pass (:79).  Everything behind it (labels, score, --save_cam / --save_label / --crf_inline, the overflow guard) is
+    unchanged; --api_path true runs the same arithmetic per image (camutils.tta_attr_map);
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -75,6 +81,28 @@ def resolve_overflow_guard(policy, gemm_mode, on_gpu, batched):
         raise ValueError(f"--overflow_guard {policy} needs the batched loop: the per-image loop (--api_path true, or --training_free false "
                          "on uniform synthetic batches) has no overflow guard - use --overflow_guard off or auto there")
     return policy
+
+
+def tta_sizes(S, scales):
+    """--cam_scales at --resize_size S -> [(S_s, g_s), ...], scale 1.0 first (pipeline.tta_sizes: the rule and what it refuses)."""
+    from ..pipeline import tta_sizes as sizes
+    return sizes(S, scales)
+
+
+def resolve_tta(args):
+    """--cam_scales / --cam_flip -> (tta_scales, tta_flip) for TrainingFreePipeline / camutils.tta_attr_map; (None, False) = the plain
+    step (the defaults "1.0" / false).  Checked here, before a model is built: the scales against --resize_size (tta_sizes), and the
+    regime - --training_free false has its own flip (cure_attr_map_flip) and no multi-scale fuse."""
+    from .infer_seg_voc import parse_scales
+    scales = parse_scales(getattr(args, "cam_scales", None) or "1.0")
+    flip = bool(getattr(args, "cam_flip", False))
+    if not flip and scales == (1.0,):
+        return None, False
+    if not bool(getattr(args, "training_free", True)):
+        raise ValueError(f"--cam_scales {','.join(str(x) for x in scales)} / --cam_flip {str(flip).lower()} belong to the training-free regime: "
+                         "--training_free false already runs its own flip (cure_attr_map_flip) - drop the two flags there")
+    tta_sizes(args.resize_size, scales)
+    return scales, flip
 
 
 def _handle_gemm_mode(model):
@@ -147,6 +175,11 @@ def get_parser():
                         "per image on the device in every batched step, keep flagged images out of the scores and run exactly those again in "
                         "exact fp32 after the loop; raise = stop at the first flagged image; off = no check; auto = rerun on the batched GPU "
                         "loop in an f16 mode, else off (bf16x3 has the fp32 exponent range, f32 is exact)")
+    p.add_argument("--cam_scales", default="1.0", type=str,
+                   help="training-free regime: fuse the LAMs of these scales of --resize_size, e.g. \"1.0,0.5,0.75,1.5\" (must hold 1.0; each "
+                        "scale is one more model pass; fused at the patch grid in front of the random walk)")
+    p.add_argument("--cam_flip", default=False, type=_bool,
+                   help="training-free regime: every scale also runs the mirrored image, the two LAMs are fused by their maximum")
     p.add_argument("--cpu_affinity", default="auto", choices=["auto", "off"],
                    help="auto: with several ranks on the node every rank pins itself (decode pool included) to its own share of the host cores")
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
@@ -509,11 +542,12 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     # the overflow guard of the f16 modes: resolved from the mode the handle is in NOW (after the start-up check)
     mode = _handle_gemm_mode(model if pipe is None else getattr(pipe, "model", None))
     policy = resolve_overflow_guard(getattr(args, "overflow_guard", "auto"), mode, torch.device(device).type == "cuda", not per_image)
+    tta_scales, tta_flip = resolve_tta(args)
     if pipe is None:
         guard = "skip" if policy in ("raise", "rerun") else None
         if training_free:
             pipe = TrainingFreePipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
-                                        caa_thre=0.79, smax=dataset.max_k(), guard=guard)
+                                        caa_thre=0.79, smax=dataset.max_k(), guard=guard, tta_scales=tta_scales, tta_flip=tta_flip)
         elif ragged:
             pipe = OptimisedLamPipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
                                         caa_thre=0.79, smax=dataset.max_k(), guard=guard)
@@ -577,6 +611,7 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
     S = args.resize_size
     on_gpu = torch.device(device).type == "cuda"
     nimg = 0
+    tta = resolve_tta(args)
     if not per_image:
         return _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu)
     for s in range(0, len(indices)):
@@ -587,12 +622,16 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
         decoded = inputs
         if inputs.dtype == torch.uint8:                                                     # decoded images: normalise on the device
             inputs = ops.normalize_img_u8(inputs)                                           # datasets/voc.py:115-116
+        full = inputs                                                                       # (what --cam_scales resizes the other scales from)
         if inputs.shape[-2:] != (S, S):
             inputs = ops.bilinear_resize(inputs, S, S, align_corners=False)                 # :74
         cls_labels = torch.from_numpy(cls).to(device, non_blocking=True)
         gt_dev = torch.from_numpy(gts).to(device, non_blocking=True)
         if training_free:
             _, _, attr_maps_raw, attn_weights, attn_pred = model(inputs)                    # :79
+            if tta[0] is not None:                                                          # :82, the same fuse as the batched step
+                from ..utils.camutils import tta_attr_map
+                attr_maps_raw = tta_attr_map(model, inputs, tta[0], tta[1], source=full)
         else:
             # optimised-LAM regime (:84-85, :91): needs the caller's decoder as model.feature_head
             from ..utils.camutils import cure_attr_map_flip
@@ -902,6 +941,7 @@ def validate(args=None, dataset=None, pipe=None):
     from . import synthetic
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
+    tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     if pipe is None:
         torch.cuda.set_device(args.local_rank)
         device = torch.device("cuda", args.local_rank)
@@ -975,7 +1015,8 @@ def validate(args=None, dataset=None, pipe=None):
                            "images_per_s_job": round(len(dataset) / secs, 2), "miou": float(score["miou"]),
                            "per_rank_hist_mass": [int(x) for x in per_rank.reshape(per_rank.shape[0], -1).sum(1).tolist()],
                            "hist_total": [[int(v) for v in row] for row in total.cpu().tolist()],       # the gathered confusion matrix itself
-                           "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size}, f)
+                           "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
+                           "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1])}, f)
     inline_hist = getattr(build_validation, "last_crf_hist", None)
     if getattr(args, "crf_post", False) and getattr(args, "crf_inline", False) and inline_hist is None and rank == 0:
         logging.info(f"--crf_inline: the {args.infer_set} split keeps the record path of the CRF stage (scored against image[:,:,0], :213-214)")

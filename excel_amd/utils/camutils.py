@@ -4,6 +4,7 @@
   cure_attr_map_flip   :8-30   (ex_fts=True needs model.feature_head, the caller's decoder, to produce ex_feats)
   multi_scale_lam      the multi-scale fuse formula of :41-61 in its evident intent:
                        per scale: maps -> bilinear resize to (h,w) -> flip-max; sum over scales; min-max normalise.
+  tta_attr_map         the same fuse at the patch grid, [B,P,F]: what the batched step feeds the random walk with
 """
 import torch
 
@@ -46,6 +47,25 @@ def multi_scale_lam(model, inputs, scales=(1.0, 0.5, 0.75, 1.5)):
         maps = model(x2)[2]                                                                                  # :53-54
         acc = ops.lam_scale_accumulate(maps, acc, hs // 16, h, w, init=acc is None)                         # :56-59 resize, flip-max, sum
     return ops.plane_minmax_normalize_(acc)                                                                  # :61-63
+
+
+@torch.no_grad()
+def tta_attr_map(model, inputs, scales=(1.0,), flip=False, source=None):
+    """Flip / multi-scale fused LAMs at the patch grid, [B,P,F] like model(inputs)[2] - the per-image form of the batched step's fuse
+    (pipeline.TrainingFreePipeline tta_scales / tta_flip; tools/infer_lam --cam_scales / --cam_flip with --api_path true): per scale of
+    pipeline.tta_sizes (1.0 first) the maps of [x_s; x_s.flip(-1)] (:50-54), then ops.lam_tta_fuse - bilinear to the grid of `inputs`,
+    max with the mirrored half (:22), sum over the scales, min-max (:59-61).
+    `source` [B,3,H,W] = the normalised image `inputs` was resized from: the other scales are then resized from IT, like the ragged
+    step makes every network input straight from the decoded pixels (no image is resized twice); default: from `inputs`."""
+    from ..pipeline import tta_sizes
+    b, c, h, w = inputs.shape
+    src = inputs if source is None else source
+    maps, grids = [], []
+    for S_s, g_s in tta_sizes(h, scales):
+        x = inputs if S_s == h else ops.bilinear_resize(src, S_s, S_s, align_corners=False)                 # :50
+        maps.append(model.attr_maps(torch.cat([x, x.flip(-1)], dim=0) if flip else x))                      # :51, :53-54
+        grids.append(g_s)
+    return ops.lam_tta_fuse(maps, grids, h // 16, flip)
 
 
 @torch.no_grad()

@@ -752,6 +752,23 @@ int excel_flip_max_normalize(const float* attr, float* out, int B, int g, int F,
 int excel_lam_scale_accumulate(const float* maps, float* acc, int B, int g, int F, int H, int W, int init, void* stream);
 int excel_plane_minmax_normalize(float* lam, long long planes, long long HW, void* stream);
 
+/* flip and multi-scale LAM fuse at the patch grid (test-time augmentation of the training-free regime, utils/camutils.py:8-63): the step
+ * between the patch-text CAM and the random walk.  maps[s] (device) = the attribute maps of scale s exactly as the model returns them,
+ * token-major [flip ? 2B : B, g[s]^2, F]; with flip, image B + b comes from the mirrored input of image b.  For every image b, class f:
+ *   r_s = bilinear resize (align_corners = 0, excel_bilinear_resize's arithmetic) of the g[s] x g[s] plane to g_out x g_out
+ *   v_s = flip ? max(r_s[b], mirror_x(r_s[B + b])) : r_s[b]
+ *   acc = v_0 + v_1 + ... in the order given ;  lam = acc - min(acc) ;  out = lam / (max(lam) + 1e-5)      (min, max over the plane)
+ * out [B, g_out^2, F] is the layout excel_refine_cams_with_aff and excel_scoremap_box_mask read.
+ * Bits: for finite inputs and flip = 1 the result equals excel_lam_scale_accumulate per scale (init at s = 0) followed by
+ * excel_plane_minmax_normalize and a permute to [B,P,F]; with ns = 1 and g[0] == g_out that is also excel_flip_max_normalize.
+ * Non-finite values: if a value that a bilinear tap reads for plane (b, f) (every value of the plane while g[s] <= 2 g_out; a zero
+ * weight still reads) is NaN or +-inf, out[b, :, f] is NaN as a whole and no other plane changes - the overflow guard's
+ * excel_nonfinite_count over `out` then flags the image (max alone would drop a NaN of one half).
+ * Limits: 1 <= ns <= 8, 1 <= g[s], g_out <= 48, B, F >= 1.  Two launches on `stream`, no workspace (out holds the sums in between),
+ * no host synchronisation; maps and g are host arrays read before the call returns. */
+int excel_lam_tta_fuse(const float* const* maps /*host [ns]*/, const int32_t* g /*host [ns]*/, int ns, int flip, int B, int F, int g_out,
+                       float* out /*[B, g_out*g_out, F]*/, void* stream);
+
 /* ------------------------------------------------------------------ live per-kernel timing (bench.py) */
 
 /* When enabled, every kernel launch is bracketed by hipEvents on its launch stream, grouped by category.
