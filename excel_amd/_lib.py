@@ -161,6 +161,8 @@ SIGNATURES = {
     "excel_seg_resize_argmax_uniform": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_f, c_f]),
     "excel_seg_softmax_resize": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "excel_seg_softmax_resize_ragged": (c_i, [c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f]),
+    "excel_conf_planes_ragged": (c_i, [c_f, c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, C.c_float, C.c_float, c_i, c_f, c_f, c_f]),
+    "excel_conf_merge_ragged": (c_i, [c_f, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_f, C.POINTER(RaggedInfo), c_i, c_f, c_i, c_f, c_f]),
     "excel_cam_overlay_ragged": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f, c_f]),
     "excel_cam_overlay": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f]),
     "excel_train_panels_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_int64)]),

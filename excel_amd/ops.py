@@ -1335,6 +1335,62 @@ def argmax_label_ragged(cams, plan, Cmax, nchan=None, cls_idx=None, out=None):
     return lab
 
 
+# ------------------------------------------------------------------ confident labels (include/excel_hip.h, "confident labels")
+def conf_half_plan(plan, down_scale=2, names=None):
+    """The half plan of utils/affutils.py:113: (H_b // ds, W_b // ds) for every image of `plan`.  An image whose half size would be
+    empty is refused here, on the host, by name."""
+    ds = int(down_scale)
+    if ds < 1:
+        raise ValueError(f"down_scale must be at least 1 (got {down_scale})")
+    hw = [(int(H) // ds, int(W) // ds) for H, W in plan.hw]
+    for b, (h, w) in enumerate(hw):
+        if h < 1 or w < 1:
+            who = str(names[b]) if names is not None else f"image {b}"
+            raise ValueError(f"{who}: {int(plan.hw[b, 0])} x {int(plan.hw[b, 1])} pixels leave nothing at down_scale {ds}")
+    return RaggedPlan(hw, plan.table.device if plan.table is not None else None)
+
+
+def conf_planes_ragged(cams, plan, half_plan, smax, nchan, high_thre, low_thre, out=None, softmax=True):
+    """utils/affutils.py:115-141 for a ragged batch: cams (smax + 1 pitched planes per image on `plan`; plane 0 is not read),
+    nchan [B] = k_b + 1 -> (planes, nchan2): 2 (smax + 1) pitched planes per image on `half_plan`, the softmax over
+    [high_thre, m_1 .. m_k] then the one over [low_thre, m_1 .. m_k], and nchan2 = 2 (k_b + 1) for par_forward_ragged.
+    Planes >= nchan2[b] and the pad columns are not written.  softmax=False (tests): the resized values alone, in the first group."""
+    if plan.B != half_plan.B:
+        raise ValueError(f"conf_planes_ragged: plans of {plan.B} and {half_plan.B} images")
+    if cams.numel() != (smax + 1) * plan.total_pix:
+        raise ValueError(f"conf_planes_ragged: cams must hold (smax + 1) * total_pix = {(smax + 1) * plan.total_pix} floats")
+    if nchan.numel() != plan.B:
+        raise ValueError(f"conf_planes_ragged: nchan holds {nchan.numel()} counts for {plan.B} images")
+    planes = _out(out, (2 * (smax + 1) * half_plan.total_pix,), torch.float32, cams.device)
+    nchan2 = torch.empty((plan.B,), dtype=torch.int32, device=cams.device)
+    check(lib().excel_conf_planes_ragged(_p(cams), _p(nchan, torch.int32), _p(plan.table, torch.int32), C.byref(plan.info),
+                                         _p(half_plan.table, torch.int32), C.byref(half_plan.info), int(smax), float(high_thre), float(low_thre),
+                                         1 if softmax else 0, _p(planes), _p(nchan2, torch.int32), _stream()), "excel_conf_planes_ragged")
+    return planes, nchan2
+
+
+def conf_merge_ragged(planes, half_plan, plan, smax, nchan, cls_idx=None, img_box=None, ignore_index=255, out=None):
+    """utils/affutils.py:94-96 for both groups, :146-156 for a ragged batch: planes (2 (smax + 1) pitched planes per image on
+    `half_plan`, PAR's output) -> tight uint8 labels on `plan`: per group bilinear + first-maximum arg-max + key lookup, then
+    lab_h where it is a class, 0 where both groups say background, ignore_index between.  img_box: int32 [B,4] (y0, y1, x0, x1) on
+    the device; pixels outside get ignore_index."""
+    if plan.B != half_plan.B:
+        raise ValueError(f"conf_merge_ragged: plans of {half_plan.B} and {plan.B} images")
+    if planes.numel() != 2 * (smax + 1) * half_plan.total_pix:
+        raise ValueError(f"conf_merge_ragged: planes must hold 2 * (smax + 1) * total_pix = {2 * (smax + 1) * half_plan.total_pix} floats")
+    if nchan.numel() != plan.B:
+        raise ValueError(f"conf_merge_ragged: nchan holds {nchan.numel()} counts for {plan.B} images")
+    if cls_idx is not None and tuple(cls_idx.shape) != (plan.B, smax):
+        raise ValueError(f"conf_merge_ragged: cls_idx must be [B={plan.B}, smax={smax}], got {tuple(cls_idx.shape)}")
+    if img_box is not None and (tuple(img_box.shape) != (plan.B, 4) or img_box.dtype != torch.int32):
+        raise ValueError(f"conf_merge_ragged: img_box must be int32 [B={plan.B}, 4], got {img_box.dtype} {tuple(img_box.shape)}")
+    lab = _out(out, (plan.total_label_pix,), torch.uint8, planes.device)
+    check(lib().excel_conf_merge_ragged(_p(planes), _p(nchan, torch.int32), _p(cls_idx, torch.int32), _p(half_plan.table, torch.int32),
+                                        C.byref(half_plan.info), _p(plan.table, torch.int32), C.byref(plan.info), int(smax),
+                                        _p(img_box, torch.int32), int(ignore_index), _p(lab, torch.uint8), _stream()), "excel_conf_merge_ragged")
+    return lab
+
+
 def argmax_label(cams, nchan=None, cls_idx=None, want_i64=False):
     """cams [B,Cmax,H,W] -> labels u8 [B,H,W] (and int64 copy if asked), valid_key lookup applied."""
     cams = f32c(cams)

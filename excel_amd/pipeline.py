@@ -51,6 +51,43 @@ def _refuse_tta(who, tta_scales, tta_flip):
                          "training-free regime (TrainingFreePipeline.run_batch / run_batch_ragged)")
 
 
+def check_conf(conf):
+    """conf = (high_thre, low_thre) of the two-threshold labels (utils/affutils.py:101-158) -> the pair as floats, or None.  Refused,
+    naming the value: a threshold outside (0, 1) and low_thre >= high_thre (the band between the two passes would be empty)."""
+    if conf is None:
+        return None
+    high, low = (float(x) for x in conf)
+    for name, v in (("high_thre", high), ("low_thre", low)):
+        if not 0.0 < v < 1.0:
+            raise ValueError(f"{name} {v} is outside (0, 1): the background score competes with min-max normalised cams")
+    if low >= high:
+        raise ValueError(f"low_thre {low} must be below high_thre {high}: the strict pass takes the high score")
+    return high, low
+
+
+def conf_labels_ragged(imgs, cams, plan, half_plan, smax, nchan, cls_idx, high_thre, low_thre, dilations=ops.PAR_DILATIONS, num_iter=20,
+                       w1=0.3, w2=0.01, img_box=None, ignore_index=255, buf=None, keep=False):
+    """refine_cams_with_bkg_v2 (utils/affutils.py:101-158) over a ragged batch, two launches around one PAR:
+        ops.conf_planes_ragged   cams (smax + 1 pitched planes per image on `plan`) -> both softmaxes on `half_plan`   (:115-141)
+        ops.par_forward_ragged   ONE pass over the 2 (k_b + 1) planes of every image: planes do not interact, the two   (:93)
+                                 groups share the affinities of the guide
+        ops.conf_merge_ragged    per group resize + arg-max + keys, the merge and img_box                               (:94-96, :146-156)
+    imgs [B,3,h,w]: what PAR resizes per image to the half plan (align_corners=True, the identity at equal sizes).
+    buf(name, numel, dtype, device) supplies step buffers (the pipeline's _buf); keep=True asks for fresh zero-filled tensors.
+    -> (tight uint8 labels on `plan`, planes, PAR output)"""
+    dev = cams.device
+    C2 = 2 * (smax + 1)
+    n = C2 * half_plan.total_pix
+    fresh = keep or buf is None
+    planes, nchan2 = ops.conf_planes_ragged(cams, plan, half_plan, smax, nchan, high_thre, low_thre,
+                                            out=torch.zeros(n, device=dev) if fresh else buf("conf_planes", n, torch.float32, dev))
+    ws = None if buf is None else buf("par_ws", ops.lib().excel_par_ragged_workspace_bytes(half_plan.total_pix, C2), torch.uint8, dev)
+    par_out = ops.par_forward_ragged(imgs, planes, half_plan, C2, dilations, num_iter, nchan=nchan2, w1=w1, w2=w2, ws=ws,
+                                     out=None if fresh else buf("conf_par_out", n, torch.float32, dev))
+    labels = ops.conf_merge_ragged(par_out, half_plan, plan, smax, nchan, cls_idx, img_box=img_box, ignore_index=ignore_index)
+    return labels, planes, par_out
+
+
 class GuardTicket:
     """The per-image non-finite counts of one guarded step on their way to the host: a pinned int32 [B] the step's stream copies
     into, and the event recorded behind that copy.  ready() never blocks; flags() waits for the event."""
@@ -99,6 +136,8 @@ class TrainingFreePipeline:
         self.caa_thre = caa_thre
         self.smax = smax
         self.hist = None
+        self.hist_conf = None               # the confident labels' matrix (run_batch_ragged(conf=)): counts the kept pixels only
+        self.last_conf_labels = None
         self._bufs = {}
 
     @property
@@ -109,6 +148,7 @@ class TrainingFreePipeline:
     def reset(self):
         self.drain()
         self.hist = None
+        self.hist_conf = None
 
     def _buf(self, name, numel, dtype=torch.float32, device=None):
         """Step-persistent scratch (cams, PAR output, PAR workspace): one grow-only flat buffer per (name, launch stream), so a step
@@ -142,10 +182,12 @@ class TrainingFreePipeline:
         self.last_flags, self.last_guard = flags, GuardTicket(host, ev)
         return flags
 
-    def _score(self, gts, labels, flags, plan=None):
+    def _score(self, gts, labels, flags, plan=None, into="hist"):
+        """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
+        hist = getattr(self, into)
         if self.guard == "skip":
-            return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, self.hist, plan=plan)
-        return ops.confusion_accumulate(gts, labels, self.num_classes, self.hist)                  # evaluate.py:9-20
+            return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, hist, plan=plan)
+        return ops.confusion_accumulate(gts, labels, self.num_classes, hist)                       # evaluate.py:9-20
 
     def _no_guard(self, what):
         if self.guard is not None:
@@ -255,14 +297,18 @@ class TrainingFreePipeline:
     # size-dependent half (input resize, up-sampling, PAR, arg-max) runs over packed, pitched planes through a tile map
     # (ops.RaggedPlan; include/excel_hip.h "ragged batches"): one launch per stage whatever the mix of sizes.
     @torch.no_grad()
-    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=448, return_intermediates=False):
+    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=448, return_intermediates=False, conf=None):
         """hwc_packed: the decoded uint8 [H_b,W_b,3] images back to back (device); plan = ops.RaggedPlan of their sizes;
         cls_labels [B,F] f32 one-hot; gts_packed: the uint8 [H_b,W_b] ground-truth maps back to back (255 = ignore) or None.
         Returns the labels as one flat uint8 tensor (image b = plan.label(labels, b)).
         Without `return_intermediates` the cams / PAR output live in uninitialised step buffers (see _buf: pad columns and unused
         channels are undefined); with it they are fresh tensors whose unused parts are zero.
         `self.last_cams` is the step's cams (smax + 1 pitched planes per image) until the next step on the same stream overwrites it:
-        a consumer queued on that stream right after the step (the --save_cam overlay) reads them without a copy."""
+        a consumer queued on that stream right after the step (the --save_cam overlay) reads them without a copy.
+        `conf` = (high_thre, low_thre) (check_conf) adds the two-threshold labels of utils/affutils.py:101-158 from those cams, on the same
+        stream right after the main labels: the return value becomes (labels, conf_labels[, intermediates]), conf_labels a flat uint8
+        tensor like labels with ignore_index 255 in the band; they stay in `self.last_conf_labels` until the next step and, with ground
+        truth, go into `self.hist_conf` (which therefore counts the kept pixels: coverage = hist_conf.sum() / hist.sum())."""
         dev = hwc_packed.device
         B = plan.B
         g = S // 16
@@ -282,12 +328,13 @@ class TrainingFreePipeline:
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
         flags = self._guard_count(attr, attn_w.w_aff, refined)
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=attn_w.w_aff), flags)
+                                      dict(attr=attr, w_aff=attn_w.w_aff), flags, conf=conf)
 
-    def _ragged_back_half(self, inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates, inter, flags=None):
+    def _ragged_back_half(self, inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates, inter, flags=None, conf=None):
         """Up-sampling + background, PAR, arg-max and confusion of a ragged step (tools/infer_lam.py:94), shared by every regime.
         inputs [B,3,S,S] = the network input PAR reads; `inter` = the regime's own intermediates (attr, w_aff); `flags` = the guard's
-        per-image counts (None without a guard)."""
+        per-image counts (None without a guard); `conf` = run_batch_ragged's (high_thre, low_thre) or None."""
+        conf = check_conf(conf)
         dev = inputs.device
         C = self.smax + 1
         keep = return_intermediates
@@ -301,9 +348,23 @@ class TrainingFreePipeline:
         labels = ops.argmax_label_ragged(par_out, plan, C, nchan, idx)                              # affutils.py:86-87
         if gts_packed is not None:
             self.hist = self._score(gts_packed, labels, flags, plan=plan)
+        if conf is None:
+            if return_intermediates:
+                return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
+            return labels
+        # the two-threshold labels (affutils.py:101-158) from the step's cams: half plan, one PAR over both groups, merge
+        half = getattr(plan, "conf_half", None)
+        if half is None:
+            half = plan.conf_half = ops.conf_half_plan(plan)
+        conf_labels, conf_planes, conf_par_out = conf_labels_ragged(inputs, cams, plan, half, self.smax, nchan, idx, conf[0], conf[1],
+                                                                    self.dilations, self.num_iter, buf=self._buf, keep=keep)
+        self.last_conf_labels = conf_labels
+        if gts_packed is not None:
+            self.hist_conf = self._score(gts_packed, conf_labels, flags, plan=plan, into="hist_conf")
         if return_intermediates:
-            return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
-        return labels
+            return labels, conf_labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls,
+                                             conf_planes=conf_planes, conf_par_out=conf_par_out, conf_plan=half, **inter)
+        return labels, conf_labels
 
     # ------------------------------------------------------------------ concurrent sub-batches
     # Every kernel of the path leaves part of the chip idle in its last round of workgroups (e.g. the N=768 GEMMs of a
@@ -432,7 +493,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
                                                feats_as_reference=True, want_raw=True, want_features=False)
 
     @torch.no_grad()
-    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=448, return_intermediates=False):
+    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=448, return_intermediates=False, conf=None):
         """Same contract as TrainingFreePipeline.run_batch_ragged (flat uint8 labels, self.hist, self.last_cams, intermediates);
         `attr` of the intermediates is the flip-TTA LAM [B,P,F], `w_aff` the seg_attn-gated affinity [B,P,P]."""
         dev = hwc_packed.device
@@ -468,7 +529,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
         refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # infer_lam.py:93
         flags = self._guard_count(attr, w_aff, refined)
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred), flags)
+                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred), flags, conf=conf)
 
 
 class ValidationPipeline(TrainingFreePipeline):
@@ -501,7 +562,7 @@ class ValidationPipeline(TrainingFreePipeline):
         self.hist_seg = None
 
     @torch.no_grad()
-    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=320, return_intermediates=False):
+    def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=320, return_intermediates=False, conf=None):
         """Same contract as TrainingFreePipeline.run_batch_ragged (flat uint8 pseudo labels, self.hist, self.last_cams, intermediates);
         with ground truth it also accumulates the seg prediction's confusion matrix into self.hist_seg.  The intermediates add
         attn_pred [B,P,P], seg [B,nc,g,g] and seg_labels (flat uint8, image b = plan.label(seg_labels, b))."""
@@ -525,4 +586,4 @@ class ValidationPipeline(TrainingFreePipeline):
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # :33
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred, seg=seg, seg_labels=seg_labels))   # :34-36
+                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred, seg=seg, seg_labels=seg_labels), conf=conf)   # :34-36

@@ -44,6 +44,13 @@ Differences from the reference, all deliberate:
     the maximum with the mirrored half, sums and min-max normalises - the `attr` the random walk reads.  The affinity is that of the
     plain scale-1.0 pass (:79).  Everything behind it (labels, score, --save_cam / --save_label / --crf_inline, the overflow guard) is
     unchanged; --api_path true runs the same arithmetic per image (camutils.tta_attr_map);
+  * `--conf_label true` adds the two-threshold pseudo labels of utils/affutils.py:101-158 (refine_cams_with_bkg_v2, which the reference
+    carries but never calls): from the step's cams, at half resolution, one PAR pass over the planes of both background scores
+    (--conf_high_thre 0.7 / --conf_low_thre 0.25, the reference's --high_thre / --low_thre defaults), and a pixel that only the strict
+    pass calls background becomes 255.  Right after each ragged step, on its stream (pipeline.run_batch_ragged(conf=)); the labels are
+    written as palette PNGs `<conf_label_dir>/<name>.png` by the device encoder and scored into a second device-side confusion matrix
+    that is gathered once like the main one: the log shows `conf_label_score` (over the kept pixels) and the coverage (kept / scored
+    pixels).  The overflow guard covers it; --api_path true runs the same arithmetic per image (affutils.conf_labels_image);
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -105,6 +112,18 @@ def resolve_tta(args):
     return scales, flip
 
 
+def resolve_conf(args):
+    """--conf_label / --conf_high_thre / --conf_low_thre -> (high_thre, low_thre) for run_batch_ragged(conf=), or None (the default:
+    the plain step).  Checked here, before a model is built (pipeline.check_conf: a threshold outside (0, 1), low_thre >= high_thre)."""
+    if not bool(getattr(args, "conf_label", False)):
+        return None
+    from ..pipeline import check_conf
+    try:
+        return check_conf((getattr(args, "conf_high_thre", 0.7), getattr(args, "conf_low_thre", 0.25)))
+    except ValueError as e:
+        raise ValueError(f"--conf_high_thre / --conf_low_thre: {e}") from None
+
+
 def _handle_gemm_mode(model):
     """The GEMM mode of the model's ViT handle, or None (no model: a stub pipeline)."""
     try:
@@ -135,6 +154,11 @@ def get_parser():
     p.add_argument("--cs_cam_dir", default=None, type=str, help="per-class overlay directory (default: cam_output_dirs)")
     p.add_argument("--save_label", default=False, type=_bool, help="write the pseudo-label maps as palette PNGs <label_dir>/<name>.png (:95)")
     p.add_argument("--label_dir", default=None, type=str, help="label PNG directory (default: label_output_dir, next to the CAM directories)")
+    p.add_argument("--conf_label", default=False, type=_bool,
+                   help="also write two-threshold pseudo labels with an ignore band (utils/affutils.py:101-158) as palette PNGs <conf_label_dir>/<name>.png")
+    p.add_argument("--conf_high_thre", default=0.7, type=float, help="--conf_label: background score of the strict pass (the reference's --high_thre)")
+    p.add_argument("--conf_low_thre", default=0.25, type=float, help="--conf_label: background score of the lenient pass (the reference's --low_thre)")
+    p.add_argument("--conf_label_dir", default=None, type=str, help="confident-label PNG directory (default: conf_label_output_dir, next to the label directory)")
     p.add_argument("--data_folder", default=None, type=str, help="VOC2012 root (JPEGImages/, SegmentationClassAug/): real data instead of --synthetic")
     p.add_argument("--list_folder", default=None, type=str, help="directory with <infer_set>.txt and cls_labels_onehot.npy")
     p.add_argument("--u8_input", default=False, type=_bool, help="feed decoded uint8 HWC images and normalise on the device")
@@ -211,6 +235,11 @@ def cam_output_dirs(model_path, infer_set, training_free=True, refine_with_aff=T
 def label_output_dir(model_path, infer_set, training_free=True, refine_with_aff=True):
     """Where --save_label writes without --label_dir: next to cam_output_dirs' directories, <infer_set>_<ckpt>_<tag>_label."""
     return cam_output_dirs(model_path, infer_set, training_free, refine_with_aff)["cam_dir"][:-len("_img")] + "_label"
+
+
+def conf_label_output_dir(model_path, infer_set, training_free=True, refine_with_aff=True):
+    """Where --conf_label writes without --conf_label_dir: <infer_set>_<ckpt>_<tag>_conf_label, next to label_output_dir's directory."""
+    return label_output_dir(model_path, infer_set, training_free, refine_with_aff)[:-len("_label")] + "_conf_label"
 
 
 LABEL_WRITERS = 2        # threads that only open / write / close the device-encoded files
@@ -565,16 +594,26 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     writers = default_cam_writers(local_world) if save_cam else 0
     cam = _CamSaver(args, writers, device_jpeg=bool(getattr(args, "cam_device_jpeg", False)) and ragged) if save_cam else None
-    lab = crf = None
-    build_validation.last_crf_hist = build_validation.last_crf_stats = build_validation.last_cam_stats = None
+    lab = crf = conf_lab = None
+    build_validation.last_crf_hist = build_validation.last_crf_stats = build_validation.last_cam_stats = build_validation.last_conf_hist = None
+    conf = resolve_conf(args)
+    if conf is not None and not (ragged or per_image):
+        raise ValueError("--conf_label runs behind the ragged step: ragged batches (--data_folder or --ragged true) or the per-image path "
+                         "(--api_path true / --training_free false)")
     if crf_inline_wanted(args) and not (ragged or per_image):
         raise ValueError("--crf_inline needs the decoded images: ragged batches (--data_folder or --ragged true) or the per-image path "
                          "(--api_path true / --training_free false)")
     try:
         lab = _LabelSaver(args) if bool(getattr(args, "save_label", False)) else None
         crf = _CrfInline(args, device) if crf_inline_wanted(args) else None
+        if conf is not None:
+            conf_lab = _LabelSaver(args, getattr(args, "conf_label_dir", None) or conf_label_output_dir(
+                getattr(args, "model_path", None), args.infer_set, training_free, bool(getattr(args, "refine_with_aff", True))))
         out = _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab, crf,
-                                build_validation.last_guard)
+                                build_validation.last_guard, conf, conf_lab)
+        if conf_lab is not None:
+            conf_lab, done = None, conf_lab
+            done.close()
         if lab is not None:                                  # every file on disk (and a writer's error raised) before the scores are reported
             lab, done = None, lab
             done.close()
@@ -596,15 +635,16 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
                 crf.close()
             except Exception:
                 pass
-        if lab is not None:                                  # on the way out of an exception: stop the writers, keep the first error
-            try:
-                lab.close()
-            except Exception:
-                pass
+        for w in (lab, conf_lab):                            # on the way out of an exception: stop the writers, keep the first error
+            if w is not None:
+                try:
+                    w.close()
+                except Exception:
+                    pass
 
 
 def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab=None,
-                      crf=None, guard=None):
+                      crf=None, guard=None, conf=None, conf_lab=None):
     from ..utils import evaluate
     from ..utils.affutils import refine_cams_with_aff, refine_cams_with_bkg_weclip
     from .. import ops
@@ -613,7 +653,8 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
     nimg = 0
     tta = resolve_tta(args)
     if not per_image:
-        return _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu)
+        return _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu, conf, conf_lab)
+    hist_conf = None
     for s in range(0, len(indices)):
         names, imgs, gts, cls = dataset.batch(indices[s:s + 1])
         inputs = torch.from_numpy(imgs).to(device, non_blocking=True)
@@ -654,12 +695,18 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
             hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
             if lab is not None:                                                             # :95 (uint8 as hist_from_labels scores them)
                 lab.uniform([names[i]], labels[:1].to(torch.uint8))
+            if conf is not None:                                                            # affutils.py:101-158 on the image's own cams
+                from ..utils.affutils import conf_labels_image
+                kept = conf_labels_image(par, inputs[i], normed, cls_lst, conf[0], conf[1])
+                hist_conf = ops.confusion_accumulate(gt_dev[i].to(torch.uint8), kept, args.num_classes, hist_conf)
+                conf_lab.uniform([names[i]], kept[None])
         nimg += len(imgs)
     torch.cuda.synchronize()
+    build_validation.last_conf_hist = hist_conf
     return hist, nimg, time.time() - t0
 
 
-def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu):
+def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu, conf=None, conf_lab=None):
     """The batched loop of build_validation: one pass over `indices`, and with the overflow guard's `rerun` policy a second pass in exact
     fp32 over the images the first one flagged - the same loop body (`steps`) and the same consumers both times."""
     from collections import deque
@@ -667,6 +714,8 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
     S = args.resize_size
     policy = guard["policy"] if guard else "off"
     pipe.hist = hist
+    if conf is not None:
+        pipe.hist_conf = torch.zeros_like(hist)
     host_cls = deque()          # the host one-hot rows, in the feeder's order (it keeps the order)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
@@ -698,7 +747,13 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
         return ((rb.names, ops.RaggedPlan(rb.hw, None), rb.images, rb.cls, rb.labels) for rb in batches)
 
     def ragged_step(names, plan, images, cls_t, labels_t):
-        out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
+        if conf is None:
+            out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
+        else:                                                                           # affutils.py:101-158, same stream, step's own cams
+            plan.conf_half = ops.conf_half_plan(plan, names=names)                      # (an image too small to halve is refused by name; the step reuses the plan)
+            main, kept, *rest = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep, conf=conf)
+            out = (main, rest[0]) if keep else main
+            conf_lab.ragged(names, plan, kept)
         cls_host = host_cls.popleft() if (cam is not None or crf is not None) else None
         if cam is not None:                                                             # :97-111, same stream, step's own cams
             cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, cls_host)
@@ -777,7 +832,7 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
         # every file of the first pass on disk before a flagged image's file is written again: the good one must be the last
         if on_gpu:
             torch.cuda.synchronize()
-        for w in (cam, lab, crf):
+        for w in (cam, lab, crf, conf_lab):
             if w is not None:
                 w.barrier()
         order, still = sorted(flagged), {}
@@ -800,6 +855,8 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
                             f"{', '.join(guard['nonfinite_in_f32'])}")
     if on_gpu:
         torch.cuda.synchronize()
+    if conf is not None:
+        build_validation.last_conf_hist = pipe.hist_conf
     return pipe.hist, nimg, time.time() - t0
 
 
@@ -942,6 +999,7 @@ def validate(args=None, dataset=None, pipe=None):
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
+    resolve_conf(args)                                                                       # ... and a bad pair of thresholds
     if pipe is None:
         torch.cuda.set_device(args.local_rank)
         device = torch.device("cuda", args.local_rank)
@@ -1017,6 +1075,20 @@ def validate(args=None, dataset=None, pipe=None):
                            "hist_total": [[int(v) for v in row] for row in total.cpu().tolist()],       # the gathered confusion matrix itself
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
                            "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1])}, f)
+    validate.last_conf = None
+    if resolve_conf(args) is not None:
+        conf_hist = getattr(build_validation, "last_conf_hist", None)
+        if conf_hist is None:                                                               # a rank with an empty shard still joins the gather
+            conf_hist = torch.zeros_like(hist)
+        _, conf_total = gather_hists(conf_hist)                                             # once, like the main matrix
+        conf_score = evaluate.scores_from_hist(conf_total)
+        coverage = float(conf_total.sum().item()) / max(float(total.sum().item()), 1.0)
+        validate.last_conf = (conf_score, conf_total, coverage)
+        if rank == 0:
+            logging.info("conf_label_score:")
+            logging.info("\n" + format_scores_table(conf_score, cat_list))
+            logging.info(f"conf_label coverage {coverage * 100:.3f} % of the scored pixels kept "
+                         f"(high_thre {args.conf_high_thre}, low_thre {args.conf_low_thre})")
     inline_hist = getattr(build_validation, "last_crf_hist", None)
     if getattr(args, "crf_post", False) and getattr(args, "crf_inline", False) and inline_hist is None and rank == 0:
         logging.info(f"--crf_inline: the {args.infer_set} split keeps the record path of the CRF stage (scored against image[:,:,0], :213-214)")

@@ -522,6 +522,36 @@ int excel_seg_softmax_resize(const float* planes, int h, int w, int nc, int H, i
 int excel_seg_softmax_resize_ragged(const float* planes, const int32_t* src_table, const excel_ragged_info* src_info, const int32_t* dst_table,
                                     const excel_ragged_info* dst_info, int nc, float* prob, void* stream);
 
+/* ------------------------------------------------------------------ confident labels: two thresholds and an ignore band (conf.hip)
+ * utils/affutils.py:101-158 (refine_cams_with_bkg_v2; twin at utils/camutils.py:264-304) makes one PAR pass per background score at
+ * half resolution and ignores the pixels only the strict pass calls background.  For a ragged batch the two passes are ONE
+ * excel_par_forward_ragged over 2 (k_b + 1) planes per image on the "half plan" (the excel_ragged_plan of (H_b / ds, W_b / ds)); these
+ * two entries are what stands in front of and behind it.  smax <= 127; neither takes a workspace.
+ *
+ * excel_conf_planes_ragged replaces :115-118 and :129-141: cams = smax + 1 pitched planes per image at the sizes of
+ * (src_table, src_info) (the excel_cam_upsample_bkg_ragged layout; plane 0 is never read), nchan[b] = k_b + 1.  Every class plane goes
+ * to the half plan (bilinear, align_corners=False: the operations and bits of excel_bilinear_resize, each value computed once) and
+ * planes = 2 (smax + 1) pitched planes per image on the half plan receives
+ *   planes [0, k_b]            softmax_c([high_thre, m_1 .. m_k])
+ *   planes [k_b + 1, 2k_b + 1] softmax_c([low_thre,  m_1 .. m_k])
+ * (maximum subtracted, sum in channel order 0..k, one division per value; a resized constant is the constant), and
+ * nchan2[b] = 2 (k_b + 1) describes the two groups to excel_par_forward_ragged.  Planes >= nchan2[b] and the pad columns stay undefined.
+ * softmax == 0 (tests): the first group receives [high_thre, m_1 .. m_k] as resized and nothing else is written. */
+int excel_conf_planes_ragged(const float* cams, const int32_t* nchan, const int32_t* src_table, const excel_ragged_info* src_info,
+                             const int32_t* half_table, const excel_ragged_info* half_info, int smax, float high_thre, float low_thre,
+                             int softmax, float* planes, int32_t* nchan2 /*device [B], out*/, void* stream);
+
+/* excel_conf_merge_ragged replaces _refine_cams2 :94-96 for both groups, :146-152 and :154-156: planes = 2 (smax + 1) pitched planes per
+ * image on the half plan (PAR's output: groups of nchan[b] = k_b + 1 planes back to back).  Per group: bilinear to the sizes of
+ * (dst_table, dst_info) (align_corners=False), arg-max with the first maximum winning, key lookup (0 -> 0, c -> cls_idx[b, c-1] + 1; no
+ * cls_idx: c) - the bits of excel_bilinear_resize + excel_argmax_label.  Then lab = lab_h; lab_h == 0 -> ignore_index; lab_h == 0 and
+ * lab_l == 0 -> 0.  img_box (optional, device int32 [B,4] = y0, y1, x0, x1, non-negative): pixels outside [y0, y1) x [x0, x1) get
+ * ignore_index.  labels_u8: tight, image b at loff_b of the destination plan. */
+int excel_conf_merge_ragged(const float* planes, const int32_t* nchan, const int32_t* cls_idx /*device [B,smax] or NULL*/,
+                            const int32_t* half_table, const excel_ragged_info* half_info, const int32_t* dst_table,
+                            const excel_ragged_info* dst_info, int smax, const int32_t* img_box /*device [B,4] or NULL*/, int ignore_index,
+                            uint8_t* labels_u8, void* stream);
+
 /* excel_dcrf_inference for a GROUP of images of a ragged batch in one chain of launches (lattice build, normalisers, mean-field steps
  * run once for the group, not once per image): what tools/infer_seg_voc.py:103-174 (crf_proc), tools/infer_seg_coco.py:144-145 and
  * utils/dcrf.py:42-68 do per image.  (table, info) = the excel_ragged_plan of the group (see "ragged batches" below).
