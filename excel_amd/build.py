@@ -18,12 +18,13 @@ HEADERS = ["common.h", "excel_internal.h", "jet.h", "excel_split_api.inc", "gemm
 # into a memory loop (round 5: one `break` in an unrolled epilogue loop sent the 320x256 GEMM's accumulators to scratch, 3.5x slower,
 # all tests green).  build() reads hipcc's kernel-resource-usage remarks and refuses to link a library that violates this.
 NO_SCRATCH = ("gemm_bf16x3_kernel", "gemm_w4_kernel", "gemm_w4x2_kernel", "attn_strip_kernel", "par_iterate_guide_kernel", "par_stats_tile_kernel",
+              "patch_text_sim_kernel", "patch_text_sim_wide_kernel",
               "cam_overlay_ragged_kernel", "train_panels_kernel", "png_rows_kernel", "png_layout_kernel", "png_crc_kernel",
               "jpeg_transform_kernel", "jpeg_code_kernel", "jpeg_layout_kernel", "jpeg_count_kernel", "jpeg_offsets_kernel", "jpeg_assemble_kernel")
 # the guard must see what it guards: every object that is supposed to hold one of these kernels has to report it in hipcc's remarks (an
 # empty or re-formatted remark stream would otherwise pass vacuously - advisor, round 5)
 NO_SCRATCH_EXPECTED = {"gemm_bf16x3": "gemm_bf16x3_kernel", "gemm_w4": "gemm_w4_kernel", "gemm_w4x2": "gemm_w4x2_kernel", "attn_strip": "attn_strip_kernel",
-                       "par": "par_iterate_guide_kernel", "camviz": "cam_overlay_ragged_kernel", "trainviz": "train_panels_kernel", "png": "png_rows_kernel", "jpeg": "jpeg_transform_kernel"}
+                       "par": "par_iterate_guide_kernel", "cam": "patch_text_sim_wide_kernel", "camviz": "cam_overlay_ragged_kernel", "trainviz": "train_panels_kernel", "png": "png_rows_kernel", "jpeg": "jpeg_transform_kernel"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value",
          # fully unroll the big register-tile epilogues (a partially unrolled loop indexes the accumulator array
          # dynamically and sends it to scratch)

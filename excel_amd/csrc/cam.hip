@@ -79,11 +79,88 @@ __global__ __launch_bounds__(1024) void cam_epilogue_kernel(float* __restrict__ 
     }
 }
 
+// T > CAM_TMAX (up to CAM_TWIDE): the same three sweeps with CAM_TWIDE / 64 class columns per lane.  A kernel of its own, so that the
+// narrow one above keeps its code for the vocabularies it serves (VOC 45 rows, COCO 103).
+#define CAM_TWIDE 512
+__global__ __launch_bounds__(1024) void cam_epilogue_wide_kernel(float* __restrict__ S, float* __restrict__ out_full,
+                                                                 float* __restrict__ out_slice, int N, int T, int ldS, int F,
+                                                                 float temp) {
+    constexpr int NV = CAM_TWIDE / 64;
+    __shared__ float w[CAM_TWIDE];
+    __shared__ float mn[16][CAM_TWIDE];
+    __shared__ float mx[16][CAM_TWIDE];
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* Sb = S + (long long)b * N * ldS;
+
+    if (wave == 0) {
+        float v[NV], e[NV], m = -INFINITY, s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { v[i] = (lane + 64 * i < T) ? Sb[lane + 64 * i] * temp : -INFINITY; m = fmaxf(m, v[i]); }
+        m = wave_max(m);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { e[i] = (lane + 64 * i < T) ? __expf(v[i] - m) : 0.f; s += e[i]; }
+        const float sum = wave_sum(s);
+        s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { e[i] = e[i] / sum; s += e[i]; }
+        const float mean = wave_sum(s) / (float)T;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) w[lane + 64 * i] = (lane + 64 * i < T) ? e[i] / mean : 0.f;
+    }
+    __syncthreads();
+
+    float wv[NV], lo[NV], hi[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { wv[i] = w[lane + 64 * i]; lo[i] = INFINITY; hi[i] = -INFINITY; }
+    for (int n = wave; n < N; n += 16) {
+        float* row = Sb + (long long)n * ldS;
+        float a[NV], s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { a[i] = (lane + 64 * i < T) ? row[lane + 64 * i] * wv[i] : 0.f; s += a[i]; }
+        const float red = wave_sum(s) / (float)T;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+            if (lane + 64 * i < T) {
+                const float v = a[i] - red;
+                row[lane + 64 * i] = v;
+                lo[i] = fminf(lo[i], v);
+                hi[i] = fmaxf(hi[i], v);
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { mn[wave][lane + 64 * i] = lo[i]; mx[wave][lane + 64 * i] = hi[i]; }
+    __syncthreads();
+    if (tid < CAM_TWIDE) {
+        float a = mn[0][tid], c = mx[0][tid];
+        for (int i = 1; i < 16; ++i) { a = fminf(a, mn[i][tid]); c = fmaxf(c, mx[i][tid]); }
+        mn[0][tid] = a;
+        mx[0][tid] = c;
+    }
+    __syncthreads();   // also orders the in-place sim writes before the re-read below (same block)
+
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { lo[i] = mn[0][lane + 64 * i]; hi[i] = mx[0][lane + 64 * i] - lo[i]; }
+    for (int n = wave; n < N; n += 16) {
+        const float* row = Sb + (long long)n * ldS;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int t = lane + 64 * i;
+            if (t < T) {
+                const float v = (row[t] - lo[i]) / hi[i];
+                if (out_full) out_full[((long long)b * N + n) * T + t] = v;
+                if (out_slice && n >= 1 && t < F) out_slice[((long long)b * (N - 1) + (n - 1)) * F + t] = v;
+            }
+        }
+    }
+}
+
 int excel_launch_cam_epilogue(float* S, float* out_full, float* out_slice, int B, int N, int T, int ldS, int F, float temp,
                               hipStream_t st) {
     ProfScope prof__(PROF_CAM_EPILOGUE, st);
-    EXCEL_CHECK_ARG(T >= 1 && T <= CAM_TMAX && F <= T && ldS >= T, "cam: need 1 <= F <= T <= %d (T=%d F=%d)", CAM_TMAX, T, F);
-    hipLaunchKernelGGL(cam_epilogue_kernel, dim3(B), dim3(1024), 0, st, S, out_full, out_slice, N, T, ldS, F, temp);
+    EXCEL_CHECK_ARG(T >= 1 && T <= CAM_TWIDE && F <= T && ldS >= T, "cam: need 1 <= F <= T <= %d (T=%d F=%d)", CAM_TWIDE, T, F);
+    if (T <= CAM_TMAX) hipLaunchKernelGGL(cam_epilogue_kernel, dim3(B), dim3(1024), 0, st, S, out_full, out_slice, N, T, ldS, F, temp);
+    else hipLaunchKernelGGL(cam_epilogue_wide_kernel, dim3(B), dim3(1024), 0, st, S, out_full, out_slice, N, T, ldS, F, temp);
     EXCEL_CHECK_LAUNCH("cam_epilogue");
     return EXCEL_OK;
 }
@@ -106,7 +183,8 @@ int excel_launch_cam_epilogue(float* S, float* out_full, float* out_slice, int B
 //      un-normalised similarities go to a [B,N,ldT] scratch (4.5 MB at B = 32), per-workgroup per-class min / max to a partial table;
 //   3. patch_text_finish_kernel: min / max over the partials (exact and order-independent), attr = (sim - min) / (max - min), slice.
 // The normalised features f are never written unless the caller asks for them (generate_clip_fts' return value).
-#define PTC_MAXCT 4            // class tiles of 32: T <= 128
+#define PTC_MAXCT 4            // class tiles of 32 held in accumulators at once: T <= 128 in one pass, wider vocabularies in chunks
+#define PTC_WIDE_T 512         // rows of the wide path (patch_text_sim_wide_kernel)
 #define PTC_NW 4               // waves (= token tiles) per workgroup
 #define PTC_HB 64              // tokens per column-norm block
 struct PtcArgs {
@@ -114,7 +192,7 @@ struct PtcArgs {
     const float* text;             // [T,C] fp32
     const unsigned short* text_s;  // [T][2C] split bf16 (bf16x3 mode)
     float* sim;                    // [B,N,ldT] scratch: un-normalised similarities
-    float* part;                   // [B,G,2,PTC_MAXCT*32] per-workgroup per-class min / max
+    float* part;                   // [B,G,2,TP] per-workgroup per-class min / max, TP = PTC_MAXCT*32 (T <= 128) or PTC_WIDE_T
     float* colsq;                  // [B,cdiv(N,PTC_HB),C] partial column sums of squares
     float* out_full;               // [B,N,T]   (may be null)
     float* out_slice;              // [B,N-1,F] (may be null)
@@ -408,18 +486,248 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_kernel(PtcArgs p) 
     }
 }
 
+// T > 128: the class axis goes through the accumulators in chunks of PTC_MAXCT * 32 rows.  The redundancy term spans ALL classes, so it
+// cannot come out of one chunk's accumulators; it is taken from the other side of the same identity,
+//   red[n] = (1/T) sum_t w[t] S[n,t] = f[n,:] . vbar,   vbar[c] = (1/T) sum_t w[t] text[t,c],
+// which needs the class-prior weights (hence the cls logits) BEFORE the matrix loop: the prologue computes w and vbar (fixed fp32
+// chains over t: identical bits in every workgroup), the first chunk's k-loop accumulates f . vbar next to the MFMAs (one fma chain
+// per lane in k order + one cross-half add: a function of the image and the token alone), and every chunk is then complete in itself:
+// scale, subtract, min / max, store - no second sweep and no wave re-reading what it stored.  x is re-read per chunk (an L2 hit: the
+// tile is 32 x C floats) with one block of look-ahead; the text rows come from global memory in both modes.
+template <bool BF>
+__global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_wide_kernel(PtcArgs p) {
+    constexpr int NW = PTC_NW, NT = NW * 64, CT = PTC_MAXCT, CH = CT * 32, EP = CH + 1;
+    __shared__ __attribute__((aligned(16))) float inv[1024];   // 1 / ||x[:, c]||_2 over the tokens
+    __shared__ __attribute__((aligned(16))) float f0[1024];    // normalised cls-token features
+    __shared__ __attribute__((aligned(16))) float vbar[1024];  // (1/T) sum_t w[t] text[t,:]
+    __shared__ float w[PTC_WIDE_T];                // cls logits, then the class-prior weights (0 for padded classes)
+    __shared__ float red_mn[NW][PTC_WIDE_T], red_mx[NW][PTC_WIDE_T];
+    __shared__ __attribute__((aligned(16))) float xs[NW][32 * PTC_XP];
+    __shared__ float ets[NW][32 * EP];             // epilogue tiles [token][class of the chunk]
+    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, kh = lane >> 5;
+    const int N = p.N, C = p.C, T = p.T;
+    const float* X = p.x_raw + (long long)b * N * C;
+    const int ntile = (N + 31) / 32;
+    const int tile = g * NW + wave;
+    const bool live = tile < ntile;
+    const int lr = lane >> 3, lc = (lane & 7) * 4;
+    const float* xq[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xq[j] = X + (long long)min(tile * 32 + lr + 8 * j, N - 1) * C + lc;    // clamped rows: masked at the end
+    const int nkb = C / 32;
+    // ---- prologue: token-axis norms (partials in block order), cls logits, class-prior weights, vbar
+    {
+        const int nblk = (N + PTC_HB - 1) / PTC_HB;
+        const float* q = p.colsq + (long long)b * nblk * C;
+        for (int c = tid; c < C; c += NT) {
+            float s = 0.f;
+            for (int k0 = 0; k0 < nblk; k0 += 8) {             // 8 partials in flight; added in block order (s + 0 is exact for the tail)
+                float v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = q[(long long)min(k0 + k, nblk - 1) * C + c];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s += (k0 + k < nblk) ? v[k] : 0.f;
+            }
+            inv[c] = 1.f / sqrtf(s);
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += NT) f0[c] = X[c] * inv[c];
+    __syncthreads();
+    // S[0,t] = sum_c f[0,c] text[t,c]: the chains of the narrow kernel (thread = class x quarter of the 16-byte pieces of a row)
+    for (int t0 = 0; t0 < T; t0 += NT / 4) {
+        const int t = t0 + (tid >> 2), q = tid & 3;
+        float s = 0.f;
+        if (t < T) {
+            const float* tr = p.text + (long long)t * C;
+#pragma unroll 8
+            for (int c = q * 4; c < C; c += 16) {
+                const f32x4 tv = *reinterpret_cast<const f32x4*>(tr + c), fv = *reinterpret_cast<const f32x4*>(f0 + c);
+                s = fmaf(fv[0], tv[0], s); s = fmaf(fv[1], tv[1], s); s = fmaf(fv[2], tv[2], s); s = fmaf(fv[3], tv[3], s);
+            }
+        }
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        if (t < T && q == 0) w[t] = s;
+    }
+    __syncthreads();
+    if (wave == 0) {       // softmax(temp * S[0,:]) / mean  (clip.py:295-297), PTC_WIDE_T / 64 values per lane
+        constexpr int NV = PTC_WIDE_T / 64;
+        float v[NV], e[NV], m = -INFINITY, s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { v[i] = (lane + 64 * i < T) ? w[lane + 64 * i] * p.temp : -INFINITY; m = fmaxf(m, v[i]); }
+        m = wave_max(m);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { e[i] = (lane + 64 * i < T) ? __expf(v[i] - m) : 0.f; s += e[i]; }
+        const float sum = wave_sum(s);
+        s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) { e[i] = e[i] / sum; s += e[i]; }
+        const float mean = wave_sum(s) / (float)T;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < NV; ++i) w[lane + 64 * i] = (lane + 64 * i < T) ? e[i] / mean : 0.f;
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += NT) {                       // one fma chain per column, t increasing
+        const float* tc = p.text + c;
+        float s = 0.f;
+#pragma unroll 8
+        for (int t = 0; t < T; ++t) s = fmaf(w[t], tc[(long long)t * C], s);
+        vbar[c] = s / (float)T;
+    }
+    __syncthreads();
+
+    float* simb = p.sim + (long long)b * N * p.ldT;
+    float* xt = xs[wave];
+    float* et = ets[wave];
+    const int nvalid = live ? min(32, N - tile * 32) : 0;    // tokens of this tile inside the image
+    const int ntok = min(tile * 32 + r, N - 1);               // token of this lane column in operand order
+    float* frow = (live && p.feats && tile * 32 + r < N) ? p.feats + ((long long)b * N + ntok) * C : nullptr;
+    float redp = 0.f, red = 0.f;
+    const int nch = (T + CH - 1) / CH;
+    for (int ch = 0; ch < nch; ++ch) {
+        const int cbase = ch * CH;
+        f32x16 acc[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[ct][e] = 0.f;
+        if (live) {
+            const unsigned short* trow[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) trow[ct] = p.text_s + (long long)min(cbase + ct * 32 + r, T - 1) * 2 * C;
+            f32x4 xv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xv[j] = *reinterpret_cast<const f32x4*>(xq[j]);
+            for (int kb = 0; kb < nkb; ++kb) {
+                // coalesced registers -> LDS tile (wave-private) -> operand order
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(&xt[(lr + 8 * j) * PTC_XP + lc]) = xv[j];
+                {   // the next block, unconditionally (the tail re-reads the last one)
+                    const int kn = min(kb + 1, nkb - 1);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) xv[j] = *reinterpret_cast<const f32x4*>(xq[j] + kn * 32);
+                }
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    const int cb = h2 * 16 + 8 * kh, c0 = kb * 32 + cb;       // this lane's 8 columns of the 16-k step
+                    const f32x4 ia = *reinterpret_cast<const f32x4*>(inv + c0), ib = *reinterpret_cast<const f32x4*>(inv + c0 + 4);
+                    const f32x4 fa = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb]) * ia;
+                    const f32x4 fb = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb + 4]) * ib;
+                    if (ch == 0) {
+                        if (frow) { *reinterpret_cast<f32x4*>(frow + c0) = fa; *reinterpret_cast<f32x4*>(frow + c0 + 4) = fb; }
+                        const f32x4 va = *reinterpret_cast<const f32x4*>(vbar + c0), vb = *reinterpret_cast<const f32x4*>(vbar + c0 + 4);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) redp = fmaf(fa[e], va[e], redp);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) redp = fmaf(fb[e], vb[e], redp);
+                    }
+                    if (BF) {
+                        splitx8 xh, xl;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const float v = (j < 4) ? fa[j] : fb[j - 4];
+                            xh[j] = split_hi(v);
+                            xl[j] = split_hi(v - (float)xh[j]);
+                        }
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) {
+                            if (cbase + ct * 32 >= T) continue;               // uniform: a class tile past the vocabulary
+                            const unsigned short* tp = trow[ct] + split_off(c0, 0);
+                            splitx8 h = *reinterpret_cast<const splitx8*>(tp), l = *reinterpret_cast<const splitx8*>(tp + 32);
+                            if (cbase + ct * 32 + r >= T) { h = splitx8{0, 0, 0, 0, 0, 0, 0, 0}; l = h; }
+                            acc[ct] = EXCEL_MFMA16(l, xh, acc[ct], 0, 0, 0);
+                            acc[ct] = EXCEL_MFMA16(h, xl, acc[ct], 0, 0, 0);
+                            acc[ct] = EXCEL_MFMA16(h, xh, acc[ct], 0, 0, 0);
+                        }
+                    } else {
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) {
+                            if (cbase + ct * 32 >= T) continue;
+                            const int cls = cbase + ct * 32 + r;
+                            f32x4 ta = {0.f, 0.f, 0.f, 0.f}, tb = ta;
+                            if (cls < T) {
+                                ta = *reinterpret_cast<const f32x4*>(p.text + (long long)cls * C + c0);
+                                tb = *reinterpret_cast<const f32x4*>(p.text + (long long)cls * C + c0 + 4);
+                            }
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[e], fa[e], acc[ct], 0, 0, 0);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(tb[e], fb[e], acc[ct], 0, 0, 0);
+                        }
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();              // the tile is re-written by the next block
+            }
+        }
+        if (ch == 0) red = redp + __shfl_xor(redp, 32, 64);
+        // sim[n,t] = w[t] S[n,t] - red[n]; through LDS as [token][class] so that lanes run over the classes (coalesced rows, in-lane min / max)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = ct * 32 + c32_row(e, lane);
+                et[r * EP + row] = acc[ct][e] * w[min(cbase + row, PTC_WIDE_T - 1)] - red;
+            }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int cc = 0; cc < CT / 2; ++cc) {
+            const int cl = cc * 64 + lane, cls = cbase + cl;
+            float a = INFINITY, c = -INFINITY;
+            if (cls < T) {
+                float* srow = simb + (long long)tile * 32 * p.ldT + cls;
+#pragma unroll 8
+                for (int k = 0; k < nvalid; ++k) {
+                    const float v = et[k * EP + cl];
+                    srow[(long long)k * p.ldT] = v;
+                    a = fminf(a, v);
+                    c = fmaxf(c, v);
+                }
+                red_mn[wave][cls] = a;
+                red_mx[wave][cls] = c;
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();                      // the epilogue tile is re-written by the next chunk
+    }
+    __syncthreads();
+    for (int t = tid; t < T; t += NT) {
+        float a = red_mn[0][t], c = red_mx[0][t];
+#pragma unroll
+        for (int i = 1; i < NW; ++i) { a = fminf(a, red_mn[i][t]); c = fmaxf(c, red_mx[i][t]); }
+        float* o = p.part + ((long long)b * p.G + g) * 2 * PTC_WIDE_T;
+        o[t] = a;
+        o[PTC_WIDE_T + t] = c;
+    }
+}
+
 // attr = (sim - min) / (max - min) over ALL tokens (clip.py:308; NaN when max == min, like the reference).  grid (cdiv(N, 64), B)
+template <int TP>               // TP: row pitch of the partial table = the most classes of the path
 __global__ __launch_bounds__(256) void patch_text_finish_kernel(PtcArgs p) {
-    __shared__ float lo[PTC_MAXCT * 32], span[PTC_MAXCT * 32];
+    __shared__ float lo[TP], span[TP];
     const int b = blockIdx.y, tid = threadIdx.x, N = p.N, T = p.T;
     if (tid < T) {
-        const float* q = p.part + (long long)b * p.G * 2 * (PTC_MAXCT * 32);
+        const float* q = p.part + (long long)b * p.G * 2 * TP;
         float a = INFINITY, c = -INFINITY;
 #pragma unroll 8
-        for (int g = 0; g < p.G; ++g) { a = fminf(a, q[g * 2 * (PTC_MAXCT * 32) + tid]); c = fmaxf(c, q[(g * 2 + 1) * (PTC_MAXCT * 32) + tid]); }
+        for (int g = 0; g < p.G; ++g) { a = fminf(a, q[g * 2 * TP + tid]); c = fmaxf(c, q[(g * 2 + 1) * TP + tid]); }
         lo[tid] = a;
         span[tid] = c - a;
     }
+    if (TP > 256)                   // the classes beyond the 256 threads (the narrow instantiation keeps the block above as its only one)
+        for (int t = tid + 256; t < T; t += 256) {
+            const float* q = p.part + (long long)b * p.G * 2 * TP;
+            float a = INFINITY, c = -INFINITY;
+#pragma unroll 8
+            for (int g = 0; g < p.G; ++g) { a = fminf(a, q[g * 2 * TP + t]); c = fmaxf(c, q[(g * 2 + 1) * TP + t]); }
+            lo[t] = a;
+            span[t] = c - a;
+        }
     __syncthreads();
     const float* simb = p.sim + (long long)b * N * p.ldT;
     const int n0 = blockIdx.x * 64, n1 = min(n0 + 64, N);
@@ -435,7 +743,7 @@ __global__ __launch_bounds__(256) void patch_text_finish_kernel(PtcArgs p) {
 static inline int ptc_groups(int N) { return cdiv(cdiv(N, 32), PTC_NW); }
 size_t excel_patch_text_cam_ws_floats(int B, int N, int C, int T, int which) {
     if (which == 0) return (size_t)B * N * ((T + 3) / 4 * 4);
-    if (which == 1) return (size_t)B * ptc_groups(N) * 2 * (PTC_MAXCT * 32);
+    if (which == 1) return (size_t)B * ptc_groups(N) * 2 * (T <= PTC_MAXCT * 32 ? PTC_MAXCT * 32 : PTC_WIDE_T);
     return (size_t)B * cdiv(N, PTC_HB) * C;
 }
 
@@ -444,7 +752,7 @@ int excel_launch_patch_text_cam(const float* x_raw, const float* text, unsigned 
                                 float* colsq_ws, float* out_full, float* out_slice, float* feats, int B, int N, int C, int T, int F, int ldT,
                                 float temp, int bf, hipStream_t st) {
     ProfScope prof__(PROF_CAM_FUSED, st, 2.0 * B * (double)N * C * T);
-    EXCEL_CHECK_ARG(T >= 1 && T <= PTC_MAXCT * 32 && F <= T && ldT >= T, "patch_text_cam: need 1 <= F <= T <= %d (T=%d F=%d)", PTC_MAXCT * 32, T, F);
+    EXCEL_CHECK_ARG(T >= 1 && T <= PTC_WIDE_T && F <= T && ldT >= T, "patch_text_cam: need 1 <= F <= T <= %d (T=%d F=%d)", PTC_WIDE_T, T, F);
     EXCEL_CHECK_ARG(C <= 1024 && (C % 32) == 0, "patch_text_cam: C must be a multiple of 32, <= 1024 (C=%d)", C);
     EXCEL_CHECK_ARG(!bf || text_split_out, "patch_text_cam: bf16x3 mode needs the split-text workspace");
     const unsigned short* text_split = text_split_out;
@@ -456,12 +764,16 @@ int excel_launch_patch_text_cam(const float* x_raw, const float* text, unsigned 
     hipLaunchKernelGGL(patch_text_prep_kernel, dim3(cdiv(N, PTC_HB), B, cdiv(C, 256) + 1), dim3(256), 0, st, a, bf ? text_split_out : nullptr);
     const int ct = cdiv(T, 32);
 #define PTC_LAUNCH(BFV, CTV, TL) hipLaunchKernelGGL((patch_text_sim_kernel<BFV, CTV, TL>), dim3(G, B), dim3(PTC_NW * 64), 0, st, a)
-    if (bf) {
+    if (T > PTC_MAXCT * 32) {
+        if (bf) hipLaunchKernelGGL((patch_text_sim_wide_kernel<true>), dim3(G, B), dim3(PTC_NW * 64), 0, st, a);
+        else hipLaunchKernelGGL((patch_text_sim_wide_kernel<false>), dim3(G, B), dim3(PTC_NW * 64), 0, st, a);
+    } else if (bf) {
         if (T <= PTC_TLDS_ROWS && C <= PTC_TLDS_C && (C % 256) == 0) { if (ct <= 1) PTC_LAUNCH(true, 1, true); else PTC_LAUNCH(true, 2, true); }
         else { if (ct <= 2) PTC_LAUNCH(true, 2, false); else PTC_LAUNCH(true, 4, false); }
     } else { if (ct <= 1) PTC_LAUNCH(false, 1, false); else if (ct == 2) PTC_LAUNCH(false, 2, false); else PTC_LAUNCH(false, 4, false); }
 #undef PTC_LAUNCH
-    hipLaunchKernelGGL(patch_text_finish_kernel, dim3(cdiv(N, 64), B), dim3(256), 0, st, a);
+    if (T <= PTC_MAXCT * 32) hipLaunchKernelGGL((patch_text_finish_kernel<PTC_MAXCT * 32>), dim3(cdiv(N, 64), B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((patch_text_finish_kernel<PTC_WIDE_T>), dim3(cdiv(N, 64), B), dim3(256), 0, st, a);
     EXCEL_CHECK_LAUNCH("patch_text_cam");
     return EXCEL_OK;
 }

@@ -56,7 +56,20 @@ __global__ __launch_bounds__(256) void nonfinite_count_kernel(const unsigned* __
 // confusion_kernel (par.hip) restricted to one image per blockIdx.y: the same LDS-private histogram, the same scalar head / 16-byte
 // body / scalar tail, with the head computed per image (gt and pred of an image share their offset, so their misalignments differ by
 // what the two base pointers differ).  tab == nullptr: uniform images of per_image pixels; else image b = [loff_b, loff_{b+1}).
+// BAND (nc * nc > GUARD_CONF_MAXBINS): blockIdx.z selects a band of GUARD_CONF_MAXBINS / nc ground-truth rows, as in confusion_kernel<true>.
 #define GUARD_CONF_MAXBINS 8192
+#define GUARD_CONF_MAXNC 256
+// (a macro: as a function the narrow kernel's byte-select operands come out as separate instructions)
+#define GUARD_CONF_COUNT(g, p)                                                              \
+    do {                                                                              \
+        if (BAND) {                                                                   \
+            const unsigned int gr_ = (unsigned int)((g) - r0);                        \
+            if (gr_ < (unsigned int)rows && (p) < nc) atomicAdd(&lh[gr_ * nc + (p)], 1u); \
+        } else {                                                                      \
+            if ((g) < nc && (p) < nc) atomicAdd(&lh[(g) * nc + (p)], 1u);             \
+        }                                                                             \
+    } while (0)
+template <bool BAND>
 __global__ __launch_bounds__(256) void confusion_masked_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ pred,
                                                                const int* __restrict__ tab, long long per_image,
                                                                const int* __restrict__ skip, int nc, unsigned long long* __restrict__ hist) {
@@ -73,14 +86,16 @@ __global__ __launch_bounds__(256) void confusion_masked_kernel(const unsigned ch
     }
     if (blockIdx.x > 0 && (long long)blockIdx.x * 256 * 16 >= n) return;     // more chunks than this image has
     gt += start; pred += start;
-    const int bins = nc * nc;
+    const int band_rows = BAND ? GUARD_CONF_MAXBINS / nc : nc;
+    const int r0 = BAND ? (int)blockIdx.z * band_rows : 0, rows = BAND ? min(band_rows, nc - r0) : nc;
+    const int bins = rows * nc;
     for (int i = threadIdx.x; i < bins; i += 256) lh[i] = 0;
     __syncthreads();
     const int mg = (int)((16 - ((uintptr_t)gt & 15)) & 15), mp = (int)((16 - ((uintptr_t)pred & 15)) & 15);
     const int head = (mg == mp) ? mg : -1;
     if (head > 0 && blockIdx.x == 0 && threadIdx.x < head && threadIdx.x < n) {
         const int g = gt[threadIdx.x], p = pred[threadIdx.x];
-        if (g < nc && p < nc) atomicAdd(&lh[g * nc + p], 1u);
+        GUARD_CONF_COUNT(g, p);
     }
     if (head >= 0) {
         gt += head; pred += head; n -= head;
@@ -95,19 +110,19 @@ __global__ __launch_bounds__(256) void confusion_masked_kernel(const unsigned ch
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int g = (gw[k >> 2] >> (8 * (k & 3))) & 255, p = (pw[k >> 2] >> (8 * (k & 3))) & 255;
-                if (g < nc && p < nc) atomicAdd(&lh[g * nc + p], 1u);
+                GUARD_CONF_COUNT(g, p);
             }
         } else {
             const long long end = (base + 16 < n) ? base + 16 : n;
             for (long long j = base; j < end; ++j) {
                 const int g = gt[j], p = pred[j];
-                if (g < nc && p < nc) atomicAdd(&lh[g * nc + p], 1u);
+                GUARD_CONF_COUNT(g, p);
             }
         }
     }
     __syncthreads();
     for (int i = threadIdx.x; i < bins; i += 256)
-        if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
+        if (lh[i]) atomicAdd(&hist[(BAND ? r0 * nc : 0) + i], (unsigned long long)lh[i]);
 }
 
 extern "C" int excel_nonfinite_count(const float* x, int B, long long per_image, int32_t* count, int init, void* stream) {
@@ -138,8 +153,8 @@ extern "C" int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_
                                                  void* stream) {
     EXCEL_CHECK_ARG(gt && pred && skip && hist, "confusion_accumulate_masked: null argument");
     EXCEL_CHECK_ARG(B >= 1 && B <= 65535, "confusion_accumulate_masked: need 1 <= B <= 65535 (B = %d)", B);
-    EXCEL_CHECK_ARG(num_classes >= 1 && num_classes * num_classes <= GUARD_CONF_MAXBINS, "confusion_accumulate_masked: num_classes %d too large",
-                    num_classes);
+    EXCEL_CHECK_ARG(num_classes >= 1 && num_classes <= GUARD_CONF_MAXNC, "confusion_accumulate_masked: need 1 <= num_classes <= %d (got %d)",
+                    GUARD_CONF_MAXNC, num_classes);
     long long max_pix;
     if (table) {
         EXCEL_CHECK_ARG(info && info->B == B, "confusion_accumulate_masked: the plan holds %d images, B = %d", info ? info->B : -1, B);
@@ -154,8 +169,12 @@ extern "C" int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_
     const long long want = cdivl(max_pix, 256 * 16);
     const long long cap = 2048 / B > 1 ? 2048 / B : 1;        // confusion_kernel's bound on the workgroups that flush a histogram
     const unsigned chunks = (unsigned)(want < cap ? (want > 0 ? want : 1) : cap);
-    hipLaunchKernelGGL(confusion_masked_kernel, dim3(chunks, B), dim3(256), 0, st, gt, pred, table, per_image, skip, num_classes,
-                       (unsigned long long*)hist);
+    if (num_classes * num_classes <= GUARD_CONF_MAXBINS)
+        hipLaunchKernelGGL(confusion_masked_kernel<false>, dim3(chunks, B), dim3(256), 0, st, gt, pred, table, per_image, skip, num_classes,
+                           (unsigned long long*)hist);
+    else
+        hipLaunchKernelGGL(confusion_masked_kernel<true>, dim3(chunks, B, (unsigned)cdivl(num_classes, GUARD_CONF_MAXBINS / num_classes)), dim3(256),
+                           0, st, gt, pred, table, per_image, skip, num_classes, (unsigned long long*)hist);
     EXCEL_CHECK_LAUNCH("confusion_accumulate_masked");
     return EXCEL_OK;
 }

@@ -644,17 +644,35 @@ __global__ __launch_bounds__(256) void argmax_label_ragged_kernel(const float* _
 }
 
 #define CONF_MAXBINS 8192
+#define CONF_MAXNC 256
+// BAND (nc * nc > CONF_MAXBINS): the histogram does not fit one workgroup's LDS, so blockIdx.y selects a band of CONF_MAXBINS / nc
+// ground-truth rows; a workgroup reads the same pixels as its twins of the other bands and counts those whose gt lies in its own.
+// Every pixel is counted by exactly one band, in 32-bit LDS counters a workgroup's share of the pixels cannot wrap (its stride loop
+// covers n / gridDim.x pixels: 2^32 of them would need n > 2^43), so the counts stay integer-exact.
+// (a macro: as a function the narrow kernel's byte-select operands come out as separate instructions)
+#define CONF_COUNT(g, p)                                                              \
+    do {                                                                              \
+        if (BAND) {                                                                   \
+            const unsigned int gr_ = (unsigned int)((g) - r0);                        \
+            if (gr_ < (unsigned int)rows && (p) < nc) atomicAdd(&lh[gr_ * nc + (p)], 1u); \
+        } else {                                                                      \
+            if ((g) < nc && (p) < nc) atomicAdd(&lh[(g) * nc + (p)], 1u);             \
+        }                                                                             \
+    } while (0)
+template <bool BAND>
 __global__ __launch_bounds__(256) void confusion_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ pred,
                                                         long long n, int nc, unsigned long long* __restrict__ hist, int head) {
     __shared__ unsigned int lh[CONF_MAXBINS];
-    const int bins = nc * nc;
+    const int band_rows = BAND ? CONF_MAXBINS / nc : nc;
+    const int r0 = BAND ? (int)blockIdx.y * band_rows : 0, rows = BAND ? min(band_rows, nc - r0) : nc;
+    const int bins = rows * nc;
     for (int i = threadIdx.x; i < bins; i += 256) lh[i] = 0;
     __syncthreads();
     // gt / pred slices of a larger tensor need not be 16-byte aligned: when both share the same misalignment a scalar head brings
     // them to a 16-byte boundary, otherwise (`head` < 0) the whole range goes through the scalar path
     if (head > 0 && blockIdx.x == 0 && threadIdx.x < head && threadIdx.x < n) {
         const int g = gt[threadIdx.x], p = pred[threadIdx.x];
-        if (g < nc && p < nc) atomicAdd(&lh[g * nc + p], 1u);
+        CONF_COUNT(g, p);
     }
     if (head >= 0) {
         gt += head; pred += head; n -= head;
@@ -669,19 +687,19 @@ __global__ __launch_bounds__(256) void confusion_kernel(const unsigned char* __r
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int g = (gw[k >> 2] >> (8 * (k & 3))) & 255, p = (pw[k >> 2] >> (8 * (k & 3))) & 255;
-                if (g < nc && p < nc) atomicAdd(&lh[g * nc + p], 1u);
+                CONF_COUNT(g, p);
             }
         } else {
             const long long end = (base + 16 < n) ? base + 16 : n;
             for (long long j = base; j < end; ++j) {
                 const int g = gt[j], p = pred[j];
-                if (g < nc && p < nc) atomicAdd(&lh[g * nc + p], 1u);
+                CONF_COUNT(g, p);
             }
         }
     }
     __syncthreads();
     for (int i = threadIdx.x; i < bins; i += 256)
-        if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
+        if (lh[i]) atomicAdd(&hist[(BAND ? r0 * nc : 0) + i], (unsigned long long)lh[i]);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -838,12 +856,16 @@ int excel_launch_argmax_label_ragged(const float* cams, const int* nchan, const 
 int excel_launch_confusion(const unsigned char* gt, const unsigned char* pred, long long n, int nc, unsigned long long* hist,
                            hipStream_t st) {
     ProfScope prof__(PROF_CONFUSION, st);
-    EXCEL_CHECK_ARG(nc >= 1 && nc * nc <= CONF_MAXBINS, "confusion: num_classes %d too large", nc);
+    EXCEL_CHECK_ARG(nc >= 1 && nc <= CONF_MAXNC, "confusion: need 1 <= num_classes <= %d (got %d)", CONF_MAXNC, nc);
     // scalar elements in front of the first 16-byte boundary (same for both pointers), or -1: no common alignment -> scalar path
     const int mg = (int)((16 - ((uintptr_t)gt & 15)) & 15), mp = (int)((16 - ((uintptr_t)pred & 15)) & 15);
     const int head = (mg == mp) ? mg : -1;
     const int blocks = (int)((cdivl(n, 256 * 16) < 2048) ? cdivl(n, 256 * 16) : 2048);
-    hipLaunchKernelGGL(confusion_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, gt, pred, n, nc, hist, head);
+    if (nc * nc <= CONF_MAXBINS)
+        hipLaunchKernelGGL(confusion_kernel<false>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, gt, pred, n, nc, hist, head);
+    else
+        hipLaunchKernelGGL(confusion_kernel<true>, dim3(blocks > 0 ? blocks : 1, cdiv(nc, CONF_MAXBINS / nc)), dim3(256), 0, st, gt, pred, n, nc,
+                           hist, head);
     EXCEL_CHECK_LAUNCH("confusion");
     return EXCEL_OK;
 }

@@ -15,11 +15,21 @@ class ExCEL_model:
     def __init__(self, clip_model=None, embedding_dim=256, in_channels=512, dataset_name="pascal_voc",
                  num_classes=21, num_atrr_clusters=112, json_file=None, img_size=320, mode="train", device="cuda",
                  state_dict=None, text_features=None, attr_bank=None, vit_cfg=None, text_attr=None, gemm_mode=None,
-                 decoder_state_dict=None, decoder_heads=8, class_names=None, tokenizer=None):
+                 decoder_state_dict=None, decoder_heads=8, class_names=None, tokenizer=None, bkg_names=None):
         """Extra keyword arguments (no network here): `state_dict` = CLIP visual weights, `text_features` [T,512] =
         output of encode_text_with_prompt_ensemble (clip/clip.py:252-269, one-time, out of scope),
         `attr_bank` [512,K] overrides the bank file, `vit_cfg` overrides the ViT-B/16 shape, `gemm_mode` = "bf16x3"
-        (default) | "f32" selects the matrix-core numerics."""
+        (default) | "f32" selects the matrix-core numerics.
+        `class_names` = the prompt list of a vocabulary of the caller's own: with `bkg_names` None it holds the foreground names
+        followed by the background names (as before); with `bkg_names` given it holds the foreground names alone, the prompts are
+        class_names + bkg_names and num_classes must be len(class_names) + 1.  Up to 254 foreground names, up to 512 prompts."""
+        if bkg_names is not None:
+            if class_names is None:
+                raise ValueError("bkg_names needs class_names (the foreground names)")
+            if num_classes != len(class_names) + 1:
+                raise ValueError(f"num_classes = {num_classes} contradicts the {len(class_names)} foreground class_names "
+                                 f"(+ background = {len(class_names) + 1})")
+            class_names = list(class_names) + list(bkg_names)
         self.num_classes = num_classes
         self.embedding_dim = embedding_dim
         self.in_channels = in_channels

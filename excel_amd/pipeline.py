@@ -103,6 +103,17 @@ class GuardTicket:
         return self._host.numpy()
 
 
+MAX_NUM_CLASSES = 255      # background + 254 foreground classes
+
+
+def check_num_classes(num_classes):
+    """The label maps are uint8 with 255 as the ignore value, and a present class c is written as the key c + 1: the largest
+    vocabulary is 254 foreground classes plus background."""
+    if not 1 <= int(num_classes) <= MAX_NUM_CLASSES:
+        raise ValueError(f"num_classes = {num_classes}: the label maps are uint8 with 255 as the ignore value, so at most "
+                         f"{MAX_NUM_CLASSES} classes (254 foreground + background) fit")
+
+
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
                  tta_scales=None, tta_flip=False):
@@ -130,6 +141,7 @@ class TrainingFreePipeline:
         if self.tta:
             _check_tta_scales(self.tta_scales)
         self.model = model
+        check_num_classes(num_classes)
         self.num_classes = num_classes
         self.dilations = tuple(dilations)
         self.num_iter = num_iter
@@ -480,6 +492,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
                  tta_scales=None, tta_flip=False):
+        check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         if getattr(model, "_dec", None) is None:
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
@@ -547,6 +560,7 @@ class ValidationPipeline(TrainingFreePipeline):
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
                  tta_scales=None, tta_flip=False):
+        check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         if getattr(model, "_dec", None) is None:
             raise ValueError("ValidationPipeline needs the decoder head: build ExCEL_model(..., decoder_state_dict=)")

@@ -29,7 +29,8 @@ def get_parser():
     p.add_argument("--list_folder", required=True, type=str, help="directory with <infer_set>.txt")
     p.add_argument("--infer_set", default="train_aug", type=str)
     p.add_argument("--dataset_name", default="pascal_voc", choices=["pascal_voc", "ms_coco"])
-    p.add_argument("--num_classes", default=None, type=int, help="default: 21 (pascal_voc) / 81 (ms_coco)")
+    p.add_argument("--num_classes", default=None, type=int, help="default: 21 (pascal_voc) / 81 (ms_coco), or the lines of --class_names + 1; at most 256")
+    p.add_argument("--class_names", default=None, type=str, help="one foreground class name per line: the rows of the table (infer_lam --class_names)")
     p.add_argument("--num_workers", default=8, type=int, help="PNG decode threads")
     p.add_argument("--batch_size", default=64, type=int, help="images decoded per device accumulation")
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
@@ -69,7 +70,15 @@ def validate(args):
     """-> {"score": scores_from_hist of the gathered matrix, "hist": [nc,nc] int64 (CPU tensor), "images": scored on this rank,
     "seconds"}: the layout of infer_seg_voc.validate."""
     from ..utils import evaluate
-    nc = args.num_classes or (81 if "coco" in args.dataset_name else 21)
+    names_fg = None
+    if getattr(args, "class_names", None):
+        from .infer_lam import _read_names
+        names_fg = _read_names(args.class_names, "--class_names")
+        if args.num_classes and args.num_classes != len(names_fg) + 1:
+            raise ValueError(f"--num_classes {args.num_classes} contradicts --class_names: {len(names_fg)} names + background")
+    nc = args.num_classes or (len(names_fg) + 1 if names_fg else (81 if "coco" in args.dataset_name else 21))
+    if not 1 <= nc <= 256:
+        raise ValueError(f"--num_classes {nc}: uint8 label maps hold at most 256 classes")
     world, rank = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0))
     on_gpu = torch.cuda.is_available()
     device = torch.device("cuda", args.local_rank) if on_gpu else torch.device("cpu")
@@ -101,6 +110,8 @@ def validate(args):
         if "coco" in args.dataset_name:
             from ..datasets import coco
             cats = coco.class_list
+        if names_fg:
+            cats = [VOC_CLASSES[0]] + names_fg
         logging.info(f"label_score of {args.pred_dir}:")
         logging.info("\n" + format_scores_table(score, cats))
         logging.info(f"mIoU {score['miou'] * 100:.3f}  images {len(names)}  ({len(mine) / max(secs, 1e-9):.1f} img/s/rank)")

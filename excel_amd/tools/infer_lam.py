@@ -132,6 +132,91 @@ def _handle_gemm_mode(model):
         return None
 
 
+class _StoreGiven(argparse.Action):
+    """store, and note in <dest>_given that the flag was on the command line (a default cannot contradict a vocabulary file)"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
+MAX_FG_CLASSES = 254       # uint8 label maps: keys 1..254, 0 = background, 255 = ignore
+MAX_TEXT_ROWS = 512        # excel_patch_text_cam
+
+
+def _read_names(path, what):
+    with open(path) as f:
+        names = [x.strip() for x in f.read().split("\n")]
+    while names and not names[-1]:
+        names.pop()                                                                         # trailing newline(s)
+    if not names:
+        raise ValueError(f"{what} {path}: no names")
+    for i, n in enumerate(names):
+        if not n:
+            raise ValueError(f"{what} {path}: line {i + 1} is empty")
+    seen = {}
+    for i, n in enumerate(names):
+        if n in seen:
+            raise ValueError(f"{what} {path}: {n!r} appears on lines {seen[n] + 1} and {i + 1}")
+        seen[n] = i
+    return names
+
+
+def load_attr_bank(path):
+    """--attr_bank: the reference's torch-saved pair [bank [C,K], flag] or an .npz with `bank` (and `flag`) -> bank [C,K] float32 tensor"""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"--attr_bank {path}: no such file")
+    if path.endswith(".npz"):
+        z = np.load(path)
+        if "bank" not in z:
+            raise ValueError(f"--attr_bank {path}: no array named `bank`")
+        bank = torch.from_numpy(np.asarray(z["bank"], np.float32))
+    else:
+        obj = torch.load(path, map_location="cpu")
+        bank = torch.as_tensor(obj[0] if isinstance(obj, (list, tuple)) else obj).float()
+    if bank.ndim != 2:
+        raise ValueError(f"--attr_bank {path}: the bank must be [C,K], got {tuple(bank.shape)}")
+    return bank
+
+
+def resolve_vocabulary(args):
+    """--class_names / --bkg_names / --attr_bank -> args.vocab = {"fg", "bkg", "bank"} (None entries where not given), args.num_classes
+    settled.  Runs before any model is built and refuses: duplicate or empty names, more than 254 foreground classes, more than 512
+    prompts, a --num_classes that contradicts the file, num_classes > 255, and real data (--data_folder) with --class_names but no
+    --attr_bank - a vocabulary is never silently paired with another data set's bank."""
+    from ..pipeline import check_num_classes
+    fg = bkg = bank = None
+    path = getattr(args, "class_names", None)
+    if path:
+        fg = _read_names(path, "--class_names")
+        if len(fg) > MAX_FG_CLASSES:
+            raise ValueError(f"--class_names {path}: {len(fg)} foreground classes; the uint8 label maps hold at most {MAX_FG_CLASSES} "
+                             "(keys 1..254, 255 = ignore)")
+        if getattr(args, "num_classes_given", False) and args.num_classes != len(fg) + 1:
+            raise ValueError(f"--num_classes {args.num_classes} contradicts --class_names {path}: {len(fg)} names + background = {len(fg) + 1}")
+        args.num_classes = len(fg) + 1
+        if getattr(args, "bkg_names", None):
+            bkg = _read_names(args.bkg_names, "--bkg_names")
+        else:
+            from ..datasets.clip_text import BACKGROUND_CATEGORY
+            bkg = list(BACKGROUND_CATEGORY)
+        both = set(fg) & set(bkg)
+        if both:
+            raise ValueError(f"--class_names / --bkg_names: {sorted(both)[0]!r} is in both lists")
+        if len(fg) + len(bkg) > MAX_TEXT_ROWS:
+            raise ValueError(f"{len(fg)} class names + {len(bkg)} background names = {len(fg) + len(bkg)} prompts; the CAM kernel takes at most "
+                             f"{MAX_TEXT_ROWS}")
+    elif getattr(args, "bkg_names", None):
+        raise ValueError("--bkg_names needs --class_names")
+    check_num_classes(args.num_classes)
+    if getattr(args, "attr_bank", None):
+        bank = load_attr_bank(args.attr_bank)
+    elif fg is not None and getattr(args, "data_folder", None):
+        raise ValueError("--data_folder with --class_names needs --attr_bank: the shipped banks belong to the VOC and COCO vocabularies")
+    args.vocab = {"fg": fg, "bkg": bkg, "bank": bank}
+    return args.vocab
+
+
 def get_parser():
     p = argparse.ArgumentParser()
     # flags kept from the reference (tools/infer_lam.py:30-60)
@@ -169,7 +254,14 @@ def get_parser():
                    help="with --crf_post: run the DenseCRF stage inside the main loop on the step's cams (no logits records, no crf_proc pass)")
     p.add_argument("--crf_ws_gb", default=16.0, type=float, help="--crf_inline: workspace budget of the DenseCRF stage in GiB; a batch is cut into groups that fit")
     p.add_argument("--crf_label_dir", default=None, type=str, help="--crf_inline: write the CRF labels as palette PNGs <dir>/<name>.png (device encoder)")
-    p.add_argument("--num_classes", default=21, type=int)
+    p.add_argument("--num_classes", default=21, type=int, action=_StoreGiven,
+                   help="default: 21, or with --class_names its lines + 1 (a contradicting value is refused)")
+    p.add_argument("--class_names", default=None, type=str,
+                   help="a vocabulary of your own: text file with one FOREGROUND class name per line (up to 254); prompts, score tables, "
+                        "overlay names follow it.  With --data_folder it needs --attr_bank")
+    p.add_argument("--bkg_names", default=None, type=str, help="with --class_names: one background prompt per line (default: the VOC background list)")
+    p.add_argument("--attr_bank", default=None, type=str,
+                   help="attribute bank file: the reference's .pth pair [bank, flag] or this package's .npz with `bank` [C,K] and `flag`")
     p.add_argument("--ignore_index", default=255, type=int)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
@@ -251,7 +343,10 @@ def default_cam_writers(local_world=1):
 
 
 def class_names(args):
-    """The data set's own class list (index 0 = background)."""
+    """The data set's own class list (index 0 = background); with --class_names, the file's."""
+    vocab = getattr(args, "vocab", None)
+    if vocab and vocab.get("fg"):
+        return [VOC_CLASSES[0]] + list(vocab["fg"])
     if "coco" in args.dataset_name:
         from ..datasets import coco
         return coco.class_list
@@ -299,7 +394,7 @@ class _CamSaver:
     def _items(self, name, present, H, W, off):
         if not self.per_class:
             return [(os.path.join(self.dir, name + ".jpg"), int(off), H, W)] if len(present) else []
-        return [(os.path.join(self.dir, f"{name}_{self.names[int(c) + 1]}.jpg"), int(off) + 3 * j * H * W, H, W) for j, c in enumerate(present)]
+        return [(os.path.join(self.dir, f"{name}_{self.names[int(c) + 1].replace('/', '_')}.jpg"), int(off) + 3 * j * H * W, H, W) for j, c in enumerate(present)]
 
     def ragged(self, names, plan, images, cams, Cmax, cls_host):
         from .. import ops
@@ -888,7 +983,8 @@ def resolve_model_inputs(args):
                            "the published archive (ViT-B-16.pt) under --clip_root / $EXCEL_CLIP_ROOT / ~/.cache/clip. "
                            "Refusing to score real data with random weights.")
     else:
-        T = 45 if args.num_classes <= 21 else 103
+        vocab = getattr(args, "vocab", None) or {}
+        T = synthetic.text_rows(args.num_classes, len(vocab["bkg"]) if vocab.get("bkg") else None, custom=bool(vocab.get("fg")))
         kw["state_dict"] = synthetic.make_vit_state_dict(seed=0)
         kw["text_features"] = synthetic.make_text_features(T)
         logging.warning("SYNTHETIC run: seeded random ViT-B/16 weights and random text features (no CLIP checkpoint resolved); "
@@ -1000,6 +1096,7 @@ def validate(args=None, dataset=None, pipe=None):
     rank = int(os.environ.get("RANK", 0))
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     resolve_conf(args)                                                                       # ... and a bad pair of thresholds
+    vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
     if pipe is None:
         torch.cuda.set_device(args.local_rank)
         device = torch.device("cuda", args.local_rank)
@@ -1040,7 +1137,8 @@ def validate(args=None, dataset=None, pipe=None):
         model = ExCEL_model(clip_model=args.model, embedding_dim=args.embedding_dim, in_channels=args.in_channels,
                             dataset_name=args.dataset_name, num_classes=args.num_classes, num_atrr_clusters=args.num_attri,
                             json_file=args.attr_json, img_size=args.resize_size, mode=args.infer_set, device=device,
-                            gemm_mode=getattr(args, "gemm_mode", None), **resolve_model_inputs(args))
+                            gemm_mode=getattr(args, "gemm_mode", None), class_names=vocab["fg"], bkg_names=vocab["bkg"],
+                            attr_bank=vocab["bank"], **resolve_model_inputs(args))
     # everything built so far (torch, the weights, the data set index) lives for the whole run: move it out of the cyclic collector's
     # reach, or every full collection walks it again - 40-70 ms of host time each (measured in bench.py, where one landed in a timed step)
     import gc
@@ -1060,6 +1158,9 @@ def validate(args=None, dataset=None, pipe=None):
     if "voc" not in args.dataset_name:
         from ..datasets import coco
         cat_list = coco.class_list
+    if vocab["fg"]:
+        cat_list = class_names(args)
+    validate.last_cat_list = cat_list
     if rank == 0:
         logging.info(f"Training_free:{args.training_free}, LAM_score:")
         logging.info("\n" + format_scores_table(score, cat_list))

@@ -48,6 +48,21 @@ def make_vit_state_dict(cfg=None, seed=0, attn_gain=2.0):
     return w
 
 
+def text_rows(num_classes, n_bkg=None, custom=False):
+    """Text rows T of a synthetic run.  The two shipped vocabularies keep their rows and therefore their bits: 45 (VOC: 20 + 25) for 21
+    classes - and, as before, for the smaller counts of the tiny training runs - and 103 (COCO: 80 + 23) for 81.  Any other count, and
+    every vocabulary given by name (`custom`), gets its (num_classes - 1) foreground rows + n_bkg background rows (default: the
+    VOC background list)."""
+    if not custom and num_classes <= 21:
+        return 45
+    if not custom and num_classes == 81:
+        return 103
+    if n_bkg is None:
+        from ..datasets.clip_text import BACKGROUND_CATEGORY
+        n_bkg = len(BACKGROUND_CATEGORY)
+    return (num_classes - 1) + n_bkg
+
+
 def make_text_features(T=45, C=512, seed=7):
     rs = np.random.RandomState(seed)
     t = rs.standard_normal((T, C)).astype(np.float32)

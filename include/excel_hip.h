@@ -308,7 +308,8 @@ int excel_seg_scale_accumulate(const float* segs, float* acc, int B, int nc, int
 
 /* clip_feature_surgery (clip/clip.py:288-310, redundant_feats=None) on normalised features:
  *   image_features [B,N,C], text [T,C] (unit rows) -> out_full [B,N,T] and/or the caller's slice
- *   out_slice [B,N-1,F] = out_full[:, 1:, :F] (model/model_excel.py:58).  workspace: B*N*ldT floats, ldT = T rounded up to 4. */
+ *   out_slice [B,N-1,F] = out_full[:, 1:, :F] (model/model_excel.py:58).  workspace: B*N*ldT floats, ldT = T rounded up to 4.
+ * 1 <= F <= T <= 512 (above 128 rows a kernel with eight class columns per lane takes over; up to 128 nothing changes). */
 size_t excel_cam_workspace_bytes(int B, int N, int T);
 int excel_clip_feature_surgery(const float* image_features, const float* text, int B, int N, int C, int T, int F,
                                float temperature, float* out_full, float* out_slice, void* workspace, void* stream);
@@ -320,7 +321,10 @@ int excel_clip_feature_surgery(const float* image_features, const float* text, i
  * normalisation over a two-stage (exact) min / max reduction.
  *   mode 1: bf16x3 (fp32 operands as bf16 hi+lo, 3 MFMAs per product), mode 2: f16x3 (IEEE-half planes), mode 0: exact fp32 MFMA.
  *   image_features [B,N,C] (optional): the normalised features generate_clip_fts returns.
- * T <= 128, C % 32 == 0, C <= 1024; x_raw, text, image_features and the workspace 16-byte aligned. */
+ * 1 <= F <= T <= 512, C % 32 == 0, C <= 1024; x_raw, text, image_features and the workspace 16-byte aligned.  Up to 128 text rows all
+ * classes of a token tile sit in the accumulators at once; above, the similarity kernel walks the class axis in chunks of 128 rows and
+ * takes the redundancy term from f . ((1/T) sum_t w[t] text[t]) (the same sum, associated the other way), so a chunk is complete in
+ * itself.  An image's maps do not depend on its place in the batch on either path. */
 size_t excel_patch_text_cam_workspace_bytes(int B, int N, int C, int T);
 int excel_patch_text_cam(const float* x_raw, const float* text, int B, int N, int C, int T, int F, float temperature, int mode,
                          float* out_full, float* out_slice, float* image_features, void* workspace, void* stream);
@@ -404,7 +408,10 @@ int excel_par_forward(const float* imgs, int h, int w, const float* masks, const
 int excel_argmax_label(const float* cams, const int32_t* nchan, const int32_t* cls_idx, int B, int Smax, int Cmax,
                        long long HW, uint8_t* labels_u8, int64_t* labels_i64, void* stream);
 
-/* _fast_hist accumulated on device (utils/evaluate.py:9-20): hist[nc*gt+pred] += 1 for gt < nc; hist is int64 [nc*nc]. */
+/* _fast_hist accumulated on device (utils/evaluate.py:9-20): hist[nc*gt+pred] += 1 for gt < nc; hist is int64 [nc*nc].
+ * 1 <= num_classes <= 256 (at 256 the label 255 is a class like any other).  Up to 90 classes (nc*nc <= 8192) a workgroup keeps the whole
+ * histogram in LDS; above, the same launch runs one set of workgroups per band of 8192 / nc ground-truth rows, each reading all pixels
+ * (2 bytes per pixel and band) and counting those of its band.  Integer-exact either way. */
 int excel_confusion_accumulate(const uint8_t* gt, const uint8_t* pred, long long n, int num_classes, int64_t* hist, void* stream);
 
 /* ------------------------------------------------------------------ ragged batches: B images of DIFFERENT label sizes in one launch
@@ -441,7 +448,7 @@ int excel_nonfinite_count(const float* x, int B, long long per_image, int32_t* c
 /* excel_confusion_accumulate restricted to the images with skip[b] == 0 (skip: e.g. the counts above).  table == NULL: B uniform images
  * of per_image pixels each (info unused); otherwise the tight label maps of the ragged plan (image b at loff_b; per_image ignored,
  * info->B == B).  Integer counts: with nothing skipped the result equals excel_confusion_accumulate over the whole array bit for bit,
- * otherwise excel_confusion_accumulate over the concatenation of the kept images. */
+ * otherwise excel_confusion_accumulate over the concatenation of the kept images.  1 <= num_classes <= 256, banded above 90 likewise. */
 int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_t* pred, int B, long long per_image, const int32_t* table,
                                       const excel_ragged_info* info, const int32_t* skip /*device [B]*/, int num_classes, int64_t* hist,
                                       void* stream);
