@@ -113,25 +113,42 @@ def epoch_shard(n, epoch, rank, world, seed=0):
     return perm[rank::world]
 
 
-def train_batches(dataset, batch_size, rank=0, world=1, seed=0, start_epoch=0, num_threads=8, ahead=3):
+def batches_per_epoch(n, world, batch_size):
+    """Full batches one rank serves per epoch: epoch_shard's cut to a multiple of `world`, then drop_last.  ValueError when there is none."""
+    nb = ((n - n % world) // world) // batch_size
+    if nb == 0:
+        raise ValueError(f"{n} samples over {world} ranks give no full batch of {batch_size}")
+    return nb
+
+
+def resume_position(step, n, world, batch_size):
+    """Where train_batches stands after `step` batches from (epoch 0, batch 0) -> (epoch, batch): the start_epoch / start_batch that
+    continue a run of `step` iterations over `n` samples.  The same on every rank."""
+    nb = batches_per_epoch(n, world, batch_size)
+    return int(step) // nb, int(step) % nb
+
+
+def train_batches(dataset, batch_size, rank=0, world=1, seed=0, start_epoch=0, num_threads=8, ahead=3, start_batch=0):
     """Endless iterator of training RaggedBatches (with `params`) over epochs start_epoch, start_epoch + 1, ...: each epoch is shuffled
     and sharded by epoch_shard, cut into `batch_size` batches with the last partial batch dropped (the reference's DataLoader
     drop_last=True), decoded by a thread pool (see threaded_batches).  `dataset.sample(idx, epoch)` -> (name, image, label, cls, params)
-    (datasets/voc.VOC12ClsDataset; label None: datasets/coco.CocoClsDataset, the batches then carry labels = None)."""
+    (datasets/voc.VOC12ClsDataset; label None: datasets/coco.CocoClsDataset, the batches then carry labels = None).
+    `start_batch`: epoch start_epoch begins at its batch start_batch (later epochs at batch 0); the batches before it are never handed to
+    the decode threads.  start_batch at or beyond the batches per epoch is a ValueError (see resume_position)."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     n = len(dataset)
 
     def chunks():
-        epoch = start_epoch
+        epoch, first = start_epoch, int(start_batch)
         while True:
             idx = epoch_shard(n, epoch, rank, world, seed)
-            nb = len(idx) // batch_size
-            if nb == 0:
-                raise ValueError(f"{n} samples over {world} ranks give no full batch of {batch_size}")
-            for i in range(nb):
+            nb = batches_per_epoch(n, world, batch_size)
+            if not 0 <= first < nb:
+                raise ValueError(f"start_batch = {first}: an epoch has {nb} batches of {batch_size} ({n} samples over {world} ranks)")
+            for i in range(first, nb):
                 yield epoch, idx[i * batch_size:(i + 1) * batch_size]
-            epoch += 1
+            epoch, first = epoch + 1, 0
 
     with ThreadPoolExecutor(max_workers=max(1, num_threads), thread_name_prefix="excel_decode") as pool:
         pending = deque()

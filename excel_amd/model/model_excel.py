@@ -86,6 +86,19 @@ class ExCEL_model:
         out.update({"decoder." + k: v for k, v in dec.items()})
         return out
 
+    def load_decoder_state_dict(self, sd):
+        """state_dict()'s inverse: head weights keyed "decoder_fts_fuse.*" / "decoder.*" go into the head this model was built with, in
+        place (ops.DecoderHandle.load_weights: no device tensor moves; ValueError naming a missing key or one of another shape, before
+        anything is copied).  The weight holders (decoder_fts_fuse, decoder) get the same dictionaries."""
+        if self._dec is None:
+            raise RuntimeError("load_decoder_state_dict needs the decoder head: build ExCEL_model with decoder_state_dict=")
+        fuse_sd = {k[len("decoder_fts_fuse."):]: v for k, v in sd.items() if k.startswith("decoder_fts_fuse.")}
+        dec_sd = {k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}
+        self._dec.load_weights(fuse_sd, dec_sd)
+        self.decoder_fts_fuse.load_state_dict(fuse_sd)
+        self.decoder.load_state_dict(dec_sd)
+        return self
+
     def to(self, *a, **k):
         return self
 

@@ -337,6 +337,76 @@ class DecoderHandle:
         dec["linear_pred.bias"] = self.t["pred_b"].detach().clone()
         return fuse, dec
 
+    def _ref_layout(self):
+        """{name in self.t: (0 = fuse_sd | 1 = dec_sd, the reference module's key, its shape there)}: state_dicts() read backwards."""
+        c = self.cfg
+        out = {}
+        for l in range(c["vit_layers"]):
+            for f, k in (("proj_w", "proj.weight"), ("proj_b", "proj.bias"), ("proj2_w", "proj_2.weight"), ("proj2_b", "proj_2.bias")):
+                out[f"fuse{l}.{f}"] = (0, f"linears_modulelist.{l}.{k}")
+        out["fuse_w"], out["fuse_b"] = (0, "linear_fuse.weight"), (0, "linear_fuse.bias")
+        for l in range(c["dec_layers"]):
+            for f, k in _BLOCK_KEYS.items():
+                out[f"blk{l}.{f}"] = (1, f"transformer.resblocks.{l}.{k}")
+        out["pred_w"], out["pred_b"] = (1, "linear_pred.weight"), (1, "linear_pred.bias")
+        return {n: (w, k, tuple(self.t[n].shape) + ((1, 1) if n in ("fuse_w", "pred_w") else ())) for n, (w, k) in out.items()}
+
+    def load_weights(self, fuse_sd, dec_sd):
+        """The inverse of state_dicts(): copies `fuse_sd` / `dec_sd` (the reference modules' keys and shapes, 1x1 conv weights as
+        [out,in,1,1]) into the EXISTING device tensors.  The C handle and the gradient table hold raw pointers into self.t, so nothing
+        is reallocated; everything is checked before the first byte is copied (ValueError naming the key: missing, or another shape)."""
+        sds = (fuse_sd, dec_sd)
+        layout = self._ref_layout()
+        for n, (w, k, shape) in layout.items():
+            if k not in sds[w]:
+                raise ValueError(f"DecoderHandle.load_weights: missing key {('decoder_fts_fuse.', 'decoder.')[w]}{k}")
+            got = tuple(torch.as_tensor(sds[w][k]).shape)
+            if got != shape:
+                raise ValueError(f"DecoderHandle.load_weights: {('decoder_fts_fuse.', 'decoder.')[w]}{k} has shape {got}, the head's is {shape}")
+        with torch.no_grad():
+            for n, (w, k, _) in layout.items():
+                self.t[n].copy_(torch.as_tensor(sds[w][k]).detach().to(torch.float32).reshape(self.t[n].shape))
+
+    def optimizer_state(self):
+        """AdamW's moments as CPU copies, {"exp_avg": {name: tensor}, "exp_avg_sq": {name: tensor}} keyed like self.t (torch.optim.AdamW's
+        names for the two buffers; its `step` is the caller's counter, see adamw_step).  None before the first adamw_step."""
+        if getattr(self, "_adam", None) is None:
+            return None
+        return {"exp_avg": {k: m.detach().cpu().clone() for k, (m, _) in self._adam.items()},
+                "exp_avg_sq": {k: v.detach().cpu().clone() for k, (_, v) in self._adam.items()}}
+
+    def check_optimizer_state(self, state):
+        """load_optimizer_state's refusals alone: ValueError naming the key on a missing or extra key, another shape or a dtype other
+        than float32."""
+        parts = ("exp_avg", "exp_avg_sq")
+        if not isinstance(state, dict) or set(state) != set(parts):
+            bad = sorted(set(parts) ^ set(state)) if isinstance(state, dict) else list(parts)
+            raise ValueError(f"DecoderHandle.load_optimizer_state: expected the keys {list(parts)}, missing or extra: {bad[0]}")
+        for part in parts:
+            for k in self.t:
+                if k not in state[part]:
+                    raise ValueError(f"DecoderHandle.load_optimizer_state: missing key {part}.{k}")
+            for k, v in state[part].items():
+                if k not in self.t:
+                    raise ValueError(f"DecoderHandle.load_optimizer_state: extra key {part}.{k}")
+                if not torch.is_tensor(v) or v.dtype != torch.float32:
+                    raise ValueError(f"DecoderHandle.load_optimizer_state: {part}.{k} is {getattr(v, 'dtype', type(v).__name__)}, "
+                                     "expected a torch.float32 tensor")
+                if tuple(v.shape) != tuple(self.t[k].shape):
+                    raise ValueError(f"DecoderHandle.load_optimizer_state: {part}.{k} has shape {tuple(v.shape)}, "
+                                     f"the parameter's is {tuple(self.t[k].shape)}")
+
+    def load_optimizer_state(self, state):
+        """What optimizer_state() returned -> the moments of the next adamw_step (created if no step ran yet).  Everything is checked
+        (check_optimizer_state) before anything is copied."""
+        self.check_optimizer_state(state)
+        if getattr(self, "_adam", None) is None:
+            self._adam = {k: (torch.zeros_like(v), torch.zeros_like(v)) for k, v in self.t.items()}
+        with torch.no_grad():
+            for k, (m, v) in self._adam.items():
+                m.copy_(state["exp_avg"][k])
+                v.copy_(state["exp_avg_sq"][k])
+
     # ------------------------------------------------------------------ training iteration (SURVEY 8f #4)
     def _grad_table(self):
         """Gradient tensors shaped like the parameters + the C table pointing at them (built once)."""

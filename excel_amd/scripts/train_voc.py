@@ -17,8 +17,33 @@ per-image loop, which --val_api_path true runs instead).  With --save_visual tru
 one launch (ops.train_panels) and writes them as <visual_dir>/iter_<N>/<panel>.png; train(tb_writer=...) hands the same grids to any
 object with add_image (utils/tbutils.py).  No TensorBoard event files are written.
 
+Stopping and continuing a run (the reference ships save_train / resume_train, utils/pyutils.py:114-181, without wiring them in; the
+state file's keys step / model_state_dict / optimizer_state_dict / lr are theirs, see utils/train_state.py):
+  --save_state_iters N   rank 0 writes <work_dir>/checkpoints/train_state_iter_<n>.pth after every N-th iteration: head weights, AdamW
+                         moments, the iteration count and the settings the continuation depends on.  Independent of --eval_iters,
+                         --save_ckpt and --save_ckpt_from; model_iter_<n>.pth files are written as without it.
+  --keep_states K        only the K newest state files stay (default 2)
+  --iters_per_run N      this process runs at most N iterations, writes the state at its last one (after that iteration's validation and
+                         checkpoint, if due) and returns: a run cut into job-sized pieces.  The stopping point is a function of the
+                         iteration count alone, so every rank stops at the same iteration.
+  --resume PATH|auto     continue from a state file; `auto`: the newest one under <work_dir>/checkpoints, from scratch when there is
+                         none - one command line serves the first job and every later one.
+Everything random in the loop is a function of (seed, iteration): the epoch's shuffle and each sample's augmentation draws
+(datasets/loader.epoch_shard, datasets/voc.py), the dropout seed, the learning rate and the lvc_iter / seg_aff_iter switches.  A resumed
+run therefore continues BIT FOR BIT: losses.txt, every model_iter_<n>.pth and the validation tables equal those of the uninterrupted
+run (tests/test_gpu_train_resume.py).  What must match between the pieces is the state's `run` dictionary (train_state.run_config: seed,
+number of ranks, --spg, size of the training list, crop size, schedule and loss settings, the variant's thresholds and switches); a
+difference is refused before anything is written.  What only reports or paces (eval_iters, log_iters, num_workers, val_batch_size, the
+visual flags) may differ.  On resume losses.txt is cut back to the state's iteration and appended to; the ETA of the log line is computed
+from the iterations done in this process and its running means restart at the resume point - neither is part of the exactness claim.
+The returned history / tables / ckpts / val_seconds cover this process's iterations only.
+Deliberately not built: (1) stopping on a signal or on wall-clock time - ranks would decide at different iterations and the first to stop
+leaves the others waiting in the gradient all-reduce, and a stop flag agreed by a collective every iteration would change the existing
+step; (2) loading torch-format optimizer state written by the reference's save_train; (3) resuming onto another number of ranks or
+another --spg - the data order depends on both, check_resume_compat refuses it.
+
   python -m excel_amd.scripts.train_voc --data_folder VOC2012 --list_folder datasets/voc --model ViT-B-16.pt --bpe_path ... \
-      [--crop_size 320 --spg 4 --max_iters 30000]
+      [--crop_size 320 --spg 4 --max_iters 30000] [--save_state_iters 2000 --iters_per_run 10000 --resume auto]
   python -m torch.distributed.run --nproc-per-node R -m excel_amd.scripts.train_voc ...       (R ranks, gradients all-reduced)
 """
 import argparse
@@ -72,6 +97,25 @@ class DecoderTrainer:
         self.seg_aff_iter, self.dropout_p, self.seed = seg_aff_iter, dropout_p, seed
         self.bkg_thre, self.high_thre, self.low_thre = bkg_thre, high_thre, low_thre       # lam_to_label of the pseu_mid panel (:211)
         self.global_step = 0
+
+    def state_dict(self):
+        """-> dict(global_step, model = the head's weights (model.state_dict(), CPU), optimizer = DecoderHandle.optimizer_state(), None
+        before the first step): with the trainer's settings, all the next train_step depends on."""
+        return dict(global_step=int(self.global_step), model={k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+                    optimizer=self.model._dec.optimizer_state())
+
+    def load_state_dict(self, state):
+        """state_dict()'s inverse, in place: head weights (ExCEL_model.load_decoder_state_dict), AdamW moments, global_step.  Refusals
+        (ValueError naming the key) come before anything is changed."""
+        dec = self.model._dec
+        if state["optimizer"] is not None:        # checked first: load_weights below already copies
+            dec.check_optimizer_state(state["optimizer"])
+        self.model.load_decoder_state_dict(state["model"])
+        if state["optimizer"] is None:
+            dec._adam = None
+        else:
+            dec.load_optimizer_state(state["optimizer"])
+        self.global_step = int(state["global_step"])
 
     @torch.no_grad()
     def pseudo_labels(self, inputs, cls_labels, attr_maps_raw, attn_weights, attn_pred, n_iter):
@@ -127,6 +171,9 @@ class DecoderTrainer:
         return dict(seg_loss=l[0], diver_loss=l[1], lr=lr, aff_pseudos=aff_pseudos, **visual)
 
 
+KEEP_STATES_DEFAULT = 2
+
+
 def get_parser():
     """scripts/train_voc.py:30-83 where the arguments apply, plus the model arguments of tools/infer_lam.py."""
     from ..tools.infer_lam import _bool
@@ -172,6 +219,16 @@ def get_parser():
     p.add_argument("--val_api_path", default=False, type=_bool,
                    help="validate with the reference's per-image loop (build_validation) on every rank instead of the batched pass split "
                         "across ranks (build_validation_ragged)")
+    # stopping and continuing (utils/train_state.py); all off by default
+    p.add_argument("--save_state_iters", default=0, type=int,
+                   help="rank 0 writes <work_dir>/checkpoints/train_state_iter_<n>.pth (weights, AdamW moments, iteration) after every "
+                        "N-th iteration; 0: never")
+    p.add_argument("--keep_states", default=KEEP_STATES_DEFAULT, type=int, help="state files kept; older ones are deleted after each write")
+    p.add_argument("--iters_per_run", default=0, type=int,
+                   help="stop after N iterations of this process and write the state there (continue with --resume); 0: no limit")
+    p.add_argument("--resume", default=None, type=str,
+                   help="a train_state_iter_<n>.pth to continue from, or `auto`: the newest under <work_dir>/checkpoints, from scratch "
+                        "when there is none")
     # model arguments of tools/infer_lam.py
     p.add_argument("--clip_root", default=None, type=str)
     p.add_argument("--bpe_path", default=None, type=str)
@@ -253,9 +310,12 @@ def train(args, model=None, variant=VOC, tb_writer=None):
     head (tests inject a small one); default: built from --model with the head at its initial weights.  `tb_writer`: any object with
     add_image(tag, chw_uint8, global_step=); rank 0 hands it the reference's six grids (:240-246) every --log_iters iterations.
     -> dict(history=[per-iteration losses], tables=[validation tables], ckpts=[paths], val_seconds=[wall seconds of each validation pass],
-    and with --save_visual true visuals=[directories written])."""
+    and with --save_visual true visuals=[directories written]), all of this process's iterations.  With any of --save_state_iters,
+    --keep_states, --iters_per_run, --resume (module docstring) also states=[state files written] and resumed_from=the state continued
+    from (None: `--resume auto` found none, or no --resume)."""
     from ..datasets import loader
     from ..engine.validatation_engine import build_validation, build_validation_ragged
+    from ..utils import train_state
     from ..utils.PAR import PAR
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
@@ -268,27 +328,65 @@ def train(args, model=None, variant=VOC, tb_writer=None):
     if rank == 0:
         os.makedirs(ckpt_dir, exist_ok=True)
     logging.info("Total gpus: %d, samples per gpu: %d..." % (world, args.spg))
+    train_dataset, val_dataset = variant.datasets(args)
+    # stopping and continuing: which state to continue from is settled, and a state of another run refused, before anything is built or written
+    save_every, keep_states = getattr(args, "save_state_iters", 0), getattr(args, "keep_states", KEEP_STATES_DEFAULT)
+    per_run, resume = getattr(args, "iters_per_run", 0), getattr(args, "resume", None)
+    stateful = save_every > 0 or per_run > 0 or resume is not None or keep_states != KEEP_STATES_DEFAULT
+    start, state, resumed_from, run_cfg, states = 0, None, None, None, []
+    if stateful:
+        if save_every < 0 or per_run < 0 or keep_states < 1:
+            raise ValueError("--save_state_iters and --iters_per_run must be >= 0, --keep_states >= 1")
+        run_cfg = train_state.run_config(args, variant, world, len(train_dataset))
+        if resume is not None:
+            resumed_from = train_state.find_latest_state(ckpt_dir) if resume == "auto" else resume
+        if resumed_from is not None:
+            state = train_state.load_train_state(resumed_from)              # every rank reads the file
+            train_state.check_resume_compat(state["run"], run_cfg)
+            start = int(state["step"])
+    stop_at = min(args.max_iters, start + per_run) if per_run > 0 else args.max_iters
     if model is None:
         model = build_model(args, device)
     par = PAR(num_iter=20, dilations=[1, 2, 4, 8, 12, 24])
-    train_dataset, val_dataset = variant.datasets(args)
     trainer = DecoderTrainer(model, par, lr=args.lr, wt_decay=args.wt_decay, warmup_iters=args.warmup_iters, max_iters=args.max_iters,
                              warmup_lr=args.warmup_lr, power=args.power, caa_thre=variant.caa_thre, w_diver=args.w_diver,
                              radius=args.radius, ignore_index=args.ignore_index, lvc_iter=variant.lvc_iter,
                              seg_aff_iter=variant.seg_aff_iter, seed=args.seed, bkg_thre=args.bkg_thre, high_thre=args.high_thre,
                              low_thre=args.low_thre)
-    batches = loader.train_batches(train_dataset, args.spg, rank=rank, world=world, seed=args.seed, num_threads=args.num_workers)
+    history, tables, ckpts, meter, val_seconds = [], [], [], [], []
+
+    def result(visuals):
+        res = dict(history=history, tables=tables, ckpts=ckpts, val_seconds=val_seconds)
+        if args.save_visual:            # a run without the flag returns what it always did
+            res["visuals"] = visuals
+        if stateful:                    # likewise
+            res["states"], res["resumed_from"] = states, resumed_from
+        return res
+
+    start_epoch = start_batch = 0
+    if state is not None:
+        trainer.load_state_dict(dict(global_step=start, model=state["model_state_dict"], optimizer=state["optimizer_state_dict"]))
+        logging.info("Resuming from %s: continuing after iteration %d of %d" % (resumed_from, start, args.max_iters))
+        if start >= args.max_iters:     # the run had finished
+            return result([])
+        start_epoch, start_batch = loader.resume_position(start, len(train_dataset), world, args.spg)
+    loss_log = None
+    if rank == 0:
+        log_path = os.path.join(args.work_dir, "losses.txt")
+        if state is not None:           # lines of iterations after the state (a process that got further) are written again
+            train_state.truncate_loss_log(log_path, start)
+        loss_log = open(log_path, "w" if state is None else "a")
+    batches = loader.train_batches(train_dataset, args.spg, rank=rank, world=world, seed=args.seed, start_epoch=start_epoch,
+                                   num_threads=args.num_workers, start_batch=start_batch)
     feeder = loader.DeviceFeeder(batches, device, aug_crop_size=args.crop_size)
     class_list = variant.class_list(args)
     first_ckpt = variant.first_ckpt_iter(args)
-    history, tables, ckpts, meter, val_seconds = [], [], [], [], []
-    loss_log = open(os.path.join(args.work_dir, "losses.txt"), "w") if rank == 0 else None
     visual_dir = args.visual_dir or os.path.join(args.work_dir, "visual")
     show = rank == 0 and (args.save_visual or tb_writer is not None)
     png_writer = None
     it = iter(feeder)
     try:
-        for n_iter in range(args.max_iters):
+        for n_iter in range(start, stop_at):
             names, plan, images, cls, labels = next(it)
             visual = show and (n_iter + 1) % args.log_iters == 0
             if visual:
@@ -305,7 +403,7 @@ def train(args, model=None, variant=VOC, tb_writer=None):
                 loss_log.flush()
             if (n_iter + 1) % args.log_iters == 0 and rank == 0:                                                   # :226-233
                 elapsed = time.time() - time0
-                eta = elapsed / (n_iter + 1) * (args.max_iters - n_iter - 1)
+                eta = elapsed / (n_iter + 1 - start) * (args.max_iters - n_iter - 1)      # the pace of this process's iterations
                 m = np.mean(np.asarray(meter), axis=0)
                 meter = []
                 logging.info("Iter: %d; Elasped: %s; ETA: %s; LR: %.3e; seg_loss: %.4f, diver_loss: %.4f"
@@ -342,16 +440,21 @@ def train(args, model=None, variant=VOC, tb_writer=None):
                     logging.info("\n" + table)
                     logging.info("Validation: %d images in %.2f s (%s)" % (len(val_dataset), val_seconds[-1],
                                                                            "per image" if args.val_api_path else f"{world} rank(s), batches of {args.val_batch_size}"))
+            # the full state: every --save_state_iters iterations, and where --iters_per_run stops an unfinished run
+            due = (save_every > 0 and (n_iter + 1) % save_every == 0) or (n_iter + 1 == stop_at and stop_at < args.max_iters)
+            if stateful and due and rank == 0:
+                st = trainer.state_dict()
+                states.append(train_state.save_train_state(train_state.state_path(ckpt_dir, n_iter + 1), n_iter + 1, st["model"],
+                                                           st["optimizer"], out["lr"], run_cfg))
+                train_state.prune_states(ckpt_dir, keep_states)
+                logging.info("Training state of iteration %d: %s" % (n_iter + 1, states[-1]))
     finally:
         it.close()                      # records the last batch's event, then DeviceFeeder.close waits for it and stops the stager
         feeder.close()
         if loss_log is not None:
             loss_log.close()
         visuals = png_writer.close() if png_writer is not None else []         # joins the writer thread, re-raises its first error
-    res = dict(history=history, tables=tables, ckpts=ckpts, val_seconds=val_seconds)
-    if args.save_visual:                # a run without the flag returns what it always did
-        res["visuals"] = visuals
-    return res
+    return result(visuals)
 
 
 if __name__ == "__main__":
