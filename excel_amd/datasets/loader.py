@@ -178,6 +178,7 @@ class DeviceFeeder:
     With `aug_crop_size` S, batches that carry `params` (train_batches) also get the training transform's table built in the staging
     thread (ops.TrainAugPlan) and staged on the copy stream with the images: `plan.aug`, for ops.train_augment(..., aug_plan=plan.aug)
     or ops.train_augment_image(..., aug_plan=plan.aug).  A batch without label maps stages no label bytes and yields labels = None.
+    Every plan also carries the batch's one-hot rows on the host, `plan.cls_host` (a numpy copy), for consumers that size their work there.
 
     A slot (pinned + device buffers) is reused only after the kernels that read it have finished: the CONSUMER's thread records an
     event on its stream when it asks for the next batch and waits for the oldest such event before it lets more than `slots` - 2
@@ -262,6 +263,7 @@ class DeviceFeeder:
                     break
                 slot = self._slots[i]                          # (the consumer frees a slot only after its kernels finished)
                 plan = self._ops.RaggedPlan(rb.hw, None)
+                plan.cls_host = rb.cls.numpy().copy()          # the host one-hot rows travel with the batch
                 with torch.cuda.stream(self._copy_stream):
                     images = self._stage(slot, "images", rb.images)
                     labels = None if rb.labels is None else self._stage(slot, "labels", rb.labels)

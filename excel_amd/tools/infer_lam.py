@@ -101,11 +101,11 @@ def resolve_tta(args):
     step (the defaults "1.0" / false).  Checked here, before a model is built: the scales against --resize_size (tta_sizes), and the
     regime - --training_free false has its own flip (cure_attr_map_flip) and no multi-scale fuse."""
     from .infer_seg_voc import parse_scales
-    scales = parse_scales(getattr(args, "cam_scales", None) or "1.0")
-    flip = bool(getattr(args, "cam_flip", False))
+    scales = parse_scales(flag_defaults(args).cam_scales or "1.0")
+    flip = bool(args.cam_flip)
     if not flip and scales == (1.0,):
         return None, False
-    if not bool(getattr(args, "training_free", True)):
+    if not args.training_free:
         raise ValueError(f"--cam_scales {','.join(str(x) for x in scales)} / --cam_flip {str(flip).lower()} belong to the training-free regime: "
                          "--training_free false already runs its own flip (cure_attr_map_flip) - drop the two flags there")
     tta_sizes(args.resize_size, scales)
@@ -115,11 +115,11 @@ def resolve_tta(args):
 def resolve_conf(args):
     """--conf_label / --conf_high_thre / --conf_low_thre -> (high_thre, low_thre) for run_batch_ragged(conf=), or None (the default:
     the plain step).  Checked here, before a model is built (pipeline.check_conf: a threshold outside (0, 1), low_thre >= high_thre)."""
-    if not bool(getattr(args, "conf_label", False)):
+    if not flag_defaults(args).conf_label:
         return None
     from ..pipeline import check_conf
     try:
-        return check_conf((getattr(args, "conf_high_thre", 0.7), getattr(args, "conf_low_thre", 0.25)))
+        return check_conf((args.conf_high_thre, args.conf_low_thre))
     except ValueError as e:
         raise ValueError(f"--conf_high_thre / --conf_low_thre: {e}") from None
 
@@ -186,16 +186,16 @@ def resolve_vocabulary(args):
     --attr_bank - a vocabulary is never silently paired with another data set's bank."""
     from ..pipeline import check_num_classes
     fg = bkg = bank = None
-    path = getattr(args, "class_names", None)
+    path = flag_defaults(args).class_names
     if path:
         fg = _read_names(path, "--class_names")
         if len(fg) > MAX_FG_CLASSES:
             raise ValueError(f"--class_names {path}: {len(fg)} foreground classes; the uint8 label maps hold at most {MAX_FG_CLASSES} "
                              "(keys 1..254, 255 = ignore)")
-        if getattr(args, "num_classes_given", False) and args.num_classes != len(fg) + 1:
+        if args.num_classes_given and args.num_classes != len(fg) + 1:
             raise ValueError(f"--num_classes {args.num_classes} contradicts --class_names {path}: {len(fg)} names + background = {len(fg) + 1}")
         args.num_classes = len(fg) + 1
-        if getattr(args, "bkg_names", None):
+        if args.bkg_names:
             bkg = _read_names(args.bkg_names, "--bkg_names")
         else:
             from ..datasets.clip_text import BACKGROUND_CATEGORY
@@ -206,12 +206,12 @@ def resolve_vocabulary(args):
         if len(fg) + len(bkg) > MAX_TEXT_ROWS:
             raise ValueError(f"{len(fg)} class names + {len(bkg)} background names = {len(fg) + len(bkg)} prompts; the CAM kernel takes at most "
                              f"{MAX_TEXT_ROWS}")
-    elif getattr(args, "bkg_names", None):
+    elif args.bkg_names:
         raise ValueError("--bkg_names needs --class_names")
     check_num_classes(args.num_classes)
-    if getattr(args, "attr_bank", None):
+    if args.attr_bank:
         bank = load_attr_bank(args.attr_bank)
-    elif fg is not None and getattr(args, "data_folder", None):
+    elif fg is not None and args.data_folder:
         raise ValueError("--data_folder with --class_names needs --attr_bank: the shipped banks belong to the VOC and COCO vocabularies")
     args.vocab = {"fg": fg, "bkg": bkg, "bank": bank}
     return args.vocab
@@ -299,7 +299,17 @@ def get_parser():
     p.add_argument("--cpu_affinity", default="auto", choices=["auto", "off"],
                    help="auto: with several ranks on the node every rank pins itself (decode pool included) to its own share of the host cores")
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
+    p.set_defaults(ragged_batches=False, run_token=None, vocab=None, num_classes_given=False)      # what the program sets itself
     return p
+
+
+def flag_defaults(args, parser=None):
+    """Tests and other programs call in with namespaces of their own: every flag of the parser (default: get_parser()) that `args`
+    lacks gets the parser's default, in place, so the code below reads args.flag.  -> args"""
+    for k, v in vars((parser or get_parser()).parse_args([])).items():
+        if not hasattr(args, k):
+            setattr(args, k, v)
+    return args
 
 
 # ------------------------------------------------------------------ CAM overlay images (tools/infer_lam.py:97-111, :242-267)
@@ -344,7 +354,7 @@ def default_cam_writers(local_world=1):
 
 def class_names(args):
     """The data set's own class list (index 0 = background); with --class_names, the file's."""
-    vocab = getattr(args, "vocab", None)
+    vocab = flag_defaults(args).vocab
     if vocab and vocab.get("fg"):
         return [VOC_CLASSES[0]] + list(vocab["fg"])
     if "coco" in args.dataset_name:
@@ -362,11 +372,10 @@ class _CamSaver:
 
     def __init__(self, args, writers, device_jpeg=False):
         from ..utils import imutils
-        self.per_class = bool(getattr(args, "save_cls_specific_cam", True))
+        self.per_class = bool(flag_defaults(args).save_cls_specific_cam)
         self.mode = "per_class" if self.per_class else "max"
-        dirs = cam_output_dirs(getattr(args, "model_path", None), args.infer_set, bool(getattr(args, "training_free", True)),
-                               bool(getattr(args, "refine_with_aff", True)))
-        self.dir = (getattr(args, "cs_cam_dir", None) or dirs["cs_cam_dir"]) if self.per_class else (getattr(args, "cam_dir", None) or dirs["cam_dir"])
+        dirs = cam_output_dirs(args.model_path, args.infer_set, bool(args.training_free), bool(args.refine_with_aff))
+        self.dir = (args.cs_cam_dir or dirs["cs_cam_dir"]) if self.per_class else (args.cam_dir or dirs["cam_dir"])
         os.makedirs(self.dir, exist_ok=True)
         self.names = class_names(args)
         self.device_jpeg = bool(device_jpeg)
@@ -434,9 +443,8 @@ class _LabelSaver:
 
     def __init__(self, args, directory=None):
         from ..utils import imutils
-        self.dir = directory or getattr(args, "label_dir", None) or label_output_dir(getattr(args, "model_path", None), args.infer_set,
-                                                                         bool(getattr(args, "training_free", True)),
-                                                                         bool(getattr(args, "refine_with_aff", True)))
+        self.dir = directory or flag_defaults(args).label_dir or label_output_dir(args.model_path, args.infer_set, bool(args.training_free),
+                                                                   bool(args.refine_with_aff))
         os.makedirs(self.dir, exist_ok=True)
         self.writer = imutils.LabelPngWriter(LABEL_WRITERS)
         self._arena = self._ws = None
@@ -473,7 +481,7 @@ CRF_RGB_WRITERS = 2      # threads that colour-code and save the --segs_crf_rgb_
 
 def crf_inline_wanted(args):
     """--crf_post true --crf_inline true, except for a test split (the reference scores against image[:,:,0] there, :213-214)."""
-    return bool(getattr(args, "crf_post", False)) and bool(getattr(args, "crf_inline", False)) and "test" not in str(args.infer_set)
+    return bool(flag_defaults(args).crf_post) and bool(args.crf_inline) and "test" not in str(args.infer_set)
 
 
 def _save_crf_rgb(path, lab):
@@ -488,15 +496,15 @@ class _CrfInline:
     batch's labels made only then, into the colour-coded files of --segs_crf_rgb_dir (a small thread pool)."""
 
     def __init__(self, args, device):
-        self.nc = args.num_classes
+        self.nc = flag_defaults(args).num_classes
         self.hist = torch.zeros((self.nc, self.nc), dtype=torch.int64, device=device)
-        self.budget = int(float(getattr(args, "crf_ws_gb", 16.0)) * 2 ** 30)
+        self.budget = int(float(args.crf_ws_gb) * 2 ** 30)
         self.groups, self.calls, self.peak_ws = 0, 0, 0
         self.lab = self.pool = None
         self.futures = []
-        if getattr(args, "crf_label_dir", None):
+        if args.crf_label_dir:
             self.lab = _LabelSaver(args, args.crf_label_dir)
-        self.rgb_dir = getattr(args, "segs_crf_rgb_dir", None)
+        self.rgb_dir = args.segs_crf_rgb_dir
         if self.rgb_dir:
             from concurrent.futures import ThreadPoolExecutor
             os.makedirs(self.rgb_dir, exist_ok=True)
@@ -562,10 +570,8 @@ class _CrfInline:
             self.pool.shutdown(wait=True)
             for f in self.futures:
                 err = err or f.exception()
-            self.pool = None
         if self.lab is not None:
-            lab, self.lab = self.lab, None
-            lab.close()
+            self.lab.close()
         if err is not None:
             raise err
 
@@ -656,100 +662,95 @@ def _check_present_classes(batches, smax):
 
 
 def build_validation(model=None, par=None, dataset=None, indices=None, device="cuda", args=None, pipe=None):
-    """-> (hist [nc,nc] int64 on device, images processed, seconds).  Mirrors :63-128."""
+    """-> (hist [nc,nc] int64 on device, images processed, seconds).  Mirrors :63-128.  Everything the run depends on is resolved here,
+    once, into `run`, for one of the two loops below; the run's `report` is published in build_validation.last_* on the way out."""
+    from types import SimpleNamespace
     from ..pipeline import OptimisedLamPipeline, TrainingFreePipeline
-    training_free = bool(getattr(args, "training_free", True))
-    ragged_batches = bool(getattr(args, "ragged_batches", False))
+    flag_defaults(args)
     # the optimised-LAM regime runs batched on ragged batches; uniform synthetic batches keep its per-image call sequence
-    per_image = args.api_path or (not training_free and not ragged_batches)
-    ragged = ragged_batches and not per_image
+    per_image = args.api_path or (not args.training_free and not args.ragged_batches)
+    ragged = bool(args.ragged_batches) and not per_image
+    on_gpu = torch.device(device).type == "cuda"
     # the overflow guard of the f16 modes: resolved from the mode the handle is in NOW (after the start-up check)
     mode = _handle_gemm_mode(model if pipe is None else getattr(pipe, "model", None))
-    policy = resolve_overflow_guard(getattr(args, "overflow_guard", "auto"), mode, torch.device(device).type == "cuda", not per_image)
+    policy = resolve_overflow_guard(args.overflow_guard, mode, on_gpu, not per_image)
     tta_scales, tta_flip = resolve_tta(args)
+    conf = resolve_conf(args)
     if pipe is None:
-        guard = "skip" if policy in ("raise", "rerun") else None
-        if training_free:
-            pipe = TrainingFreePipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
-                                        caa_thre=0.79, smax=dataset.max_k(), guard=guard, tta_scales=tta_scales, tta_flip=tta_flip)
+        kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79, smax=dataset.max_k(),
+                  guard="skip" if policy in ("raise", "rerun") else None)
+        if args.training_free:
+            pipe = TrainingFreePipeline(model, tta_scales=tta_scales, tta_flip=tta_flip, **kw)
         elif ragged:
-            pipe = OptimisedLamPipeline(model, num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter,
-                                        caa_thre=0.79, smax=dataset.max_k(), guard=guard)
+            pipe = OptimisedLamPipeline(model, **kw)
     elif policy != "off" and getattr(pipe, "guard", None) is None:
         # a caller's pipeline keeps the guard it was built with: without one there are no flags to act on
         logging.warning(f"--overflow_guard {policy}: the supplied pipeline was built without a guard - running unguarded")
         policy = "off"
-    build_validation.last_guard = {"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []}
-    hist = torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device)
-    t0 = time.time()
-    save_cam = bool(getattr(args, "save_cam", False))
-    if save_cam and not (ragged or per_image):
-        raise ValueError("--save_cam needs the decoded images: ragged batches (--data_folder or --ragged true) or the per-image path "
-                         "(--api_path true / --training_free false)")
+    report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
-    writers = default_cam_writers(local_world) if save_cam else 0
-    cam = _CamSaver(args, writers, device_jpeg=bool(getattr(args, "cam_device_jpeg", False)) and ragged) if save_cam else None
-    lab = crf = conf_lab = None
-    build_validation.last_crf_hist = build_validation.last_crf_stats = build_validation.last_cam_stats = build_validation.last_conf_hist = None
-    conf = resolve_conf(args)
-    if conf is not None and not (ragged or per_image):
-        raise ValueError("--conf_label runs behind the ragged step: ragged batches (--data_folder or --ragged true) or the per-image path "
-                         "(--api_path true / --training_free false)")
-    if crf_inline_wanted(args) and not (ragged or per_image):
-        raise ValueError("--crf_inline needs the decoded images: ragged batches (--data_folder or --ragged true) or the per-image path "
-                         "(--api_path true / --training_free false)")
+    run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, guard=report["guard"], report=report,
+                          local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
+                          hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
+                          consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
     try:
-        lab = _LabelSaver(args) if bool(getattr(args, "save_label", False)) else None
-        crf = _CrfInline(args, device) if crf_inline_wanted(args) else None
+        for wanted, needs in ((args.save_cam, "--save_cam needs the decoded images"), (conf is not None, "--conf_label runs behind the ragged step"),
+                              (crf_inline_wanted(args), "--crf_inline needs the decoded images")):
+            if wanted and not (ragged or per_image):
+                raise ValueError(f"{needs}: ragged batches (--data_folder or --ragged true) or the per-image path "
+                                 "(--api_path true / --training_free false)")
+        if args.save_cam:
+            run.consumers["cam"] = _CamSaver(args, run.writers, device_jpeg=bool(args.cam_device_jpeg) and ragged)
+        if args.save_label:
+            run.consumers["lab"] = _LabelSaver(args)
+        if crf_inline_wanted(args):
+            run.consumers["crf"] = _CrfInline(args, device)
         if conf is not None:
-            conf_lab = _LabelSaver(args, getattr(args, "conf_label_dir", None) or conf_label_output_dir(
-                getattr(args, "model_path", None), args.infer_set, training_free, bool(getattr(args, "refine_with_aff", True))))
-        out = _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab, crf,
-                                build_validation.last_guard, conf, conf_lab)
-        if conf_lab is not None:
-            conf_lab, done = None, conf_lab
-            done.close()
-        if lab is not None:                                  # every file on disk (and a writer's error raised) before the scores are reported
-            lab, done = None, lab
-            done.close()
-        if crf is not None:
-            crf, done = None, crf
-            done.close()
-            build_validation.last_crf_hist = done.hist
-            build_validation.last_crf_stats = dict(calls=done.calls, groups=done.groups, peak_workspace_bytes=done.peak_ws)
-        return out
+            run.consumers["conf_lab"] = _LabelSaver(args, args.conf_label_dir or conf_label_output_dir(
+                args.model_path, args.infer_set, bool(args.training_free), bool(args.refine_with_aff)))
+        out = (_per_image_loop if per_image else _batched_loop)(run)
+    except BaseException:
+        _close_consumers(run, failed=True)
+        raise
+    else:
+        _close_consumers(run, failed=False)      # every file on disk (and a writer's error raised) before the scores are reported
     finally:
-        if cam is not None:
-            try:
-                files = cam.close()
-            finally:
-                build_validation.last_cam_stats = dict(device_jpeg=cam.device_jpeg, files=getattr(cam.writer, "files", 0), batches=cam.batches,
-                                                       bytes_to_host=cam.copied, host_fallbacks=getattr(cam.writer, "fallbacks", 0))
-        if crf is not None:
-            try:
-                crf.close()
-            except Exception:
-                pass
-        for w in (lab, conf_lab):                            # on the way out of an exception: stop the writers, keep the first error
-            if w is not None:
-                try:
-                    w.close()
-                except Exception:
-                    pass
+        build_validation.last_guard, build_validation.last_crf_hist, build_validation.last_crf_stats, build_validation.last_cam_stats, \
+            build_validation.last_conf_hist = (report[k] for k in ("guard", "crf_hist", "crf_stats", "cam_stats", "conf_hist"))
+    return out
 
 
-def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0, per_image, ragged, training_free, cam, writers, lab=None,
-                      crf=None, guard=None, conf=None, conf_lab=None):
+def _close_consumers(run, failed):
+    """Every consumer is closed once, on every path, and the overlay statistics are recorded.  After a loop that ran through, the first
+    writer's error is raised and only a clean close hands out the CRF stage's matrix; after one that `failed`, the loop's own exception stays."""
+    first = None
+    for c in run.consumers.values():
+        try:
+            c.close()
+        except Exception as e:
+            first = first or e
+    cam, crf = run.consumers.get("cam"), run.consumers.get("crf")
+    if cam is not None:
+        run.report["cam_stats"] = dict(device_jpeg=cam.device_jpeg, files=getattr(cam.writer, "files", 0), batches=cam.batches,
+                                       bytes_to_host=cam.copied, host_fallbacks=getattr(cam.writer, "fallbacks", 0))
+    if first is not None and not failed:
+        raise first
+    if crf is not None and not failed:
+        run.report["crf_hist"] = crf.hist
+        run.report["crf_stats"] = dict(calls=crf.calls, groups=crf.groups, peak_workspace_bytes=crf.peak_ws)
+
+
+def _per_image_loop(run):
+    """The reference's call sequence, image by image (--api_path true, and --training_free false on uniform synthetic batches)."""
     from ..utils import evaluate
     from ..utils.affutils import refine_cams_with_aff, refine_cams_with_bkg_weclip
     from .. import ops
-    S = args.resize_size
-    on_gpu = torch.device(device).type == "cuda"
-    nimg = 0
-    tta = resolve_tta(args)
-    if not per_image:
-        return _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu, conf, conf_lab)
-    hist_conf = None
+    args, model, par, dataset, indices, device, S = run.args, run.model, run.par, run.dataset, run.indices, run.device, run.S
+    training_free, tta, conf, hist = args.training_free, run.tta, run.conf, run.hist
+    cam, lab, crf, conf_lab = (run.consumers.get(k) for k in ("cam", "lab", "crf", "conf_lab"))
+    nimg, hist_conf = 0, None
     for s in range(0, len(indices)):
         names, imgs, gts, cls = dataset.batch(indices[s:s + 1])
         inputs = torch.from_numpy(imgs).to(device, non_blocking=True)
@@ -782,9 +783,9 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
             labels, normed = refine_cams_with_bkg_weclip(refined, inputs[i], cls_lst, par, gts.shape[-2:])   # :94
             if crf is not None:                                                             # :179-237 without a record
                 crf.image(str(names[i]), decoded[i], normed, cls_lst, gt_dev[i])
-            elif getattr(args, "crf_post", False):                                          # :116-119 record for the CRF stage
+            elif args.crf_post:                                                             # :116-119 record for the CRF stage
                 from ..utils import imutils
-                imutils.save_logits(args.logits_dir, str(names[i]), normed, cls_lst, run_token=getattr(args, "run_token", None))
+                imutils.save_logits(args.logits_dir, str(names[i]), normed, cls_lst, run_token=args.run_token)
             if cam is not None:                                                             # :97-111
                 cam.image(names[i], decoded[i], normed, cls_lst)
             hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
@@ -797,49 +798,45 @@ def _build_validation(model, par, dataset, indices, device, args, pipe, hist, t0
                 conf_lab.uniform([names[i]], kept[None])
         nimg += len(imgs)
     torch.cuda.synchronize()
-    build_validation.last_conf_hist = hist_conf
-    return hist, nimg, time.time() - t0
+    run.report["conf_hist"] = hist_conf
+    return hist, nimg, time.time() - run.t0
 
 
-def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, cam, writers, lab, crf, guard, on_gpu, conf=None, conf_lab=None):
+def _batched_loop(run):
     """The batched loop of build_validation: one pass over `indices`, and with the overflow guard's `rerun` policy a second pass in exact
     fp32 over the images the first one flagged - the same loop body (`steps`) and the same consumers both times."""
     from collections import deque
     from .. import ops
-    S = args.resize_size
-    policy = guard["policy"] if guard else "off"
-    pipe.hist = hist
+    args, dataset, indices, device, pipe, S, on_gpu = run.args, run.dataset, run.indices, run.device, run.pipe, run.S, run.on_gpu
+    ragged, guard, conf = run.ragged, run.guard, run.conf
+    cam, lab, crf, conf_lab = (run.consumers.get(k) for k in ("cam", "lab", "crf", "conf_lab"))
+    policy = guard["policy"]
+    pipe.hist = run.hist
     if conf is not None:
-        pipe.hist_conf = torch.zeros_like(hist)
-    host_cls = deque()          # the host one-hot rows, in the feeder's order (it keeps the order)
+        pipe.hist_conf = torch.zeros_like(run.hist)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
-        from ..datasets.loader import ragged_batches
+        from ..datasets.loader import DeviceFeeder, ragged_batches, threaded_batches
         from ..utils import imutils
-        keep = bool(getattr(args, "crf_post", False)) and crf is None      # the record path of the CRF stage; --crf_inline needs no copies
-        nw = int(getattr(args, "num_workers", -1))
+        keep = bool(args.crf_post) and crf is None           # the record path of the CRF stage; --crf_inline needs no copies
+        nw = int(args.num_workers)
         if nw < 0:                                           # the JPEG encoders of --save_cam share this rank's CPUs
-            nw = max(2, default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))) - writers)
+            nw = max(2, default_decode_workers(run.local_world) - run.writers)
 
     def feed_of(idxs):
-        if getattr(args, "decode", "threads") == "processes" and nw > 0:    # the reference's mechanism (DataLoader worker processes, :167)
+        if args.decode == "processes" and nw > 0:                           # the reference's mechanism (DataLoader worker processes, :167)
             batches = ragged_batches(dataset, idxs, args.batch_size, num_workers=nw, pin_memory=False)
         else:                                                               # default: a thread pool (datasets/loader.threaded_batches)
-            from ..datasets.loader import threaded_batches
             batches = threaded_batches(dataset, idxs, args.batch_size, num_threads=max(nw, 1))
         batches = _check_present_classes(batches, pipe.smax)
-        if cam is not None or crf is not None:
-
-            def _tap(bs):
-                for rb in bs:
-                    host_cls.append(rb.cls.numpy().copy())
-                    yield rb
-            batches = _tap(batches)
         if on_gpu:
-            from ..datasets.loader import DeviceFeeder
             return DeviceFeeder(batches, device)              # H2D on a copy stream, a few batches ahead
-        # (control-flow tests: a stub pipeline on CPU tensors)
-        return ((rb.names, ops.RaggedPlan(rb.hw, None), rb.images, rb.cls, rb.labels) for rb in batches)
+
+        def on_host(rb):                                      # (control-flow tests: a stub pipeline on CPU tensors)
+            plan = ops.RaggedPlan(rb.hw, None)
+            plan.cls_host = rb.cls.numpy().copy()             # what DeviceFeeder attaches
+            return rb.names, plan, rb.images, rb.cls, rb.labels
+        return map(on_host, batches)
 
     def ragged_step(names, plan, images, cls_t, labels_t):
         if conf is None:
@@ -849,11 +846,10 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
             main, kept, *rest = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep, conf=conf)
             out = (main, rest[0]) if keep else main
             conf_lab.ragged(names, plan, kept)
-        cls_host = host_cls.popleft() if (cam is not None or crf is not None) else None
         if cam is not None:                                                             # :97-111, same stream, step's own cams
-            cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, cls_host)
+            cam.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, plan.cls_host)
         if crf is not None:                                                             # :179-237, same stream, step's own cams
-            nchan_host = np.minimum((cls_host != 0).sum(1), pipe.smax).astype(np.int32) + 1
+            nchan_host = np.minimum((plan.cls_host != 0).sum(1), pipe.smax).astype(np.int32) + 1
             skip = pipe.last_flags if getattr(pipe, "guard", None) == "skip" else None  # flagged images stay out of the CRF scores too
             crf.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, pipe.last_nchan, nchan_host, pipe.last_cls_idx, labels_t, skip)
         if lab is not None:                                                             # :95, same stream, the labels just scored
@@ -864,7 +860,7 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
             for b, name in enumerate(names):
                 k = min(int(ncls[b]), pipe.smax)            # (ncls <= smax is enforced below; the record stays consistent anyway)
                 imutils.save_logits(args.logits_dir, name, plan.planes(inter["cams"], b, pipe.smax + 1)[:k + 1], cls_idx[b, :k].astype(np.int64),
-                                    run_token=getattr(args, "run_token", None))
+                                    run_token=args.run_token)
 
     def uniform_step(idxs):
         names, imgs, gts, cls = dataset.batch(idxs)
@@ -927,9 +923,8 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
         # every file of the first pass on disk before a flagged image's file is written again: the good one must be the last
         if on_gpu:
             torch.cuda.synchronize()
-        for w in (cam, lab, crf, conf_lab):
-            if w is not None:
-                w.barrier()
+        for c in run.consumers.values():
+            c.barrier()
         order, still = sorted(flagged), {}
         found_guard, pipe.guard = pipe.guard, "observe"       # count again, score everything: fp32's own result is final
         try:
@@ -951,8 +946,8 @@ def _batched_validation(dataset, indices, device, args, pipe, hist, t0, ragged, 
     if on_gpu:
         torch.cuda.synchronize()
     if conf is not None:
-        build_validation.last_conf_hist = pipe.hist_conf
-    return pipe.hist, nimg, time.time() - t0
+        run.report["conf_hist"] = pipe.hist_conf
+    return pipe.hist, nimg, time.time() - run.t0
 
 
 def resolve_model_inputs(args):
@@ -966,7 +961,7 @@ def resolve_model_inputs(args):
     from .. import clip
     from . import synthetic
     kw = {}
-    ckpt = clip.clip.find_checkpoint(args.model, getattr(args, "clip_root", None))
+    ckpt = clip.clip.find_checkpoint(flag_defaults(args).model, args.clip_root)
     if ckpt is not None:
         sd = clip.clip.read_checkpoint(ckpt)
         kw["state_dict"] = sd
@@ -976,20 +971,20 @@ def resolve_model_inputs(args):
             raise RuntimeError(f"{ckpt}: the checkpoint has no text tower (text_projection ...): the class / background prompts of "
                                "model/model_excel.py:31-33 cannot be encoded")
         from ..clip import bpe
-        kw["tokenizer"] = bpe.BPETokenizer(getattr(args, "bpe_path", None))            # raises FileNotFoundError with the remedy
+        kw["tokenizer"] = bpe.BPETokenizer(args.bpe_path)         # raises FileNotFoundError with the remedy
         logging.info(f"CLIP weights: {ckpt}")
-    elif getattr(args, "data_folder", None):
+    elif args.data_folder:
         raise RuntimeError(f"--data_folder given but no CLIP checkpoint found for --model {args.model!r}: pass a checkpoint path, or put "
                            "the published archive (ViT-B-16.pt) under --clip_root / $EXCEL_CLIP_ROOT / ~/.cache/clip. "
                            "Refusing to score real data with random weights.")
     else:
-        vocab = getattr(args, "vocab", None) or {}
+        vocab = args.vocab or {}
         T = synthetic.text_rows(args.num_classes, len(vocab["bkg"]) if vocab.get("bkg") else None, custom=bool(vocab.get("fg")))
         kw["state_dict"] = synthetic.make_vit_state_dict(seed=0)
         kw["text_features"] = synthetic.make_text_features(T)
         logging.warning("SYNTHETIC run: seeded random ViT-B/16 weights and random text features (no CLIP checkpoint resolved); "
                         "the mIoU below is a throughput / plumbing check, not a result")
-    if not bool(getattr(args, "training_free", True)):
+    if not args.training_free:
         if not args.model_path or not os.path.isfile(args.model_path):
             raise RuntimeError("--training_free false needs --model_path (the trained decoder checkpoint, tools/infer_lam.py:150-160)")
         trained = torch.load(args.model_path, map_location="cpu")
@@ -1014,6 +1009,7 @@ def crf_proc(args, rank=0, world=1, device="cuda"):
     from ..utils import evaluate, imutils
     from ..utils.dcrf import DenseCRF
     from .. import ops
+    flag_defaults(args)
     with open(os.path.join(args.list_folder, args.infer_set) + ".txt") as f:
         name_list = [x for x in f.read().split("\n") if x]                                  # :182-184
     images_path = os.path.join(args.data_folder, "JPEGImages")
@@ -1025,8 +1021,7 @@ def crf_proc(args, rank=0, world=1, device="cuda"):
         rec = os.path.join(args.logits_dir, name + ".npy")
         # records carry the token of the run that wrote them (validate() draws one and shares it with every rank): no dependence on
         # file-system time stamps or clocks.  A caller that runs build_validation + crf_proc without a token accepts any record.
-        token = getattr(args, "run_token", None)
-        if not os.path.isfile(rec) or (token is not None and imutils.logits_run_token(rec) != token):
+        if not os.path.isfile(rec) or (args.run_token is not None and imutils.logits_run_token(rec) != args.run_token):
             raise RuntimeError(f"crf_proc: {rec} was not written by this run (missing or stale): the CRF stage scores the records of the "
                                "main loop (tools/infer_lam.py:116-119), never those of an earlier one")
         lams, keys = imutils.load_logits(rec)                                               # :203-206
@@ -1039,7 +1034,7 @@ def crf_proc(args, rank=0, world=1, device="cuda"):
         pred = prob.argmax(0)                                                               # :222
         keys_t = torch.from_numpy(np.pad(np.asarray(keys) + 1, (1, 0), mode="constant")).to(device)   # :225
         pred_crf = keys_t[pred].to(torch.uint8)                                             # :226
-        if getattr(args, "segs_crf_rgb_dir", None):
+        if args.segs_crf_rgb_dir:
             os.makedirs(args.segs_crf_rgb_dir, exist_ok=True)
             Image.fromarray(imutils.encode_cmap(pred_crf.cpu().numpy())).save(os.path.join(args.segs_crf_rgb_dir, name + ".png"))   # :228
         hist = ops.confusion_accumulate(torch.from_numpy(np.array(label, dtype=np.uint8)).to(device), pred_crf, args.num_classes, hist)
@@ -1053,7 +1048,7 @@ def _gemm_self_check(model, dataset, idx, args, device, world):
     difference): every rank runs the same mode, and a rank whose shard is EMPTY (fewer images than ranks) still joins every collective
     with a difference of 0 instead of leaving the others waiting."""
     from .. import ops
-    S = args.resize_size
+    S = flag_defaults(args).resize_size
     take = [int(i) for i in idx[:4]]
     inputs = None
     if take:
@@ -1075,7 +1070,7 @@ def _gemm_self_check(model, dataset, idx, args, device, world):
             return float(t.item())
         return diff
 
-    tol = float(getattr(args, "gemm_check_tol", 5e-4))
+    tol = float(args.gemm_check_tol)
     out = model.check_numerics(inputs, tol=tol, fallback=True, reduce=share)
     before, after, ladder = out["mode_before"], out["mode_after"], out["ladder"]
     if after != before:
@@ -1094,8 +1089,12 @@ def validate(args=None, dataset=None, pipe=None):
     from . import synthetic
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
+    flag_defaults(args)
+    # what this call reports: every attribute starts over, None where a stage does not run
+    validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
+    validate.last_conf = validate.last_crf = None
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
-    resolve_conf(args)                                                                       # ... and a bad pair of thresholds
+    conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
     if pipe is None:
         torch.cuda.set_device(args.local_rank)
@@ -1105,7 +1104,7 @@ def validate(args=None, dataset=None, pipe=None):
     if world > 1 and not dist.is_initialized():
         dist.init_process_group(backend=args.backend)                                       # :133
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
-    if pipe is None and getattr(args, "cpu_affinity", "auto") == "auto" and local_world > 1:
+    if pipe is None and args.cpu_affinity == "auto" and local_world > 1:
         cores = pin_rank_to_cores(int(os.environ.get("LOCAL_RANK", args.local_rank)), local_world)
         if cores and rank == 0:
             logging.info(f"rank 0 pinned to {len(cores)} of the host's cores (every rank takes its own share; --cpu_affinity off disables)")
@@ -1117,7 +1116,7 @@ def validate(args=None, dataset=None, pipe=None):
     args.run_token = tok[0]
     if dataset is not None:
         args.ragged_batches = True
-    elif getattr(args, "data_folder", None):
+    elif args.data_folder:
         # :156-163: every image has its own size.  The reference's harness always builds the VOC data set (:132); a COCO tree
         # (--dataset_name ms_coco, BASELINE configs[4]) gets the COCO reader of datasets/coco.py here
         if "coco" in args.dataset_name:
@@ -1128,16 +1127,16 @@ def validate(args=None, dataset=None, pipe=None):
             dataset = voc.VOC12SegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.infer_set, stage="val")
         args.ragged_batches = True
     else:
-        args.ragged_batches = bool(getattr(args, "ragged", False))
+        args.ragged_batches = bool(args.ragged)
         dataset = synthetic.SyntheticSegDataset(args.synthetic, (args.resize_size, args.resize_size), num_classes=args.num_classes,
-                                                seed=args.seed, u8_images=getattr(args, "u8_input", False), ragged=args.ragged_batches)
+                                                seed=args.seed, u8_images=args.u8_input, ragged=args.ragged_batches)
     model = None
     if pipe is None:
         from ..model.model_excel import ExCEL_model
         model = ExCEL_model(clip_model=args.model, embedding_dim=args.embedding_dim, in_channels=args.in_channels,
                             dataset_name=args.dataset_name, num_classes=args.num_classes, num_atrr_clusters=args.num_attri,
                             json_file=args.attr_json, img_size=args.resize_size, mode=args.infer_set, device=device,
-                            gemm_mode=getattr(args, "gemm_mode", None), class_names=vocab["fg"], bkg_names=vocab["bkg"],
+                            gemm_mode=args.gemm_mode, class_names=vocab["fg"], bkg_names=vocab["bkg"],
                             attr_bank=vocab["bank"], **resolve_model_inputs(args))
     # everything built so far (torch, the weights, the data set index) lives for the whole run: move it out of the cyclic collector's
     # reach, or every full collection walks it again - 40-70 ms of host time each (measured in bench.py, where one landed in a timed step)
@@ -1146,7 +1145,7 @@ def validate(args=None, dataset=None, pipe=None):
     gc.freeze()
     par = PAR(num_iter=20, dilations=[1, 2, 4, 8, 12, 24])                                  # :168
     idx = shard_indices(len(dataset), rank, world)                                          # :166
-    if model is not None and getattr(args, "gemm_check", True):              # every rank joins, also one with an empty shard
+    if model is not None and args.gemm_check:                                # every rank joins, also one with an empty shard
         validate.last_gemm_check = _gemm_self_check(model, dataset, idx, args, device, world)
     hist, nimg, secs = build_validation(model, par, dataset, idx, device, args, pipe=pipe)
     validate.last_model = model                                                             # handle for callers / tests
@@ -1165,7 +1164,7 @@ def validate(args=None, dataset=None, pipe=None):
         logging.info(f"Training_free:{args.training_free}, LAM_score:")
         logging.info("\n" + format_scores_table(score, cat_list))
         logging.info(f"mIoU {score['miou'] * 100:.3f}  images {int(nimg) * world}  ({nimg / secs:.1f} img/s/rank)")
-        if getattr(args, "json_out", None):
+        if args.json_out:
             # one self-checking record per run (tools_dev/scale.sh): wall time, rate and every rank's scored-pixel mass
             import json
             with open(args.json_out, "w") as f:
@@ -1176,9 +1175,8 @@ def validate(args=None, dataset=None, pipe=None):
                            "hist_total": [[int(v) for v in row] for row in total.cpu().tolist()],       # the gathered confusion matrix itself
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
                            "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1])}, f)
-    validate.last_conf = None
-    if resolve_conf(args) is not None:
-        conf_hist = getattr(build_validation, "last_conf_hist", None)
+    if conf is not None:
+        conf_hist = build_validation.last_conf_hist
         if conf_hist is None:                                                               # a rank with an empty shard still joins the gather
             conf_hist = torch.zeros_like(hist)
         _, conf_total = gather_hists(conf_hist)                                             # once, like the main matrix
@@ -1190,10 +1188,10 @@ def validate(args=None, dataset=None, pipe=None):
             logging.info("\n" + format_scores_table(conf_score, cat_list))
             logging.info(f"conf_label coverage {coverage * 100:.3f} % of the scored pixels kept "
                          f"(high_thre {args.conf_high_thre}, low_thre {args.conf_low_thre})")
-    inline_hist = getattr(build_validation, "last_crf_hist", None)
-    if getattr(args, "crf_post", False) and getattr(args, "crf_inline", False) and inline_hist is None and rank == 0:
+    inline_hist = build_validation.last_crf_hist
+    if args.crf_post and args.crf_inline and inline_hist is None and rank == 0:
         logging.info(f"--crf_inline: the {args.infer_set} split keeps the record path of the CRF stage (scored against image[:,:,0], :213-214)")
-    if inline_hist is not None or (getattr(args, "crf_post", False) and getattr(args, "data_folder", None)):     # :173-174
+    if inline_hist is not None or (args.crf_post and args.data_folder):                     # :173-174
         if inline_hist is not None:                                                         # scored in the loop: one gather, like the main histogram
             _, crf_total = gather_hists(inline_hist)
             crf_score = evaluate.scores_from_hist(crf_total)

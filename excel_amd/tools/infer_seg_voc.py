@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .infer_lam import _bool, flag_defaults
 
 
 @torch.no_grad()
@@ -73,10 +74,6 @@ def validate_seg(model, batches, num_classes, resize_size, scales=(1.0, 0.5, 0.7
 
 
 # ------------------------------------------------------------------ the evaluation program (tools/infer_seg_voc.py:23-45, :176-240)
-def _bool(x):
-    return x.lower() in ["true", "1", "yes"]
-
-
 def parse_scales(x):
     """"0.7,1.0,1.2,1.5" (or a sequence) -> tuple of floats."""
     if isinstance(x, str):
@@ -207,8 +204,8 @@ def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None):
     from ..utils.dcrf import DenseCRF
     nc = int(args.num_classes)
     crf = bool(args.crf_post)
-    batched = crf and bool(getattr(args, "crf_batched", True))
-    budget = int(float(getattr(args, "crf_ws_gb", 16.0)) * 2 ** 30)
+    batched = crf and bool(args.crf_batched)
+    budget = int(float(args.crf_ws_gb) * 2 ** 30)
     sizes = scale_sizes(args.resize_size, parse_scales(args.scales))
     flips = [s != 1.0 or variant.flip_first for _, s in sizes]
     post = DenseCRF(**CRF_PARAMS) if crf else None
@@ -288,7 +285,7 @@ def build_model(args, device):
     kw = infer_lam.resolve_model_inputs(ns)
     return ExCEL_model(clip_model=args.model, embedding_dim=args.embedding_dim, in_channels=args.in_channels, dataset_name=args.dataset_name,
                        num_classes=args.num_classes, num_atrr_clusters=args.num_attri, json_file=args.attr_json, img_size=args.resize_size,
-                       mode=args.infer_set, device=device, gemm_mode=getattr(args, "gemm_mode", None), **kw)
+                       mode=args.infer_set, device=device, gemm_mode=args.gemm_mode, **kw)
 
 
 def validate(args, model=None, variant=VOC):
@@ -299,6 +296,7 @@ def validate(args, model=None, variant=VOC):
     from ..datasets.loader import DeviceFeeder, threaded_batches
     from ..utils import evaluate
     from . import infer_lam
+    flag_defaults(args, get_parser())
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
     torch.cuda.set_device(args.local_rank)
@@ -323,7 +321,7 @@ def validate(args, model=None, variant=VOC):
         if model is None:
             model = build_model(args, device)
         idx = infer_lam.shard_indices(len(dataset), rank, world)                              # one image per r, r+R, ...
-        if getattr(args, "gemm_check", True):
+        if args.gemm_check:
             infer_lam._gemm_self_check(model, dataset, idx, args, device, world)
         nw = int(args.num_workers)
         if nw < 0:

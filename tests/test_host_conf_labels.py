@@ -196,6 +196,36 @@ def test_conf_labels_go_through_the_guard_rerun_and_the_one_gather(monkeypatch, 
     assert infer_lam.validate.last_conf is None
 
 
+def test_a_writer_that_fails_on_close_is_raised_before_any_score_and_every_writer_is_closed_once(monkeypatch, caplog):
+    import logging
+    import test_host_overflow_guard as G
+    from excel_amd.tools import infer_lam
+
+    class Stub(G._GuardStub):
+        hist_conf = None
+
+        def run_batch_ragged(self, images, plan, cls, gts, S=448, return_intermediates=False, conf=None):
+            labels = super().run_batch_ragged(images, plan, cls, gts, S=S)
+            return labels, labels
+
+    class Saver(G._FakeLabelSaver):
+        def __init__(self, args, directory=None):
+            self.tag = "conf" if directory == "conf_dir" else "main"
+
+        def close(self):
+            self.log.append(("close", self.tag))
+            raise OSError(f"disk full ({self.tag})")
+
+    Saver.log = log = []
+    monkeypatch.setattr(infer_lam, "_LabelSaver", Saver)
+    args = G._args("--save_label", "true", "--conf_label", "true", "--conf_label_dir", "conf_dir")
+    with caplog.at_level(logging.INFO), pytest.raises(OSError, match="disk full"):
+        infer_lam.validate(args, dataset=G._IndexedSet(5), pipe=Stub(None))
+    assert sum(1 for e in log if e[0] == "write") == 4                                  # the loop ran through: 2 steps, both writers
+    assert sorted(e for e in log if e[0] == "close") == [("close", "conf"), ("close", "main")]
+    assert "LAM_score" not in caplog.text and "mIoU" not in caplog.text and "conf_label_score" not in caplog.text
+
+
 def test_conf_label_needs_the_ragged_step():
     from excel_amd.tools import infer_lam
     args = infer_lam.get_parser().parse_args(["--conf_label", "true", "--synthetic", "4"])

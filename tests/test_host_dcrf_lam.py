@@ -182,7 +182,6 @@ def test_main_loop_runs_the_stage_once_per_batch_without_records(monkeypatch, tm
     pipe = _StubPipe()
     args = infer_lam.get_parser().parse_args(["--batch_size", "5", "--num_workers", "0", "--crf_post", "true", "--crf_inline", "true",
                                               "--crf_ws_gb", "0.25", "--logits_dir", str(logits)])
-    infer_lam.validate.last_crf = None
     infer_lam.validate(args, dataset=_TinyRaggedSet(n), pipe=pipe)
     ds = _TinyRaggedSet(n)
     assert [c["plan"].B for c in calls] == [5, 5, 2]
@@ -205,6 +204,34 @@ def test_main_loop_runs_the_stage_once_per_batch_without_records(monkeypatch, tm
     with pytest.raises(AssertionError, match="no copies"):
         infer_lam.validate(args, dataset=_TinyRaggedSet(n), pipe=_StubPipe())
     assert len(calls) == 3
+
+
+def test_a_second_run_reports_nothing_of_the_first(monkeypatch):
+    """validate twice in one process: with the inline CRF stage and the confident labels, then with neither - what the second call
+    leaves in validate.last_* / build_validation.last_* is its own (None for the stages it did not run)."""
+    import test_host_overflow_guard as G
+    from excel_amd import ops
+    from excel_amd.tools import infer_lam
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+
+    class ConfPipe(_StubPipe):
+        def run_batch_ragged(self, images, plan, cls, gts, S=448, return_intermediates=False, conf=None):
+            labels = super().run_batch_ragged(images, plan, cls, gts, S=S, return_intermediates=return_intermediates)
+            return labels, labels
+
+    G._FakeLabelSaver.log = []
+    monkeypatch.setattr(infer_lam, "_LabelSaver", G._FakeLabelSaver)
+    monkeypatch.setattr(ops, "dcrf_lam_ragged", lambda images_u8, plan, *a, **k: ((images_u8.view(-1, 3)[:, 1] % 21).to(torch.uint8), None))
+    monkeypatch.setattr(ops, "confusion_accumulate", lambda gt, pred, nc, hist=None: hist)
+    flags = ["--batch_size", "5", "--num_workers", "0"]
+    first = infer_lam.get_parser().parse_args(flags + ["--crf_post", "true", "--crf_inline", "true", "--conf_label", "true"])
+    infer_lam.validate(first, dataset=_TinyRaggedSet(7), pipe=ConfPipe())
+    assert infer_lam.validate.last_crf is not None and infer_lam.validate.last_conf is not None
+    assert infer_lam.build_validation.last_crf_hist is not None and infer_lam.build_validation.last_conf_hist is not None
+    infer_lam.validate(infer_lam.get_parser().parse_args(flags), dataset=_TinyRaggedSet(7), pipe=_StubPipe())
+    assert infer_lam.validate.last_crf is None and infer_lam.validate.last_conf is None
+    assert infer_lam.build_validation.last_crf_hist is None and infer_lam.build_validation.last_conf_hist is None
 
 
 def test_gpu_tests_use_the_programs_parameter_set():
