@@ -89,6 +89,7 @@ SIGNATURES = {
     "excel_gemm_f16x2": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
     "excel_gemm_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_int32)]),
     "excel_attn_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_int32)]),
+    "excel_patch_text_cam_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_int32)]),
     "excel_layernorm": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, C.c_float, c_f]),
     "excel_vit_create": (c_i, [C.POINTER(VitConfig), C.POINTER(VitWeights), C.POINTER(C.c_void_p)]),
     "excel_vit_destroy": (None, [C.c_void_p]),

@@ -17,7 +17,7 @@ void excel_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* excel_last_error(void) { return g_err; }
-extern "C" int excel_abi_version(void) { return 4; }
+extern "C" int excel_abi_version(void) { return 5; }
 #ifndef EXCEL_BUILD_ID
 #define EXCEL_BUILD_ID "unstamped"
 #endif
@@ -227,6 +227,16 @@ extern "C" int excel_attn_plan(int B, int H, int N, int gemm_mode, int surgery, 
     const int v[EXCEL_ATTN_PLAN_INTS] = {p.path, p.ntiles, p.ntw, p.nw, p.nw_full, p.rp_ntypes, p.rp_grid[0], p.rp_grid[1], p.rp_grid[2],
                                          p.grid[0], p.grid[1], p.grid[2], p.block, p.split_c};
     for (int i = 0; i < EXCEL_ATTN_PLAN_INTS; ++i) plan[i] = v[i];
+    return EXCEL_OK;
+}
+
+extern "C" int excel_patch_text_cam_plan(int B, int N, int C, int T, int gemm_mode, int32_t* plan) {
+    EXCEL_CHECK_ARG(plan && B >= 1 && B <= 65535 && N >= 1 && N <= (1 << 20) && T >= 1 && T <= PTC_WIDE_T && C >= 32 && C <= 1024 && (C % 32) == 0 &&
+                    gemm_mode >= 0 && gemm_mode <= 3, "patch_text_cam_plan: bad argument");
+    const CamPlan p = cam_plan(B, N, C, T, gemm_mode);
+    const int v[EXCEL_CAM_PLAN_INTS] = {p.kernel, p.split, p.ct, p.tlds, p.G, p.prep_grid[0], p.prep_grid[1], p.prep_grid[2], p.sim_grid[0],
+                                        p.sim_grid[1], p.block, p.finish_grid[0], p.finish_grid[1], p.finish_pitch};
+    for (int i = 0; i < EXCEL_CAM_PLAN_INTS; ++i) plan[i] = v[i];
     return EXCEL_OK;
 }
 

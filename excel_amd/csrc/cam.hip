@@ -183,10 +183,7 @@ int excel_launch_cam_epilogue(float* S, float* out_full, float* out_slice, int B
 //      un-normalised similarities go to a [B,N,ldT] scratch (4.5 MB at B = 32), per-workgroup per-class min / max to a partial table;
 //   3. patch_text_finish_kernel: min / max over the partials (exact and order-independent), attr = (sim - min) / (max - min), slice.
 // The normalised features f are never written unless the caller asks for them (generate_clip_fts' return value).
-#define PTC_MAXCT 4            // class tiles of 32 held in accumulators at once: T <= 128 in one pass, wider vocabularies in chunks
-#define PTC_WIDE_T 512         // rows of the wide path (patch_text_sim_wide_kernel)
-#define PTC_NW 4               // waves (= token tiles) per workgroup
-#define PTC_HB 64              // tokens per column-norm block
+// (PTC_MAXCT, PTC_WIDE_T, PTC_NW, PTC_HB and the LDS text bank's PTC_TLDS_ROWS x PTC_TLDS_C: excel_internal.h, next to cam_plan())
 struct PtcArgs {
     const float* x_raw;            // [B,N,C]
     const float* text;             // [T,C] fp32
@@ -248,8 +245,6 @@ __device__ __forceinline__ float half_max(float v) {
 // the same rows, and fragment loads of 16 bytes per lane from 32 different rows are address-bound in the vector memory path (measured:
 // 2/3 of the kernel's 41 us with text and x both read as per-lane row pieces).  x_raw tiles are read COALESCED (8 lanes = one 128-byte
 // row piece) and turned into MFMA operand order through a wave-private LDS tile.
-#define PTC_TLDS_ROWS 48
-#define PTC_TLDS_C 512
 #define PTC_XP 36              // LDS pitch (floats) of the 32 x 32 x-tile: conflict-free 16-byte operand reads
 #define PTC_PFB 4              // 32-column blocks of x in flight per wave
 template <bool BF, int CT, bool TLDS>
@@ -740,10 +735,10 @@ __global__ __launch_bounds__(256) void patch_text_finish_kernel(PtcArgs p) {
     }
 }
 
-static inline int ptc_groups(int N) { return cdiv(cdiv(N, 32), PTC_NW); }
 size_t excel_patch_text_cam_ws_floats(int B, int N, int C, int T, int which) {
+    const CamPlan pl = cam_plan(B, N, C, T, 0);                // G and the table's pitch are the same in every mode
     if (which == 0) return (size_t)B * N * ((T + 3) / 4 * 4);
-    if (which == 1) return (size_t)B * ptc_groups(N) * 2 * (T <= PTC_MAXCT * 32 ? PTC_MAXCT * 32 : PTC_WIDE_T);
+    if (which == 1) return (size_t)B * pl.G * 2 * pl.finish_pitch;
     return (size_t)B * cdiv(N, PTC_HB) * C;
 }
 
@@ -759,21 +754,32 @@ int excel_launch_patch_text_cam(const float* x_raw, const float* text, unsigned 
     // the kernels read x_raw / text / the split text and write feats with 16-byte vectors
     EXCEL_CHECK_ARG((((uintptr_t)x_raw | (uintptr_t)text | (uintptr_t)text_split | (uintptr_t)feats | (uintptr_t)sim_ws) & 15) == 0,
                     "patch_text_cam: x_raw, text, image_features and the workspace must be 16-byte aligned");
-    const int G = ptc_groups(N);
-    PtcArgs a{x_raw, text, text_split, sim_ws, part_ws, colsq_ws, out_full, out_slice, feats, N, C, T, F, ldT, G, temp};
-    hipLaunchKernelGGL(patch_text_prep_kernel, dim3(cdiv(N, PTC_HB), B, cdiv(C, 256) + 1), dim3(256), 0, st, a, bf ? text_split_out : nullptr);
-    const int ct = cdiv(T, 32);
-#define PTC_LAUNCH(BFV, CTV, TL) hipLaunchKernelGGL((patch_text_sim_kernel<BFV, CTV, TL>), dim3(G, B), dim3(PTC_NW * 64), 0, st, a)
-    if (T > PTC_MAXCT * 32) {
-        if (bf) hipLaunchKernelGGL((patch_text_sim_wide_kernel<true>), dim3(G, B), dim3(PTC_NW * 64), 0, st, a);
-        else hipLaunchKernelGGL((patch_text_sim_wide_kernel<false>), dim3(G, B), dim3(PTC_NW * 64), 0, st, a);
-    } else if (bf) {
-        if (T <= PTC_TLDS_ROWS && C <= PTC_TLDS_C && (C % 256) == 0) { if (ct <= 1) PTC_LAUNCH(true, 1, true); else PTC_LAUNCH(true, 2, true); }
-        else { if (ct <= 2) PTC_LAUNCH(true, 2, false); else PTC_LAUNCH(true, 4, false); }
-    } else { if (ct <= 1) PTC_LAUNCH(false, 1, false); else if (ct == 2) PTC_LAUNCH(false, 2, false); else PTC_LAUNCH(false, 4, false); }
+    // which instance runs, and on which grids, is cam_plan()'s decision alone (cam_plan.hip): this function launches what the plan names
+    // (this translation unit's split type is the caller's: the split modes choose alike)
+    const CamPlan pl = cam_plan(B, N, C, T, bf ? 1 : 0);
+    PtcArgs a{x_raw, text, text_split, sim_ws, part_ws, colsq_ws, out_full, out_slice, feats, N, C, T, F, ldT, pl.G, temp};
+    hipLaunchKernelGGL(patch_text_prep_kernel, dim3(pl.prep_grid[0], pl.prep_grid[1], pl.prep_grid[2]), dim3(256), 0, st, a,
+                       bf ? text_split_out : nullptr);
+    const dim3 sim_grid(pl.sim_grid[0], pl.sim_grid[1]), fin_grid(pl.finish_grid[0], pl.finish_grid[1]);
+#define PTC_LAUNCH(BFV, CTV, TL) hipLaunchKernelGGL((patch_text_sim_kernel<BFV, CTV, TL>), sim_grid, dim3(pl.block), 0, st, a)
+    if (pl.kernel == CAM_WIDE) {
+        if (pl.split) hipLaunchKernelGGL((patch_text_sim_wide_kernel<true>), sim_grid, dim3(pl.block), 0, st, a);
+        else hipLaunchKernelGGL((patch_text_sim_wide_kernel<false>), sim_grid, dim3(pl.block), 0, st, a);
+    } else {
+        switch (pl.split * 100 + pl.ct * 10 + pl.tlds) {       // the seven narrow instances
+            case 111: PTC_LAUNCH(true, 1, true); break;
+            case 121: PTC_LAUNCH(true, 2, true); break;
+            case 120: PTC_LAUNCH(true, 2, false); break;
+            case 140: PTC_LAUNCH(true, 4, false); break;
+            case 10: PTC_LAUNCH(false, 1, false); break;
+            case 20: PTC_LAUNCH(false, 2, false); break;
+            case 40: PTC_LAUNCH(false, 4, false); break;
+            default: EXCEL_CHECK_ARG(false, "patch_text_cam: the plan names no instance (split=%d ct=%d tlds=%d)", pl.split, pl.ct, pl.tlds);
+        }
+    }
 #undef PTC_LAUNCH
-    if (T <= PTC_MAXCT * 32) hipLaunchKernelGGL((patch_text_finish_kernel<PTC_MAXCT * 32>), dim3(cdiv(N, 64), B), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((patch_text_finish_kernel<PTC_WIDE_T>), dim3(cdiv(N, 64), B), dim3(256), 0, st, a);
+    if (pl.finish_pitch == PTC_MAXCT * 32) hipLaunchKernelGGL((patch_text_finish_kernel<PTC_MAXCT * 32>), fin_grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((patch_text_finish_kernel<PTC_WIDE_T>), fin_grid, dim3(256), 0, st, a);
     EXCEL_CHECK_LAUNCH("patch_text_cam");
     return EXCEL_OK;
 }

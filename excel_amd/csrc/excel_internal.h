@@ -85,6 +85,28 @@ struct AttnPlan {
     int split_c;               // strip with both sweeps: strips per XCD chunk (StripArgs::split_c), else 0
 };
 AttnPlan attn_plan(int B, int H, int N, int gemm_mode, int surgery, int want_w);
+// Kernel selection of the fused patch-text CAM (cam_plan.hip): which instance of the similarity kernel runs for (mode, T, C), with the
+// grids of its three launches.  Host arithmetic on integers, shared by the launcher (cam.hip: it launches exactly what the plan names)
+// and the host query of the C ABI (excel_patch_text_cam_plan).
+enum { CAM_NARROW = 0, CAM_WIDE = 1 };
+constexpr int PTC_MAXCT = 4;          // class tiles of 32 held in accumulators at once: T <= 128 in one pass, wider vocabularies in chunks
+constexpr int PTC_WIDE_T = 512;       // rows of the wide path (patch_text_sim_wide_kernel)
+constexpr int PTC_NW = 4;             // waves (= token tiles) per workgroup
+constexpr int PTC_HB = 64;            // tokens per column-norm block
+constexpr int PTC_TLDS_ROWS = 48;     // the split text bank is staged in LDS up to this many rows ...
+constexpr int PTC_TLDS_C = 512;       // ... of this many columns (and C % 256 == 0: whole 1-KB LDS-DMA pieces per split row)
+struct CamPlan {
+    int kernel;                // CAM_NARROW: patch_text_sim_kernel<split, ct, tlds> (T <= 128); CAM_WIDE: patch_text_sim_wide_kernel<split>
+    int split;                 // a split-plane mode (bf16x3, f16x3, f16x2): 16-bit MFMAs on hi / lo planes; 0: exact fp32
+    int ct;                    // narrow: the instantiated class tiles of 32 (1 / 2 / 4); wide: 0
+    int tlds;                  // narrow split instances: the text bank is staged in LDS
+    int G;                     // workgroups per image: cdiv(cdiv(N, 32), PTC_NW)
+    int prep_grid[3];          // patch_text_prep_kernel, 256 threads
+    int sim_grid[2], block;    // the similarity kernel
+    int finish_grid[2];        // patch_text_finish_kernel<finish_pitch>, 256 threads
+    int finish_pitch;          // row pitch of the per-workgroup min / max table: 128 (narrow) or 512 (wide)
+};
+CamPlan cam_plan(int B, int N, int C, int T, int gemm_mode);
 // the plain half matrix of the weights, [N][ldbh] at a 16-byte aligned address, can feed the compact-weight four-wave instances
 inline bool gemm_half_ok(bool aligned, int N, int K, int ldbh) {
     return aligned && ldbh >= K && (ldbh & 7) == 0 && (long long)N * ldbh * 2 < 0x7fffffffLL;

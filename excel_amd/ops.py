@@ -129,6 +129,20 @@ def attn_plan(B, H, N, mode="bf16x3", surgery=True, want_w=True):
                 grid=tuple(v[9:12]), block=v[12], split_c=v[13])
 
 
+CAM_PLAN_KERNELS = ("narrow", "wide")                             # excel_patch_text_cam_plan (include/excel_hip.h)
+
+
+def cam_plan(B, N, C_, T, mode="bf16x3"):
+    """The kernels patch_text_cam runs B images of N tokens x C_ columns against T text rows on in `mode` (host arithmetic only): the
+    similarity kernel ("narrow": T <= 128, instance <split, ct class tiles of 32, tlds = text bank staged in LDS>; "wide": class chunks,
+    ct = 0), the workgroups per image and the grids of the prep / similarity / finish launches, the pitch of the min / max table."""
+    plan = (C.c_int32 * 14)()
+    check(lib().excel_patch_text_cam_plan(B, N, C_, T, GEMM_MODES[mode], plan), "excel_patch_text_cam_plan")
+    v = list(plan)
+    return dict(kernel=CAM_PLAN_KERNELS[v[0]], split=bool(v[1]), ct=v[2], tlds=bool(v[3]), groups=v[4], prep_grid=tuple(v[5:8]),
+                sim_grid=tuple(v[8:10]), block=v[10], finish_grid=tuple(v[11:13]), finish_pitch=v[13])
+
+
 def layernorm(x, w, b, eps=1e-5):
     D = x.shape[-1]
     y = torch.empty_like(x)

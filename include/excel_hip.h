@@ -87,6 +87,18 @@ int excel_gemm_plan(int M, int N, int K, int batch, int out_mode, int has_residu
  *   chunk when the strip kernel's two sweeps run as separate workgroups (surgery and want_w), else 0.  Unused fields are 0. */
 #define EXCEL_ATTN_PLAN_INTS 14
 int excel_attn_plan(int B, int H, int N, int gemm_mode, int surgery, int want_w, int32_t* plan /*host*/);
+/* Which kernels excel_patch_text_cam runs B images of N tokens x C columns against T text rows on (a HOST function: no device work; the
+ * launcher itself launches what this names).  gemm_mode as in excel_vit_set_gemm_mode (0 f32, 1 bf16x3, 2 f16x3, 3 f16x2: the CAM runs
+ * f16x2 as f16x3).  1 <= T <= 512, C a multiple of 32 up to 1024.
+ * plan[EXCEL_CAM_PLAN_INTS] = {kernel, split, ct, tlds, groups, prep_grid x, y, z, sim_grid x, y, block, finish_grid x, y, finish_pitch}:
+ *   kernel: 0 the narrow similarity kernel (T <= 128: all classes in the accumulators at once), 1 the wide one (class chunks of 128);
+ *   split: 1 in the split-plane modes (three 16-bit MFMAs per product), 0 exact fp32;  ct: the narrow instance's class tiles of 32
+ *   (1 / 2 / 4; 0 for the wide kernel);  tlds: the narrow split instance stages the text bank in LDS (T <= 48, C <= 512, C % 256 == 0:
+ *   ct = 1 / 2; otherwise the split instances are ct = 2 / 4 and the f32 ones 1 / 2 / 4);  groups = cdiv(cdiv(N, 32), 4) workgroups per
+ *   image;  prep_grid (cdiv(N, 64), B, cdiv(C, 256) + 1) and finish_grid (cdiv(N, 64), B) of 256 threads, sim_grid (groups, B) of `block`;
+ *   finish_pitch: row pitch of the per-workgroup min / max table (128 narrow, 512 wide). */
+#define EXCEL_CAM_PLAN_INTS 14
+int excel_patch_text_cam_plan(int B, int N, int C, int T, int gemm_mode, int32_t* plan /*host*/);
 
 /* LayerNorm over the last dim, fp32, eps as given (clip/clip_surgery_model.py:271-277). */
 int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream);
