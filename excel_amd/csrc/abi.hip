@@ -17,7 +17,7 @@ void excel_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* excel_last_error(void) { return g_err; }
-extern "C" int excel_abi_version(void) { return 5; }
+extern "C" int excel_abi_version(void) { return 6; }
 #ifndef EXCEL_BUILD_ID
 #define EXCEL_BUILD_ID "unstamped"
 #endif

@@ -43,14 +43,18 @@ class CocoDataset:
 class CocoSegDataset(CocoDataset):
     """(name, image uint8 [h,w,3], label uint8 [h,w], cls_label f32 [80]); `batch` as in datasets/voc.VOC12SegDataset."""
 
-    def __init__(self, root_dir=None, name_list_dir=None, split="val", stage="val", ignore_index=255, **kwargs):
+    def __init__(self, root_dir=None, name_list_dir=None, split="val", stage="val", ignore_index=255, cls_labels_optional=False, **kwargs):
+        """`cls_labels_optional`: as in datasets/voc.VOC12SegDataset (a run that predicts its tags needs no cls_labels_onehot.npy)."""
         super().__init__(root_dir, name_list_dir, split, stage)
         self.ignore_index = ignore_index
-        self.label_list = load_cls_label_list(name_list_dir) if stage != "test" else None
+        self.has_cls_labels = stage != "test"
+        if cls_labels_optional and not os.path.isfile(os.path.join(name_list_dir, "cls_labels_onehot.npy")):
+            self.has_cls_labels = False
+        self.label_list = load_cls_label_list(name_list_dir) if self.has_cls_labels else None
 
     def __getitem__(self, idx):
         full, short, image, label = super().__getitem__(idx)
-        cls = np.zeros(len(class_list) - 1, np.float32) if self.stage == "test" else np.asarray(self.label_list[full], np.float32)
+        cls = np.zeros(len(class_list) - 1, np.float32) if self.label_list is None else np.asarray(self.label_list[full], np.float32)
         return full, np.ascontiguousarray(image[..., :3], np.uint8), np.ascontiguousarray(label, np.uint8), cls
 
     def max_k(self):

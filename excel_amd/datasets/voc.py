@@ -54,14 +54,21 @@ class VOC12SegDataset(VOC12Dataset):
     """Inference-time samples: (name, image uint8 [h,w,3], label uint8 [h,w], cls_label f32 [20]).  `batch` keeps the calling
     convention of tools/synthetic.SyntheticSegDataset so tools/infer_lam.build_validation can consume either."""
 
-    def __init__(self, root_dir=None, name_list_dir=None, split="val", stage="val", ignore_index=255, **kwargs):
+    def __init__(self, root_dir=None, name_list_dir=None, split="val", stage="val", ignore_index=255, cls_labels_optional=False,
+                 num_fg=None, **kwargs):
+        """`cls_labels_optional` (a run that predicts its tags, tools/infer_lam --tags clip): without cls_labels_onehot.npy the samples
+        carry rows of `num_fg` zeros and `has_cls_labels` is False; with the file nothing changes (its rows then score the tagger)."""
         super().__init__(root_dir, name_list_dir, split, stage)
         self.ignore_index = ignore_index
-        self.label_list = load_cls_label_list(name_list_dir) if stage != "test" else None
+        self.num_fg = int(num_fg) if num_fg else len(class_list) - 1
+        self.has_cls_labels = stage != "test"
+        if cls_labels_optional and not os.path.isfile(os.path.join(name_list_dir, "cls_labels_onehot.npy")):
+            self.has_cls_labels = False
+        self.label_list = load_cls_label_list(name_list_dir) if self.has_cls_labels else None
 
     def __getitem__(self, idx):
         name, image, label = super().__getitem__(idx)
-        cls = np.zeros(len(class_list) - 1, np.float32) if self.stage == "test" else np.asarray(self.label_list[name], np.float32)
+        cls = np.zeros(self.num_fg, np.float32) if self.label_list is None else np.asarray(self.label_list[name], np.float32)
         return name, np.ascontiguousarray(image[..., :3], np.uint8), np.ascontiguousarray(label, np.uint8), cls
 
     def max_k(self):

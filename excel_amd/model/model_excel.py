@@ -129,6 +129,7 @@ class ExCEL_model:
         _, attr_maps_raw, _ = ops.patch_text_cam(r["x_raw"], self._text_rows, num_fg=self.num_classes - 1,
                                                  mode=self.encoder.visual.handle().gemm_mode())
         self.last_all_feats = all_feats
+        self.last_x_raw = r["x_raw"]        # (a reference, like last_all_feats: row 0 of every image is what image_tags reads)
         seg = attn_fts = attn_pred = None
         if self._dec is not None:
             attn_fts, seg = self._dec.forward(all_feats)                                                                # :60-68
@@ -156,6 +157,18 @@ class ExCEL_model:
         r = self.encoder.encode_image(img, True, None, want_w_aff=False, n_attn_out=0, want_raw=True, want_features=False)
         return ops.patch_text_cam(r["x_raw"], self._text_rows, num_fg=self.num_classes - 1,
                                   mode=self.encoder.visual.handle().gemm_mode())[1]
+
+    def image_tags(self, thre=0.2, kmax=6, scale=100.0, x_raw=None):
+        """CLIP's zero-shot tags of the images of the last forward() -> (onehot [B,F], scores [B,F]) on the device, F = num_classes - 1:
+        ops.clip_tags over row 0 of `last_x_raw` - CLIP's own image embedding, the reference puts the class token of the original
+        path back before ln_post / proj (clip/clip_surgery_model.py:442-446) - and the text rows the CAM uses.  attr_maps() and
+        seg_logits() leave last_x_raw alone: under flip / multi-scale the tags are those of the un-mirrored scale-1.0 pass, the pass
+        that supplies the affinity.  `x_raw` overrides the kept tensor ([B,N,C] or [B,C])."""
+        if x_raw is None:
+            x_raw = getattr(self, "last_x_raw", None)
+            if x_raw is None:
+                raise RuntimeError("image_tags reads the x_raw of the last forward(): call the model first, or pass x_raw=")
+        return ops.clip_tags(x_raw, self._text_rows, self.num_classes - 1, scale=scale, thre=thre, kmax=kmax)
 
     def check_numerics(self, img, tol=5e-4, fallback=True, reduce=None):
         """Guard of the fast matrix-core modes on the caller's OWN weights and images.  "bf16x3" carries 16 mantissa bits per operand:

@@ -1514,6 +1514,32 @@ def nonfinite_count(x, out=None, init=True):
     return out
 
 
+# ------------------------------------------------------------------ image tags (include/excel_hip.h, "image tags")
+def clip_tags(x, text_rows, num_fg, scale=100.0, thre=0.2, kmax=6, want_scores=True):
+    """CLIP's zero-shot tags of B images -> (onehot [B,num_fg] f32, scores [B,num_fg] f32 or None): the rows cls_compact reads.
+    x: [B,N,C] (row 0 of every image is used where it lies: the tower's x_raw, whose class-token row is CLIP's image embedding) or a
+    compact [B,C]; text_rows [T,C], the num_fg foreground rows first.  scores = the softmax over ALL T rows of scale * cosine; a class is
+    tagged when it is among the kmax best foreground scores and reaches thre times the best one (the best is always tagged; a tie goes to
+    the lower index).  A row with a non-finite logit gets class 0 alone and NaN scores.  One launch, no scratch memory, no synchronisation."""
+    if x.dim() not in (2, 3):
+        raise ValueError(f"clip_tags: x must be [B,N,C] or [B,C], got {tuple(x.shape)}")
+    x = f32c(x)
+    text_rows = f32c(text_rows)
+    B, C_ = int(x.shape[0]), int(x.shape[-1])
+    stride = int(x.shape[1]) * C_ if x.dim() == 3 else C_
+    T = int(text_rows.shape[0])
+    if text_rows.dim() != 2 or int(text_rows.shape[1]) != C_:
+        raise ValueError(f"clip_tags: text_rows must be [T,{C_}], got {tuple(text_rows.shape)}")
+    if x.data_ptr() % 16 or text_rows.data_ptr() % 16:       # a view at an odd offset: the kernel reads 16 bytes at a time
+        x = x.clone() if x.data_ptr() % 16 else x
+        text_rows = text_rows.clone() if text_rows.data_ptr() % 16 else text_rows
+    onehot = torch.empty((B, int(num_fg)), dtype=torch.float32, device=x.device)
+    scores = torch.empty((B, int(num_fg)), dtype=torch.float32, device=x.device) if want_scores else None
+    check(lib().excel_clip_tags(_p(x), stride, _p(text_rows), B, C_, T, int(num_fg), float(scale), float(thre), int(kmax), _p(onehot),
+                                _p(scores), _stream()), "excel_clip_tags")
+    return onehot, scores
+
+
 def confusion_accumulate_masked(gt_u8, pred_u8, num_classes, skip, hist=None, plan=None):
     """confusion_accumulate over the images with skip[b] == 0 (skip: int32 [B], device - e.g. nonfinite_count's counters).
     plan=None: gt / pred are uniform [B,H,W] maps; with a RaggedPlan they are its tight label maps back to back."""

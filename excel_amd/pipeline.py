@@ -103,6 +103,49 @@ class GuardTicket:
         return self._host.numpy()
 
 
+class TagTicket:
+    """The predicted tags of one step on their way to the host (the GuardTicket pattern): pinned float32 [B,F] copies of the one-hot
+    rows and the scores, and the event recorded behind them on the step's stream.  ready() never blocks; tags() waits for the event."""
+
+    def __init__(self, onehot, scores, event):
+        self._onehot, self._scores, self._event = onehot, scores, event
+
+    def ready(self):
+        return self._event.query()
+
+    def tags(self):
+        """-> (onehot [B,F], scores [B,F]) as numpy arrays"""
+        self._event.synchronize()
+        return self._onehot.numpy(), self._scores.numpy()
+
+
+def check_tagger(tagger, smax, num_classes):
+    """tagger = dict(thre=, kmax=, scale=) of the predicted image tags (ops.clip_tags; defaults 0.2 / smax / 100.0) -> the complete dict,
+    or None.  Refused, naming `tagger`: an unknown key, thre outside [0, 1], scale <= 0, kmax outside [1, num_classes - 1] and
+    kmax != smax - the compacted class list has smax slots, and the tagger is what caps the number of present classes."""
+    if tagger is None:
+        return None
+    if not isinstance(tagger, dict) or set(tagger) - {"thre", "kmax", "scale"}:
+        raise ValueError(f"tagger must be a dict with the keys thre, kmax, scale (got {tagger!r})")
+    out = dict(thre=float(tagger.get("thre", 0.2)), kmax=int(tagger.get("kmax", smax)), scale=float(tagger.get("scale", 100.0)))
+    if not 0.0 <= out["thre"] <= 1.0:
+        raise ValueError(f"tagger: thre {out['thre']} is outside [0, 1] (it is relative to the best foreground score)")
+    if not out["scale"] > 0.0:
+        raise ValueError(f"tagger: scale {out['scale']} must be positive (CLIP's logit scale is 100)")
+    if not 1 <= out["kmax"] <= int(num_classes) - 1:
+        raise ValueError(f"tagger: kmax {out['kmax']} is outside [1, {int(num_classes) - 1}] (num_classes - 1 foreground classes)")
+    if out["kmax"] != int(smax):
+        raise ValueError(f"tagger: kmax {out['kmax']} must equal smax {smax}: the compacted class list has smax slots and the tagger is "
+                         "what caps the number of present classes")
+    return out
+
+
+def _refuse_tagger(who, tagger):
+    if tagger is not None:
+        raise ValueError(f"{who} has no predicted image tags (tagger={tagger!r}): the option belongs to the training-free regime "
+                         "(TrainingFreePipeline.run_batch / run_batch_ragged)")
+
+
 MAX_NUM_CLASSES = 255      # background + 254 foreground classes
 
 
@@ -116,7 +159,7 @@ def check_num_classes(num_classes):
 
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False):
+                 tta_scales=None, tta_flip=False, tagger=None):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -130,7 +173,12 @@ class TrainingFreePipeline:
         `tta_scales` / `tta_flip` = test-time augmentation of the LAMs (utils/camutils.py:8-63), off by default (None / False, also for
         the single scale (1.0,) without flip: today's step, launch for launch).  With it, run_batch / run_batch_ragged run the model once
         per scale of `tta_scales` (tta_sizes: 1.0 must be among them) on [x; mirror x] (tta_flip) and ops.lam_tta_fuse fuses the maps at
-        the patch grid of scale 1.0 into the `attr` the random walk reads; the affinity is that of the un-mirrored scale-1.0 pass."""
+        the patch grid of scale 1.0 into the `attr` the random walk reads; the affinity is that of the un-mirrored scale-1.0 pass.
+        `tagger` = dict(thre=, kmax=, scale=) (check_tagger; kmax must equal smax), off by default (None: today's step, launch for
+        launch).  With it, run_batch / run_batch_ragged ignore the values of `cls_labels` (None is accepted): right after the scale-1.0
+        forward, model.image_tags predicts the one-hot rows on the device (ops.clip_tags over CLIP's image embedding and the text rows)
+        and those go to ops.cls_compact.  They stay in `last_tags` = (onehot, scores) (device [B,F], until the next step) and travel to
+        the host behind `last_tag_ticket` (a TagTicket) - no synchronisation.  Everything behind cls_compact is untouched."""
         if guard not in GUARD_MODES:
             raise ValueError(f"guard must be one of {GUARD_MODES} (got {guard!r})")
         self.guard = guard
@@ -147,6 +195,8 @@ class TrainingFreePipeline:
         self.num_iter = num_iter
         self.caa_thre = caa_thre
         self.smax = smax
+        self.tagger = check_tagger(tagger, smax, num_classes)
+        self.last_tags = self.last_tag_ticket = None
         self.hist = None
         self.hist_conf = None               # the confident labels' matrix (run_batch_ragged(conf=)): counts the kept pixels only
         self.last_conf_labels = None
@@ -193,6 +243,28 @@ class TrainingFreePipeline:
         ev.record()
         self.last_flags, self.last_guard = flags, GuardTicket(host, ev)
         return flags
+
+    # ------------------------------------------------------------------ predicted image tags
+    def _tags(self, cls_labels):
+        """Without a tagger: the caller's one-hot rows.  With one: the rows model.image_tags predicts from the forward that has just run
+        (the un-mirrored scale-1.0 pass), kept in last_tags, plus their pinned copy and event (last_tag_ticket) on the step's stream."""
+        if self.tagger is None:
+            return cls_labels
+        onehot, scores = self.model.image_tags(**self.tagger)
+        self.last_tags = (onehot, scores)
+        h1 = torch.empty(onehot.shape, dtype=torch.float32, pin_memory=True)
+        h2 = torch.empty(scores.shape, dtype=torch.float32, pin_memory=True)
+        h1.copy_(onehot, non_blocking=True)
+        h2.copy_(scores, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.last_tag_ticket = TagTicket(h1, h2, ev)
+        return onehot
+
+    def _no_tagger(self, what):
+        if self.tagger is not None:
+            raise ValueError(f"{what} has no predicted image tags (tagger={self.tagger!r}): use run_batch or run_batch_ragged, or build "
+                             "the pipeline without tagger")
 
     def _score(self, gts, labels, flags, plan=None, into="hist"):
         """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
@@ -251,10 +323,11 @@ class TrainingFreePipeline:
             return self.model.attr_maps(x)
         return torch.cat([self.model.attr_maps(x[lo:lo + step]) for lo in range(0, n, step)], 0)
 
-    def _tta_attr(self, S, make_input):
+    def _tta_attr(self, S, make_input, cls_labels=None):
         """One model pass per scale (tta_sizes(S, tta_scales): 1.0 first) over make_input(S_s) = [B or 2B, 3, S_s, S_s], then the fuse.
         Scale 1.0's un-mirrored half runs as the plain step does and supplies the affinity (tools/infer_lam.py:79 before :82); every
-        other pass asks the tower for the maps alone.  -> (attr [B,P,F], attn_weights of scale 1.0)"""
+        other pass asks the tower for the maps alone; with a tagger that pass also supplies the tags (_tags).
+        -> (attr [B,P,F], attn_weights of scale 1.0, the step's one-hot rows)"""
         g = S // 16
         maps, grids, attn_w = [], [], None
         for S_s, g_s in tta_sizes(S, self.tta_scales):
@@ -262,25 +335,27 @@ class TrainingFreePipeline:
             B = x.shape[0] // 2 if self.tta_flip else x.shape[0]
             if attn_w is None:
                 _, _, m, attn_w, _ = self.model(x[:B])                                              # infer_lam.py:79
+                cls_labels = self._tags(cls_labels)
                 if self.tta_flip:
                     m = torch.cat([m, self._tta_maps(x[B:], g * g)], 0)
             else:
                 m = self._tta_maps(x, g * g)
             maps.append(m)
             grids.append(g_s)
-        return ops.lam_tta_fuse(maps, grids, g, self.tta_flip), attn_w
+        return ops.lam_tta_fuse(maps, grids, g, self.tta_flip), attn_w, cls_labels
 
     @torch.no_grad()
     def run_batch(self, inputs, cls_labels, gts=None, label_hw=None, return_intermediates=False):
-        """inputs [B,3,S,S] f32 (normalised, already at the network size), cls_labels [B,F] f32 one-hot,
-        gts [B,H,W] uint8 (255 = ignore) or None.  Returns labels [B,H,W] uint8 (device)."""
+        """inputs [B,3,S,S] f32 (normalised, already at the network size), cls_labels [B,F] f32 one-hot (ignored, and may be None, when the
+        pipeline has a tagger), gts [B,H,W] uint8 (255 = ignore) or None.  Returns labels [B,H,W] uint8 (device)."""
         B, _, S, _ = inputs.shape
         g = S // 16
         H, W = (gts.shape[-2:] if gts is not None else (label_hw or (S, S)))
         if self.tta:
-            attr, attn_w = self._tta_attr(S, lambda S_s: self._tta_uniform_input(inputs, S_s))
+            attr, attn_w, cls_labels = self._tta_attr(S, lambda S_s: self._tta_uniform_input(inputs, S_s), cls_labels)
         else:
             _, _, attr, attn_w, _ = self.model(inputs)                                              # infer_lam.py:79
+            cls_labels = self._tags(cls_labels)
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
         flags = self._guard_count(attr, attn_w.w_aff, refined)
@@ -311,7 +386,8 @@ class TrainingFreePipeline:
     @torch.no_grad()
     def run_batch_ragged(self, hwc_packed, plan, cls_labels, gts_packed=None, S=448, return_intermediates=False, conf=None):
         """hwc_packed: the decoded uint8 [H_b,W_b,3] images back to back (device); plan = ops.RaggedPlan of their sizes;
-        cls_labels [B,F] f32 one-hot; gts_packed: the uint8 [H_b,W_b] ground-truth maps back to back (255 = ignore) or None.
+        cls_labels [B,F] f32 one-hot (ignored, and may be None, when the pipeline has a tagger); gts_packed: the uint8 [H_b,W_b]
+        ground-truth maps back to back (255 = ignore) or None.
         Returns the labels as one flat uint8 tensor (image b = plan.label(labels, b)).
         Without `return_intermediates` the cams / PAR output live in uninitialised step buffers (see _buf: pad columns and unused
         channels are undefined); with it they are fresh tensors whose unused parts are zero.
@@ -331,11 +407,12 @@ class TrainingFreePipeline:
                 x = self._tta_ragged_input(hwc_packed, plan, S_s, "inputs" if not first else "tta_inputs")
                 first.append(x)
                 return x
-            attr, attn_w = self._tta_attr(S, make)
+            attr, attn_w, cls_labels = self._tta_attr(S, make, cls_labels)
             inputs = first[0][:B]
         else:
             inputs = ops.normalize_resize_u8_ragged(hwc_packed, plan, S, out=self._buf("inputs", B * 3 * S * S, device=dev).view(B, 3, S, S))  # voc.py:115, infer_lam.py:74
             _, _, attr, attn_w, _ = self.model(inputs)                                              # infer_lam.py:79
+            cls_labels = self._tags(cls_labels)
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
         flags = self._guard_count(attr, attn_w.w_aff, refined)
@@ -389,6 +466,7 @@ class TrainingFreePipeline:
         """Same contract as run_batch; the returned labels and self.hist are complete only after drain()."""
         self._no_guard("run_batch_split")
         self._no_tta("run_batch_split")
+        self._no_tagger("run_batch_split")
         B, _, S, _ = inputs.shape
         nsplit = max(1, min(nsplit, B))
         if nsplit == 1:
@@ -433,6 +511,7 @@ class TrainingFreePipeline:
     def run_batch_overlapped(self, inputs, cls_labels, gts=None, label_hw=None):
         self._no_guard("run_batch_overlapped")
         self._no_tta("run_batch_overlapped")
+        self._no_tagger("run_batch_overlapped")
         sa, sb = self._streams()
         cur = torch.cuda.current_stream()
         B, _, S, _ = inputs.shape
@@ -491,9 +570,10 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False):
+                 tta_scales=None, tta_flip=False, tagger=None):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
+        _refuse_tagger("OptimisedLamPipeline", tagger)
         if getattr(model, "_dec", None) is None:
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
@@ -559,9 +639,10 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False):
+                 tta_scales=None, tta_flip=False, tagger=None):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
+        _refuse_tagger("ValidationPipeline", tagger)
         if getattr(model, "_dec", None) is None:
             raise ValueError("ValidationPipeline needs the decoder head: build ExCEL_model(..., decoder_state_dict=)")
         if guard is not None:

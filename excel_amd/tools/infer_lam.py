@@ -51,6 +51,17 @@ Differences from the reference, all deliberate:
     written as palette PNGs `<conf_label_dir>/<name>.png` by the device encoder and scored into a second device-side confusion matrix
     that is gathered once like the main one: the log shows `conf_label_score` (over the kept pixels) and the coverage (kept / scored
     pixels).  The overflow guard covers it; --api_path true runs the same arithmetic per image (affutils.conf_labels_image);
+  * `--tags clip` (training-free regime, batched loop; default `labels` = cls_labels_onehot.npy): the present classes of every image are
+    predicted on the device right after the scale-1.0 forward, from CLIP's own image embedding (row 0 of x_raw, the class token the
+    reference puts back at clip/clip_surgery_model.py:442-446) and the class + background prompts (ops.clip_tags: softmax over all prompts
+    at --tag_scale 100, a class within --tag_thre 0.2 of the image's best one, at most --tag_max 6, the best always kept); the reference
+    never tags images itself (its tools carry an unused --tag_threshold 0.2).  The pipeline is built with smax = --tag_max; the rows come
+    back behind a ticket (no wait in the loop) for `--save_tags PATH` (the format of cls_labels_onehot.npy: a later --tags labels run
+    reads it; one all_gather_object, rank 0 writes) and, where image-level labels exist, the third table `tag_score` (per class and micro
+    precision / recall / F1, mean utils/evaluate.multilabel_score).  `--unlabeled true` reads a plain folder of images
+    (datasets/images.ImageListDataset: no SegmentationClassAug, nothing scored, so one of --save_label / --conf_label / --save_tags is
+    required).  --save_cam and the CRF stages size host-side work from the class list and are refused with --tags clip: --save_tags
+    first, then --tags labels.  The default --tag_thre is provisional (tag quality is unmeasured);
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -122,6 +133,94 @@ def resolve_conf(args):
         return check_conf((args.conf_high_thre, args.conf_low_thre))
     except ValueError as e:
         raise ValueError(f"--conf_high_thre / --conf_low_thre: {e}") from None
+
+
+TAG_SOURCES = ("labels", "clip")
+
+
+def resolve_tags(args, have_dataset=False):
+    """--tags / --tag_thre / --tag_max / --tag_scale / --unlabeled / --save_tags -> the `tagger` of TrainingFreePipeline
+    (dict(thre=, kmax=, scale=)) for --tags clip, or None (--tags labels, the default: the image-level labels of cls_labels_onehot.npy).
+    Checked here, before a device or a model is touched (args.num_classes must be settled: resolve_vocabulary runs first); every refusal
+    names its flag.  `have_dataset`: the caller supplies the data set itself (validate(dataset=)), so --unlabeled needs no --data_folder."""
+    flag_defaults(args)
+    if args.tags not in TAG_SOURCES:
+        raise ValueError(f"--tags must be one of {TAG_SOURCES} (got {args.tags!r})")
+    if args.unlabeled:
+        if not args.data_folder and not have_dataset:
+            raise ValueError("--unlabeled true reads a folder of images (--data_folder with JPEGImages/, --list_folder with <infer_set>.txt): "
+                             "--synthetic samples always carry their labels")
+        if not args.list_folder and not have_dataset:
+            raise ValueError("--unlabeled true needs --list_folder: the image ids come from <list_folder>/<infer_set>.txt")
+        if args.crf_post:
+            raise ValueError("--unlabeled true has no ground truth to score: --crf_post scores the DenseCRF labels against it - drop one of the two")
+        if args.api_path:
+            raise ValueError("--unlabeled true runs on the batched loop: --api_path true scores every image against its ground truth")
+        if not (args.save_label or args.conf_label or args.save_tags):
+            raise ValueError("--unlabeled true scores nothing, so the run must write something: give at least one of --save_label true, "
+                             "--conf_label true, --save_tags PATH")
+    if args.save_tags and args.tags != "clip":
+        raise ValueError("--save_tags writes the predicted tags: it needs --tags clip")
+    if args.tags == "labels":
+        return None
+    if not args.training_free:
+        raise ValueError("--tags clip belongs to the training-free regime: --training_free false has no tagger (OptimisedLamPipeline)")
+    if args.api_path:
+        raise ValueError("--tags clip runs on the batched loop: --api_path true is the reference's per-image call sequence, which reads the "
+                         "image-level labels")
+    for flag in ("save_cam", "crf_post", "crf_inline"):
+        if getattr(args, flag):
+            raise ValueError(f"--tags clip cannot feed --{flag} true yet: that stage sizes its work from the host copy of the class list "
+                             "when the step is enqueued, and predicted tags exist on the device only.  Take the two-run route: first "
+                             f"--tags clip --save_tags <list_folder>/cls_labels_onehot.npy, then --tags labels --{flag} true")
+    F = int(args.num_classes) - 1
+    if not 1 <= int(args.tag_max) <= F:
+        raise ValueError(f"--tag_max {args.tag_max} is outside [1, {F}] (num_classes - 1 foreground classes)")
+    if not 0.0 <= float(args.tag_thre) <= 1.0:
+        raise ValueError(f"--tag_thre {args.tag_thre} is outside [0, 1]: the threshold is relative to the best foreground score")
+    if not float(args.tag_scale) > 0.0:
+        raise ValueError(f"--tag_scale {args.tag_scale} must be positive (CLIP's logit scale is 100)")
+    return dict(thre=float(args.tag_thre), kmax=int(args.tag_max), scale=float(args.tag_scale))
+
+
+def tag_report(rows, truth, num_fg):
+    """The predicted tags of a run -> its report.  rows = {name: one-hot [F]} (what --save_tags writes), truth = {name: one-hot [F]} of the
+    image-level labels for the images that have them (may be empty).  -> {"images", "tags_per_image": histogram list (index = number of
+    tags), "scored": images with labels, and for those "counts" {tp, fp, fn, tn} (they add up to scored x F), "per_class_counts" [F][3]
+    (tp, fp, fn), "score" (evaluate.tag_scores) and "image_f1" (mean of evaluate.multilabel_score per image); None without labels}."""
+    from ..utils import evaluate
+    F = int(num_fg)
+    hist = np.zeros(F + 1, np.int64)
+    for r in rows.values():
+        hist[int((np.asarray(r) != 0).sum())] += 1
+    out = {"images": len(rows), "tags_per_image": [int(v) for v in hist[:int(np.flatnonzero(hist).max()) + 1]] if len(rows) else [],
+           "scored": 0, "counts": None, "per_class_counts": None, "score": None, "image_f1": None}
+    names = sorted(n for n in rows if n in truth)
+    if not names:
+        return out
+    P = np.stack([np.asarray(rows[n]) != 0 for n in names])
+    T = np.stack([np.asarray(truth[n]) != 0 for n in names])
+    pc = np.stack([(P & T).sum(0), (P & ~T).sum(0), (~P & T).sum(0)], 1).astype(np.int64)
+    tp, fp, fn = (int(v) for v in pc.sum(0))
+    out.update(scored=len(names), counts={"tp": tp, "fp": fp, "fn": fn, "tn": len(names) * F - tp - fp - fn},
+               per_class_counts=[[int(v) for v in row] for row in pc], score=evaluate.tag_scores(pc),
+               image_f1=float(np.mean([evaluate.multilabel_score(T[i], P[i]) for i in range(len(names))])))
+    return out
+
+
+def save_tags_file(path, rows):
+    """--save_tags: {name: one-hot float32 [F]} in exactly the format of cls_labels_onehot.npy (datasets/voc.load_cls_label_list reads it
+    back), written next to its place and moved there in one step."""
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    tmp = os.path.join(d, f".{os.path.basename(path)}.{os.getpid()}.tmp")
+    try:
+        with open(tmp, "wb") as f:
+            np.save(f, {str(n): np.asarray(rows[n], np.float32) for n in sorted(rows)}, allow_pickle=True)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
 
 
 def _handle_gemm_mode(model):
@@ -296,6 +395,18 @@ def get_parser():
                         "scale is one more model pass; fused at the patch grid in front of the random walk)")
     p.add_argument("--cam_flip", default=False, type=_bool,
                    help="training-free regime: every scale also runs the mirrored image, the two LAMs are fused by their maximum")
+    p.add_argument("--tags", default="labels", choices=list(TAG_SOURCES),
+                   help="where the present classes of an image come from: labels = cls_labels_onehot.npy (default); clip = predicted on the "
+                        "device from CLIP's image embedding and the class / background prompts (training-free regime, batched loop)")
+    p.add_argument("--tag_thre", default=0.2, type=float,
+                   help="--tags clip: a class is tagged when its score reaches this fraction of the image's best class score (the best is always kept)")
+    p.add_argument("--tag_max", default=6, type=int, help="--tags clip: at most this many tags per image (the pipeline's smax)")
+    p.add_argument("--tag_scale", default=100.0, type=float, help="--tags clip: the logit scale in front of the softmax over all prompts")
+    p.add_argument("--save_tags", default=None, type=str,
+                   help="--tags clip: write the predicted tags here in the format of cls_labels_onehot.npy (a later --tags labels run reads them)")
+    p.add_argument("--unlabeled", default=False, type=_bool,
+                   help="a folder of images without ground truth: --data_folder/JPEGImages/<id>.jpg for the ids of --list_folder/<infer_set>.txt; "
+                        "nothing is scored, so give --save_label, --conf_label or --save_tags")
     p.add_argument("--cpu_affinity", default="auto", choices=["auto", "off"],
                    help="auto: with several ranks on the node every rank pins itself (decode pool included) to its own share of the host cores")
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
@@ -676,11 +787,12 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     policy = resolve_overflow_guard(args.overflow_guard, mode, on_gpu, not per_image)
     tta_scales, tta_flip = resolve_tta(args)
     conf = resolve_conf(args)
+    tagger = resolve_tags(args, have_dataset=True)
     if pipe is None:
-        kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79, smax=dataset.max_k(),
-                  guard="skip" if policy in ("raise", "rerun") else None)
+        kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
+                  smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None)
         if args.training_free:
-            pipe = TrainingFreePipeline(model, tta_scales=tta_scales, tta_flip=tta_flip, **kw)
+            pipe = TrainingFreePipeline(model, tta_scales=tta_scales, tta_flip=tta_flip, tagger=tagger, **kw)
         elif ragged:
             pipe = OptimisedLamPipeline(model, **kw)
     elif policy != "off" and getattr(pipe, "guard", None) is None:
@@ -688,10 +800,10 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         logging.warning(f"--overflow_guard {policy}: the supplied pipeline was built without a guard - running unguarded")
         policy = "off"
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
-                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, guard=report["guard"], report=report,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
@@ -719,6 +831,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     finally:
         build_validation.last_guard, build_validation.last_crf_hist, build_validation.last_crf_stats, build_validation.last_cam_stats, \
             build_validation.last_conf_hist = (report[k] for k in ("guard", "crf_hist", "crf_stats", "cam_stats", "conf_hist"))
+        build_validation.last_tags = report["tags"]
     return out
 
 
@@ -808,7 +921,9 @@ def _batched_loop(run):
     from collections import deque
     from .. import ops
     args, dataset, indices, device, pipe, S, on_gpu = run.args, run.dataset, run.indices, run.device, run.pipe, run.S, run.on_gpu
-    ragged, guard, conf = run.ragged, run.guard, run.conf
+    ragged, guard, conf, tagger = run.ragged, run.guard, run.conf, run.tagger
+    truth_known = bool(getattr(dataset, "has_cls_labels", True))      # the samples' one-hot rows are image-level labels (not placeholders)
+    step_cls = [None]           # the host one-hot rows of the step enqueued last
     cam, lab, crf, conf_lab = (run.consumers.get(k) for k in ("cam", "lab", "crf", "conf_lab"))
     policy = guard["policy"]
     pipe.hist = run.hist
@@ -828,7 +943,8 @@ def _batched_loop(run):
             batches = ragged_batches(dataset, idxs, args.batch_size, num_workers=nw, pin_memory=False)
         else:                                                               # default: a thread pool (datasets/loader.threaded_batches)
             batches = threaded_batches(dataset, idxs, args.batch_size, num_threads=max(nw, 1))
-        batches = _check_present_classes(batches, pipe.smax)
+        if tagger is None:                                    # (predicted tags are capped at smax by the tagger itself)
+            batches = _check_present_classes(batches, pipe.smax)
         if on_gpu:
             return DeviceFeeder(batches, device)              # H2D on a copy stream, a few batches ahead
 
@@ -839,6 +955,7 @@ def _batched_loop(run):
         return map(on_host, batches)
 
     def ragged_step(names, plan, images, cls_t, labels_t):
+        step_cls[0] = getattr(plan, "cls_host", None)
         if conf is None:
             out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
         else:                                                                           # affutils.py:101-158, same stream, step's own cams
@@ -864,6 +981,7 @@ def _batched_loop(run):
 
     def uniform_step(idxs):
         names, imgs, gts, cls = dataset.batch(idxs)
+        step_cls[0] = cls
         inputs = torch.from_numpy(imgs).to(device, non_blocking=True)
         if inputs.dtype == torch.uint8:                                                     # decoded images: normalise on the device
             inputs = ops.normalize_img_u8(inputs)                                           # datasets/voc.py:115-116
@@ -907,11 +1025,33 @@ def _batched_loop(run):
                                        f"beyond the IEEE-half range 65 504) for {', '.join(names[b] for b in bad)}: run these images in f32 "
                                        "(--overflow_guard rerun, or --gemm_mode f32)")
 
+    # --tags clip: the predicted rows come back behind the step's tag ticket, like the guard's flags; a later row of an image (the
+    # fp32 second pass) replaces the earlier one
+    tag_pending, tag_rows, tag_truth = deque(), {}, {}
+
+    def tag_enqueue(names):
+        ticket = getattr(pipe, "last_tag_ticket", None)
+        if ticket is None:
+            raise RuntimeError("--tags clip: the pipeline left no last_tag_ticket (it was built without a tagger)")
+        tag_pending.append((ticket, [str(n) for n in names], step_cls[0] if truth_known else None))
+
+    def tag_take(wait):
+        while tag_pending and (wait or tag_pending[0][0].ready()):
+            ticket, names, truth = tag_pending.popleft()
+            onehot = np.asarray(ticket.tags()[0])
+            for b, n in enumerate(names):
+                tag_rows[n] = np.array(onehot[b], np.float32)
+                if truth is not None:
+                    tag_truth[n] = np.array(truth[b], np.float32)
+
     nimg, pos, flagged = 0, 0, {}
     for names in steps(indices):
         if policy != "off":
             enqueue(names, indices[pos:pos + len(names)])
             take(False, flagged)                              # never a wait inside the loop
+        if tagger is not None:
+            tag_enqueue(names)
+            tag_take(False)
         pos += len(names)
         nimg += len(names)
     if policy != "off":
@@ -932,6 +1072,8 @@ def _batched_loop(run):
                 pos = 0
                 for names in steps(np.asarray(order, dtype=np.asarray(indices).dtype)):
                     enqueue(names, order[pos:pos + len(names)])
+                    if tagger is not None:
+                        tag_enqueue(names)                    # the fp32 row replaces the first pass's
                     pos += len(names)
                     guard["rerun"] += len(names)
                 take(True, still, first_pass=False)           # (also: the fp32 forwards are done before the mode goes back)
@@ -947,6 +1089,9 @@ def _batched_loop(run):
         torch.cuda.synchronize()
     if conf is not None:
         run.report["conf_hist"] = pipe.hist_conf
+    if tagger is not None:
+        tag_take(True)
+        run.report["tags"] = dict(rows=tag_rows, truth=tag_truth, **tag_report(tag_rows, tag_truth, args.num_classes - 1))
     return pipe.hist, nimg, time.time() - run.t0
 
 
@@ -1042,6 +1187,17 @@ def crf_proc(args, rank=0, world=1, device="cuda"):
     return evaluate.scores_from_hist(total), total                                          # :233
 
 
+def _tags_json(tags, tagger):
+    """validate.last_tags without the rows, as plain JSON types (the --json_out record of a --tags clip run)."""
+    out = {k: tags[k] for k in ("images", "tags_per_image", "scored", "counts", "image_f1")}
+    out.update(thre=tagger["thre"], kmax=tagger["kmax"], scale=tagger["scale"], micro=None, per_class=None)
+    if tags["score"] is not None:
+        sc = tags["score"]
+        out["micro"] = sc["micro"]
+        out["per_class"] = {m: [float(v) for v in sc[m].values()] for m in ("precision", "recall", "f1")}
+    return out
+
+
 def _gemm_self_check(model, dataset, idx, args, device, world):
     """ExCEL_model.check_numerics (the one implementation of the bf16x3 -> f16x3 -> f32 ladder) on the first (up to 4) samples of this
     rank's shard, resized like the loop resizes them (:74).  With several ranks every rung's verdict is shared (all-reduce MAX of the
@@ -1092,10 +1248,11 @@ def validate(args=None, dataset=None, pipe=None):
     flag_defaults(args)
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
-    validate.last_conf = validate.last_crf = None
+    validate.last_conf = validate.last_crf = validate.last_tags = None
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
+    tagger = resolve_tags(args, have_dataset=dataset is not None)                            # ... and tags nobody can supply
     if pipe is None:
         torch.cuda.set_device(args.local_rank)
         device = torch.device("cuda", args.local_rank)
@@ -1116,15 +1273,27 @@ def validate(args=None, dataset=None, pipe=None):
     args.run_token = tok[0]
     if dataset is not None:
         args.ragged_batches = True
+    elif args.unlabeled:
+        # a plain folder of images: no SegmentationClassAug, and image-level labels only where --tags labels asks for them
+        from ..datasets import images, voc
+        have = bool(args.list_folder) and os.path.isfile(os.path.join(args.list_folder, "cls_labels_onehot.npy"))
+        if tagger is None and not have:
+            raise FileNotFoundError(f"--tags labels reads {os.path.join(str(args.list_folder), 'cls_labels_onehot.npy')}: no such file "
+                                    "(--tags clip predicts the tags, --save_tags writes such a file)")
+        dataset = images.ImageListDataset(args.data_folder, args.list_folder, split=args.infer_set, num_fg=args.num_classes - 1,
+                                          label_list=voc.load_cls_label_list(args.list_folder) if have else None)
+        args.ragged_batches = True
     elif args.data_folder:
         # :156-163: every image has its own size.  The reference's harness always builds the VOC data set (:132); a COCO tree
         # (--dataset_name ms_coco, BASELINE configs[4]) gets the COCO reader of datasets/coco.py here
         if "coco" in args.dataset_name:
             from ..datasets import coco
-            dataset = coco.CocoSegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.infer_set, stage="val")
+            dataset = coco.CocoSegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.infer_set, stage="val",
+                                          cls_labels_optional=tagger is not None)
         else:
             from ..datasets import voc
-            dataset = voc.VOC12SegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.infer_set, stage="val")
+            dataset = voc.VOC12SegDataset(root_dir=args.data_folder, name_list_dir=args.list_folder, split=args.infer_set, stage="val",
+                                          cls_labels_optional=tagger is not None, num_fg=args.num_classes - 1)
         args.ragged_batches = True
     else:
         args.ragged_batches = bool(args.ragged)
@@ -1152,7 +1321,22 @@ def validate(args=None, dataset=None, pipe=None):
     validate.last_guard = build_validation.last_guard                                       # the overflow guard's report (rank-local)
     per_rank, total = gather_hists(hist)
     validate.last_per_rank = per_rank
-    score = evaluate.scores_from_hist(total)
+    score = None if args.unlabeled else evaluate.scores_from_hist(total)                    # (no ground truth: nothing to score)
+    tags = None
+    if tagger is not None:
+        # the predicted rows of every rank, once: every rank joins, also one whose shard is empty
+        mine = build_validation.last_tags or {"rows": {}, "truth": {}}
+        parts = [{"rows": mine["rows"], "truth": mine["truth"]}]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, {"rows": mine["rows"], "truth": mine["truth"]})
+        rows, truth = {}, {}
+        for part in parts:
+            rows.update(part["rows"])
+            truth.update(part["truth"])
+        tags = validate.last_tags = dict(rows=rows, **tag_report(rows, truth, args.num_classes - 1))
+        if args.save_tags and rank == 0:
+            save_tags_file(args.save_tags, rows)
     cat_list = VOC_CLASSES                                                                  # :123
     if "voc" not in args.dataset_name:
         from ..datasets import coco
@@ -1161,20 +1345,34 @@ def validate(args=None, dataset=None, pipe=None):
         cat_list = class_names(args)
     validate.last_cat_list = cat_list
     if rank == 0:
-        logging.info(f"Training_free:{args.training_free}, LAM_score:")
-        logging.info("\n" + format_scores_table(score, cat_list))
-        logging.info(f"mIoU {score['miou'] * 100:.3f}  images {int(nimg) * world}  ({nimg / secs:.1f} img/s/rank)")
+        if score is not None:
+            logging.info(f"Training_free:{args.training_free}, LAM_score:")
+            logging.info("\n" + format_scores_table(score, cat_list))
+            logging.info(f"mIoU {score['miou'] * 100:.3f}  images {int(nimg) * world}  ({nimg / secs:.1f} img/s/rank)")
+        else:
+            logging.info(f"--unlabeled true: no ground truth, nothing scored  images {int(nimg) * world}  ({nimg / secs:.1f} img/s/rank)")
+        if tags is not None:
+            logging.info(f"tags (--tags clip, thre {tagger['thre']}, at most {tagger['kmax']}, scale {tagger['scale']}): {tags['images']} images, "
+                         f"tags per image {dict((k, v) for k, v in enumerate(tags['tags_per_image']) if v)}"
+                         + (f", written to {args.save_tags}" if args.save_tags else ""))
+            if tags["score"] is not None:
+                logging.info("tag_score:")
+                logging.info("\n" + format_scores_table(tags["score"], cat_list[1:], metric_names=("precision", "recall", "f1")))
+                m = tags["score"]["micro"]
+                logging.info(f"tag_score micro precision {m['precision']:.4f} recall {m['recall']:.4f} f1 {m['f1']:.4f}  "
+                             f"mean image F1 (multilabel_score) {tags['image_f1']:.4f}  over {tags['scored']} images with labels")
         if args.json_out:
             # one self-checking record per run (tools_dev/scale.sh): wall time, rate and every rank's scored-pixel mass
             import json
             with open(args.json_out, "w") as f:
                 json.dump({"world": world, "rccl_ranks": int(dist.get_world_size()) if world > 1 else 1, "images_rank0": int(nimg),
                            "images_total": int(len(dataset)), "seconds_rank0": round(secs, 3), "images_per_s_rank0": round(nimg / secs, 2),
-                           "images_per_s_job": round(len(dataset) / secs, 2), "miou": float(score["miou"]),
+                           "images_per_s_job": round(len(dataset) / secs, 2), "miou": float(score["miou"]) if score is not None else None,
                            "per_rank_hist_mass": [int(x) for x in per_rank.reshape(per_rank.shape[0], -1).sum(1).tolist()],
                            "hist_total": [[int(v) for v in row] for row in total.cpu().tolist()],       # the gathered confusion matrix itself
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
-                           "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1])}, f)
+                           "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1]),
+                           **({"tags": _tags_json(tags, tagger)} if tags is not None else {})}, f)
     if conf is not None:
         conf_hist = build_validation.last_conf_hist
         if conf_hist is None:                                                               # a rank with an empty shard still joins the gather

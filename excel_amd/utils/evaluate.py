@@ -40,3 +40,32 @@ def scores_from_hist(hist):
 
 def scores(label_trues, label_preds, num_classes=21):
     return scores_from_hist(hist_from_labels(label_trues, label_preds, num_classes))
+
+
+def multilabel_score(y_true, y_pred):
+    """utils/evaluate.py:4-6 (sklearn.metrics.f1_score on one binary row) in numpy: 2 TP / (2 TP + FP + FN), 0 where that denominator
+    is 0 (sklearn's zero_division default returns 0 there too)."""
+    t, p = np.asarray(y_true).reshape(-1) != 0, np.asarray(y_pred).reshape(-1) != 0
+    tp, fp, fn = int((t & p).sum()), int((~t & p).sum()), int((t & ~p).sum())
+    den = 2 * tp + fp + fn
+    return 2.0 * tp / den if den else 0.0
+
+
+def tag_scores(counts):
+    """Predicted image tags against the image-level labels: counts int64 [F,3] = per class (TP, FP, FN) over the images ->
+    {"precision", "recall", "f1": {class: value}, "micro": {"precision", "recall", "f1"}, "tp", "fp", "fn"} - a ratio whose denominator
+    is 0 is 0 (a class nobody has and nobody predicted scores 0, like multilabel_score)."""
+    c = np.asarray(counts, np.float64).reshape(-1, 3)
+
+    def prf(tp, fp, fn):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p = np.where(tp + fp > 0, tp / (tp + fp), 0.0)
+            r = np.where(tp + fn > 0, tp / (tp + fn), 0.0)
+            f = np.where(2 * tp + fp + fn > 0, 2 * tp / (2 * tp + fp + fn), 0.0)
+        return p, r, f
+    p, r, f = prf(c[:, 0], c[:, 1], c[:, 2])
+    mp, mr, mf = prf(c[:, 0].sum(), c[:, 1].sum(), c[:, 2].sum())
+    n = c.shape[0]
+    return {"precision": dict(zip(range(n), p)), "recall": dict(zip(range(n), r)), "f1": dict(zip(range(n), f)),
+            "micro": {"precision": float(mp), "recall": float(mr), "f1": float(mf)},
+            "tp": int(c[:, 0].sum()), "fp": int(c[:, 1].sum()), "fn": int(c[:, 2].sum())}

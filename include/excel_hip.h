@@ -465,6 +465,27 @@ int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_t* pred, in
                                       const excel_ragged_info* info, const int32_t* skip /*device [B]*/, int num_classes, int64_t* hist,
                                       void* stream);
 
+/* ------------------------------------------------------------------ image tags: the one-hot rows excel_cls_compact reads, predicted
+ * Row 0 of the tower's x_raw is CLIP's own image embedding: the reference puts the class token of the original attention path back
+ * before ln_post / proj (clip/clip_surgery_model.py:442-446).  The reference never tags images itself (weakly-supervised segmentation
+ * assumes the tags; its tools carry an unused --tag_threshold 0.2); this entry is CLIP's zero-shot classification over the same text
+ * rows the CAM uses, so a batched step runs without image-level labels and without a host synchronisation.
+ *   x_cls  = the class-token row of image 0; image b's row is at x_cls + b * stride floats (stride = N * C for x_raw [B,N,C], C for a
+ *            compact [B,C]);  text [T,C], the F <= T foreground rows first (the others are background prompts);
+ *   cos[t] = <x, text_t> / (||x|| ||text_t||), both norms computed here (the rows need not be unit-norm);
+ *   p[t]   = softmax over ALL T rows of scale * cos[t] (the background prompts compete; scale = 100 is CLIP's logit scale);
+ *   rank[f] = #{g < F : p[g] > p[f] or (p[g] == p[f] and g < f)}   - a tie goes to the lower class index;
+ *   tag[f] = rank[f] < kmax and (rank[f] == 0 or p[f] >= rel_thre * max_f p[f]).
+ * The threshold is relative to the best foreground score (the absolute mass depends on how many prompts compete) and the top-1 class is
+ * always kept: an image with finite logits never has an empty row, and never more than kmax tags.  An image whose logits are not all
+ * finite (a NaN / inf in its row, a zero row) gets tag = {class 0} and a row of NaNs in scores_out - never an empty row; every CAM of
+ * such an image is non-finite as well (the class token weights all of them), so the overflow guard above flags it.
+ *   onehot_out f32 [B,F] (1.0 / 0.0, every element written);  scores_out f32 [B,F] = p[f], or NULL.
+ * One 256-thread workgroup per image; no workspace, no atomics.  EXCEL_ERR_ARG unless 1 <= F <= T <= 512, F <= 254, C % 4 == 0,
+ * C <= 1024, stride >= C, stride % 4 == 0, x_cls and text 16-byte aligned, 1 <= kmax <= F, 0 <= rel_thre <= 1, scale > 0. */
+int excel_clip_tags(const float* x_cls, long long stride, const float* text, int B, int C, int T, int F, float scale, float rel_thre,
+                    int kmax, float* onehot_out, float* scores_out, void* stream);
+
 /* datasets/transforms.normalize_img + HWC->CHW + the harness' input resize (tools/infer_lam.py:74: F.interpolate bilinear,
  * align_corners=False, no antialias) for decoded images of different sizes: hwc = the uint8 [H_b,W_b,3] images back to back
  * (image b at byte 3 * loff_b) -> out [B,3,S,S] f32.  Same operations (same bits) as excel_normalize_img_u8 + excel_bilinear_resize. */
