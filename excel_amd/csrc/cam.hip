@@ -10,106 +10,46 @@
 
 namespace EXCEL_SPLIT_NS {     // compiled once per 16-bit split type (excel_internal.h, build.py)
 
-#define CAM_TMAX 128
+#define CAM_TMAX 128           // the vocabularies served so far (VOC 45 rows, COCO 103): 2 class columns per lane
+#define CAM_TWIDE 512          // T > CAM_TMAX: the same kernel with CAM_TWIDE / 64 class columns per lane
 
+// Class-prior weights  w = softmax(temp * logit) / mean  (clip/clip.py:295-297) by ONE wave, NV classes per lane (class lane + 64 i);
+// padded classes get 0.  `logit` may be `w` itself (the fused kernels keep the cls logits there): every read comes before the barrier.
+template <int NV>
+__device__ __forceinline__ void class_prior(float* w, const float* logit, float temp, int T, int lane) {
+    float v[NV], e[NV], m = -INFINITY, s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { v[i] = (lane + 64 * i < T) ? logit[lane + 64 * i] * temp : -INFINITY; m = fmaxf(m, v[i]); }
+    m = wave_max(m);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { e[i] = (lane + 64 * i < T) ? __expf(v[i] - m) : 0.f; s += e[i]; }
+    const float sum = wave_sum(s);
+    s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { e[i] = e[i] / sum; s += e[i]; }
+    const float mean = wave_sum(s) / (float)T;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) w[lane + 64 * i] = (lane + 64 * i < T) ? e[i] / mean : 0.f;
+}
+
+template <int NV>              // class columns per lane: T <= 64 NV
 __global__ __launch_bounds__(1024) void cam_epilogue_kernel(float* __restrict__ S, float* __restrict__ out_full,
                                                             float* __restrict__ out_slice, int N, int T, int ldS, int F,
                                                             float temp) {
-    __shared__ float w[CAM_TMAX];
-    __shared__ float mn[16][CAM_TMAX];
-    __shared__ float mx[16][CAM_TMAX];
+    constexpr int TM = 64 * NV;
+    __shared__ float w[TM];
+    __shared__ float mn[16][TM];
+    __shared__ float mx[16][TM];
     const int b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float* Sb = S + (long long)b * N * ldS;
 
     // --- class-prior weights from the cls token row (wave 0)
-    if (wave == 0) {
-        float v0 = (lane < T) ? Sb[lane] * temp : -INFINITY;
-        float v1 = (lane + 64 < T) ? Sb[lane + 64] * temp : -INFINITY;
-        const float m = wave_max(fmaxf(v0, v1));
-        float e0 = (lane < T) ? __expf(v0 - m) : 0.f;
-        float e1 = (lane + 64 < T) ? __expf(v1 - m) : 0.f;
-        const float sum = wave_sum(e0 + e1);
-        e0 = e0 / sum;
-        e1 = e1 / sum;
-        const float mean = wave_sum(e0 + e1) / (float)T;
-        if (lane < T) w[lane] = e0 / mean;
-        if (lane + 64 < T) w[lane + 64] = e1 / mean;
-    }
+    if (wave == 0) class_prior<NV>(w, Sb, temp, T, lane);
     __syncthreads();
 
     // --- sim rows (one wave per token row, lanes over t), in place; per-lane running min/max per column
-    const float w0 = (lane < T) ? w[lane] : 0.f;
-    const float w1 = (lane + 64 < T) ? w[lane + 64] : 0.f;
-    float mn0 = INFINITY, mn1 = INFINITY, mx0 = -INFINITY, mx1 = -INFINITY;
-    for (int n = wave; n < N; n += 16) {
-        float* row = Sb + (long long)n * ldS;
-        const float a0 = (lane < T) ? row[lane] * w0 : 0.f;
-        const float a1 = (lane + 64 < T) ? row[lane + 64] * w1 : 0.f;
-        const float red = wave_sum(a0 + a1) / (float)T;
-        const float s0 = a0 - red, s1 = a1 - red;
-        if (lane < T) { row[lane] = s0; mn0 = fminf(mn0, s0); mx0 = fmaxf(mx0, s0); }
-        if (lane + 64 < T) { row[lane + 64] = s1; mn1 = fminf(mn1, s1); mx1 = fmaxf(mx1, s1); }
-    }
-    mn[wave][lane] = mn0; mn[wave][lane + 64] = mn1;
-    mx[wave][lane] = mx0; mx[wave][lane + 64] = mx1;
-    __syncthreads();
-    if (tid < CAM_TMAX) {
-        float a = mn[0][tid], c = mx[0][tid];
-        for (int i = 1; i < 16; ++i) { a = fminf(a, mn[i][tid]); c = fmaxf(c, mx[i][tid]); }
-        mn[0][tid] = a;
-        mx[0][tid] = c;
-    }
-    __syncthreads();   // also orders the in-place sim writes before the re-read below (same block)
-
-    const float lo0 = mn[0][lane], lo1 = mn[0][lane + 64];
-    const float d0 = mx[0][lane] - lo0, d1 = mx[0][lane + 64] - lo1;
-    for (int n = wave; n < N; n += 16) {
-        const float* row = Sb + (long long)n * ldS;
-        if (lane < T) {
-            const float v = (row[lane] - lo0) / d0;
-            if (out_full) out_full[((long long)b * N + n) * T + lane] = v;
-            if (out_slice && n >= 1 && lane < F) out_slice[((long long)b * (N - 1) + (n - 1)) * F + lane] = v;
-        }
-        if (lane + 64 < T) {
-            const float v = (row[lane + 64] - lo1) / d1;
-            if (out_full) out_full[((long long)b * N + n) * T + lane + 64] = v;
-            if (out_slice && n >= 1 && lane + 64 < F) out_slice[((long long)b * (N - 1) + (n - 1)) * F + lane + 64] = v;
-        }
-    }
-}
-
-// T > CAM_TMAX (up to CAM_TWIDE): the same three sweeps with CAM_TWIDE / 64 class columns per lane.  A kernel of its own, so that the
-// narrow one above keeps its code for the vocabularies it serves (VOC 45 rows, COCO 103).
-#define CAM_TWIDE 512
-__global__ __launch_bounds__(1024) void cam_epilogue_wide_kernel(float* __restrict__ S, float* __restrict__ out_full,
-                                                                 float* __restrict__ out_slice, int N, int T, int ldS, int F,
-                                                                 float temp) {
-    constexpr int NV = CAM_TWIDE / 64;
-    __shared__ float w[CAM_TWIDE];
-    __shared__ float mn[16][CAM_TWIDE];
-    __shared__ float mx[16][CAM_TWIDE];
-    const int b = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* Sb = S + (long long)b * N * ldS;
-
-    if (wave == 0) {
-        float v[NV], e[NV], m = -INFINITY, s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) { v[i] = (lane + 64 * i < T) ? Sb[lane + 64 * i] * temp : -INFINITY; m = fmaxf(m, v[i]); }
-        m = wave_max(m);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) { e[i] = (lane + 64 * i < T) ? __expf(v[i] - m) : 0.f; s += e[i]; }
-        const float sum = wave_sum(s);
-        s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) { e[i] = e[i] / sum; s += e[i]; }
-        const float mean = wave_sum(s) / (float)T;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) w[lane + 64 * i] = (lane + 64 * i < T) ? e[i] / mean : 0.f;
-    }
-    __syncthreads();
-
     float wv[NV], lo[NV], hi[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) { wv[i] = w[lane + 64 * i]; lo[i] = INFINITY; hi[i] = -INFINITY; }
@@ -131,7 +71,7 @@ __global__ __launch_bounds__(1024) void cam_epilogue_wide_kernel(float* __restri
 #pragma unroll
     for (int i = 0; i < NV; ++i) { mn[wave][lane + 64 * i] = lo[i]; mx[wave][lane + 64 * i] = hi[i]; }
     __syncthreads();
-    if (tid < CAM_TWIDE) {
+    if (tid < TM) {
         float a = mn[0][tid], c = mx[0][tid];
         for (int i = 1; i < 16; ++i) { a = fminf(a, mn[i][tid]); c = fmaxf(c, mx[i][tid]); }
         mn[0][tid] = a;
@@ -159,8 +99,8 @@ int excel_launch_cam_epilogue(float* S, float* out_full, float* out_slice, int B
                               hipStream_t st) {
     ProfScope prof__(PROF_CAM_EPILOGUE, st);
     EXCEL_CHECK_ARG(T >= 1 && T <= CAM_TWIDE && F <= T && ldS >= T, "cam: need 1 <= F <= T <= %d (T=%d F=%d)", CAM_TWIDE, T, F);
-    if (T <= CAM_TMAX) hipLaunchKernelGGL(cam_epilogue_kernel, dim3(B), dim3(1024), 0, st, S, out_full, out_slice, N, T, ldS, F, temp);
-    else hipLaunchKernelGGL(cam_epilogue_wide_kernel, dim3(B), dim3(1024), 0, st, S, out_full, out_slice, N, T, ldS, F, temp);
+    if (T <= CAM_TMAX) hipLaunchKernelGGL((cam_epilogue_kernel<CAM_TMAX / 64>), dim3(B), dim3(1024), 0, st, S, out_full, out_slice, N, T, ldS, F, temp);
+    else hipLaunchKernelGGL((cam_epilogue_kernel<CAM_TWIDE / 64>), dim3(B), dim3(1024), 0, st, S, out_full, out_slice, N, T, ldS, F, temp);
     EXCEL_CHECK_LAUNCH("cam_epilogue");
     return EXCEL_OK;
 }
@@ -230,22 +170,125 @@ __global__ __launch_bounds__(256) void patch_text_prep_kernel(PtcArgs p, unsigne
     p.colsq[((long long)b * gridDim.x + blk) * p.C + c] = s;
 }
 
-__device__ __forceinline__ float half_min(float v) {          // over the 32 lanes of a wave half
+// ---- the pieces the narrow and the wide similarity kernel share (workgroups of PTC_NW waves; tid = threadIdx.x)
+#define PTC_XP 36              // LDS pitch (floats) of the 32 x 32 x-tile: conflict-free 16-byte operand reads
+
+// inv[c] = 1 / ||x[b, :, c]||_2 over the tokens, from the image's partial column sums of squares
+__device__ __forceinline__ void ptc_inv_norms(float* inv, const float* colsq, int b, int N, int C, int tid) {
+    const int nblk = (N + PTC_HB - 1) / PTC_HB;
+    const float* q = colsq + (long long)b * nblk * C;
+    for (int c = tid; c < C; c += PTC_NW * 64) {
+        float s = 0.f;
+        for (int k0 = 0; k0 < nblk; k0 += 8) {             // 8 partials in flight; added in block order (s + 0 is exact for the tail)
+            float v[8];
 #pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
+            for (int k = 0; k < 8; ++k) v[k] = q[(long long)min(k0 + k, nblk - 1) * C + c];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += (k0 + k < nblk) ? v[k] : 0.f;
+        }
+        inv[c] = 1.f / sqrtf(s);
+    }
 }
-__device__ __forceinline__ float half_max(float v) {
+
+// cls logits  w[t] = S[0,t] = sum_c f[0,c] text[t,c]: thread = (class, quarter of the 16-byte pieces of a row), fixed fp32 fma chains
+// (identical bits in every workgroup and for every batch composition).
+__device__ __forceinline__ void ptc_cls_logits(float* w, const float* f0, const float* text, int T, int C, int tid) {
+    for (int t0 = 0; t0 < T; t0 += PTC_NW * 16) {
+        const int t = t0 + (tid >> 2), q = tid & 3;
+        float s = 0.f;
+        if (t < T) {
+            const float* tr = text + (long long)t * C;
+#pragma unroll 8
+            for (int c = q * 4; c < C; c += 16) {
+                const f32x4 tv = *reinterpret_cast<const f32x4*>(tr + c), fv = *reinterpret_cast<const f32x4*>(f0 + c);
+                s = fmaf(fv[0], tv[0], s); s = fmaf(fv[1], tv[1], s); s = fmaf(fv[2], tv[2], s); s = fmaf(fv[3], tv[3], s);
+            }
+        }
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        if (t < T && q == 0) w[t] = s;
+    }
+}
+
+// The lane's 8 normalised columns c0 .. c0 + 7 of a 16-k step (fa | fb) from row r of the wave's x-tile, cb = c0 mod 32
+__device__ __forceinline__ void ptc_x_operand(f32x4& fa, f32x4& fb, const float* xt, const float* inv, int r, int cb, int c0) {
+    const f32x4 ia = *reinterpret_cast<const f32x4*>(inv + c0), ib = *reinterpret_cast<const f32x4*>(inv + c0 + 4);
+    fa = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb]) * ia;
+    fb = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb + 4]) * ib;
+}
+
+// One 16-k step of  S^T[class][token] += text . x'^T  over the CT class tiles from class cbase on; trow[ct]: the split text row of this
+// lane's class in tile ct (padded class rows: clamped by the caller, zeroed here).  SKIP (the wide kernel's last chunk) leaves out a
+// class tile that lies past the vocabulary.
+template <bool BF, int CT, bool SKIP>
+__device__ __forceinline__ void ptc_matrix_step(f32x16 (&acc)[CT], const f32x4& fa, const f32x4& fb, const unsigned short* (&trow)[CT],
+                                                const float* text, int cbase, int c0, int r, int T, int C) {
+    if (BF) {
+        splitx8 xh, xl;
 #pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
+        for (int j = 0; j < 8; ++j) {
+            const float v = (j < 4) ? fa[j] : fb[j - 4];
+            xh[j] = split_hi(v);
+            xl[j] = split_hi(v - (float)xh[j]);
+        }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            if (SKIP && cbase + ct * 32 >= T) continue;               // uniform: a class tile past the vocabulary
+            const unsigned short* tp = trow[ct] + split_off(c0, 0);
+            splitx8 h = *reinterpret_cast<const splitx8*>(tp), l = *reinterpret_cast<const splitx8*>(tp + 32);
+            if (cbase + ct * 32 + r >= T) { h = splitx8{0, 0, 0, 0, 0, 0, 0, 0}; l = h; }
+            acc[ct] = EXCEL_MFMA16(l, xh, acc[ct], 0, 0, 0);
+            acc[ct] = EXCEL_MFMA16(h, xl, acc[ct], 0, 0, 0);
+            acc[ct] = EXCEL_MFMA16(h, xh, acc[ct], 0, 0, 0);
+        }
+    } else {
+        // exact fp32: v_mfma_f32_32x32x2_f32 takes k = {kh}: feed the lane's 8 columns as 8 k-pairs (kh selects the column
+        // within a pair consistently for both operands: any consistent k order gives the same fma chain per output)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            if (SKIP && cbase + ct * 32 >= T) continue;
+            const int cls = cbase + ct * 32 + r;
+            f32x4 ta = {0.f, 0.f, 0.f, 0.f}, tb = ta;
+            if (cls < T) {
+                ta = *reinterpret_cast<const f32x4*>(text + (long long)cls * C + c0);
+                tb = *reinterpret_cast<const f32x4*>(text + (long long)cls * C + c0 + 4);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[e], fa[e], acc[ct], 0, 0, 0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(tb[e], fb[e], acc[ct], 0, 0, 0);
+        }
+    }
+}
+
+// Epilogue tile with the lanes over the CLASSES: one class column of the wave's [token][class] LDS tile (et, pitch EP) goes to its sim
+// column (srow; across the lanes a token row is one coalesced store), with the class's in-lane min / max over the tile's nvalid tokens
+template <int EP>
+__device__ __forceinline__ void ptc_store_class(const float* et, float* srow, int ldT, int nvalid, float& a, float& c) {
+#pragma unroll 8
+    for (int k = 0; k < nvalid; ++k) {
+        const float v = et[k * EP];
+        srow[(long long)k * ldT] = v;
+        a = fminf(a, v);
+        c = fmaxf(c, v);
+    }
+}
+
+// min / max of class t over the workgroup's waves -> the partial table's rows of workgroup wg = b G + g (pitch TP)
+template <int TP>
+__device__ __forceinline__ void ptc_write_partial(float* part, long long wg, const float (*mn)[TP], const float (*mx)[TP], int t) {
+    float a = mn[0][t], c = mx[0][t];
+#pragma unroll
+    for (int i = 1; i < PTC_NW; ++i) { a = fminf(a, mn[i][t]); c = fmaxf(c, mx[i][t]); }
+    float* o = part + wg * 2 * TP;
+    o[t] = a;
+    o[TP + t] = c;
 }
 
 // TLDS: the split text bank (T <= PTC_TLDS_ROWS rows of 2C bf16) is staged in LDS once per workgroup - the four waves multiply against
 // the same rows, and fragment loads of 16 bytes per lane from 32 different rows are address-bound in the vector memory path (measured:
 // 2/3 of the kernel's 41 us with text and x both read as per-lane row pieces).  x_raw tiles are read COALESCED (8 lanes = one 128-byte
 // row piece) and turned into MFMA operand order through a wave-private LDS tile.
-#define PTC_XP 36              // LDS pitch (floats) of the 32 x 32 x-tile: conflict-free 16-byte operand reads
 #define PTC_PFB 4              // 32-column blocks of x in flight per wave
 template <bool BF, int CT, bool TLDS>
 __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_kernel(PtcArgs p) {
@@ -298,19 +341,7 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_kernel(PtcArgs p) 
                                                  (__attribute__((address_space(3))) void*)(tsm + row * TPITCH + pc * 512), 16, 0, 0);
             }
         }
-        const int nblk = (N + PTC_HB - 1) / PTC_HB;
-        const float* q = p.colsq + (long long)b * nblk * C;
-        for (int c = tid; c < C; c += NT) {
-            float s = 0.f;
-            for (int k0 = 0; k0 < nblk; k0 += 8) {             // 8 partials in flight; added in block order (s + 0 is exact for the tail)
-                float v[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = q[(long long)min(k0 + k, nblk - 1) * C + c];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) s += (k0 + k < nblk) ? v[k] : 0.f;
-            }
-            inv[c] = 1.f / sqrtf(s);
-        }
+        ptc_inv_norms(inv, p.colsq, b, N, C, tid);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the LDS-DMA pieces (and the x prefetch) have landed
         for (int t = tid; t < PTC_MAXCT * 32; t += NT) w[t] = 0.f;
     }
@@ -327,7 +358,7 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_kernel(PtcArgs p) 
         const int ntok = min(tile * 32 + r, N - 1);           // token of this lane column in operand order
         float* frow = (p.feats && tile * 32 + r < N) ? p.feats + ((long long)b * N + ntok) * C : nullptr;
         float* xt = xs[wave];
-        // text operand rows of this lane (padded class rows: clamped, zeroed below)
+        // text operand rows of this lane (padded class rows: clamped, zeroed in the matrix step)
         const unsigned short* trow[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -352,44 +383,10 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_kernel(PtcArgs p) 
 #pragma unroll
                 for (int h2 = 0; h2 < 2; ++h2) {
                     const int cb = h2 * 16 + 8 * kh, c0 = kb * 32 + cb;       // this lane's 8 columns of the 16-k step
-                    const f32x4 ia = *reinterpret_cast<const f32x4*>(inv + c0), ib = *reinterpret_cast<const f32x4*>(inv + c0 + 4);
-                    const f32x4 fa = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb]) * ia;
-                    const f32x4 fb = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb + 4]) * ib;
+                    f32x4 fa, fb;
+                    ptc_x_operand(fa, fb, xt, inv, r, cb, c0);
                     if (frow) { *reinterpret_cast<f32x4*>(frow + c0) = fa; *reinterpret_cast<f32x4*>(frow + c0 + 4) = fb; }
-                    if (BF) {
-                        splitx8 xh, xl;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float v = (j < 4) ? fa[j] : fb[j - 4];
-                            xh[j] = split_hi(v);
-                            xl[j] = split_hi(v - (float)xh[j]);
-                        }
-#pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) {
-                            const unsigned short* tp = trow[ct] + split_off(c0, 0);
-                            splitx8 h = *reinterpret_cast<const splitx8*>(tp), l = *reinterpret_cast<const splitx8*>(tp + 32);
-                            if (ct * 32 + r >= T) { h = splitx8{0, 0, 0, 0, 0, 0, 0, 0}; l = h; }
-                            acc[ct] = EXCEL_MFMA16(l, xh, acc[ct], 0, 0, 0);
-                            acc[ct] = EXCEL_MFMA16(h, xl, acc[ct], 0, 0, 0);
-                            acc[ct] = EXCEL_MFMA16(h, xh, acc[ct], 0, 0, 0);
-                        }
-                    } else {
-                        // exact fp32: v_mfma_f32_32x32x2_f32 takes k = {kh}: feed the lane's 8 columns as 8 k-pairs (kh selects the column
-                        // within a pair consistently for both operands: any consistent k order gives the same fma chain per output)
-#pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) {
-                            const int cls = ct * 32 + r;
-                            f32x4 ta = {0.f, 0.f, 0.f, 0.f}, tb = ta;
-                            if (cls < T) {
-                                ta = *reinterpret_cast<const f32x4*>(p.text + (long long)cls * C + c0);
-                                tb = *reinterpret_cast<const f32x4*>(p.text + (long long)cls * C + c0 + 4);
-                            }
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[e], fa[e], acc[ct], 0, 0, 0);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(tb[e], fb[e], acc[ct], 0, 0, 0);
-                        }
-                    }
+                    ptc_matrix_step<BF, CT, false>(acc, fa, fb, trow, p.text, 0, c0, r, T, C);
                 }
                 __builtin_amdgcn_wave_barrier();              // the tile is re-written by the next block
                 }
@@ -397,39 +394,11 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_kernel(PtcArgs p) 
         }
     }
     // ---- class-prior weights  softmax(temp * S[0,:]) / mean  (clip.py:295-297), AFTER the matrix loop (it needs them only in the
-    // epilogue).  S[0,t] = sum_c f[0,c] text[t,c]: thread = (class, quarter of the 16-byte pieces of a row), fixed fp32 fma chains
-    // (identical bits in every workgroup and for every batch composition).
+    // epilogue), from the cls logits in w
     __syncthreads();
-    for (int t0 = 0; t0 < T; t0 += NT / 4) {
-        const int t = t0 + (tid >> 2), q = tid & 3;
-        float s = 0.f;
-        if (t < T) {
-            const float* tr = p.text + (long long)t * C;
-#pragma unroll 8
-            for (int c = q * 4; c < C; c += 16) {
-                const f32x4 tv = *reinterpret_cast<const f32x4*>(tr + c), fv = *reinterpret_cast<const f32x4*>(f0 + c);
-                s = fmaf(fv[0], tv[0], s); s = fmaf(fv[1], tv[1], s); s = fmaf(fv[2], tv[2], s); s = fmaf(fv[3], tv[3], s);
-            }
-        }
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        if (t < T && q == 0) w[t] = s;
-    }
+    ptc_cls_logits(w, f0, p.text, T, C, tid);
     __syncthreads();
-    if (wave == 0) {
-        float v[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) v[i] = (lane + 64 * i < T) ? w[lane + 64 * i] * p.temp : -INFINITY;
-        const float m = wave_max(fmaxf(v[0], v[1]));
-        float e0 = (lane < T) ? __expf(v[0] - m) : 0.f, e1 = (lane + 64 < T) ? __expf(v[1] - m) : 0.f;
-        const float sum = wave_sum(e0 + e1);
-        e0 = e0 / sum;
-        e1 = e1 / sum;
-        const float mean = wave_sum(e0 + e1) / (float)T;
-        __builtin_amdgcn_wave_barrier();
-        w[lane] = (lane < T) ? e0 / mean : 0.f;
-        w[lane + 64] = (lane + 64 < T) ? e1 / mean : 0.f;
-    }
+    if (wave == 0) class_prior<PTC_MAXCT * 32 / 64>(w, w, p.temp, T, lane);
     __syncthreads();
     // sim[n,t] = w[t] S[n,t] - (1/T) sum_t' w[t'] S[n,t']      (clip.py:301-306 in GEMM form); per-class min / max of this tile
     float part = 0.f;
@@ -458,27 +427,11 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_kernel(PtcArgs p) 
     for (int cc = 0; cc < (CT + 1) / 2; ++cc) {
         const int cls = cc * 64 + lane;
         float a = INFINITY, c = -INFINITY;
-        if (cls < T) {
-            float* srow = simb + (long long)tile * 32 * p.ldT + cls;
-#pragma unroll 8
-            for (int k = 0; k < nvalid; ++k) {
-                const float v = et[k * EP + cls];
-                srow[(long long)k * p.ldT] = v;
-                a = fminf(a, v);
-                c = fmaxf(c, v);
-            }
-        }
+        if (cls < T) ptc_store_class<EP>(et + cls, simb + (long long)tile * 32 * p.ldT + cls, p.ldT, nvalid, a, c);
         if (cls < CT * 32) { red_mn[wave][cls] = a; red_mx[wave][cls] = c; }
     }
     __syncthreads();
-    if (tid < CT * 32) {
-        float a = red_mn[0][tid], c = red_mx[0][tid];
-#pragma unroll
-        for (int i = 1; i < NW; ++i) { a = fminf(a, red_mn[i][tid]); c = fmaxf(c, red_mx[i][tid]); }
-        float* o = p.part + ((long long)b * p.G + g) * 2 * (PTC_MAXCT * 32);
-        o[tid] = a;
-        o[PTC_MAXCT * 32 + tid] = c;
-    }
+    if (tid < CT * 32) ptc_write_partial<PTC_MAXCT * 32>(p.part, (long long)b * p.G + g, red_mn, red_mx, tid);
 }
 
 // T > 128: the class axis goes through the accumulators in chunks of PTC_MAXCT * 32 rows.  The redundancy term spans ALL classes, so it
@@ -513,58 +466,13 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_wide_kernel(PtcArg
     for (int j = 0; j < 4; ++j) xq[j] = X + (long long)min(tile * 32 + lr + 8 * j, N - 1) * C + lc;    // clamped rows: masked at the end
     const int nkb = C / 32;
     // ---- prologue: token-axis norms (partials in block order), cls logits, class-prior weights, vbar
-    {
-        const int nblk = (N + PTC_HB - 1) / PTC_HB;
-        const float* q = p.colsq + (long long)b * nblk * C;
-        for (int c = tid; c < C; c += NT) {
-            float s = 0.f;
-            for (int k0 = 0; k0 < nblk; k0 += 8) {             // 8 partials in flight; added in block order (s + 0 is exact for the tail)
-                float v[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = q[(long long)min(k0 + k, nblk - 1) * C + c];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) s += (k0 + k < nblk) ? v[k] : 0.f;
-            }
-            inv[c] = 1.f / sqrtf(s);
-        }
-    }
+    ptc_inv_norms(inv, p.colsq, b, N, C, tid);
     __syncthreads();
     for (int c = tid; c < C; c += NT) f0[c] = X[c] * inv[c];
     __syncthreads();
-    // S[0,t] = sum_c f[0,c] text[t,c]: the chains of the narrow kernel (thread = class x quarter of the 16-byte pieces of a row)
-    for (int t0 = 0; t0 < T; t0 += NT / 4) {
-        const int t = t0 + (tid >> 2), q = tid & 3;
-        float s = 0.f;
-        if (t < T) {
-            const float* tr = p.text + (long long)t * C;
-#pragma unroll 8
-            for (int c = q * 4; c < C; c += 16) {
-                const f32x4 tv = *reinterpret_cast<const f32x4*>(tr + c), fv = *reinterpret_cast<const f32x4*>(f0 + c);
-                s = fmaf(fv[0], tv[0], s); s = fmaf(fv[1], tv[1], s); s = fmaf(fv[2], tv[2], s); s = fmaf(fv[3], tv[3], s);
-            }
-        }
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        if (t < T && q == 0) w[t] = s;
-    }
+    ptc_cls_logits(w, f0, p.text, T, C, tid);
     __syncthreads();
-    if (wave == 0) {       // softmax(temp * S[0,:]) / mean  (clip.py:295-297), PTC_WIDE_T / 64 values per lane
-        constexpr int NV = PTC_WIDE_T / 64;
-        float v[NV], e[NV], m = -INFINITY, s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) { v[i] = (lane + 64 * i < T) ? w[lane + 64 * i] * p.temp : -INFINITY; m = fmaxf(m, v[i]); }
-        m = wave_max(m);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) { e[i] = (lane + 64 * i < T) ? __expf(v[i] - m) : 0.f; s += e[i]; }
-        const float sum = wave_sum(s);
-        s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) { e[i] = e[i] / sum; s += e[i]; }
-        const float mean = wave_sum(s) / (float)T;
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < NV; ++i) w[lane + 64 * i] = (lane + 64 * i < T) ? e[i] / mean : 0.f;
-    }
+    if (wave == 0) class_prior<PTC_WIDE_T / 64>(w, w, p.temp, T, lane);     // softmax(temp * S[0,:]) / mean  (clip.py:295-297)
     __syncthreads();
     for (int c = tid; c < C; c += NT) {                       // one fma chain per column, t increasing
         const float* tc = p.text + c;
@@ -610,9 +518,8 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_wide_kernel(PtcArg
 #pragma unroll
                 for (int h2 = 0; h2 < 2; ++h2) {
                     const int cb = h2 * 16 + 8 * kh, c0 = kb * 32 + cb;       // this lane's 8 columns of the 16-k step
-                    const f32x4 ia = *reinterpret_cast<const f32x4*>(inv + c0), ib = *reinterpret_cast<const f32x4*>(inv + c0 + 4);
-                    const f32x4 fa = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb]) * ia;
-                    const f32x4 fb = *reinterpret_cast<const f32x4*>(&xt[r * PTC_XP + cb + 4]) * ib;
+                    f32x4 fa, fb;
+                    ptc_x_operand(fa, fb, xt, inv, r, cb, c0);
                     if (ch == 0) {
                         if (frow) { *reinterpret_cast<f32x4*>(frow + c0) = fa; *reinterpret_cast<f32x4*>(frow + c0 + 4) = fb; }
                         const f32x4 va = *reinterpret_cast<const f32x4*>(vbar + c0), vb = *reinterpret_cast<const f32x4*>(vbar + c0 + 4);
@@ -621,40 +528,7 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_wide_kernel(PtcArg
 #pragma unroll
                         for (int e = 0; e < 4; ++e) redp = fmaf(fb[e], vb[e], redp);
                     }
-                    if (BF) {
-                        splitx8 xh, xl;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float v = (j < 4) ? fa[j] : fb[j - 4];
-                            xh[j] = split_hi(v);
-                            xl[j] = split_hi(v - (float)xh[j]);
-                        }
-#pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) {
-                            if (cbase + ct * 32 >= T) continue;               // uniform: a class tile past the vocabulary
-                            const unsigned short* tp = trow[ct] + split_off(c0, 0);
-                            splitx8 h = *reinterpret_cast<const splitx8*>(tp), l = *reinterpret_cast<const splitx8*>(tp + 32);
-                            if (cbase + ct * 32 + r >= T) { h = splitx8{0, 0, 0, 0, 0, 0, 0, 0}; l = h; }
-                            acc[ct] = EXCEL_MFMA16(l, xh, acc[ct], 0, 0, 0);
-                            acc[ct] = EXCEL_MFMA16(h, xl, acc[ct], 0, 0, 0);
-                            acc[ct] = EXCEL_MFMA16(h, xh, acc[ct], 0, 0, 0);
-                        }
-                    } else {
-#pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) {
-                            if (cbase + ct * 32 >= T) continue;
-                            const int cls = cbase + ct * 32 + r;
-                            f32x4 ta = {0.f, 0.f, 0.f, 0.f}, tb = ta;
-                            if (cls < T) {
-                                ta = *reinterpret_cast<const f32x4*>(p.text + (long long)cls * C + c0);
-                                tb = *reinterpret_cast<const f32x4*>(p.text + (long long)cls * C + c0 + 4);
-                            }
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[e], fa[e], acc[ct], 0, 0, 0);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(tb[e], fb[e], acc[ct], 0, 0, 0);
-                        }
-                    }
+                    ptc_matrix_step<BF, CT, true>(acc, fa, fb, trow, p.text, cbase, c0, r, T, C);
                 }
                 __builtin_amdgcn_wave_barrier();              // the tile is re-written by the next block
             }
@@ -675,14 +549,7 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_wide_kernel(PtcArg
             const int cl = cc * 64 + lane, cls = cbase + cl;
             float a = INFINITY, c = -INFINITY;
             if (cls < T) {
-                float* srow = simb + (long long)tile * 32 * p.ldT + cls;
-#pragma unroll 8
-                for (int k = 0; k < nvalid; ++k) {
-                    const float v = et[k * EP + cl];
-                    srow[(long long)k * p.ldT] = v;
-                    a = fminf(a, v);
-                    c = fmaxf(c, v);
-                }
+                ptc_store_class<EP>(et + cl, simb + (long long)tile * 32 * p.ldT + cls, p.ldT, nvalid, a, c);
                 red_mn[wave][cls] = a;
                 red_mx[wave][cls] = c;
             }
@@ -691,14 +558,18 @@ __global__ __launch_bounds__(PTC_NW * 64) void patch_text_sim_wide_kernel(PtcArg
         __builtin_amdgcn_wave_barrier();                      // the epilogue tile is re-written by the next chunk
     }
     __syncthreads();
-    for (int t = tid; t < T; t += NT) {
-        float a = red_mn[0][t], c = red_mx[0][t];
-#pragma unroll
-        for (int i = 1; i < NW; ++i) { a = fminf(a, red_mn[i][t]); c = fmaxf(c, red_mx[i][t]); }
-        float* o = p.part + ((long long)b * p.G + g) * 2 * PTC_WIDE_T;
-        o[t] = a;
-        o[PTC_WIDE_T + t] = c;
-    }
+    for (int t = tid; t < T; t += NT) ptc_write_partial<PTC_WIDE_T>(p.part, (long long)b * p.G + g, red_mn, red_mx, t);
+}
+
+// min and max - min of class t over the G rows of the image's partial table q (exact and order-independent)
+template <int TP>
+__device__ __forceinline__ void ptc_class_range(float* lo, float* span, const float* q, int G, int t) {
+    __builtin_assume(t >= 0);       // a class index: the table offsets below are zero-extended, as when t is the thread id itself
+    float a = INFINITY, c = -INFINITY;
+#pragma unroll 8
+    for (int g = 0; g < G; ++g) { a = fminf(a, q[g * 2 * TP + t]); c = fmaxf(c, q[(g * 2 + 1) * TP + t]); }
+    lo[t] = a;
+    span[t] = c - a;
 }
 
 // attr = (sim - min) / (max - min) over ALL tokens (clip.py:308; NaN when max == min, like the reference).  grid (cdiv(N, 64), B)
@@ -706,23 +577,9 @@ template <int TP>               // TP: row pitch of the partial table = the most
 __global__ __launch_bounds__(256) void patch_text_finish_kernel(PtcArgs p) {
     __shared__ float lo[TP], span[TP];
     const int b = blockIdx.y, tid = threadIdx.x, N = p.N, T = p.T;
-    if (tid < T) {
-        const float* q = p.part + (long long)b * p.G * 2 * TP;
-        float a = INFINITY, c = -INFINITY;
-#pragma unroll 8
-        for (int g = 0; g < p.G; ++g) { a = fminf(a, q[g * 2 * TP + tid]); c = fmaxf(c, q[(g * 2 + 1) * TP + tid]); }
-        lo[tid] = a;
-        span[tid] = c - a;
-    }
-    if (TP > 256)                   // the classes beyond the 256 threads (the narrow instantiation keeps the block above as its only one)
-        for (int t = tid + 256; t < T; t += 256) {
-            const float* q = p.part + (long long)b * p.G * 2 * TP;
-            float a = INFINITY, c = -INFINITY;
-#pragma unroll 8
-            for (int g = 0; g < p.G; ++g) { a = fminf(a, q[g * 2 * TP + t]); c = fmaxf(c, q[(g * 2 + 1) * TP + t]); }
-            lo[t] = a;
-            span[t] = c - a;
-        }
+    if (tid < T) ptc_class_range<TP>(lo, span, p.part + (long long)b * p.G * 2 * TP, p.G, tid);
+    if (TP > 256)                   // the classes beyond the 256 threads (the narrow instantiation keeps the line above as its only one)
+        for (int t = tid + 256; t < T; t += 256) ptc_class_range<TP>(lo, span, p.part + (long long)b * p.G * 2 * TP, p.G, t);
     __syncthreads();
     const float* simb = p.sim + (long long)b * N * p.ldT;
     const int n0 = blockIdx.x * 64, n1 = min(n0 + 64, N);
