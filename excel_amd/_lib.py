@@ -148,6 +148,7 @@ SIGNATURES = {
     "excel_par_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "excel_par_forward": (c_i, [c_f, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_i, C.POINTER(C.c_int32), c_i, c_i,
                                 C.c_float, C.c_float, c_f, c_f, c_i, c_f]),
+    "excel_par_plan": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_int32), c_i, c_i, c_i, c_i, c_i, C.POINTER(C.c_int32)]),
     "excel_ragged_plan": (c_i, [C.POINTER(C.c_int32), c_i, C.POINTER(RaggedInfo), C.POINTER(C.c_int32)]),
     "excel_normalize_resize_u8_ragged": (c_i, [c_f, c_f, c_i, c_i, C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f]),
     "excel_normalize_resize_u8_ragged_mirror": (c_i, [c_f, c_f, c_i, c_i, C.POINTER(C.c_double), C.POINTER(C.c_double), c_f, c_f]),

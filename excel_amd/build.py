@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libexcel_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16x3.hip", "gemm_w4.hip", "gemm_plan.hip", "norm.hip", "attn.hip", "attn_f32.hip", "attn_strip.hip", "attn_plan.hip", "cam.hip", "cam_plan.hip", "aff.hip", "par.hip", "attr.hip", "tta.hip", "lvc.hip", "decoder.hip", "train.hip", "crf.hip", "aug.hip", "segeval.hip", "conf.hip", "camviz.hip", "trainviz.hip", "png.hip", "jpeg.hip", "guard.hip", "tag.hip", "abi.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16x3.hip", "gemm_w4.hip", "gemm_plan.hip", "norm.hip", "attn.hip", "attn_f32.hip", "attn_strip.hip", "attn_plan.hip", "cam.hip", "cam_plan.hip", "aff.hip", "par.hip", "par_plan.hip", "attr.hip", "tta.hip", "lvc.hip", "decoder.hip", "train.hip", "crf.hip", "aug.hip", "segeval.hip", "conf.hip", "camviz.hip", "trainviz.hip", "png.hip", "jpeg.hip", "guard.hip", "tag.hip", "abi.hip"]
 # the translation units that depend on the 16-bit type of the split operand planes are compiled twice: bf16 (namespace excel_bf16) and,
 # with -DEXCEL_SPLIT_F16, IEEE half (namespace excel_f16, objects *_f16.o) - the "f16x3" matrix-core mode (common.h, excel_internal.h)
 SPLIT_SOURCES = ["gemm_bf16x3.hip", "gemm_w4.hip", "norm.hip", "attn.hip", "attn_strip.hip", "cam.hip"]

@@ -809,28 +809,24 @@ extern "C" int excel_par_forward(const float* imgs, int h, int w, const float* m
     float* pp = (float*)(base + align_up((size_t)B * 8 * ndil * hw * sizeof(float), 256));
     float* guide = (float*)((char*)pp + align_up((size_t)B * Cmax * hw * sizeof(float), 256));
     hipStream_t st = ST(stream);
-    const float* gimg = imgs;
-    if (h != H || w != W) {   // F.interpolate(..., align_corners=True) (PAR.py:67)
-        TRY(excel_launch_bilinear_ac(imgs, guide, B * 3, h, w, H, W, st));
-        gimg = guide;
-    }
-    // Affinities: either streamed as 8*ndil planes per image (EXCEL_PAR_STREAM_AFFINITIES, or a shape / dilation set the tiled kernel
-    // does not take), or recomputed in every step from the guide image and 5 per-pixel statistics: bit-identical weights from a
-    // tenth of the bytes (par.hip).
+    // the resize, the form of the affinities (streamed planes or statistics the step recomputes them from) and both kernels: par_plan.hip
+    const float* gimg = (h != H || w != W) ? guide : imgs;
+    const bool aligned16 = ((((uintptr_t)gimg | (uintptr_t)aff | (uintptr_t)masks | (uintptr_t)out | (uintptr_t)pp) & 15) == 0);
+    const ParShape shape = {B, Cmax, h, w, H, W, (long long)hw, 0, dilations, ndil, n_iter, (flags & EXCEL_PAR_STREAM_AFFINITIES) ? 1 : 0, 0, aligned16};
+    const ParPlan plan = par_plan(shape);
+    if (plan.resize) TRY(excel_launch_bilinear_ac(imgs, guide, B * 3, h, w, H, W, st));   // F.interpolate(..., align_corners=True) (PAR.py:67)
     const TileGeo geo = uniform_geo(B, H, W);
-    const bool recompute = !(flags & EXCEL_PAR_STREAM_AFFINITIES) && n_iter > 0 && (W % 4) == 0 && (((uintptr_t)pp & 15) == 0) &&
-                           excel_par_guide_supported(gimg, aff, masks, out, Cmax, (long long)hw, W, dilations, ndil);
-    TRY(excel_launch_par_affinity(gimg, aff, geo, 0, dilations, ndil, w1, w2, st, recompute ? 1 : 0));
-    if (n_iter == 0) {
+    TRY(excel_launch_par_affinity(gimg, aff, geo, dilations, ndil, w1, w2, plan, st));
+    if (plan.step == PAR_STEP_NONE) {
         hipMemcpyAsync(out, masks, sizeof(float) * (size_t)B * Cmax * hw, hipMemcpyDeviceToDevice, st);
         return EXCEL_OK;
     }
-    if (recompute)
+    if (plan.step == PAR_STEP_RECOMPUTE)
         return par_jacobi(masks, out, pp, n_iter, [&](const float* cur, float* dst) {
-            return excel_launch_par_iterate_guide(gimg, aff, cur, dst, nchan, Cmax, geo, 0, dilations, ndil, w1, w2, st);
+            return excel_launch_par_iterate_guide(gimg, aff, cur, dst, nchan, Cmax, geo, dilations, ndil, w1, w2, plan, st);
         });
     return par_jacobi(masks, out, pp, n_iter, [&](const float* cur, float* dst) {
-        return excel_launch_par_iterate(aff, cur, dst, nchan, B, Cmax, H, W, dilations, ndil, st);
+        return excel_launch_par_iterate(aff, cur, dst, nchan, Cmax, H, W, dilations, ndil, w1, w2, plan, st);
     });
 }
 
@@ -844,7 +840,7 @@ extern "C" int excel_par_forward_ragged(const float* imgs, int h, int w, const f
                                         const excel_ragged_info* info, int Cmax, const int32_t* dilations, int ndil, int n_iter, float w1,
                                         float w2, float* out, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(imgs && masks && out && workspace && dilations && table && info, "par_forward_ragged: null argument");
-    EXCEL_CHECK_ARG(n_iter >= 1 && Cmax > 0 && h > 0 && w > 0 && info->B > 0, "par_forward_ragged: bad n_iter / shape");
+    EXCEL_CHECK_ARG(Cmax > 0 && h > 0 && w > 0 && info->B > 0, "par_forward_ragged: bad n_iter / shape");
     const size_t tp = (size_t)info->total_pix;
     char* base = (char*)workspace;
     float* stats = (float*)base;
@@ -852,17 +848,35 @@ extern "C" int excel_par_forward_ragged(const float* imgs, int h, int w, const f
     float* guide = (float*)((char*)pp + align_up((size_t)Cmax * tp * sizeof(float), 256));
     hipStream_t st = ST(stream);
     const TileGeo geo = ragged_geo(table, info->B);
-    // (every pitch of the ragged layout is a multiple of 4 floats by construction - excel_ragged_plan - so 4 stands for all of them)
-    EXCEL_CHECK_ARG(excel_par_guide_supported(guide, stats, masks, out, Cmax, info->max_plane_pix, 4, dilations, ndil) && (((uintptr_t)pp & 15) == 0),
+    const bool aligned16 = ((((uintptr_t)guide | (uintptr_t)stats | (uintptr_t)masks | (uintptr_t)out | (uintptr_t)pp) & 15) == 0);
+    const ParShape shape = {info->B, Cmax, h, w, 0, 0, info->max_plane_pix, info->total_tiles, dilations, ndil, n_iter, 0, 1, aligned16};
+    const ParPlan plan = par_plan(shape);
+    EXCEL_CHECK_ARG(plan.refused != PAR_REFUSE_NITER, "par_forward_ragged: bad n_iter / shape");
+    EXCEL_CHECK_ARG(!plan.refused,
                     "par_forward_ragged: needs dilations [1,2,4,8,12,24], 16-byte aligned buffers and max(Cmax,5) * H * Wp * 4 < 2^31 per image "
                     "(Wp = W rounded up to 4)");
-    // the guide always goes through the align_corners=True resize (PAR.py:67): it is the identity where (H_b, W_b) == (h, w), and it
-    // brings the uniform [B,3,h,w] network input into the pitched per-image layout
     TRY(excel_launch_bilinear_ac_ragged(imgs, guide, h, w, geo, info->total_tiles, st));
-    TRY(excel_launch_par_affinity(guide, stats, geo, info->total_tiles, dilations, ndil, w1, w2, st, 1));
+    TRY(excel_launch_par_affinity(guide, stats, geo, dilations, ndil, w1, w2, plan, st));
     return par_jacobi(masks, out, pp, n_iter, [&](const float* cur, float* dst) {
-        return excel_launch_par_iterate_guide(guide, stats, cur, dst, nchan, Cmax, geo, info->total_tiles, dilations, ndil, w1, w2, st);
+        return excel_launch_par_iterate_guide(guide, stats, cur, dst, nchan, Cmax, geo, dilations, ndil, w1, w2, plan, st);
     });
+}
+
+// (a batch of B images of H x W each stands for the ragged batch: its largest plane and its tile list are what the launch depends on)
+extern "C" int excel_par_plan(int B, int Cmax, int h, int w, int H, int W, const int32_t* dilations, int ndil, int n_iter, int flags, int ragged,
+                              int aligned16, int32_t* plan) {
+    EXCEL_CHECK_ARG(plan && dilations && B >= 1 && Cmax >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1 && ndil >= 1 && ndil <= 8 && n_iter >= 0 &&
+                    (flags & ~EXCEL_PAR_STREAM_AFFINITIES) == 0 && (ragged == 0 || ragged == 1) && (aligned16 == 0 || aligned16 == 1),
+                    "par_plan: bad argument");
+    for (int i = 0; i < ndil; ++i) EXCEL_CHECK_ARG(dilations[i] >= 1, "par_plan: dilations must be >= 1 (got %d)", dilations[i]);
+    const long long Wp = ragged ? (W + 3LL) / 4 * 4 : W, tiles = (long long)B * ((W + 63) / 64) * ((H + 15) / 16);
+    EXCEL_CHECK_ARG(B <= 65535 && tiles < (1LL << 31), "par_plan: batch too large for one launch");
+    const ParShape shape = {B, Cmax, h, w, H, W, (long long)H * Wp, ragged ? (int)tiles : 0, dilations, ndil, n_iter, flags ? 1 : 0, ragged, aligned16};
+    const ParPlan p = par_plan(shape);
+    const int v[EXCEL_PAR_PLAN_INTS] = {p.resize, p.stats, p.nd, p.step, p.stats_grid[0], p.stats_grid[1], p.stats_grid[2], p.stats_block,
+                                        p.step_grid[0], p.step_grid[1], p.step_grid[2], p.step_block, p.tiles_interior, p.tiles_border, p.refused};
+    for (int i = 0; i < EXCEL_PAR_PLAN_INTS; ++i) plan[i] = v[i];
+    return EXCEL_OK;
 }
 
 extern "C" int excel_argmax_label_ragged(const float* cams, const int32_t* nchan, const int32_t* cls_idx, const int32_t* table,

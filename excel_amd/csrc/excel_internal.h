@@ -128,14 +128,45 @@ int excel_launch_matvec(const float* T, const float* v, const int* ncls, float* 
 int excel_launch_cam_upsample_bkg(const float* r, const int* ncls, float* rn, float* cams, int B, int g, int Smax, int H, int W,
                                   int zero_unused, hipStream_t st);
 struct TileGeo;
-int excel_launch_par_affinity(const float* img, float* aff, const TileGeo& geo, int total_tiles, const int* dil, int ndil, float w1, float w2,
-                              hipStream_t st, int compact = 0);
-int excel_par_guide_supported(const void* guide, const void* stats, const void* in, const void* out, int Cmax, long long max_plane, int Wp,
-                              const int* dil, int ndil);
+// Kernel selection of the pixel-adaptive refinement (par_plan.hip): the statistics kernel and its output form, the step kernel, the
+// grids of both launches and the tile kinds of one image.  Host arithmetic on integers, shared by excel_par_forward,
+// excel_par_forward_ragged, the launchers of par.hip (they launch exactly what the plan names) and the host query of the C ABI
+// (excel_par_plan).
+enum { PAR_STATS_TILE = 0, PAR_STATS_POINT_COMPACT = 1, PAR_STATS_POINT_PLANES = 2 };
+enum { PAR_STEP_NONE = 0, PAR_STEP_RECOMPUTE = 1, PAR_STEP_STREAM = 2 };
+enum { PAR_REFUSE_NITER = 1, PAR_REFUSE_DILATIONS = 2, PAR_REFUSE_ALIGN = 3, PAR_REFUSE_SIZE = 4 };
+constexpr int PAR_HALO = 24;          // the largest dilation of the standard set: halo of a 64 x 16 tile
+struct ParShape {
+    int B, Cmax;
+    int h, w;                  // the guide as given (network input)
+    int H, W;                  // masks of a uniform batch; ragged: one image (tile kinds), or 0 for a batch of mixed sizes
+    long long max_plane;       // the largest H_b * Wp_b of the launch (uniform: H * W)
+    int total_tiles;           // ragged: 64 x 16 tiles of the whole batch
+    const int* dil;            // host
+    int ndil, n_iter;
+    int stream;                // EXCEL_PAR_STREAM_AFFINITIES
+    int ragged;
+    int aligned16;             // guide, statistics, masks, out and the ping-pong buffer are 16-byte aligned
+};
+struct ParPlan {
+    int resize;                // the guide goes through the align_corners=True resize
+    int stats;                 // PAR_STATS_TILE: par_stats_tile_kernel<ragged>; _POINT_COMPACT: par_affinity_kernel<nd, ragged> writing the 5
+                               // statistics; _POINT_PLANES: par_affinity_kernel<nd, false> writing 8 * nd planes
+    int nd;                    // dilations (the pointwise kernel's instance)
+    int step;                  // PAR_STEP_NONE (n_iter == 0: masks are copied); _RECOMPUTE: par_iterate_guide_kernel<ragged>; _STREAM: par_iterate_stream_kernel
+    int stats_grid[3], stats_block;
+    int step_grid[3], step_block;      // all 0 for PAR_STEP_NONE
+    int tiles_interior, tiles_border;  // tile kernels: tiles of ONE H x W image staged in 16-byte pieces / in 4-byte pieces with clamped columns
+    int refused;               // ragged only: PAR_REFUSE_* when excel_par_forward_ragged does not take the request (everything else 0), else 0
+};
+bool par_dil_ok(const int* dil, int ndil);
+ParPlan par_plan(const ParShape& s);
+int excel_launch_par_affinity(const float* img, float* aff, const TileGeo& geo, const int* dil, int ndil, float w1, float w2, const ParPlan& plan,
+                              hipStream_t st);
 int excel_launch_par_iterate_guide(const float* guide, const float* stats, const float* in, float* out, const int* nchan, int Cmax,
-                                   const TileGeo& geo, int total_tiles, const int* dil, int ndil, float w1, float w2, hipStream_t st);
-int excel_launch_par_iterate(const float* aff, const float* in, float* out, const int* nchan, int B, int Cmax, int H, int W,
-                             const int* dil, int ndil, hipStream_t st);
+                                   const TileGeo& geo, const int* dil, int ndil, float w1, float w2, const ParPlan& plan, hipStream_t st);
+int excel_launch_par_iterate(const float* aff, const float* in, float* out, const int* nchan, int Cmax, int H, int W, const int* dil, int ndil,
+                             float w1, float w2, const ParPlan& plan, hipStream_t st);
 int excel_launch_bilinear_ac_ragged(const float* in, float* out, int h, int w, const TileGeo& geo, int total_tiles, hipStream_t st);
 int excel_launch_argmax_label_ragged(const float* cams, const int* nchan, const int* cls_idx, int Smax, int Cmax, const TileGeo& geo,
                                      int total_tiles, unsigned char* lab8, hipStream_t st);

@@ -567,8 +567,13 @@ __global__ __launch_bounds__(512, 4) void par_stats_tile_kernel(const float* __r
 
 // F.interpolate(mode='bilinear', align_corners=True) (PAR.py:67): planes of h x w -> H x W
 __device__ __forceinline__ float bilinear_ac_px(const float* __restrict__ p, int h, int w, int H, int W, int x, int y) {
+#pragma clang fp contract(off)   // (see fy below)
     const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
     const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    // The source position is ROUNDED before the weight is taken from it (ATen: src = scale * dst, lambda = src - floor(src)).  With
+    // contraction allowed, `fy - y0` fuses with the product into one fma (__fmul_rn does not stop that: it is inlined as a plain
+    // multiplication) and the weight keeps what the rounding of fy (4e-6 near 47) drops: guides 60 fp32 roundings off the
+    // reference's, PAR outputs off by 2e-5 (tests/test_gpu_par_shapes.py, ragged batch).  The blend's own fmaf calls stay fused.
     const float fy = sy * (float)y, fx = sx * (float)x;
     const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
     const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
@@ -744,66 +749,48 @@ static int make_dil(const int* dil, int ndil, float w1, float w2, ParDil* out) {
         default: CALL(8); break;            \
     }
 
-// The recomputing step is built for the dilation set every caller of the reference uses, [1,2,4,8,12,24] (tools/infer_lam.py:168,
-// scripts/train_voc.py:112, scripts/train_coco.py:110): 6 x 8 float2 weights stay in registers (96 of 128 VGPRs), halo 24, tap
-// offsets as compile-time immediates.  Any other set goes through the streamed kernel.
-static bool par_dil_ok(const int* dil, int ndil) {
-    static const int want[6] = {1, 2, 4, 8, 12, 24};
-    if (ndil != 6) return false;
-    for (int i = 0; i < 6; ++i)
-        if (dil[i] != want[i]) return false;
-    return true;
-}
-// geo.tab != nullptr: ragged batch of `total_tiles` 64x16 tiles (img / aff in the pitched layout); else uniform [B,.,H,W]
-int excel_launch_par_affinity(const float* img, float* aff, const TileGeo& geo, int total_tiles, const int* dil, int ndil, float w1, float w2,
-                              hipStream_t st, int compact) {
+// Which kernel runs, in which form and on which grid, is par_plan()'s decision alone (par_plan.hip): the launchers below launch what the
+// plan names.  geo.tab != nullptr: ragged batch (img / aff in the pitched layout); else uniform [B,.,H,W]
+static dim3 grid3(const int* g) { return dim3(g[0], g[1], g[2]); }
+
+int excel_launch_par_affinity(const float* img, float* aff, const TileGeo& geo, const int* dil, int ndil, float w1, float w2, const ParPlan& plan,
+                              hipStream_t st) {
     ProfScope prof__(PROF_PAR_AFFINITY, st);
     ParDil dl;
     int rc = make_dil(dil, ndil, w1, w2, &dl);
     if (rc) return rc;
-    // compact statistics of the standard dilation set, 16-byte aligned pitched planes: the tile kernel
-    const bool tiled = compact && par_dil_ok(dil, ndil) && ((((uintptr_t)img | (uintptr_t)aff) & 15) == 0) &&
-                       (geo.tab ? true : (geo.W % 4 == 0 && geo.W >= 8 && 5LL * geo.H * geo.W * 4 < (1LL << 31)));
+    const dim3 grid = grid3(plan.stats_grid), block(plan.stats_block);
     if (geo.tab) {
-        EXCEL_CHECK_ARG(compact && ndil == 6, "par_affinity: ragged batches use the compact statistics of the 6-dilation kernel");
-        if (tiled) hipLaunchKernelGGL((par_stats_tile_kernel<true>), dim3(total_tiles), dim3(512), 0, st, img, aff, geo, w1);
-        else hipLaunchKernelGGL((par_affinity_kernel<6, true>), dim3(total_tiles, 4), dim3(256), 0, st, img, aff, dl, geo, w1, 1);
-    } else if (tiled) {
-        hipLaunchKernelGGL((par_stats_tile_kernel<false>), dim3(cdiv(geo.W, 64), cdiv(geo.H, 16), geo.B), dim3(512), 0, st, img, aff, geo, w1);
+        EXCEL_CHECK_ARG(plan.stats != PAR_STATS_POINT_PLANES && ndil == 6, "par_affinity: ragged batches use the compact statistics of the 6-dilation kernel");
+        if (plan.stats == PAR_STATS_TILE) hipLaunchKernelGGL((par_stats_tile_kernel<true>), grid, block, 0, st, img, aff, geo, w1);
+        else hipLaunchKernelGGL((par_affinity_kernel<6, true>), grid, block, 0, st, img, aff, dl, geo, w1, 1);
+    } else if (plan.stats == PAR_STATS_TILE) {
+        hipLaunchKernelGGL((par_stats_tile_kernel<false>), grid, block, 0, st, img, aff, geo, w1);
     } else {
-#define CALL(N) hipLaunchKernelGGL((par_affinity_kernel<N, false>), dim3(cdiv(geo.W, 64), cdiv(geo.H, 4), geo.B), dim3(256), 0, st, img, aff, dl, geo, w1, compact ? 1 : 0)
-        ND_SWITCH(ndil, CALL)
+#define CALL(N) hipLaunchKernelGGL((par_affinity_kernel<N, false>), grid, block, 0, st, img, aff, dl, geo, w1, plan.stats == PAR_STATS_POINT_COMPACT ? 1 : 0)
+        ND_SWITCH(plan.nd, CALL)
 #undef CALL
     }
     EXCEL_CHECK_LAUNCH("par_affinity");
     return EXCEL_OK;
 }
 
-int excel_launch_par_iterate(const float* aff, const float* in, float* out, const int* nchan, int B, int Cmax, int H, int W,
-                             const int* dil, int ndil, hipStream_t st) {
+int excel_launch_par_iterate(const float* aff, const float* in, float* out, const int* nchan, int Cmax, int H, int W, const int* dil, int ndil,
+                             float w1, float w2, const ParPlan& plan, hipStream_t st) {
     ProfScope prof__(PROF_PAR_ITERATE, st);
+    EXCEL_CHECK_ARG(plan.step == PAR_STEP_STREAM, "par_iterate: the plan names another step kernel");
     ParDil dl;
-    int rc = make_dil(dil, ndil, 0.3f, 0.01f, &dl);
+    int rc = make_dil(dil, ndil, w1, w2, &dl);
     if (rc) return rc;
-    hipLaunchKernelGGL(par_iterate_stream_kernel, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, aff, in, out, nchan, dl, ndil, Cmax, H, W);
+    hipLaunchKernelGGL(par_iterate_stream_kernel, grid3(plan.step_grid), dim3(plan.step_block), 0, st, aff, in, out, nchan, dl, ndil, Cmax, H, W);
     EXCEL_CHECK_LAUNCH("par_iterate");
     return EXCEL_OK;
 }
 
-// max_plane: the largest H * Wp of the launch; the LDS-DMA offsets inside one image are 32-bit (buffer descriptor per image)
-int excel_par_guide_supported(const void* guide, const void* stats, const void* in, const void* out, int Cmax, long long max_plane, int Wp,
-                              const int* dil, int ndil) {
-    // (any pitch that is a multiple of 4 floats works, down to Wp = 4: border tiles clamp their source columns per lane -
-    // tests/test_gpu_ops.py::test_ragged_tiny_images, test_par_uniform_narrow_images)
-    const bool vec = (Wp % 4) == 0 && Wp >= 4 && ((((uintptr_t)guide | (uintptr_t)stats | (uintptr_t)in | (uintptr_t)out) & 15) == 0);
-    const long long planes = Cmax > 5 ? Cmax : 5;
-    return (vec && par_dil_ok(dil, ndil) && planes * max_plane * 4 < (1LL << 31)) ? 1 : 0;
-}
-
-// One Jacobi step with the affinities recomputed from (guide, stats).  The caller has checked excel_par_guide_supported.
+// One Jacobi step with the affinities recomputed from (guide, stats).
 int excel_launch_par_iterate_guide(const float* guide, const float* stats, const float* in, float* out, const int* nchan, int Cmax,
-                                   const TileGeo& geo, int total_tiles, const int* dil, int ndil, float w1, float w2, hipStream_t st) {
-    EXCEL_CHECK_ARG(par_dil_ok(dil, ndil), "par_iterate_guide: unsupported dilation set");
+                                   const TileGeo& geo, const int* dil, int ndil, float w1, float w2, const ParPlan& plan, hipStream_t st) {
+    EXCEL_CHECK_ARG(plan.step == PAR_STEP_RECOMPUTE && par_dil_ok(dil, ndil), "par_iterate_guide: unsupported dilation set");
     ProfScope prof__(PROF_PAR_ITERATE, st);
     ParDil dl;
     int rc = make_dil(dil, ndil, w1, w2, &dl);
@@ -813,11 +800,11 @@ int excel_launch_par_iterate_guide(const float* guide, const float* stats, const
     static const int env_dbg = getenv("EXCEL_PAR_DBG") ? atoi(getenv("EXCEL_PAR_DBG")) : 0;
     dbg = env_dbg;
 #endif
+    const dim3 grid = grid3(plan.step_grid), block(plan.step_block);
     if (geo.tab)
-        hipLaunchKernelGGL((par_iterate_guide_kernel<true>), dim3(total_tiles), dim3(512), 0, st, guide, stats, in, out, nchan, dl, Cmax, geo, dbg);
+        hipLaunchKernelGGL((par_iterate_guide_kernel<true>), grid, block, 0, st, guide, stats, in, out, nchan, dl, Cmax, geo, dbg);
     else
-        hipLaunchKernelGGL((par_iterate_guide_kernel<false>), dim3(cdiv(geo.W, 64), cdiv(geo.H, 16), geo.B), dim3(512), 0, st, guide, stats,
-                           in, out, nchan, dl, Cmax, geo, dbg);
+        hipLaunchKernelGGL((par_iterate_guide_kernel<false>), grid, block, 0, st, guide, stats, in, out, nchan, dl, Cmax, geo, dbg);
     EXCEL_CHECK_LAUNCH("par_iterate_guide");
     return EXCEL_OK;
 }

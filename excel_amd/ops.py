@@ -925,6 +925,26 @@ def par_forward(imgs, masks, dilations=PAR_DILATIONS, num_iter=20, nchan=None, w
     return out
 
 
+PAR_PLAN_STATS = ("tile", "pointwise_compact", "pointwise_planes")   # excel_par_plan (include/excel_hip.h)
+PAR_PLAN_STEPS = ("none", "recompute", "stream")
+PAR_PLAN_REFUSALS = (None, "n_iter", "dilations", "alignment", "size")
+
+
+def par_plan(B, Cmax, H, W, dilations=PAR_DILATIONS, num_iter=20, guide_hw=None, stream_affinities=False, ragged=False, aligned16=True):
+    """The kernels par_forward (ragged=False) or par_forward_ragged (ragged=True: B images of H x W each) runs on (host arithmetic
+    only): whether the guide (guide_hw, default (H, W)) is resized, the statistics kernel ("tile" / "pointwise_compact" /
+    "pointwise_planes") and its instance nd, the step kernel ("none" / "recompute" / "stream"), both grids and block sizes, the interior
+    and border tiles of one image (tile kernels), and for a ragged request the library does not take, `refused` = the reason."""
+    h, w = (H, W) if guide_hw is None else guide_hw
+    dil = (C.c_int32 * len(dilations))(*dilations)
+    plan = (C.c_int32 * 15)()
+    check(lib().excel_par_plan(B, Cmax, h, w, H, W, dil, len(dilations), num_iter, 1 if stream_affinities else 0, int(ragged), int(aligned16),
+                               plan), "excel_par_plan")
+    v = list(plan)
+    return dict(resize=bool(v[0]), stats=PAR_PLAN_STATS[v[1]], nd=v[2], step=PAR_PLAN_STEPS[v[3]], stats_grid=tuple(v[4:7]), stats_block=v[7],
+                step_grid=tuple(v[8:11]), step_block=v[11], tiles_interior=v[12], tiles_border=v[13], refused=PAR_PLAN_REFUSALS[v[14]])
+
+
 # ------------------------------------------------------------------ ragged batches (images of different label sizes in one launch)
 class RaggedPlan:
     """Tile map + offsets of a batch of images with different (H_b, W_b) (include/excel_hip.h, "ragged batches").

@@ -416,6 +416,27 @@ int excel_par_forward(const float* imgs, int h, int w, const float* masks, const
                       const int32_t* dilations /*host*/, int ndil, int n_iter, float w1, float w2, float* out,
                       void* workspace, int flags, void* stream);
 
+/* Which kernels excel_par_forward (ragged = 0) or excel_par_forward_ragged (ragged = 1) runs a request on (a HOST function: no device
+ * work; both entries and their launchers take every decision from the same function).  B images, Cmax mask planes, guide [h, w], masks
+ * [H, W]; ragged = 1: a batch of B images of H x W each in the pitched layout.  flags as for excel_par_forward; aligned16: the guide, the
+ * workspace, masks and out are all 16-byte aligned (what the entries find out from their pointers).
+ * plan[EXCEL_PAR_PLAN_INTS] = {resize, stats, nd, step, stats_grid x, y, z, stats_block, step_grid x, y, z, step_block, tiles_interior,
+ *                              tiles_border, refused}:
+ *   resize: the guide goes through the align_corners=True resize ((h, w) != (H, W); always for ragged batches);
+ *   stats: 0 the tile kernel writing the 5 statistics (recomputing step, W >= 8), 1 the pointwise kernel <nd> writing the 5 statistics
+ *          (recomputing step, W == 4), 2 the pointwise kernel <nd> writing 8 * nd affinity planes (streamed step);  nd = ndil;
+ *   step: 0 none (n_iter == 0: masks are copied), 1 the recomputing tile kernel (dilations [1,2,4,8,12,24], W % 4 == 0 in the uniform
+ *         layout, aligned16, max(Cmax,5) * H * Wp * 4 < 2^31, no EXCEL_PAR_STREAM_AFFINITIES), 2 the streamed-plane kernel;
+ *   grids: tile kernels (cdiv(W,64), cdiv(H,16), B) of 512 threads, pointwise and streamed kernels (cdiv(W,64), cdiv(H,4), B) of 256;
+ *          ragged: (tiles of the batch, 1 or 4, 1);  step grid and block are 0 for step == 0;
+ *   tiles_interior / tiles_border (tile kernels, else 0): the 64 x 16 tiles of ONE image staged in 16-byte pieces (x0 - 24 >= 0 and
+ *          x0 + 88 <= W) / in 4-byte pieces with clamped columns;
+ *   refused (ragged = 1): 0, or why excel_par_forward_ragged returns EXCEL_ERR_ARG: 1 n_iter < 1, 2 dilations, 3 alignment, 4 the 2^31
+ *          limit; every other field is then 0. */
+#define EXCEL_PAR_PLAN_INTS 15
+int excel_par_plan(int B, int Cmax, int h, int w, int H, int W, const int32_t* dilations /*host*/, int ndil, int n_iter, int flags,
+                   int ragged, int aligned16, int32_t* plan /*host*/);
+
 /* refined.argmax(1) -> valid_key lookup (utils/affutils.py:86-87, :168).  cls_idx may be NULL (identity keys). */
 int excel_argmax_label(const float* cams, const int32_t* nchan, const int32_t* cls_idx, int B, int Smax, int Cmax,
                        long long HW, uint8_t* labels_u8, int64_t* labels_i64, void* stream);
