@@ -133,13 +133,9 @@ __global__ void pos_resize_kernel(const float* __restrict__ pos, float* __restri
     const int n = (int)(i / D);
     if (n == 0) { out[i] = pos[d]; return; }
     const int y = (n - 1) / g, x = (n - 1) % g;
-    const float sc = (float)side / (float)g;
-    float fy = fmaxf(sc * ((float)y + 0.5f) - 0.5f, 0.f), fx = fmaxf(sc * ((float)x + 0.5f) - 0.5f, 0.f);
-    const int y0 = min((int)fy, side - 1), x0 = min((int)fx, side - 1);
-    const int y1 = min(y0 + 1, side - 1), x1 = min(x0 + 1, side - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const BilinearTap t = bilinear_tap(x, y, side, side, g, g, 0);
     auto at = [&](int yy, int xx) { return pos[(long long)(1 + yy * side + xx) * D + d]; };
-    out[i] = (1.f - ly) * ((1.f - lx) * at(y0, x0) + lx * at(y0, x1)) + ly * ((1.f - lx) * at(y1, x0) + lx * at(y1, x1));
+    out[i] = bilinear_blend(t, at(t.y0, t.x0), at(t.y0, t.x1), at(t.y1, t.x0), at(t.y1, t.x1));
 }
 
 __global__ void attn_layer_mean_kernel(const float* __restrict__ attn, int B, int N, int first, int nl, float* __restrict__ out) {

@@ -133,15 +133,10 @@ __global__ __launch_bounds__(256) void lam_scale_accumulate_kernel(const float* 
     const int x = (int)(i % W), y = (int)((i / W) % H);
     const int f = (int)((i / ((long long)W * H)) % F), b = (int)(i / ((long long)W * H * F));
     auto sample = [&](int bb, int xx) {   // F.interpolate(bilinear, align_corners=False) of map [g,g] at (y, xx)
-        const float fy = fmaxf(((float)g / (float)H) * ((float)y + 0.5f) - 0.5f, 0.f);
-        const float fx = fmaxf(((float)g / (float)W) * ((float)xx + 0.5f) - 0.5f, 0.f);
-        const int y0 = min((int)fy, g - 1), x0 = min((int)fx, g - 1);
-        const int y1 = min(y0 + 1, g - 1), x1 = min(x0 + 1, g - 1);
-        const float ly = fy - (float)y0, lx = fx - (float)x0;
+        const BilinearTap t = bilinear_tap(xx, y, g, g, H, W, 0);
         const float* m = maps + (long long)bb * g * g * F + f;
-        const float top = (1.f - lx) * m[(long long)(y0 * g + x0) * F] + lx * m[(long long)(y0 * g + x1) * F];
-        const float bot = (1.f - lx) * m[(long long)(y1 * g + x0) * F] + lx * m[(long long)(y1 * g + x1) * F];
-        return (1.f - ly) * top + ly * bot;
+        auto at = [&](int yy, int xc) { return m[(long long)(yy * g + xc) * F]; };
+        return bilinear_blend(t, at(t.y0, t.x0), at(t.y0, t.x1), at(t.y1, t.x0), at(t.y1, t.x1));
     };
     const float v = fmaxf(sample(b, x), sample(b + B, W - 1 - x));     // torch.max(lam[:b], lam[b:].flip(-1))
     acc[i] = init ? v : acc[i] + v;
@@ -159,15 +154,9 @@ __global__ __launch_bounds__(256) void seg_scale_accumulate_kernel(const float* 
     const int x = (int)(i % W), y = (int)((i / W) % H);
     const long long plane = i / ((long long)W * H);           // b * nc + c
     auto sample = [&](long long pl, int xx) {
-        const float fy = fmaxf(((float)h / (float)H) * ((float)y + 0.5f) - 0.5f, 0.f);
-        const float fx = fmaxf(((float)w / (float)W) * ((float)xx + 0.5f) - 0.5f, 0.f);
-        const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
-        const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-        const float ly = fy - (float)y0, lx = fx - (float)x0;
+        const BilinearTap t = bilinear_tap(xx, y, h, w, H, W, 0);
         const float* m = segs + pl * h * w;
-        const float top = (1.f - lx) * m[y0 * w + x0] + lx * m[y0 * w + x1];
-        const float bot = (1.f - lx) * m[y1 * w + x0] + lx * m[y1 * w + x1];
-        return (1.f - ly) * top + ly * bot;
+        return bilinear_blend(t, m[t.y0 * w + t.x0], m[t.y0 * w + t.x1], m[t.y1 * w + t.x0], m[t.y1 * w + t.x1]);
     };
     float v = sample(plane, x);
     if (flip_mean) v = (v + sample(plane + (long long)B * nc, W - 1 - x)) / 2.f;     // (segs[:1] + segs[1:].flip(-1)) / 2  (:79)

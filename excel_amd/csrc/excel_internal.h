@@ -226,27 +226,37 @@ namespace excel_f16 {
 // unqualified calls (decoder.hip, lvc.hip, train.hip, ...: exact-fp32 paths that never write split planes) mean the bf16 build
 using namespace excel_bf16;
 
-// ---------------------------------------------------------------- bilinear taps (attr.hip bilinear_resize, segeval.hip)
-// source index / weights of F.interpolate(mode='bilinear'): ATen area_pixel_compute_source_index (align_corners=False:
-// scale*(dst+0.5)-0.5 clamped at 0) and the two-stage blend, in explicit operations so that every kernel using it rounds alike
-struct BilinearTap { int y0, y1, x0, x1; float ly, lx; };
-__device__ __forceinline__ BilinearTap bilinear_tap(int x, int y, int h, int w, int H, int W, int align_corners) {
-    float fy, fx;
-    if (align_corners) {
-        fy = ((H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f) * (float)y;
-        fx = ((W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f) * (float)x;
-    } else {
-        fy = fmaxf(__fsub_rn(__fmul_rn((float)h / (float)H, (float)y + 0.5f), 0.5f), 0.f);
-        fx = fmaxf(__fsub_rn(__fmul_rn((float)w / (float)W, (float)x + 0.5f), 0.5f), 0.f);
-    }
-    BilinearTap t;
-    t.y0 = min((int)fy, h - 1); t.x0 = min((int)fx, w - 1);
-    t.y1 = min(t.y0 + 1, h - 1); t.x1 = min(t.x0 + 1, w - 1);
-    t.ly = fy - (float)t.y0; t.lx = fx - (float)t.x0;
+// ---------------------------------------------------------------- the bilinear sampler: every F.interpolate(mode='bilinear') site
+// One axis of ATen's area_pixel_compute_source_index: output index d of n_out -> the two source indices in [0, n_in) and the weight
+// of the second.  Contraction is off, so the operations below are the ones that run, in every kernel this is inlined into:
+//   align_corners=False: f = max(fma(n_in / n_out, d + 0.5, -0.5), 0) - the product and the -0.5 in ONE rounding (what hipcc -O3
+//     made of `scale * (d + 0.5f) - 0.5f` at every site before they shared this body; __fmul_rn / __fsub_rn do not prevent it, they
+//     are inlined as plain operations);
+//   align_corners=True: f = scale * d, ROUNDED before the weight is taken from it (ATen: lambda = src - floor(src)).  Fused into
+//     one fma, `f - i0` keeps what the rounding of f drops (4e-6 near 47) and PAR's outputs move by 2e-5
+//     (tests/test_gpu_par_shapes.py, ragged batch).
+struct LinearTap { int i0, i1; float l; };
+__device__ __forceinline__ LinearTap linear_tap(int d, int n_in, int n_out, int align_corners) {
+#pragma clang fp contract(off)
+    const float f = align_corners ? ((n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f) * (float)d
+                                  : fmaxf(fmaf((float)n_in / (float)n_out, (float)d + 0.5f, -0.5f), 0.f);
+    LinearTap t;
+    t.i0 = min((int)f, n_in - 1);
+    t.i1 = min(t.i0 + 1, n_in - 1);
+    t.l = f - (float)t.i0;
     return t;
 }
+struct BilinearTap { int y0, y1, x0, x1; float ly, lx; };
+__device__ __forceinline__ BilinearTap bilinear_tap(int x, int y, int h, int w, int H, int W, int align_corners) {
+    const LinearTap ty = linear_tap(y, h, H, align_corners), tx = linear_tap(x, w, W, align_corners);
+    return BilinearTap{ty.i0, ty.i1, tx.i0, tx.i1, ty.l, tx.l};
+}
+// the two-stage blend: each (1 - l) product rounded, then one fma per stage
+__device__ __forceinline__ float bilinear_blend(float ly, float lx, float p00, float p01, float p10, float p11) {
+    const float top = fmaf(lx, p01, __fmul_rn(1.f - lx, p00));
+    const float bot = fmaf(lx, p11, __fmul_rn(1.f - lx, p10));
+    return fmaf(ly, bot, __fmul_rn(1.f - ly, top));
+}
 __device__ __forceinline__ float bilinear_blend(const BilinearTap& t, float p00, float p01, float p10, float p11) {
-    const float top = fmaf(t.lx, p01, __fmul_rn(1.f - t.lx, p00));
-    const float bot = fmaf(t.lx, p11, __fmul_rn(1.f - t.lx, p10));
-    return fmaf(t.ly, bot, __fmul_rn(1.f - t.ly, top));
+    return bilinear_blend(t.ly, t.lx, p00, p01, p10, p11);
 }

@@ -566,30 +566,15 @@ __global__ __launch_bounds__(512, 4) void par_stats_tile_kernel(const float* __r
 }
 
 // F.interpolate(mode='bilinear', align_corners=True) (PAR.py:67): planes of h x w -> H x W
-__device__ __forceinline__ float bilinear_ac_px(const float* __restrict__ p, int h, int w, int H, int W, int x, int y) {
-#pragma clang fp contract(off)   // (see fy below)
-    const float sy = (H > 1) ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sx = (W > 1) ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    // The source position is ROUNDED before the weight is taken from it (ATen: src = scale * dst, lambda = src - floor(src)).  With
-    // contraction allowed, `fy - y0` fuses with the product into one fma (__fmul_rn does not stop that: it is inlined as a plain
-    // multiplication) and the weight keeps what the rounding of fy (4e-6 near 47) drops: guides 60 fp32 roundings off the
-    // reference's, PAR outputs off by 2e-5 (tests/test_gpu_par_shapes.py, ragged batch).  The blend's own fmaf calls stay fused.
-    const float fy = sy * (float)y, fx = sx * (float)x;
-    const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
-    const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
-    const float top = fmaf(lx, p[y0 * w + x1], __fmul_rn(1.f - lx, p[y0 * w + x0]));
-    const float bot = fmaf(lx, p[y1 * w + x1], __fmul_rn(1.f - lx, p[y1 * w + x0]));
-    return fmaf(ly, bot, __fmul_rn(1.f - ly, top));
-}
-
 __global__ __launch_bounds__(256) void bilinear_ac_kernel(const float* __restrict__ in, float* __restrict__ out, int planes,
                                                           int h, int w, int H, int W) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)planes * H * W) return;
     const int x = (int)(i % W), y = (int)((i / W) % H);
     const long long pl = i / ((long long)W * H);
-    out[i] = bilinear_ac_px(in + pl * h * w, h, w, H, W, x, y);
+    const BilinearTap t = bilinear_tap(x, y, h, w, H, W, 1);
+    const float* p = in + pl * h * w;
+    out[i] = bilinear_blend(t, p[t.y0 * w + t.x0], p[t.y0 * w + t.x1], p[t.y1 * w + t.x0], p[t.y1 * w + t.x1]);
 }
 
 // ragged: in [B,3,h,w] (uniform) -> the pitched guide planes of every image at its own (H_b, W_b); grid (tiles, 3 channels)
@@ -603,7 +588,9 @@ __global__ __launch_bounds__(256) void bilinear_ac_ragged_kernel(const float* __
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int y = t.y0 + (threadIdx.x >> 6) + 4 * r;
-        if (y < t.H) o[(long long)y * t.Wp + x] = bilinear_ac_px(p, h, w, t.H, t.W, x, y);
+        if (y >= t.H) continue;
+        const BilinearTap tp = bilinear_tap(x, y, h, w, t.H, t.W, 1);
+        o[(long long)y * t.Wp + x] = bilinear_blend(tp, p[tp.y0 * w + tp.x0], p[tp.y0 * w + tp.x1], p[tp.y1 * w + tp.x0], p[tp.y1 * w + tp.x1]);
     }
 }
 

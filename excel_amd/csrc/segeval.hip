@@ -26,33 +26,13 @@ struct SegScales {
     float last_scale;                    // (float)(1.0 / ns): the mean over scales folded into the last step
 };
 
-// seg_scale_accumulate_kernel's arithmetic, operation for operation.  Its source leaves the fusing of multiplies and adds to the
-// compiler; these helpers spell out the result the compiler produced for it (gfx950, -O3: the source coordinate as one fma; in the
-// direct sample top and the final blend fused on the (1 - w) product's side, bot on the other; in the mirrored sample the final
-// blend as two products and an add), with contraction switched off so that no other fusing can change a bit.  The GPU tests pin
-// the fused kernel to the chain of seg_scale_accumulate calls bit for bit.
-__device__ __forceinline__ float seg_src_coord(int g, int D, int d) {
-#pragma clang fp contract(off)
-    return fmaxf(fmaf((float)g / (float)D, (float)d + 0.5f, -0.5f), 0.f);
-}
-__device__ __forceinline__ float seg_sample(const float* m, int y0, int y1, int x0, int x1, float ly, float lx) {
-#pragma clang fp contract(off)
-    const float top = fmaf(lx, m[y0 + x1], (1.f - lx) * m[y0 + x0]);
-    const float bot = fmaf(1.f - lx, m[y1 + x0], lx * m[y1 + x1]);
-    return fmaf(ly, bot, (1.f - ly) * top);
-}
-__device__ __forceinline__ float seg_sample_mirrored(const float* m, int y0, int y1, int x0, int x1, float ly, float lx) {
-#pragma clang fp contract(off)
-    const float top = fmaf(lx, m[y0 + x1], (1.f - lx) * m[y0 + x0]);
-    const float bot = fmaf(1.f - lx, m[y1 + x0], lx * m[y1 + x1]);
-    return (1.f - ly) * top + ly * bot;
-}
-
 // One workgroup per 64 x 16 tile; lane (tx, ty) = (tid % 16, tid / 16) owns pixels x0 + 4 tx .. +3 of row y0 + ty, so the pitched
 // planes are stored 16 bytes per lane (rows are padded to 4 floats; the pad columns get the value of the clamped sample, which is
 // in bounds and never read as a pixel).  The separable bilinear taps of every scale - row taps of the tile's 16 rows, column taps
-// of its 64 columns and of their mirror images W-1-x - are computed once per tile into LDS with seg_scale_accumulate_kernel's
-// expressions; the class loop then only gathers and blends.
+// of its 64 columns and of their mirror images W-1-x - are computed once per tile into LDS; the class loop then only gathers and
+// blends.  The taps and the blend are seg_scale_accumulate_kernel's (linear_tap, bilinear_blend) and the steps around the sample
+// are written as there, with contraction off so that nothing fuses across them: the GPU tests pin this kernel to the chain of
+// seg_scale_accumulate calls bit for bit.
 __global__ __launch_bounds__(256) void seg_msc_fuse_ragged_kernel(SegScales sc, int B, int nc, TileGeo geo, float* __restrict__ planes,
                                                                   unsigned char* __restrict__ labels) {
 #pragma clang fp contract(off)
@@ -67,17 +47,15 @@ __global__ __launch_bounds__(256) void seg_msc_fuse_ragged_kernel(SegScales sc, 
         if (s < sc.ns) {
             const int g = sc.g[s];
             if (tid < 64) {
-                // fx of seg_scale_accumulate_kernel's sample(), for x and for the mirrored W - 1 - x
-                const int x = t.x0 + tid, xf = t.W - 1 - x;
-                const float fx = seg_src_coord(g, t.W, x), ff = seg_src_coord(g, t.W, xf);
-                const int a0 = min((int)fx, g - 1), b0 = min((int)ff, g - 1);
-                cx0[s][tid] = a0; cx1[s][tid] = min(a0 + 1, g - 1); clx[s][tid] = fx - (float)a0;
-                fx0[s][tid] = b0; fx1[s][tid] = min(b0 + 1, g - 1); flx[s][tid] = ff - (float)b0;
+                // the column taps of x and of the mirrored W - 1 - x
+                const int x = t.x0 + tid;
+                const LinearTap c = linear_tap(x, g, t.W, 0), f = linear_tap(t.W - 1 - x, g, t.W, 0);
+                cx0[s][tid] = c.i0; cx1[s][tid] = c.i1; clx[s][tid] = c.l;
+                fx0[s][tid] = f.i0; fx1[s][tid] = f.i1; flx[s][tid] = f.l;
             } else if (tid < 80) {
-                const int r = tid - 64, y = t.y0 + r;
-                const float fy = seg_src_coord(g, t.H, y);
-                const int a0 = min((int)fy, g - 1);
-                ry0[s][r] = a0 * g; ry1[s][r] = min(a0 + 1, g - 1) * g; rly[s][r] = fy - (float)a0;
+                const int r = tid - 64;
+                const LinearTap ry = linear_tap(t.y0 + r, g, t.H, 0);
+                ry0[s][r] = ry.i0 * g; ry1[s][r] = ry.i1 * g; rly[s][r] = ry.l;
             }
         }
     }
@@ -103,8 +81,12 @@ __global__ __launch_bounds__(256) void seg_msc_fuse_ragged_kernel(SegScales sc, 
                 for (int k = 0; k < 4; ++k) {
                     const int col = 4 * tx + k;
                     // seg_scale_accumulate_kernel: sample(plane, x), then (v + sample(plane + B*nc, W-1-x)) / 2 where flip_mean is set
-                    float v = seg_sample(m, y0, y1, cx0[s][col], cx1[s][col], ly, clx[s][col]);
-                    if (sc.flip[s]) v = (v + seg_sample_mirrored(mf, y0, y1, fx0[s][col], fx1[s][col], ly, flx[s][col])) * 0.5f;
+                    const int a0 = cx0[s][col], a1 = cx1[s][col];
+                    float v = bilinear_blend(ly, clx[s][col], m[y0 + a0], m[y0 + a1], m[y1 + a0], m[y1 + a1]);
+                    if (sc.flip[s]) {
+                        const int b0 = fx0[s][col], b1 = fx1[s][col];
+                        v = (v + bilinear_blend(ly, flx[s][col], mf[y0 + b0], mf[y0 + b1], mf[y1 + b0], mf[y1 + b1])) * 0.5f;
+                    }
                     v = s == 0 ? v : acc[k] + v;
                     acc[k] = v * (s == sc.ns - 1 ? sc.last_scale : 1.f);
                 }

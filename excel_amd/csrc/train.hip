@@ -12,14 +12,6 @@
 
 #define TR_NPART 256
 
-// F.interpolate(bilinear, align_corners=False) source coordinates of output index o (size O) in an input of size I
-__device__ __forceinline__ void bil_src(int o, int O, int I, int& i0, int& i1, float& l) {
-    const float f = fmaxf(((float)I / (float)O) * ((float)o + 0.5f) - 0.5f, 0.f);
-    i0 = min((int)f, I - 1);
-    i1 = min(i0 + 1, I - 1);
-    l = f - (float)i0;
-}
-
 // per-pixel cross entropy of the up-sampled logits, split into the background (label 0) and foreground (label 1..nc-1) terms;
 // partial[blk] = {bg_ce_sum, fg_ce_sum, bg_count, fg_count}
 __global__ __launch_bounds__(256) void tr_seg_ce_kernel(const float* __restrict__ up, const unsigned char* __restrict__ lab, int nc, long long HW,
@@ -89,7 +81,7 @@ __global__ __launch_bounds__(256) void tr_seg_grad_kernel(float* __restrict__ up
 }
 
 // adjoint of the bilinear up-sampling: one wave per low-resolution cell gathers, in a fixed order, every high-resolution pixel
-// whose interpolation stencil touches the cell (weights recomputed exactly as the forward computes them)
+// whose interpolation stencil touches the cell (linear_tap: the indices and weights of the forward, excel_launch_bilinear_resize)
 __global__ __launch_bounds__(64) void tr_bilinear_adjoint_kernel(const float* __restrict__ dup, float* __restrict__ dseg, int g_h, int g_w, int H,
                                                                  int W) {
     const int cell = blockIdx.x, plane = blockIdx.y;              // plane = b * nc + c
@@ -102,12 +94,9 @@ __global__ __launch_bounds__(64) void tr_bilinear_adjoint_kernel(const float* __
     float acc = 0.f;
     for (int t = threadIdx.x; t < n; t += 64) {
         const int y = y_lo + t / nx, x = x_lo + t % nx;
-        int y0, y1, x0, x1;
-        float ly, lx;
-        bil_src(y, H, g_h, y0, y1, ly);
-        bil_src(x, W, g_w, x0, x1, lx);
-        const float wy = (y0 == ci ? 1.f - ly : 0.f) + (y1 == ci ? ly : 0.f);
-        const float wx = (x0 == cj ? 1.f - lx : 0.f) + (x1 == cj ? lx : 0.f);
+        const LinearTap ty = linear_tap(y, g_h, H, 0), tx = linear_tap(x, g_w, W, 0);
+        const float wy = (ty.i0 == ci ? 1.f - ty.l : 0.f) + (ty.i1 == ci ? ty.l : 0.f);
+        const float wx = (tx.i0 == cj ? 1.f - tx.l : 0.f) + (tx.i1 == cj ? tx.l : 0.f);
         acc += wy * wx * src[(long long)y * W + x];
     }
     acc = wave_sum(acc);

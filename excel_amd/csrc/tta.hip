@@ -24,30 +24,12 @@ struct TtaScales {
     int ns;
 };
 
-// lam_scale_accumulate_kernel's arithmetic (attr.hip), operation for operation.  Its source leaves the fusing of multiplies and adds
-// to the compiler; these helpers spell out what the compiler made of it (gfx950, -O3: the source coordinate as one fma, top fused on
-// the lx product's side, bot on the (1 - lx) side, the final blend as two products and an add - in both of its samples), with
-// contraction switched off so that no other fusing can change a bit.  The GPU tests pin the fuse to the chain of
-// lam_scale_accumulate + plane_minmax_normalize bit for bit.
-__device__ __forceinline__ float tta_src_coord(int g, int D, int d) {
-#pragma clang fp contract(off)
-    return fmaxf(fmaf((float)g / (float)D, (float)d + 0.5f, -0.5f), 0.f);
-}
-// m = the (image, class) plane's first element; token stride F
-__device__ __forceinline__ float tta_sample(const float* __restrict__ m, int F, int g, int G, int y, int x) {
-#pragma clang fp contract(off)
-    const float fy = tta_src_coord(g, G, y), fx = tta_src_coord(g, G, x);
-    const int y0 = min((int)fy, g - 1), x0 = min((int)fx, g - 1);
-    const int y1 = min(y0 + 1, g - 1), x1 = min(x0 + 1, g - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
-    const float top = fmaf(lx, m[(y0 * g + x1) * F], (1.f - lx) * m[(y0 * g + x0) * F]);
-    const float bot = fmaf(1.f - lx, m[(y1 * g + x0) * F], lx * m[(y1 * g + x1) * F]);
-    return (1.f - ly) * top + ly * bot;
-}
 __device__ __forceinline__ bool tta_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
-// one thread per output value, (b, token, class) with the class fastest.  fmaxf drops a NaN (and -inf) of one half, so a non-finite
-// sample of either half is carried on as a NaN: the sum stays non-finite and the normalise pass sees it.
+// one thread per output value, (b, token, class) with the class fastest.  The sample is lam_scale_accumulate_kernel's (attr.hip:
+// bilinear_tap + bilinear_blend), and contraction is off so that nothing fuses across the steps around it: the GPU tests pin the
+// fuse to the chain of lam_scale_accumulate + plane_minmax_normalize bit for bit.  fmaxf drops a NaN (and -inf) of one half, so a
+// non-finite sample of either half is carried on as a NaN: the sum stays non-finite and the normalise pass sees it.
 __global__ __launch_bounds__(256) void lam_tta_accumulate_kernel(TtaScales sc, int B, int F, int G, int flip, float* __restrict__ out) {
 #pragma clang fp contract(off)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -61,9 +43,14 @@ __global__ __launch_bounds__(256) void lam_tta_accumulate_kernel(TtaScales sc, i
         if (s < sc.ns) {
             const int g = sc.g[s];
             const long long img = (long long)g * g * F;
-            float v = tta_sample(sc.maps[s] + b * img + f, F, g, G, y, x);
+            auto sample = [&](const float* __restrict__ m, int xx) {   // m = the (image, class) plane's first element; token stride F
+                const BilinearTap t = bilinear_tap(xx, y, g, g, G, G, 0);
+                auto at = [&](int yy, int xc) { return m[(yy * g + xc) * F]; };
+                return bilinear_blend(t, at(t.y0, t.x0), at(t.y0, t.x1), at(t.y1, t.x0), at(t.y1, t.x1));
+            };
+            float v = sample(sc.maps[s] + b * img + f, x);
             if (flip) {
-                const float c = tta_sample(sc.maps[s] + (b + B) * img + f, F, g, G, y, G - 1 - x);   // lam[B + b].flip(-1)
+                const float c = sample(sc.maps[s] + (b + B) * img + f, G - 1 - x);   // lam[B + b].flip(-1)
                 v = (tta_nonfinite(v) || tta_nonfinite(c)) ? NAN : fmaxf(v, c);
             }
             acc = s == 0 ? v : acc + v;
