@@ -83,26 +83,6 @@ extern "C" int excel_prof_collect(double* ms, long long* launches, double* work)
     return EXCEL_OK;
 }
 
-#define ST(s) ((hipStream_t)(s))
-#define TRY(x)                  \
-    do {                        \
-        int rc__ = (x);         \
-        if (rc__) return rc__;  \
-    } while (0)
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static GemmArgs gemm_args(const float* A, const float* B, float* C, const float* bias, const float* res, int M, int N, int K,
-                          int lda, int ldb, int ldc, int ldr, int act) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.res = res;
-    g.M = M; g.N = N; g.K = K; g.Kld = (K + 3) / 4 * 4;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr;
-    g.act = act; g.out_mode = GEMM_OUT_PLAIN; g.alpha = 1.f; g.zdiv = 1;
-    return g;
-}
-
 static GemmBfArgs gemm_bf_args(const void* A, const unsigned short* W, float* C, void* Cs, const float* bias, const float* res,
                                int M, int N, int K, int ldc, int ldr, int act, int out_mode) {
     GemmBfArgs g;
@@ -444,24 +424,23 @@ static VitWs vit_ws_layout(const excel_vit_config& c, int B, int S, char* base) 
     VitWs w;
     w.NP = (N + 3) / 4 * 4;
     w.KP = (N + 31) / 32 * 32;            // K of the bf16x3 A_sum.V GEMM (zero padded)
-    size_t off = 0;
-    auto take = [&](size_t floats) { float* p = (float*)(base + off); off += align_up(floats * sizeof(float), 256); return p; };
-    w.x = take(M * D);
-    w.xo = take(M * D);
-    w.y = take(M * D);
-    w.ao = take(M * D);                   // also the patch-embed GEMM output [B*P, D]
-    w.qkvh = take(M * 3 * D);
-    w.qkvs = take(M * 3 * D);             // split-bf16 copy of q|k|v for the bf16x3 attention scores (bf16x3 mode)
+    Workspace ws(base);
+    w.x = ws.take<float>(M * D);
+    w.xo = ws.take<float>(M * D);
+    w.y = ws.take<float>(M * D);
+    w.ao = ws.take<float>(M * D);                   // also the patch-embed GEMM output [B*P, D]
+    w.qkvh = ws.take<float>(M * 3 * D);
+    w.qkvs = ws.take<float>(M * 3 * D);             // split-bf16 copy of q|k|v for the bf16x3 attention scores (bf16x3 mode)
     {   // MLP hidden [M,4D]; also holds the im2col matrix [B*P, 3*ps*ps]
         const size_t col = (size_t)B * (N - 1) * 3 * c.patch * c.patch;
-        w.hbuf = take(M * 4 * D > col ? M * 4 * D : col);
+        w.hbuf = ws.take<float>(M * 4 * D > col ? M * 4 * D : col);
     }
-    w.stats = take((size_t)B * c.heads * 4 * N * 2);
-    w.a_sum = take((size_t)B * N * w.KP);              // fp32 [B,N,NP] or split bf16 [B,N][2*KP]
-    w.vt = take((size_t)B * D * w.KP);                 // V^T split [B][D][2*KP] (bf16x3 mode)
-    w.fraw = take(M * c.out_dim);
-    w.ss = take((size_t)B * c.out_dim);
-    w.total = off;
+    w.stats = ws.take<float>((size_t)B * c.heads * 4 * N * 2);
+    w.a_sum = ws.take<float>((size_t)B * N * w.KP);              // fp32 [B,N,NP] or split bf16 [B,N][2*KP]
+    w.vt = ws.take<float>((size_t)B * D * w.KP);                 // V^T split [B][D][2*KP] (bf16x3 mode)
+    w.fraw = ws.take<float>(M * c.out_dim);
+    w.ss = ws.take<float>((size_t)B * c.out_dim);
+    w.total = ws.total();
     return w;
 }
 
@@ -567,20 +546,26 @@ static int vit_forward_impl(EXCEL_VIT_FWD_ARGS) {
 }
 
 // ------------------------------------------------------------------------------------ CAM
-extern "C" size_t excel_cam_workspace_bytes(int B, int N, int T) {
-    return align_up((size_t)B * N * ((T + 3) / 4 * 4) * sizeof(float), 256);
+struct CamWs { float* S; int ldT; size_t total; };         // S [B*N, ldT]: the token-text similarities, rows padded to 4 floats
+static CamWs cam_ws_layout(int B, int N, int T, void* base) {
+    CamWs w;
+    Workspace ws(base);
+    w.ldT = (T + 3) / 4 * 4;
+    w.S = ws.take<float>((size_t)B * N * w.ldT);
+    w.total = ws.total();
+    return w;
 }
+extern "C" size_t excel_cam_workspace_bytes(int B, int N, int T) { return cam_ws_layout(B, N, T, nullptr).total; }
 
 extern "C" int excel_clip_feature_surgery(const float* image_features, const float* text, int B, int N, int C, int T, int F,
                                           float temperature, float* out_full, float* out_slice, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(image_features && text && workspace && (out_full || out_slice), "clip_feature_surgery: null argument");
     EXCEL_CHECK_ARG((C % 4) == 0, "clip_feature_surgery: C must be a multiple of 4");
-    const int ldT = (T + 3) / 4 * 4;
-    float* S = (float*)workspace;
+    const CamWs w = cam_ws_layout(B, N, T, workspace);
     // S[b*N+n, t] = f . text[t]  -- one NT GEMM over all B*N token rows (text shared)
-    GemmArgs ga = gemm_args(image_features, text, S, nullptr, nullptr, B * N, T, C, C, C, ldT, 0, GEMM_ACT_NONE);
+    GemmArgs ga = gemm_args(image_features, text, w.S, nullptr, nullptr, B * N, T, C, C, C, w.ldT, 0, GEMM_ACT_NONE);
     TRY(excel_launch_gemm(ga, true, 1, ST(stream)));
-    return excel_launch_cam_epilogue(S, out_full, out_slice, B, N, T, ldT, F, temperature, ST(stream));
+    return excel_launch_cam_epilogue(w.S, out_full, out_slice, B, N, T, w.ldT, F, temperature, ST(stream));
 }
 
 // Fused path (cam.hip): token-axis norm + similarity on the matrix core + surgery epilogue, straight from the un-normalised token
@@ -588,13 +573,12 @@ extern "C" int excel_clip_feature_surgery(const float* image_features, const flo
 struct PtcWs { float *sim, *part, *colsq; unsigned short* ts; size_t total; };
 static PtcWs ptc_ws_layout(int B, int N, int C, int T, char* base) {
     PtcWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
-    w.sim = (float*)take(excel_patch_text_cam_ws_floats(B, N, C, T, 0) * sizeof(float));
-    w.ts = (unsigned short*)take((size_t)T * C * sizeof(float));
-    w.part = (float*)take(excel_patch_text_cam_ws_floats(B, N, C, T, 1) * sizeof(float));
-    w.colsq = (float*)take(excel_patch_text_cam_ws_floats(B, N, C, T, 2) * sizeof(float));
-    w.total = off;
+    Workspace ws(base);
+    w.sim = ws.take<float>(excel_patch_text_cam_ws_floats(B, N, C, T, 0));
+    w.ts = ws.take<unsigned short>((size_t)T * C * 2);        // the split text bank: hi and lo planes
+    w.part = ws.take<float>(excel_patch_text_cam_ws_floats(B, N, C, T, 1));
+    w.colsq = ws.take<float>(excel_patch_text_cam_ws_floats(B, N, C, T, 2));
+    w.total = ws.total();
     return w;
 }
 extern "C" size_t excel_patch_text_cam_workspace_bytes(int B, int N, int C, int T) { return ptc_ws_layout(B, N, C, T, nullptr).total; }
@@ -622,21 +606,29 @@ extern "C" int excel_attn_layer_mean(const float* attn, int Lw, int B, int N, in
     return EXCEL_OK;
 }
 
-extern "C" size_t excel_trans_mat_workspace_bytes(int B, int P) {
-    return 2 * align_up((size_t)B * P * P * sizeof(float), 256) + align_up((size_t)B * P * sizeof(float), 256);
+// random walk: the transition matrix T and its symmetrised form [B,P,P], the column sums [B,P]; the refinement adds the masked score
+// maps v and the intermediate u = Tsym v [B,Smax,P] (Smax = 0: none)
+struct WalkWs { float *T, *Tsym, *cs, *v, *u; size_t total; };
+static WalkWs walk_ws_layout(int B, int P, int Smax, void* base) {
+    WalkWs w;
+    Workspace ws(base);
+    w.T = ws.take<float>((size_t)B * P * P);
+    w.Tsym = ws.take<float>((size_t)B * P * P);
+    w.cs = ws.take<float>((size_t)B * P);
+    w.v = ws.take<float>((size_t)B * Smax * P);
+    w.u = ws.take<float>((size_t)B * Smax * P);
+    w.total = ws.total();
+    return w;
 }
+extern "C" size_t excel_trans_mat_workspace_bytes(int B, int P) { return walk_ws_layout(B, P, 0, nullptr).total; }
 
 extern "C" int excel_compute_trans_mat(const float* w_aff, int B, int P, float* trans_out, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(w_aff && trans_out && workspace, "compute_trans_mat: null argument");
     EXCEL_CHECK_ARG((P % 4) == 0, "compute_trans_mat: P must be a multiple of 4 (P=%d)", P);
-    char* base = (char*)workspace;
-    const size_t mat = align_up((size_t)B * P * P * sizeof(float), 256);
-    float* T = (float*)base;
-    float* Tsym = (float*)(base + mat);
-    float* cs = (float*)(base + 2 * mat);
-    TRY(excel_launch_trans_mat_sym(w_aff, T, Tsym, cs, B, P, ST(stream)));
+    const WalkWs w = walk_ws_layout(B, P, 0, workspace);
+    TRY(excel_launch_trans_mat_sym(w_aff, w.T, w.Tsym, w.cs, B, P, ST(stream)));
     // Tsym . Tsym ; Tsym symmetric => B operand [N,K] = Tsym itself (NT form)
-    GemmArgs ga = gemm_args(Tsym, Tsym, trans_out, nullptr, nullptr, P, P, P, P, P, P, 0, GEMM_ACT_NONE);
+    GemmArgs ga = gemm_args(w.Tsym, w.Tsym, trans_out, nullptr, nullptr, P, P, P, P, P, P, 0, GEMM_ACT_NONE);
     ga.sA = ga.sB = ga.sC = (long long)P * P;
     return excel_launch_gemm(ga, true, B, ST(stream));
 }
@@ -653,28 +645,18 @@ extern "C" int excel_scoremap_box_mask(const float* attr, const int32_t* cls_idx
     return excel_launch_bbox_mask(attr, cls_idx, ncls, B, g, F, Smax, caa_thre, v_out, mask_out, ST(stream));
 }
 
-extern "C" size_t excel_refine_workspace_bytes(int B, int P, int Smax) {
-    return 2 * align_up((size_t)B * P * P * sizeof(float), 256) + align_up((size_t)B * P * sizeof(float), 256) +
-           2 * align_up((size_t)B * Smax * P * sizeof(float), 256);
-}
+extern "C" size_t excel_refine_workspace_bytes(int B, int P, int Smax) { return walk_ws_layout(B, P, Smax, nullptr).total; }
 
 extern "C" int excel_refine_cams_with_aff(const float* attr, const float* w_aff, const int32_t* cls_idx, const int32_t* ncls, int B,
                                           int g, int F, int Smax, double caa_thre, float* refined, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(attr && w_aff && cls_idx && ncls && refined && workspace, "refine_cams_with_aff: null argument");
     const int P = g * g;
-    char* base = (char*)workspace;
-    const size_t mat = align_up((size_t)B * P * P * sizeof(float), 256);
-    const size_t vec = align_up((size_t)B * Smax * P * sizeof(float), 256);
-    float* T = (float*)base;
-    float* Tsym = (float*)(base + mat);
-    float* cs = (float*)(base + 2 * mat);
-    float* v = (float*)(base + 2 * mat + align_up((size_t)B * P * sizeof(float), 256));
-    float* u = (float*)((char*)v + vec);
+    const WalkWs w = walk_ws_layout(B, P, Smax, workspace);
     hipStream_t st = ST(stream);
-    TRY(excel_launch_trans_mat_sym(w_aff, T, Tsym, cs, B, P, st));
-    TRY(excel_launch_bbox_mask(attr, cls_idx, ncls, B, g, F, Smax, caa_thre, v, nullptr, st));
-    TRY(excel_launch_matvec(Tsym, v, ncls, u, B, P, Smax, st));          // u = Tsym (mask.g)
-    TRY(excel_launch_matvec(Tsym, u, ncls, refined, B, P, Smax, st));    // refined = Tsym u = (Tsym.Tsym)(mask.g)
+    TRY(excel_launch_trans_mat_sym(w_aff, w.T, w.Tsym, w.cs, B, P, st));
+    TRY(excel_launch_bbox_mask(attr, cls_idx, ncls, B, g, F, Smax, caa_thre, w.v, nullptr, st));
+    TRY(excel_launch_matvec(w.Tsym, w.v, ncls, w.u, B, P, Smax, st));        // u = Tsym (mask.g)
+    TRY(excel_launch_matvec(w.Tsym, w.u, ncls, refined, B, P, Smax, st));    // refined = Tsym u = (Tsym.Tsym)(mask.g)
     return EXCEL_OK;
 }
 
@@ -775,11 +757,21 @@ extern "C" int excel_train_augment_image(const uint8_t* hwc, const int32_t* tabl
 }
 
 // ------------------------------------------------------------------------------------ PAR / labels / metric
-extern "C" size_t excel_par_workspace_bytes(int B, int Cmax, int H, int W, int ndil) {
-    const size_t hw = (size_t)H * W;
-    return align_up((size_t)B * 8 * ndil * hw * sizeof(float), 256) + align_up((size_t)B * Cmax * hw * sizeof(float), 256) +
-           align_up((size_t)B * 3 * hw * sizeof(float), 256);
+// affinities [aff_planes planes: 8 per dilation streamed, or the 5 statistics the step recomputes them from] + ping-pong [Cmax planes] +
+// resized guide [3 planes]; `pix` = the pixels of one plane over the whole batch (ragged: in the pitched layout)
+struct ParWs { float *aff, *pp, *guide; size_t total; };
+static ParWs par_ws_layout(size_t pix, int aff_planes, int Cmax, void* base) {
+    ParWs w;
+    Workspace ws(base);
+    w.aff = ws.take<float>(aff_planes * pix);
+    w.pp = ws.take<float>(Cmax * pix);
+    w.guide = ws.take<float>(3 * pix);
+    w.total = ws.total();
+    return w;
 }
+static ParWs par_ws_uniform(int B, int Cmax, int H, int W, int ndil, void* base) { return par_ws_layout((size_t)B * H * W, 8 * ndil, Cmax, base); }
+static ParWs par_ws_ragged(long long total_pix, int Cmax, void* base) { return par_ws_layout((size_t)total_pix, 5, Cmax, base); }
+extern "C" size_t excel_par_workspace_bytes(int B, int Cmax, int H, int W, int ndil) { return par_ws_uniform(B, Cmax, H, W, ndil, nullptr).total; }
 
 // ping-pong so that the LAST step writes `out`: out, pp alternate backwards from the end
 template <class Step>
@@ -800,10 +792,8 @@ extern "C" int excel_par_forward(const float* imgs, int h, int w, const float* m
     EXCEL_CHECK_ARG(n_iter >= 0 && ndil >= 1 && ndil <= 8, "par_forward: bad n_iter/ndil");
     EXCEL_CHECK_ARG(B > 0 && Cmax > 0 && H > 0 && W > 0 && h > 0 && w > 0, "par_forward: bad shape");
     const size_t hw = (size_t)H * W;
-    char* base = (char*)workspace;
-    float* aff = (float*)base;
-    float* pp = (float*)(base + align_up((size_t)B * 8 * ndil * hw * sizeof(float), 256));
-    float* guide = (float*)((char*)pp + align_up((size_t)B * Cmax * hw * sizeof(float), 256));
+    const ParWs ws = par_ws_uniform(B, Cmax, H, W, ndil, workspace);
+    float *aff = ws.aff, *pp = ws.pp, *guide = ws.guide;
     hipStream_t st = ST(stream);
     // the resize, the form of the affinities (streamed planes or statistics the step recomputes them from) and both kernels: par_plan.hip
     const float* gimg = (h != H || w != W) ? guide : imgs;
@@ -826,22 +816,15 @@ extern "C" int excel_par_forward(const float* imgs, int h, int w, const float* m
     });
 }
 
-// statistics [5 planes] + ping-pong [Cmax planes] + resized guide [3 planes], all in the pitched ragged layout
-extern "C" size_t excel_par_ragged_workspace_bytes(long long total_pix, int Cmax) {
-    return align_up((size_t)5 * total_pix * sizeof(float), 256) + align_up((size_t)Cmax * total_pix * sizeof(float), 256) +
-           align_up((size_t)3 * total_pix * sizeof(float), 256);
-}
+extern "C" size_t excel_par_ragged_workspace_bytes(long long total_pix, int Cmax) { return par_ws_ragged(total_pix, Cmax, nullptr).total; }
 
 extern "C" int excel_par_forward_ragged(const float* imgs, int h, int w, const float* masks, const int32_t* nchan, const int32_t* table,
                                         const excel_ragged_info* info, int Cmax, const int32_t* dilations, int ndil, int n_iter, float w1,
                                         float w2, float* out, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(imgs && masks && out && workspace && dilations && table && info, "par_forward_ragged: null argument");
     EXCEL_CHECK_ARG(Cmax > 0 && h > 0 && w > 0 && info->B > 0, "par_forward_ragged: bad n_iter / shape");
-    const size_t tp = (size_t)info->total_pix;
-    char* base = (char*)workspace;
-    float* stats = (float*)base;
-    float* pp = (float*)(base + align_up(5 * tp * sizeof(float), 256));
-    float* guide = (float*)((char*)pp + align_up((size_t)Cmax * tp * sizeof(float), 256));
+    const ParWs ws = par_ws_ragged(info->total_pix, Cmax, workspace);
+    float *stats = ws.aff, *pp = ws.pp, *guide = ws.guide;
     hipStream_t st = ST(stream);
     const TileGeo geo = ragged_geo(table, info->B);
     const bool aligned16 = ((((uintptr_t)guide | (uintptr_t)stats | (uintptr_t)masks | (uintptr_t)out | (uintptr_t)pp) & 15) == 0);

@@ -29,7 +29,6 @@ constexpr int IGNORE = 255;
 enum { R_H = 0, R_W, R_H2, R_W2, R_LOFF, R_WS, R_XOFF, R_KX, R_YOFF, R_KY, R_NX, R_NY, R_FLIP, R_HPAD, R_WPAD, R_HP, R_WP, R_CH = 18,
        R_CW = 28 };
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 size_t hist_bytes(int B) { return align_up((size_t)B * NCAND * 256 * sizeof(int), 256); }
 size_t choice_bytes(int B) { return align_up((size_t)B * 2 * sizeof(int), 256); }
 

@@ -83,8 +83,6 @@ __global__ __launch_bounds__(256) void cam_overlay_ragged_kernel(const uint8_t* 
     }
 }
 
-#define ST(s) ((hipStream_t)(s))
-
 static int camviz_launch(const uint8_t* hwc, const float* cams, int Cmax, const int32_t* ncls, int k_single, const int64_t* out_off,
                          TileGeo geo, long long ntiles, int mode, const double* tables, uint8_t* out, void* stream) {
     if (ntiles == 0) return EXCEL_OK;

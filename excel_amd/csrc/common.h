@@ -32,8 +32,34 @@ void excel_set_error(const char* fmt, ...);
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// return-on-error for the int status codes of the launchers
+#define TRY(x)                  \
+    do {                        \
+        int rc__ = (x);         \
+        if (rc__) return rc__;  \
+    } while (0)
+
+#define ST(s) ((hipStream_t)(s))   // the C ABI's `void* stream`
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// A caller-allocated workspace is described ONCE, by a layout function that takes its sub-buffers from this carver in order: every
+// sub-buffer starts 256-byte aligned.  The size query is that function on a null base (pointers stay null, total() is the size);
+// the launch calls it on the workspace it was given.
+struct Workspace {
+    char* base;
+    size_t off = 0;
+    explicit Workspace(void* b) : base((char*)b) {}
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += align_up(count * sizeof(T), 256);
+        return p;
+    }
+    size_t total() const { return off; }
+};
 
 #define WAVE 64
 

@@ -117,7 +117,6 @@ __global__ __launch_bounds__(256) void conf_merge_ragged_kernel(const float* __r
     }
 }
 
-#define ST(s) ((hipStream_t)(s))
 static const long long kI32 = 2147483647ll;
 
 static int conf_check_plans(const char* who, const excel_ragged_info* src_info, const excel_ragged_info* half_info, int smax) {

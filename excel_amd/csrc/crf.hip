@@ -23,7 +23,6 @@
 #include "common.h"
 #include "excel_internal.h"
 
-#define TRY(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 #define CRF_KS 8                 // shorts per stored key (D <= 6: short 7 carries the image index of a group)
 #define CRF_IMG_SLOT 7
 #define CRF_MAX_IMAGES 32767
@@ -402,39 +401,57 @@ struct CrfLattice {
     long long npv;
     int D;
 };
-static size_t crf_al(size_t b) { return (b + 255) / 256 * 256; }
-static size_t crf_lattice_bytes(long long N, int D, unsigned* cap_out) {
-    const long long npv = N * (D + 1);
-    unsigned cap = 1024;
-    while ((long long)cap < 2 * npv) cap <<= 1;
-    if (cap_out) *cap_out = cap;
-    return 2 * crf_al(sizeof(CrfKey) * npv) + crf_al(4 * npv) + crf_al(4 * N) + crf_al(4ull * cap) + 3 * crf_al(4 * npv) + 256 +
-           crf_al(sizeof(int2) * (size_t)npv * (D + 1));
-}
-static CrfLattice crf_lattice_layout(char*& p, long long N, int D) {
+static CrfLattice crf_lattice_layout(Workspace& ws, long long N, int D) {
     CrfLattice L;
-    unsigned cap;
-    crf_lattice_bytes(N, D, &cap);
     const long long npv = N * (D + 1);
-    auto take = [&](size_t b) { char* r = p; p += crf_al(b); return r; };
-    L.keys = (CrfKey*)take(sizeof(CrfKey) * npv); L.lkeys = (CrfKey*)take(sizeof(CrfKey) * npv);
-    L.bary = (float*)take(4 * npv); L.norm = (float*)take(4 * N);
-    L.table = (int*)take(4ull * cap);
-    L.rep = (int*)take(4 * npv); L.latidx = (int*)take(4 * npv); L.offset = (int*)take(4 * npv);
-    L.counter = (int*)take(256);
-    L.nbr = (int2*)take(sizeof(int2) * (size_t)npv * (D + 1));
+    unsigned cap = 1024;                                        // hash slots: the first power of two >= 2 per vertex
+    while ((long long)cap < 2 * npv) cap <<= 1;
+    L.keys = ws.take<CrfKey>(npv); L.lkeys = ws.take<CrfKey>(npv);
+    L.bary = ws.take<float>(npv); L.norm = ws.take<float>(N);
+    L.table = ws.take<int>(cap);
+    L.rep = ws.take<int>(npv); L.latidx = ws.take<int>(npv); L.offset = ws.take<int>(npv);
+    L.counter = ws.take<int>(1);
+    L.nbr = ws.take<int2>((size_t)npv * (D + 1));
     L.mask = cap - 1; L.npv = npv; L.D = D;
     return L;
 }
 
-// per lattice: build tables + fixed-point accumulators [npv*C] + two float lattices [npv*C]; Q [N,C]; ones [N].  N = the pixels of the
-// image, or of the whole group: the group shares one set of tables, so a group of one costs what the image costs alone.
-static size_t crf_workspace_bytes(long long N, int C) {
-    return crf_lattice_bytes(N, 2, nullptr) + crf_lattice_bytes(N, 5, nullptr) + crf_al(8 * (N * 3) * C) + 2 * crf_al(4 * (N * 3) * C) +
-           crf_al(8 * (N * 6) * C) + 2 * crf_al(4 * (N * 6) * C) + crf_al(4 * N * C) + crf_al(4 * N);
+// The workspace of all three entries.  Per lattice (Gaussian D = 2, bilateral D = 5): the build tables, then the fixed-point accumulators
+// [npv*C] and two float lattices [npv*C] of each side; Q [N,C]; ones [N]; LAM groups: + one class count per lattice point (capacity: one
+// per vertex) of both lattices.  N = the pixels of the image, or of the whole group: the group shares one set of tables, so a group of
+// one costs what the image costs alone.
+struct CrfWs {
+    CrfLattice Lg, Lb;
+    CrfSide sg, sb;
+    float *Q, *ones;
+    int *cg, *cb;                // LAM only
+    size_t total;
+};
+static CrfWs crf_ws_layout(long long N, int C, bool lam, void* base) {
+    CrfWs w;
+    Workspace ws(base);
+    w.Lg = crf_lattice_layout(ws, N, 2);
+    w.Lb = crf_lattice_layout(ws, N, 5);
+    auto side = [&](CrfSide& s, const CrfLattice& L) {
+        s.offset = L.offset; s.bary = L.bary; s.norm = L.norm; s.nbr = L.nbr; s.counter = L.counter; s.npv = L.npv; s.Dp1 = L.D + 1;
+        s.alpha = 1.0f / (1.0f + powf(2.0f, (float)-L.D));
+        s.seg_start = s.seg_cnt = s.seg_list = nullptr;
+        s.acc = ws.take<long long>((size_t)L.npv * C);
+        s.lat0 = ws.take<float>((size_t)L.npv * C);
+        s.lat1 = ws.take<float>((size_t)L.npv * C);
+    };
+    side(w.sg, w.Lg);
+    side(w.sb, w.Lb);
+    w.Q = ws.take<float>((size_t)N * C);
+    w.ones = ws.take<float>(N);
+    w.cg = lam ? ws.take<int>(w.Lg.npv) : nullptr;
+    w.cb = lam ? ws.take<int>(w.Lb.npv) : nullptr;
+    w.sg.ncls = w.cg; w.sb.ncls = w.cb;
+    w.total = ws.total();
+    return w;
 }
-// LAM groups: + one class count per lattice point (capacity: one per vertex) of both lattices
-static size_t crf_lam_workspace_bytes(long long N, int Cg) { return crf_workspace_bytes(N, Cg) + crf_al(4 * (N * 3)) + crf_al(4 * (N * 6)); }
+static size_t crf_workspace_bytes(long long N, int C) { return crf_ws_layout(N, C, false, nullptr).total; }
+static size_t crf_lam_workspace_bytes(long long N, int Cg) { return crf_ws_layout(N, Cg, true, nullptr).total; }
 // vertex indices (6 per pixel on the bilateral lattice) are ints and the hash table holds 2x as many slots, counted in 32 bits
 static bool crf_fits(long long N) { return N >= 1 && N * 6 <= (1ll << 30); }
 
@@ -500,31 +517,16 @@ static int crf_run(const unsigned char* rgb_hwc, const float* prob, int prob_is_
                    const CrfParams& P, float* q_out, unsigned char* labels, void* workspace, hipStream_t st, const CrfLam& lam = CrfLam{}) {
     static_assert(true, "the message-passing kernels are written for the D = 2 (Gaussian) and D = 5 (bilateral) lattices of DenseCRF2D");
     const int iters = P.iters;
-    char* p = (char*)workspace;
-    CrfLattice Lg = crf_lattice_layout(p, N, 2), Lb = crf_lattice_layout(p, N, 5);
-    CrfSide sg, sb;
-    auto side = [&](CrfSide& s, const CrfLattice& L) {
-        s.offset = L.offset; s.bary = L.bary; s.norm = L.norm; s.nbr = L.nbr; s.counter = L.counter; s.npv = L.npv; s.Dp1 = L.D + 1;
-        s.alpha = 1.0f / (1.0f + powf(2.0f, (float)-L.D));
-        s.seg_start = s.seg_cnt = s.seg_list = nullptr;
-        s.ncls = nullptr;
-        s.acc = (long long*)p; p += crf_al(8 * L.npv * C);
-        s.lat0 = (float*)p; p += crf_al(4 * L.npv * C);
-        s.lat1 = (float*)p; p += crf_al(4 * L.npv * C);
-    };
-    side(sg, Lg);
-    side(sb, Lb);
-    float* Q = (float*)p; p += crf_al(4 * N * C);
-    float* ones = (float*)p; p += crf_al(4 * N);
+    CrfWs w = crf_ws_layout(N, C, LAM, workspace);
+    const CrfLattice &Lg = w.Lg, &Lb = w.Lb;
+    CrfSide &sg = w.sg, &sb = w.sb;
+    float *Q = w.Q, *ones = w.ones;
     TRY(crf_build<2>(Lg, rgb_hwc, tab, B, N, H, W, P.pos_xy_std, 1.f, st));
     TRY(crf_build<5>(Lb, rgb_hwc, tab, B, N, H, W, P.bi_xy_std, P.bi_rgb_std, st));
     if (LAM) {                                                  // before the CSR build takes lkeys over
-        int* cg = (int*)p; p += crf_al(4 * Lg.npv);
-        int* cb = (int*)p; p += crf_al(4 * Lb.npv);
-        hipLaunchKernelGGL(crf_point_classes_kernel, dim3((unsigned)cdivl(Lg.npv, 256)), dim3(256), 0, st, Lg.lkeys, Lg.counter, lam.nchan, B, C, cg);
-        hipLaunchKernelGGL(crf_point_classes_kernel, dim3((unsigned)cdivl(Lb.npv, 256)), dim3(256), 0, st, Lb.lkeys, Lb.counter, lam.nchan, B, C, cb);
+        hipLaunchKernelGGL(crf_point_classes_kernel, dim3((unsigned)cdivl(Lg.npv, 256)), dim3(256), 0, st, Lg.lkeys, Lg.counter, lam.nchan, B, C, w.cg);
+        hipLaunchKernelGGL(crf_point_classes_kernel, dim3((unsigned)cdivl(Lb.npv, 256)), dim3(256), 0, st, Lb.lkeys, Lb.counter, lam.nchan, B, C, w.cb);
         EXCEL_CHECK_LAUNCH("dcrf point classes");
-        sg.ncls = cg; sb.ncls = cb;
     }
     TRY(crf_csr_build(Lg, sg, st));
     TRY(crf_csr_build(Lb, sb, st));

@@ -63,19 +63,36 @@ static DecWs dec_ws_layout(const excel_decoder_config& c, int B, int g, char* ba
     const size_t M = (size_t)B * P;
     w.Pp = (P + 3) / 4 * 4;
     w.ncp = (c.num_classes + 3) / 4 * 4;
-    size_t off = 0;
-    auto take = [&](size_t floats) { float* p = (float*)(base + off); off += align_up(floats * sizeof(float), 256); return p; };
-    w.h1 = take(M * E);
-    w.cat = take(M * (size_t)c.vit_layers * E);
-    w.x = take(M * E);
-    w.y = take(M * E);
-    w.qkv = take(M * 3 * E);
-    w.s = take((size_t)B * c.heads * P * w.Pp);
-    w.ao = take(M * E);
-    w.hb = take(M * 4 * E);
-    w.segt = take(M * w.ncp);
-    w.total = off;
+    Workspace ws(base);
+    w.h1 = ws.take<float>(M * E);
+    w.cat = ws.take<float>(M * (size_t)c.vit_layers * E);
+    w.x = ws.take<float>(M * E);
+    w.y = ws.take<float>(M * E);
+    w.qkv = ws.take<float>(M * 3 * E);
+    w.s = ws.take<float>((size_t)B * c.heads * P * w.Pp);
+    w.ao = ws.take<float>(M * E);
+    w.hb = ws.take<float>(M * 4 * E);
+    w.segt = ws.take<float>(M * w.ncp);
+    w.total = ws.total();
     return w;
+}
+
+int excel_launch_dec_attention(const float* qkv, float* scores, float* attn_out, int B, int P, int Pp, int E, int H, int causal, hipStream_t st) {
+    const int hd = E / H;
+    // scores[b,h] = scale * q k^T   (batched NT over (b,h))
+    GemmArgs sc = gemm_args(qkv, qkv + (size_t)H * P * hd, scores, nullptr, nullptr, P, P, hd, hd, hd, Pp, 0, GEMM_ACT_NONE);
+    sc.alpha = 1.f / sqrtf((float)hd); sc.zdiv = H;
+    sc.sA = sc.sB = (long long)3 * H * P * hd; sc.sA2 = sc.sB2 = (long long)P * hd;
+    sc.sC = (long long)H * P * Pp; sc.sC2 = (long long)P * Pp;
+    TRY(excel_launch_gemm(sc, true, B * H, st));
+    TRY(excel_launch_dec_softmax(scores, (long long)B * H * P, P, Pp, causal, st));
+    // out[b, :, h*hd:(h+1)*hd] = P[b,h] . v[b,h]   (batched NN, heads merged through the column offset)
+    GemmArgs pv = gemm_args(scores, qkv + (size_t)2 * H * P * hd, attn_out, nullptr, nullptr, P, hd, P, Pp, hd, E, 0, GEMM_ACT_NONE);
+    pv.Kld = Pp; pv.zdiv = H;
+    pv.sA = (long long)H * P * Pp; pv.sA2 = (long long)P * Pp;
+    pv.sB = (long long)3 * H * P * hd; pv.sB2 = (long long)P * hd;
+    pv.sC = (long long)P * E; pv.sC2 = hd;
+    return excel_launch_gemm(pv, false, B * H, st);
 }
 
 // Stack of pre-LN residual blocks (nn.MultiheadAttention + QuickGELU MLP): x [B*P, E] updated in place.
@@ -83,36 +100,20 @@ static DecWs dec_ws_layout(const excel_decoder_config& c, int B, int g, char* ba
 static int preln_blocks(const excel_decoder_block_weights* blocks, int n_layers, float* x, float* y, float* qkv, float* sbuf, float* ao,
                         float* hb, int B, int P, int Pp, int E, int H, int causal, hipStream_t st) {
     const int hd = E / H, M = B * P;
-    const float scale = 1.f / sqrtf((float)hd);
     for (int l = 0; l < n_layers; ++l) {
         const excel_decoder_block_weights& bw = blocks[l];
-        TRYD(excel_launch_layernorm(x, nullptr, 1, bw.ln1_w, bw.ln1_b, y, M, E, 1e-5f, st));
-        GemmArgs q = ga0(y, bw.in_proj_w, qkv, bw.in_proj_b, nullptr, M, 3 * E, E, E, E, 3 * E, 0, GEMM_ACT_NONE);
+        TRY(excel_launch_layernorm(x, nullptr, 1, bw.ln1_w, bw.ln1_b, y, M, E, 1e-5f, st));
+        GemmArgs q = gemm_args(y, bw.in_proj_w, qkv, bw.in_proj_b, nullptr, M, 3 * E, E, E, E, 3 * E, 0, GEMM_ACT_NONE);
         q.out_mode = GEMM_OUT_QKV_HEADMAJOR; q.tokN = P; q.heads = H; q.hd = hd;                 // -> [B,3,H,P,hd]
-        TRYD(excel_launch_gemm(q, true, 1, st));
-        // scores[b,h] = scale * q k^T   (batched NT over (b,h))
-        GemmArgs sc = ga0(qkv, qkv + (size_t)H * P * hd, sbuf, nullptr, nullptr, P, P, hd, hd, hd, Pp, 0, GEMM_ACT_NONE);
-        sc.alpha = scale; sc.zdiv = H;
-        sc.sA = sc.sB = (long long)3 * H * P * hd; sc.sA2 = sc.sB2 = (long long)P * hd;
-        sc.sC = (long long)H * P * Pp; sc.sC2 = (long long)P * Pp;
-        TRYD(excel_launch_gemm(sc, true, B * H, st));
-        hipLaunchKernelGGL(dec_row_softmax_kernel, dim3((unsigned)cdivl((long long)B * H * P, 4)), dim3(256), 0, st, sbuf, (long long)B * H * P,
-                           P, Pp, causal);
-        EXCEL_CHECK_LAUNCH("preln_blocks/softmax");
-        // out[b, :, h*hd:(h+1)*hd] = P[b,h] . v[b,h]   (batched NN, heads merged through the column offset)
-        GemmArgs pv = ga0(sbuf, qkv + (size_t)2 * H * P * hd, ao, nullptr, nullptr, P, hd, P, Pp, hd, E, 0, GEMM_ACT_NONE);
-        pv.Kld = Pp; pv.zdiv = H;
-        pv.sA = (long long)H * P * Pp; pv.sA2 = (long long)P * Pp;
-        pv.sB = (long long)3 * H * P * hd; pv.sB2 = (long long)P * hd;
-        pv.sC = (long long)P * E; pv.sC2 = hd;
-        TRYD(excel_launch_gemm(pv, false, B * H, st));
-        GemmArgs op = ga0(ao, bw.out_proj_w, x, bw.out_proj_b, x, M, E, E, E, E, E, E, GEMM_ACT_NONE);       // x += out_proj(.)
-        TRYD(excel_launch_gemm(op, true, 1, st));
-        TRYD(excel_launch_layernorm(x, nullptr, 1, bw.ln2_w, bw.ln2_b, y, M, E, 1e-5f, st));
-        GemmArgs f1 = ga0(y, bw.fc1_w, hb, bw.fc1_b, nullptr, M, 4 * E, E, E, E, 4 * E, 0, GEMM_ACT_QUICKGELU);
-        TRYD(excel_launch_gemm(f1, true, 1, st));
-        GemmArgs f2 = ga0(hb, bw.fc2_w, x, bw.fc2_b, x, M, E, 4 * E, 4 * E, 4 * E, E, E, GEMM_ACT_NONE);      // x += mlp(ln_2(x))
-        TRYD(excel_launch_gemm(f2, true, 1, st));
+        TRY(excel_launch_gemm(q, true, 1, st));
+        TRY(excel_launch_dec_attention(qkv, sbuf, ao, B, P, Pp, E, H, causal, st));
+        GemmArgs op = gemm_args(ao, bw.out_proj_w, x, bw.out_proj_b, x, M, E, E, E, E, E, E, GEMM_ACT_NONE);       // x += out_proj(.)
+        TRY(excel_launch_gemm(op, true, 1, st));
+        TRY(excel_launch_layernorm(x, nullptr, 1, bw.ln2_w, bw.ln2_b, y, M, E, 1e-5f, st));
+        GemmArgs f1 = gemm_args(y, bw.fc1_w, hb, bw.fc1_b, nullptr, M, 4 * E, E, E, E, 4 * E, 0, GEMM_ACT_QUICKGELU);
+        TRY(excel_launch_gemm(f1, true, 1, st));
+        GemmArgs f2 = gemm_args(hb, bw.fc2_w, x, bw.fc2_b, x, M, E, 4 * E, 4 * E, 4 * E, E, E, GEMM_ACT_NONE);      // x += mlp(ln_2(x))
+        TRY(excel_launch_gemm(f2, true, 1, st));
     }
     return EXCEL_OK;
 }
@@ -154,14 +155,14 @@ extern "C" int excel_decoder_forward(excel_decoder_t h, const float* all_feats, 
     // ---- SegFormerHead: per ViT layer Linear -> ReLU -> Linear on the patch tokens (cls row skipped), channel concat, 1x1 fuse
     for (int l = 0; l < L; ++l) {
         const excel_fuse_layer_weights& fw = h->fuse[l];
-        GemmArgs a = ga0(all_feats + ((size_t)l * B * N + 1) * D, fw.proj_w, ws.h1, fw.proj_b, nullptr, P, E, D, D, D, E, 0, GEMM_ACT_RELU);
+        GemmArgs a = gemm_args(all_feats + ((size_t)l * B * N + 1) * D, fw.proj_w, ws.h1, fw.proj_b, nullptr, P, E, D, D, D, E, 0, GEMM_ACT_RELU);
         a.sA = (long long)N * D; a.sC = (long long)P * E;                       // one image per batch entry: rows 1..P of [N,D]
-        TRYD(excel_launch_gemm(a, true, B, st));                                // segformer_head.py:23-24
-        GemmArgs b2 = ga0(ws.h1, fw.proj2_w, ws.cat + (size_t)l * E, fw.proj2_b, nullptr, M, E, E, E, E, L * E, 0, GEMM_ACT_NONE);
-        TRYD(excel_launch_gemm(b2, true, 1, st));                               // :25, written at channel offset l*E (:73)
+        TRY(excel_launch_gemm(a, true, B, st));                                // segformer_head.py:23-24
+        GemmArgs b2 = gemm_args(ws.h1, fw.proj2_w, ws.cat + (size_t)l * E, fw.proj2_b, nullptr, M, E, E, E, E, L * E, 0, GEMM_ACT_NONE);
+        TRY(excel_launch_gemm(b2, true, 1, st));                               // :25, written at channel offset l*E (:73)
     }
-    GemmArgs fz = ga0(ws.cat, h->w.fuse_w, ws.x, h->w.fuse_b, nullptr, M, E, L * E, L * E, L * E, E, 0, GEMM_ACT_NONE);
-    TRYD(excel_launch_gemm(fz, true, 1, st));                                   // :74 (dropout inactive in eval)
+    GemmArgs fz = gemm_args(ws.cat, h->w.fuse_w, ws.x, h->w.fuse_b, nullptr, M, E, L * E, L * E, L * E, E, 0, GEMM_ACT_NONE);
+    TRY(excel_launch_gemm(fz, true, 1, st));                                   // :74 (dropout inactive in eval)
     if (attn_fts_out) {
         hipLaunchKernelGGL(dec_transpose_kernel, dim3(cdiv(P, 32), cdiv(E, 32), B), dim3(256), 0, st, ws.x, attn_fts_out, P, E, E, P);
         EXCEL_CHECK_LAUNCH("decoder/attn_fts");
@@ -169,9 +170,9 @@ extern "C" int excel_decoder_forward(excel_decoder_t h, const float* all_feats, 
     if (!seg_out) return EXCEL_OK;
 
     // ---- DecoderTransformer: pre-LN residual blocks (TransDecoder.py:78-83), tokens [B*P, E]
-    TRYD(preln_blocks(h->blocks.data(), c.dec_layers, ws.x, ws.y, ws.qkv, ws.s, ws.ao, ws.hb, B, P, ws.Pp, E, H, 0, st));
-    GemmArgs lp = ga0(ws.x, h->w.pred_w, ws.segt, h->w.pred_b, nullptr, M, nc, E, E, E, ws.ncp, 0, GEMM_ACT_NONE);   // linear_pred (:122)
-    TRYD(excel_launch_gemm(lp, true, 1, st));
+    TRY(preln_blocks(h->blocks.data(), c.dec_layers, ws.x, ws.y, ws.qkv, ws.s, ws.ao, ws.hb, B, P, ws.Pp, E, H, 0, st));
+    GemmArgs lp = gemm_args(ws.x, h->w.pred_w, ws.segt, h->w.pred_b, nullptr, M, nc, E, E, E, ws.ncp, 0, GEMM_ACT_NONE);   // linear_pred (:122)
+    TRY(excel_launch_gemm(lp, true, 1, st));
     hipLaunchKernelGGL(dec_transpose_kernel, dim3(cdiv(P, 32), cdiv(nc, 32), B), dim3(256), 0, st, ws.segt, seg_out, P, nc, ws.ncp, P);
     EXCEL_CHECK_LAUNCH("decoder/seg");
     return EXCEL_OK;
@@ -238,11 +239,11 @@ static TextWs text_ws_layout(const excel_text_config& c, int B, char* base) {
     const int P = c.context_length, E = c.width;
     const size_t M = (size_t)B * P;
     w.Pp = (P + 3) / 4 * 4;
-    size_t off = 0;
-    auto take = [&](size_t floats) { float* p = (float*)(base + off); off += align_up(floats * sizeof(float), 256); return p; };
-    w.x = take(M * E); w.y = take(M * E); w.qkv = take(M * 3 * E); w.s = take((size_t)B * c.heads * P * w.Pp);
-    w.ao = take(M * E); w.hb = take(M * 4 * E); w.rows = take((size_t)B * E);
-    w.total = off;
+    Workspace ws(base);
+    w.x = ws.take<float>(M * E); w.y = ws.take<float>(M * E); w.qkv = ws.take<float>(M * 3 * E);
+    w.s = ws.take<float>((size_t)B * c.heads * P * w.Pp);
+    w.ao = ws.take<float>(M * E); w.hb = ws.take<float>(M * 4 * E); w.rows = ws.take<float>((size_t)B * E);
+    w.total = ws.total();
     return w;
 }
 
@@ -272,12 +273,12 @@ extern "C" int excel_text_encode(excel_text_t h, const int32_t* tokens, int B, f
     EXCEL_CHECK_ARG(workspace_bytes >= ws.total, "excel_text_encode: workspace too small (%zu < %zu)", workspace_bytes, ws.total);
     hipLaunchKernelGGL(text_embed_kernel, dim3(M), dim3(256), 0, st, tokens, h->w.token_embedding, h->w.positional_embedding, ws.x, P, E, c.vocab_size);
     EXCEL_CHECK_LAUNCH("text/embed");                                                                                // :552-554
-    TRYD(preln_blocks(h->blocks.data(), c.layers, ws.x, ws.y, ws.qkv, ws.s, ws.ao, ws.hb, B, P, ws.Pp, E, c.heads, 1, st));   // :556
-    TRYD(excel_launch_layernorm(ws.x, nullptr, 1, h->w.ln_final_w, h->w.ln_final_b, ws.y, M, E, 1e-5f, st));       // :558
+    TRY(preln_blocks(h->blocks.data(), c.layers, ws.x, ws.y, ws.qkv, ws.s, ws.ao, ws.hb, B, P, ws.Pp, E, c.heads, 1, st));   // :556
+    TRY(excel_launch_layernorm(ws.x, nullptr, 1, h->w.ln_final_w, h->w.ln_final_b, ws.y, M, E, 1e-5f, st));       // :558
     hipLaunchKernelGGL(text_eot_gather_kernel, dim3(B), dim3(64), 0, st, tokens, ws.y, ws.rows, P, E);              // :562
     EXCEL_CHECK_LAUNCH("text/eot");
     // rows [B,E] @ text_projection [E, embed_dim]   (NN GEMM)
-    GemmArgs pj = ga0(ws.rows, h->w.text_projection, out, nullptr, nullptr, B, c.embed_dim, E, E, c.embed_dim, c.embed_dim, 0, GEMM_ACT_NONE);
+    GemmArgs pj = gemm_args(ws.rows, h->w.text_projection, out, nullptr, nullptr, B, c.embed_dim, E, E, c.embed_dim, c.embed_dim, 0, GEMM_ACT_NONE);
     return excel_launch_gemm(pj, false, 1, st);
 }
 

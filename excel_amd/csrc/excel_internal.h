@@ -23,7 +23,16 @@ struct GemmArgs {
     int tokN, heads, hd;  // GEMM_OUT_QKV_HEADMAJOR: C is [B,3,heads,tokN,hd]
     float alpha;
 };
-
+// one unbatched plain-output GEMM (Kld = K rounded up to 4, alpha = 1); callers set strides / out_mode / alpha on the result
+inline GemmArgs gemm_args(const float* A, const float* B, float* C, const float* bias, const float* res, int M, int N, int K, int lda, int ldb,
+                          int ldc, int ldr, int act) {
+    GemmArgs g{};
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.res = res;
+    g.M = M; g.N = N; g.K = K; g.Kld = (K + 3) / 4 * 4;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr;
+    g.act = act; g.out_mode = GEMM_OUT_PLAIN; g.alpha = 1.f; g.zdiv = 1;
+    return g;
+}
 
 // bf16x3 GEMM (gemm_bf16x3.hip): A, B are "split" tensors [rows][2][K] bf16 (hi plane, lo plane)
 struct GemmBfArgs {

@@ -12,8 +12,6 @@
 #include "common.h"
 #include "excel_internal.h"
 
-#define ST(s) ((hipStream_t)(s))
-
 __device__ __forceinline__ int nonfinite_bits(unsigned u) { return (u & 0x7f800000u) == 0x7f800000u; }
 
 // Pure streaming read: x is only 4-byte aligned and per_image is arbitrary, so an image starts anywhere in a 16-byte line.  Chunk 0's

@@ -453,8 +453,6 @@ __global__ __launch_bounds__(256) void jpeg_assemble_kernel(const JpegRec* __res
 }
 
 // ---------------------------------------------------------------- host
-#define ST(s) ((hipStream_t)(s))
-
 struct JpegPlan {
     unsigned long long arena, blocks, words, workspace;
     unsigned long long off_start, off_coef, off_words, off_dyn;      // byte offsets in the workspace (recs at 0)
@@ -474,12 +472,11 @@ static bool jpeg_plan(const int32_t* hw, int n, JpegPlan& p) {
         p.words += ((nblk * JPEG_BLOCK_BYTES + 8 + JPEG_CHUNK - 1) / JPEG_CHUNK) * (JPEG_CHUNK / 4);
         p.max_blocks = nblk > p.max_blocks ? nblk : p.max_blocks;
     }
-    auto up = [](unsigned long long v) { return (v + 255) & ~255ull; };
-    p.off_dyn = up((unsigned long long)n * sizeof(JpegRec));
-    p.off_start = p.off_dyn + up((unsigned long long)n * sizeof(JpegDyn));
-    p.off_coef = p.off_start + up(p.blocks * 8);
-    p.off_words = p.off_coef + up(p.blocks * 128);
-    p.workspace = p.off_words + up(p.words * 4);
+    p.off_dyn = align_up((size_t)n * sizeof(JpegRec), 256);
+    p.off_start = p.off_dyn + align_up((size_t)n * sizeof(JpegDyn), 256);
+    p.off_coef = p.off_start + align_up(p.blocks * 8, 256);
+    p.off_words = p.off_coef + align_up(p.blocks * 128, 256);
+    p.workspace = p.off_words + align_up(p.words * 4, 256);
     return true;
 }
 

@@ -7,8 +7,6 @@
 #include "common.h"
 #include "excel_internal.h"
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // ---------------------------------------------------------------------------------------------- feature affinity
 // f [B,C,P]: inv[b,p] = 1 / max(||f[b,:,p]||, 1e-12)        (F.normalize(dim=1))
 __global__ __launch_bounds__(256) void lvc_col_invnorm_kernel(const float* __restrict__ f, float* __restrict__ inv, int C, int P) {
@@ -99,37 +97,39 @@ __global__ __launch_bounds__(256) void lvc_finish_kernel(float* __restrict__ sim
     lvc_finish_row(sim + row * P, mean[0] * beta, P, gamma, mode, lane);
 }
 
-size_t excel_feature_affinity_ws_bytes(int B, int C, int P) {
-    const int Cp = (C + 3) / 4 * 4;
-    return align_up((size_t)B * P * sizeof(float), 256) + align_up((size_t)B * P * Cp * sizeof(float), 256) +
-           align_up(1024 * sizeof(double), 256) + 256;
+// inverse norms [B,P], normalised features [B,P,Cp], 1024 double partials per group, one mean per group (the whole-batch form is one group)
+struct AffWs { float *inv, *fn, *mean; double* partial; int Cp; size_t total; };
+static AffWs aff_ws_layout(int B, int C, int P, int ngroups, void* base) {
+    AffWs w;
+    w.Cp = (C + 3) / 4 * 4;
+    Workspace ws(base);
+    w.inv = ws.take<float>((size_t)B * P);
+    w.fn = ws.take<float>((size_t)B * P * w.Cp);
+    w.partial = ws.take<double>((size_t)ngroups * 1024);
+    w.mean = ws.take<float>(ngroups);
+    w.total = ws.total();
+    return w;
 }
+// fn [B,P,Cp] = the channel-normalised features; sim[b] = fn[b] . fn[b]^T (exact fp32 MFMA GEMM, NT form, one image per batch entry)
+static int lvc_normalized_sim(const float* feats, int B, int C, int P, const AffWs& w, float* out, const char* who, hipStream_t st) {
+    hipLaunchKernelGGL(lvc_col_invnorm_kernel, dim3(cdiv(P, 256), B), dim3(256), 0, st, feats, w.inv, C, P);
+    hipLaunchKernelGGL(lvc_transpose_scale_kernel, dim3(cdiv(P, 32), cdiv(w.Cp, 32), B), dim3(256), 0, st, feats, w.inv, w.fn, C, w.Cp, P);
+    EXCEL_CHECK_LAUNCH(who);
+    GemmArgs g = gemm_args(w.fn, w.fn, out, nullptr, nullptr, P, P, w.Cp, w.Cp, w.Cp, P, 0, GEMM_ACT_NONE);
+    g.sA = g.sB = (long long)P * w.Cp; g.sC = (long long)P * P;
+    return excel_launch_gemm(g, true, B, st);
+}
+
+size_t excel_feature_affinity_ws_bytes(int B, int C, int P) { return aff_ws_layout(B, C, P, 1, nullptr).total; }
 
 int excel_launch_feature_affinity(const float* feats, int B, int C, int P, float beta, float gamma, int mode, float* out, void* ws,
                                   hipStream_t st) {
     ProfScope prof__(PROF_OTHER, st);
     EXCEL_CHECK_ARG(feats && out && ws && B > 0 && C > 0 && P > 0 && (mode == 0 || mode == 1), "feature_affinity: bad argument");
-    const int Cp = (C + 3) / 4 * 4;
-    char* base = (char*)ws;
-    float* inv = (float*)base;
-    base += align_up((size_t)B * P * sizeof(float), 256);
-    float* fn = (float*)base;
-    base += align_up((size_t)B * P * Cp * sizeof(float), 256);
-    double* partial = (double*)base;
-    base += align_up(1024 * sizeof(double), 256);
-    float* mean = (float*)base;
-    hipLaunchKernelGGL(lvc_col_invnorm_kernel, dim3(cdiv(P, 256), B), dim3(256), 0, st, feats, inv, C, P);
-    hipLaunchKernelGGL(lvc_transpose_scale_kernel, dim3(cdiv(P, 32), cdiv(Cp, 32), B), dim3(256), 0, st, feats, inv, fn, C, Cp, P);
-    EXCEL_CHECK_LAUNCH("feature_affinity/normalize");
-    // sim[b] = fn[b] . fn[b]^T  (exact fp32 MFMA GEMM, NT form, batched)
-    GemmArgs g{};
-    g.A = fn; g.B = fn; g.C = out; g.bias = nullptr; g.res = nullptr;
-    g.M = P; g.N = P; g.K = Cp; g.Kld = Cp; g.lda = Cp; g.ldb = Cp; g.ldc = P; g.ldr = 0;
-    g.sA = g.sB = (long long)P * Cp; g.sC = (long long)P * P; g.sR = 0; g.sBias = 0;
-    g.zdiv = 1; g.sA2 = g.sB2 = g.sC2 = 0;
-    g.act = GEMM_ACT_NONE; g.out_mode = GEMM_OUT_PLAIN; g.tokN = g.heads = g.hd = 0; g.alpha = 1.f;
-    int rc = excel_launch_gemm(g, true, B, st);
-    if (rc) return rc;
+    const AffWs w = aff_ws_layout(B, C, P, 1, ws);
+    float* mean = w.mean;
+    double* partial = w.partial;
+    TRY(lvc_normalized_sim(feats, B, C, P, w, out, "feature_affinity/normalize", st));
     const long long n = (long long)B * P * P;
     const int nparts = (int)min((long long)1024, cdivl(n, 4096));
     hipLaunchKernelGGL(lvc_partial_sum_kernel, dim3(nparts), dim3(256), 0, st, out, n, partial);
@@ -199,10 +199,7 @@ __global__ __launch_bounds__(256) void lvc_group_finish_kernel(float* __restrict
 static int lvc_group_nparts(long long n) { return (int)min((long long)1024, cdivl(n, 4096)); }
 
 size_t excel_feature_affinity_grouped_ws_bytes(int B, int C, int P, int group) {
-    const int Cp = (C + 3) / 4 * 4;
-    const int ngroups = group > 0 ? B / group : 0;
-    return align_up((size_t)B * P * sizeof(float), 256) + align_up((size_t)B * P * Cp * sizeof(float), 256) +
-           align_up((size_t)ngroups * 1024 * sizeof(double), 256) + align_up((size_t)ngroups * sizeof(float), 256);
+    return aff_ws_layout(B, C, P, group > 0 ? B / group : 0, nullptr).total;
 }
 
 int excel_launch_feature_affinity_grouped(const float* feats, int B, int C, int P, int group, int member_stride, float beta, float gamma,
@@ -211,28 +208,11 @@ int excel_launch_feature_affinity_grouped(const float* feats, int B, int C, int 
     EXCEL_CHECK_ARG(feats && out && ws && B > 0 && C > 0 && P > 0 && (mode == 0 || mode == 1), "feature_affinity_grouped: bad argument");
     EXCEL_CHECK_ARG(group >= 1 && member_stride >= 1 && B % ((long long)group * member_stride) == 0,
                     "feature_affinity_grouped: B=%d is not a multiple of group (%d) x member_stride (%d)", B, group, member_stride);
-    const int Cp = (C + 3) / 4 * 4;
     const int ngroups = B / group;
-    char* base = (char*)ws;
-    float* inv = (float*)base;
-    base += align_up((size_t)B * P * sizeof(float), 256);
-    float* fn = (float*)base;
-    base += align_up((size_t)B * P * Cp * sizeof(float), 256);
-    double* partial = (double*)base;
-    base += align_up((size_t)ngroups * 1024 * sizeof(double), 256);
-    float* mean = (float*)base;
-    hipLaunchKernelGGL(lvc_col_invnorm_kernel, dim3(cdiv(P, 256), B), dim3(256), 0, st, feats, inv, C, P);
-    hipLaunchKernelGGL(lvc_transpose_scale_kernel, dim3(cdiv(P, 32), cdiv(Cp, 32), B), dim3(256), 0, st, feats, inv, fn, C, Cp, P);
-    EXCEL_CHECK_LAUNCH("feature_affinity_grouped/normalize");
-    // sim[b] = fn[b] . fn[b]^T for every image: the GEMM of excel_launch_feature_affinity (one image per batch entry)
-    GemmArgs g{};
-    g.A = fn; g.B = fn; g.C = out; g.bias = nullptr; g.res = nullptr;
-    g.M = P; g.N = P; g.K = Cp; g.Kld = Cp; g.lda = Cp; g.ldb = Cp; g.ldc = P; g.ldr = 0;
-    g.sA = g.sB = (long long)P * Cp; g.sC = (long long)P * P; g.sR = 0; g.sBias = 0;
-    g.zdiv = 1; g.sA2 = g.sB2 = g.sC2 = 0;
-    g.act = GEMM_ACT_NONE; g.out_mode = GEMM_OUT_PLAIN; g.tokN = g.heads = g.hd = 0; g.alpha = 1.f;
-    int rc = excel_launch_gemm(g, true, B, st);
-    if (rc) return rc;
+    const AffWs w = aff_ws_layout(B, C, P, ngroups, ws);
+    float* mean = w.mean;
+    double* partial = w.partial;
+    TRY(lvc_normalized_sim(feats, B, C, P, w, out, "feature_affinity_grouped/normalize", st));
     const long long PP = (long long)P * P, n = PP * group;      // a standalone call on one group: n = group * P * P
     const int nparts = lvc_group_nparts(n);
     hipLaunchKernelGGL(lvc_group_partial_sum_kernel, dim3(nparts, ngroups), dim3(256), 0, st, out, PP, group, member_stride, partial);
@@ -306,17 +286,25 @@ __global__ __launch_bounds__(256) void lvc_select_mean_kernel(const float* __res
     out[(long long)b * n + i] = acc * mask[b * (L + 1) + L] * seg[(long long)b * n + i];      // :193, :195
 }
 
-size_t excel_attn_select_ws_bytes(int B, int n_layers) {
-    return align_up((size_t)B * n_layers * 64 * sizeof(double), 256) + align_up((size_t)B * (n_layers + 1) * sizeof(float), 256);
+struct SelectWs { double* partial; float* mask; size_t total; };
+static SelectWs select_ws_layout(int B, int n_layers, void* base) {
+    SelectWs w;
+    Workspace ws(base);
+    w.partial = ws.take<double>((size_t)B * n_layers * 64);        // 64 chunks per (image, layer)
+    w.mask = ws.take<float>((size_t)B * (n_layers + 1));
+    w.total = ws.total();
+    return w;
 }
+size_t excel_attn_select_ws_bytes(int B, int n_layers) { return select_ws_layout(B, n_layers, nullptr).total; }
 
 int excel_launch_attn_select_mean(const float* attn, int Lw, int B, int N, int first_layer, int n_layers, const float* seg_attn,
                                   float* out, void* ws, hipStream_t st) {
     ProfScope prof__(PROF_OTHER, st);
     EXCEL_CHECK_ARG(attn && seg_attn && out && ws && first_layer >= 0 && n_layers >= 1 && n_layers <= 16 && first_layer + n_layers <= Lw,
                     "attn_select_mean: bad layer range");
-    double* partial = (double*)ws;
-    float* mask = (float*)((char*)ws + align_up((size_t)B * n_layers * 64 * sizeof(double), 256));
+    const SelectWs w = select_ws_layout(B, n_layers, ws);
+    double* partial = w.partial;
+    float* mask = w.mask;
     hipLaunchKernelGGL(lvc_layer_diff_kernel, dim3(64, n_layers, B), dim3(256), 0, st, attn, seg_attn, B, N, first_layer, partial);
     hipLaunchKernelGGL(lvc_layer_mask_kernel, dim3(B), dim3(64), 0, st, partial, 64, n_layers, mask);
     const long long n = (long long)(N - 1) * (N - 1);

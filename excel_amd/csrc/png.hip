@@ -306,8 +306,6 @@ __global__ __launch_bounds__(256) void png_crc_kernel(uint8_t* __restrict__ aren
     }
 }
 
-#define ST(s) ((hipStream_t)(s))
-
 extern "C" size_t excel_png_labels_bound_bytes(int H, int W) { return H >= 1 && W >= 1 ? (size_t)png_bound(H, W) : 0; }
 
 extern "C" size_t excel_png_labels_workspace_bytes(int B, int max_h) {

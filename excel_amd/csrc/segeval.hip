@@ -178,7 +178,6 @@ __global__ __launch_bounds__(256) void seg_softmax_resize_kernel(const float* __
     for (int c = 0; c < nc; ++c) prob[(long long)c * HW + i] = expf(val(c) - m) * inv;
 }
 
-#define ST(s) ((hipStream_t)(s))
 static const long long kI32 = 2147483647ll;
 
 extern "C" int excel_seg_msc_fuse_ragged(const float* const* segs, const int32_t* g, const int32_t* flip_mean, int ns, int nc, const int32_t* table,

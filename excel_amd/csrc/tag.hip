@@ -18,7 +18,6 @@
 #include "common.h"
 #include "excel_internal.h"
 
-#define ST(s) ((hipStream_t)(s))
 #define TAG_MAXC 1024
 #define TAG_MAXT 512
 #define TAG_MAXF 254

@@ -165,9 +165,17 @@ __global__ __launch_bounds__(256) void tr_aff_grad_kernel(const unsigned char* _
     dap[i] = t == 1 ? -0.5f * w_diver / stats[2] : (t == 0 ? 0.5f * w_diver / stats[3] : 0.f);
 }
 
-size_t excel_train_losses_ws_bytes(int B, int nc, int H, int W) {
-    return align_up((size_t)B * nc * H * W * sizeof(float), 256) + align_up((size_t)TR_NPART * 4 * sizeof(double), 256) + 256;
+struct LossWs { float *up, *stats; double* partial; size_t total; };
+static LossWs loss_ws_layout(int B, int nc, int H, int W, void* base) {
+    LossWs w;
+    Workspace ws(base);
+    w.up = ws.take<float>((size_t)B * nc * H * W);         // the up-sampled logits, then their gradient in place
+    w.partial = ws.take<double>((size_t)TR_NPART * 4);
+    w.stats = ws.take<float>(4);                            // bg_n, fg_n, pos_count, neg_count
+    w.total = ws.total();
+    return w;
 }
+size_t excel_train_losses_ws_bytes(int B, int nc, int H, int W) { return loss_ws_layout(B, nc, H, W, nullptr).total; }
 
 int excel_launch_train_losses(const float* seg, const float* attn_pred, const unsigned char* pseudo, const unsigned char* aff_labels, int B, int nc,
                               int g_h, int g_w, int H, int W, int radius, int ignore, float w_seg, float w_diver, float* losses, float* d_seg,
@@ -176,12 +184,9 @@ int excel_launch_train_losses(const float* seg, const float* attn_pred, const un
     ProfScope prof__(PROF_OTHER, st);
     EXCEL_CHECK_ARG(seg && attn_pred && pseudo && losses && d_seg && d_attn_pred && ws, "train_losses: null argument");
     EXCEL_CHECK_ARG(B > 0 && nc > 1 && g_h > 0 && g_w > 0 && H % g_h == 0 && W % g_w == 0 && H / g_h == W / g_w, "train_losses: label size must be a multiple of the token grid");
-    char* base = (char*)ws;
-    float* up = (float*)base;
-    base += align_up((size_t)B * nc * H * W * sizeof(float), 256);
-    double* partial = (double*)base;
-    base += align_up((size_t)TR_NPART * 4 * sizeof(double), 256);
-    float* stats = (float*)base;                                  // bg_n, fg_n, pos_count, neg_count
+    const LossWs lw = loss_ws_layout(B, nc, H, W, ws);
+    float *up = lw.up, *stats = lw.stats;
+    double* partial = lw.partial;
     const long long HW = (long long)H * W, npix = (long long)B * HW;
     int rc = excel_launch_bilinear_resize(seg, up, (long long)B * nc, g_h, g_w, H, W, 0, st);       // train_voc.py:202
     if (rc) return rc;
@@ -463,26 +468,25 @@ static TrainWs train_ws_layout(const excel_decoder_config& c, int B, int g, char
     w.Pp = (P + 3) / 4 * 4;
     w.Mp = (int)((M + 3) / 4 * 4);
     w.ncp = (c.num_classes + 3) / 4 * 4;
-    size_t off = 0;
-    auto take = [&](size_t floats) { float* p = (float*)(base + off); off += align_up(floats * sizeof(float), 256); return p; };
-    w.z1 = take((size_t)L * M * E); w.h1 = take((size_t)L * M * E); w.cat = take(M * (size_t)L * E); w.fts = take(M * E);
-    w.inv = take(M); w.fn = take(M * E); w.ap = take((size_t)B * P * P);
-    w.xin = take((size_t)nl * M * E); w.qkv = take((size_t)nl * M * 3 * E); w.pm = take((size_t)nl * B * H * P * w.Pp);
-    w.ao = take((size_t)nl * M * E); w.x1 = take((size_t)nl * M * E); w.zm = take((size_t)nl * M * 4 * E);
-    w.hq = take(M * std::max((size_t)nl * 4 * E, (size_t)L * E));      // the backward's d(cat) [M, L*E] reuses it
-    w.xfin = take(M * E);
-    w.dx = take(M * E); w.dt1 = take(M * E); w.dt4 = take(M * (size_t)std::max(4 * E, c.vit_width));   // also the [M, D] token gather
-    w.dqkvh = take(M * 3 * E); w.dqkvr = take(M * 3 * E);
-    w.dpm = take((size_t)B * H * P * w.Pp);
+    Workspace ws(base);
+    w.z1 = ws.take<float>((size_t)L * M * E); w.h1 = ws.take<float>((size_t)L * M * E); w.cat = ws.take<float>(M * (size_t)L * E); w.fts = ws.take<float>(M * E);
+    w.inv = ws.take<float>(M); w.fn = ws.take<float>(M * E); w.ap = ws.take<float>((size_t)B * P * P);
+    w.xin = ws.take<float>((size_t)nl * M * E); w.qkv = ws.take<float>((size_t)nl * M * 3 * E); w.pm = ws.take<float>((size_t)nl * B * H * P * w.Pp);
+    w.ao = ws.take<float>((size_t)nl * M * E); w.x1 = ws.take<float>((size_t)nl * M * E); w.zm = ws.take<float>((size_t)nl * M * 4 * E);
+    w.hq = ws.take<float>(M * std::max((size_t)nl * 4 * E, (size_t)L * E));      // the backward's d(cat) [M, L*E] reuses it
+    w.xfin = ws.take<float>(M * E);
+    w.dx = ws.take<float>(M * E); w.dt1 = ws.take<float>(M * E); w.dt4 = ws.take<float>(M * (size_t)std::max(4 * E, c.vit_width));   // also the [M, D] token gather
+    w.dqkvh = ws.take<float>(M * 3 * E); w.dqkvr = ws.take<float>(M * 3 * E);
+    w.dpm = ws.take<float>((size_t)B * H * P * w.Pp);
     const size_t widest = (size_t)std::max(std::max(4 * E, L * E), w.ncp);     // widest dY^T of tr_linear_bwd (linear_pred: nc columns)
-    w.tr = take(widest * (size_t)w.Mp > (size_t)B * H * P * w.Pp ? widest * (size_t)w.Mp : (size_t)B * H * P * w.Pp);
-    w.tp = take((size_t)B * H * P * w.Pp);
-    w.dfn = take(M * E > (size_t)B * P * P ? M * E : (size_t)B * P * P);
-    w.mean = take(64);
-    w.segt = take(M * w.ncp);
-    w.stat = (float2*)take(2 * M);
-    w.partial = (double*)take(2 * TR_NPART);
-    w.total = off;
+    w.tr = ws.take<float>(widest * (size_t)w.Mp > (size_t)B * H * P * w.Pp ? widest * (size_t)w.Mp : (size_t)B * H * P * w.Pp);
+    w.tp = ws.take<float>((size_t)B * H * P * w.Pp);
+    w.dfn = ws.take<float>(M * E > (size_t)B * P * P ? M * E : (size_t)B * P * P);
+    w.mean = ws.take<float>(64);
+    w.segt = ws.take<float>(M * w.ncp);
+    w.stat = ws.take<float2>(M);
+    w.partial = ws.take<double>(TR_NPART);
+    w.total = ws.total();
     return w;
 }
 
@@ -512,22 +516,22 @@ extern "C" int excel_decoder_forward_train(excel_decoder_t h, const float* all_f
     const size_t ME = (size_t)M * E;
     for (int l = 0; l < L; ++l) {                                                                // segformer_head.py:68-73
         const excel_fuse_layer_weights& fw = h->fuse[l];
-        GemmArgs a = ga0(all_feats + ((size_t)l * B * N + 1) * D, fw.proj_w, ws.z1 + l * ME, fw.proj_b, nullptr, P, E, D, D, D, E, 0, GEMM_ACT_NONE);
+        GemmArgs a = gemm_args(all_feats + ((size_t)l * B * N + 1) * D, fw.proj_w, ws.z1 + l * ME, fw.proj_b, nullptr, P, E, D, D, D, E, 0, GEMM_ACT_NONE);
         a.sA = (long long)N * D; a.sC = (long long)P * E;
-        TRYD(excel_launch_gemm(a, true, B, st));
-        TRYD(tr_launch_act(ws.z1 + l * ME, ws.h1 + l * ME, (long long)ME, 0, st));
-        GemmArgs b2 = ga0(ws.h1 + l * ME, fw.proj2_w, ws.cat + (size_t)l * E, fw.proj2_b, nullptr, M, E, E, E, E, L * E, 0, GEMM_ACT_NONE);
-        TRYD(excel_launch_gemm(b2, true, 1, st));
+        TRY(excel_launch_gemm(a, true, B, st));
+        TRY(tr_launch_act(ws.z1 + l * ME, ws.h1 + l * ME, (long long)ME, 0, st));
+        GemmArgs b2 = gemm_args(ws.h1 + l * ME, fw.proj2_w, ws.cat + (size_t)l * E, fw.proj2_b, nullptr, M, E, E, E, E, L * E, 0, GEMM_ACT_NONE);
+        TRY(excel_launch_gemm(b2, true, 1, st));
     }
-    GemmArgs fz = ga0(ws.cat, h->w.fuse_w, ws.fts, h->w.fuse_b, nullptr, M, E, L * E, L * E, L * E, E, 0, GEMM_ACT_NONE);
-    TRYD(excel_launch_gemm(fz, true, 1, st));                                                    // :74
+    GemmArgs fz = gemm_args(ws.cat, h->w.fuse_w, ws.fts, h->w.fuse_b, nullptr, M, E, L * E, L * E, L * E, E, 0, GEMM_ACT_NONE);
+    TRY(excel_launch_gemm(fz, true, 1, st));                                                    // :74
     if (dropout_p > 0.f)                                                                         // :75
         hipLaunchKernelGGL(tr_dropout2d_kernel, dim3((unsigned)cdivl((long long)ME, 256)), dim3(256), 0, st, ws.fts, B, P, E, dropout_p, dropout_seed);
     // attn_pred (model_excel.py:70-76)
     hipLaunchKernelGGL(tr_row_normalize_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, ws.fts, ws.fn, ws.inv, M, E);
-    GemmArgs sm = ga0(ws.fn, ws.fn, ws.ap, nullptr, nullptr, P, P, E, E, E, P, 0, GEMM_ACT_NONE);
+    GemmArgs sm = gemm_args(ws.fn, ws.fn, ws.ap, nullptr, nullptr, P, P, E, E, E, P, 0, GEMM_ACT_NONE);
     sm.sA = sm.sB = (long long)P * E; sm.sC = (long long)P * P;
-    TRYD(excel_launch_gemm(sm, true, B, st));
+    TRY(excel_launch_gemm(sm, true, B, st));
     const long long nap = (long long)B * P * P;
     const int np = (int)min((long long)TR_NPART, cdivl(nap, 1024));
     hipLaunchKernelGGL(tr_sum_kernel, dim3(np), dim3(256), 0, st, ws.ap, nap, ws.partial);
@@ -535,7 +539,6 @@ extern "C" int excel_decoder_forward_train(excel_decoder_t h, const float* all_f
     hipLaunchKernelGGL(tr_sigmoid_affine_kernel, dim3((unsigned)cdivl(nap, 256)), dim3(256), 0, st, ws.ap, ws.mean, nap, 1.f, 3.f);
     hipMemcpyAsync(attn_pred_out, ws.ap, sizeof(float) * (size_t)nap, hipMemcpyDeviceToDevice, st);
     // decoder transformer (TransDecoder.py:78-83)
-    const float scale = 1.f / sqrtf((float)hd);
     const size_t SP = (size_t)B * H * P * ws.Pp;
     const float* x = ws.fts;
     for (int l = 0; l < nl; ++l) {
@@ -548,37 +551,26 @@ extern "C" int excel_decoder_forward_train(excel_decoder_t h, const float* all_f
         float* x1 = ws.x1 + l * ME;
         float* zm = ws.zm + (size_t)l * M * 4 * E;
         float* hq = ws.hq + (size_t)l * M * 4 * E;
-        TRYD(excel_launch_layernorm(xin, nullptr, 1, bw.ln1_w, bw.ln1_b, ws.dt1, M, E, 1e-5f, st));
-        GemmArgs q = ga0(ws.dt1, bw.in_proj_w, qkv, bw.in_proj_b, nullptr, M, 3 * E, E, E, E, 3 * E, 0, GEMM_ACT_NONE);
+        TRY(excel_launch_layernorm(xin, nullptr, 1, bw.ln1_w, bw.ln1_b, ws.dt1, M, E, 1e-5f, st));
+        GemmArgs q = gemm_args(ws.dt1, bw.in_proj_w, qkv, bw.in_proj_b, nullptr, M, 3 * E, E, E, E, 3 * E, 0, GEMM_ACT_NONE);
         q.out_mode = GEMM_OUT_QKV_HEADMAJOR; q.tokN = P; q.heads = H; q.hd = hd;
-        TRYD(excel_launch_gemm(q, true, 1, st));
-        GemmArgs sc = ga0(qkv, qkv + (size_t)H * P * hd, pm, nullptr, nullptr, P, P, hd, hd, hd, ws.Pp, 0, GEMM_ACT_NONE);
-        sc.alpha = scale; sc.zdiv = H;
-        sc.sA = sc.sB = (long long)3 * H * P * hd; sc.sA2 = sc.sB2 = (long long)P * hd;
-        sc.sC = (long long)H * P * ws.Pp; sc.sC2 = (long long)P * ws.Pp;
-        TRYD(excel_launch_gemm(sc, true, B * H, st));
-        TRYD(excel_launch_dec_softmax(pm, (long long)B * H * P, P, ws.Pp, 0, st));
-        GemmArgs pv = ga0(pm, qkv + (size_t)2 * H * P * hd, ao, nullptr, nullptr, P, hd, P, ws.Pp, hd, E, 0, GEMM_ACT_NONE);
-        pv.Kld = ws.Pp; pv.zdiv = H;
-        pv.sA = (long long)H * P * ws.Pp; pv.sA2 = (long long)P * ws.Pp;
-        pv.sB = (long long)3 * H * P * hd; pv.sB2 = (long long)P * hd;
-        pv.sC = (long long)P * E; pv.sC2 = hd;
-        TRYD(excel_launch_gemm(pv, false, B * H, st));
-        GemmArgs op = ga0(ao, bw.out_proj_w, x1, bw.out_proj_b, xin, M, E, E, E, E, E, E, GEMM_ACT_NONE);        // x1 = xin + out_proj(ao)
-        TRYD(excel_launch_gemm(op, true, 1, st));
-        TRYD(excel_launch_layernorm(x1, nullptr, 1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
-        GemmArgs f1 = ga0(ws.dt1, bw.fc1_w, zm, bw.fc1_b, nullptr, M, 4 * E, E, E, E, 4 * E, 0, GEMM_ACT_NONE);
-        TRYD(excel_launch_gemm(f1, true, 1, st));
-        TRYD(tr_launch_act(zm, hq, (long long)M * 4 * E, 1, st));
+        TRY(excel_launch_gemm(q, true, 1, st));
+        TRY(excel_launch_dec_attention(qkv, pm, ao, B, P, ws.Pp, E, H, 0, st));       // pm keeps the probabilities for the backward
+        GemmArgs op = gemm_args(ao, bw.out_proj_w, x1, bw.out_proj_b, xin, M, E, E, E, E, E, E, GEMM_ACT_NONE);        // x1 = xin + out_proj(ao)
+        TRY(excel_launch_gemm(op, true, 1, st));
+        TRY(excel_launch_layernorm(x1, nullptr, 1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
+        GemmArgs f1 = gemm_args(ws.dt1, bw.fc1_w, zm, bw.fc1_b, nullptr, M, 4 * E, E, E, E, 4 * E, 0, GEMM_ACT_NONE);
+        TRY(excel_launch_gemm(f1, true, 1, st));
+        TRY(tr_launch_act(zm, hq, (long long)M * 4 * E, 1, st));
         float* xout = (l + 1 < nl) ? ws.xin + (l + 1) * ME : ws.xfin;
-        GemmArgs f2 = ga0(hq, bw.fc2_w, xout, bw.fc2_b, x1, M, E, 4 * E, 4 * E, 4 * E, E, E, GEMM_ACT_NONE);          // x2 = x1 + mlp
-        TRYD(excel_launch_gemm(f2, true, 1, st));
+        GemmArgs f2 = gemm_args(hq, bw.fc2_w, xout, bw.fc2_b, x1, M, E, 4 * E, 4 * E, 4 * E, E, E, GEMM_ACT_NONE);          // x2 = x1 + mlp
+        TRY(excel_launch_gemm(f2, true, 1, st));
         x = xout;
     }
     if (nl == 0) hipMemcpyAsync(ws.xfin, ws.fts, sizeof(float) * ME, hipMemcpyDeviceToDevice, st);
-    GemmArgs lp = ga0(ws.xfin, h->w.pred_w, ws.segt, h->w.pred_b, nullptr, M, nc, E, E, E, ws.ncp, 0, GEMM_ACT_NONE);
-    TRYD(excel_launch_gemm(lp, true, 1, st));
-    TRYD(excel_launch_dec_transpose(ws.segt, seg_out, B, P, nc, ws.ncp, P, st));
+    GemmArgs lp = gemm_args(ws.xfin, h->w.pred_w, ws.segt, h->w.pred_b, nullptr, M, nc, E, E, E, ws.ncp, 0, GEMM_ACT_NONE);
+    TRY(excel_launch_gemm(lp, true, 1, st));
+    TRY(excel_launch_dec_transpose(ws.segt, seg_out, B, P, nc, ws.ncp, P, st));
     return EXCEL_OK;
 }
 
@@ -586,17 +578,17 @@ extern "C" int excel_decoder_forward_train(excel_decoder_t h, const float* all_f
 static int tr_linear_bwd(const float* dY, int ldy, const float* X, int ldx, const float* W, float* dW, float* db, float* dX, int lddx, int M, int out,
                          int in, TrainWs& ws, hipStream_t st) {
     // dY^T [out, Mp] (zero padded K tail) then NN: dW = dY^T [out,M] . X [M,in]
-    TRYD(excel_launch_dec_transpose(dY, ws.tr, 1, M, out, ldy, ws.Mp, st));
-    GemmArgs gw = ga0(ws.tr, X, dW, nullptr, nullptr, out, in, M, ws.Mp, ldx, in, 0, GEMM_ACT_NONE);
+    TRY(excel_launch_dec_transpose(dY, ws.tr, 1, M, out, ldy, ws.Mp, st));
+    GemmArgs gw = gemm_args(ws.tr, X, dW, nullptr, nullptr, out, in, M, ws.Mp, ldx, in, 0, GEMM_ACT_NONE);
     gw.Kld = ws.Mp;
-    TRYD(excel_launch_gemm(gw, false, 1, st));
+    TRY(excel_launch_gemm(gw, false, 1, st));
     if (db) {
         hipLaunchKernelGGL(tr_colsum_kernel, dim3(cdiv(out, 64)), dim3(256), 0, st, dY, db, M, out, ldy);
         EXCEL_CHECK_LAUNCH("train/colsum");
     }
     if (dX) {                                                      // dX = dY [M,out] . W [out,in]   (NN)
-        GemmArgs gx = ga0(dY, W, dX, nullptr, nullptr, M, in, out, ldy, in, lddx, 0, GEMM_ACT_NONE);
-        TRYD(excel_launch_gemm(gx, false, 1, st));
+        GemmArgs gx = gemm_args(dY, W, dX, nullptr, nullptr, M, in, out, ldy, in, lddx, 0, GEMM_ACT_NONE);
+        TRY(excel_launch_gemm(gx, false, 1, st));
     }
     return EXCEL_OK;
 }
@@ -632,8 +624,8 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
 
     // linear_pred: seg [B,nc,P] -> token-major d_seg_tok [M, ncp]
     hipMemsetAsync(ws.segt, 0, sizeof(float) * (size_t)M * ws.ncp, st);
-    TRYD(excel_launch_dec_transpose(d_seg, ws.segt, B, nc, P, P, ws.ncp, st));          // [B,nc,P] -> [B,P,ncp] (pad columns zero)
-    TRYD(tr_linear_bwd(ws.segt, ws.ncp, ws.xfin, E, h->w.pred_w, W(grads->pred_w), W(grads->pred_b), ws.dx, E, M, nc, E, ws, st));
+    TRY(excel_launch_dec_transpose(d_seg, ws.segt, B, nc, P, P, ws.ncp, st));          // [B,nc,P] -> [B,P,ncp] (pad columns zero)
+    TRY(tr_linear_bwd(ws.segt, ws.ncp, ws.xfin, E, h->w.pred_w, W(grads->pred_w), W(grads->pred_b), ws.dx, E, M, nc, E, ws, st));
 
     for (int l = nl - 1; l >= 0; --l) {
         const excel_decoder_block_weights& bw = h->blocks[l];
@@ -646,54 +638,54 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         const float* zm = ws.zm + (size_t)l * M * 4 * E;
         const float* hq = ws.hq + (size_t)l * M * 4 * E;
         // x2 = x1 + fc2(hq): dhq = dx . W2 ; dW2 = dx^T hq
-        TRYD(tr_linear_bwd(ws.dx, E, hq, 4 * E, bw.fc2_w, W(gb.fc2_w), W(gb.fc2_b), ws.dt4, 4 * E, M, E, 4 * E, ws, st));
+        TRY(tr_linear_bwd(ws.dx, E, hq, 4 * E, bw.fc2_w, W(gb.fc2_w), W(gb.fc2_b), ws.dt4, 4 * E, M, E, 4 * E, ws, st));
         hipLaunchKernelGGL(tr_act_bwd_kernel, dim3((unsigned)cdivl((long long)M * 4 * E, 256)), dim3(256), 0, st, zm, ws.dt4, (long long)M * 4 * E, 1);
         // y2 = LN2(x1) recomputed (cheap) into dt1 for dW1
-        TRYD(excel_launch_layernorm(x1, nullptr, 1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
-        TRYD(tr_linear_bwd(ws.dt4, 4 * E, ws.dt1, E, bw.fc1_w, W(gb.fc1_w), W(gb.fc1_b), ws.dfn, E, M, 4 * E, E, ws, st));   // dfn <- dy2
+        TRY(excel_launch_layernorm(x1, nullptr, 1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
+        TRY(tr_linear_bwd(ws.dt4, 4 * E, ws.dt1, E, bw.fc1_w, W(gb.fc1_w), W(gb.fc1_b), ws.dfn, E, M, 4 * E, E, ws, st));   // dfn <- dy2
         // dx1 = dx + LN2_bwd(dy2)
         hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, x1, ws.dfn, bw.ln2_w, ws.dx, ws.dt1, ws.stat, M, E, 1e-5f);
         hipLaunchKernelGGL(tr_ln_param_grad_kernel, dim3(cdiv(E, 64)), dim3(256), 0, st, x1, ws.dfn, ws.stat, W(gb.ln2_w), W(gb.ln2_b), M, E);
         // now dt1 = dx1.  x1 = xin + out_proj(ao): dao = dx1 . Wo ; dWo = dx1^T ao
-        TRYD(tr_linear_bwd(ws.dt1, E, ao, E, bw.out_proj_w, W(gb.out_proj_w), W(gb.out_proj_b), ws.dx, E, M, E, E, ws, st));       // dx <- dao
+        TRY(tr_linear_bwd(ws.dt1, E, ao, E, bw.out_proj_w, W(gb.out_proj_w), W(gb.out_proj_b), ws.dx, E, M, E, E, ws, st));       // dx <- dao
         // attention backward per (b,h): dO = dao[:, h*hd:(h+1)*hd]
         //   dP = dO V^T   (batched NT, K = hd)
-        GemmArgs gp = ga0(ws.dx, qkv + (size_t)2 * H * P * hd, ws.dpm, nullptr, nullptr, P, P, hd, E, hd, ws.Pp, 0, GEMM_ACT_NONE);
+        GemmArgs gp = gemm_args(ws.dx, qkv + (size_t)2 * H * P * hd, ws.dpm, nullptr, nullptr, P, P, hd, E, hd, ws.Pp, 0, GEMM_ACT_NONE);
         gp.zdiv = H;
         gp.sA = (long long)P * E; gp.sA2 = hd;
         gp.sB = (long long)3 * H * P * hd; gp.sB2 = (long long)P * hd;
         gp.sC = (long long)H * P * ws.Pp; gp.sC2 = (long long)P * ws.Pp;
-        TRYD(excel_launch_gemm(gp, true, B * H, st));
+        TRY(excel_launch_gemm(gp, true, B * H, st));
         //   dV = P^T dO : P^T via transpose, then NN with B = dO (pitch E)
-        TRYD(excel_launch_dec_transpose(pm, ws.tp, B * H, P, P, ws.Pp, ws.Pp, st));
+        TRY(excel_launch_dec_transpose(pm, ws.tp, B * H, P, P, ws.Pp, ws.Pp, st));
         float* dqh = ws.dqkvh;
-        GemmArgs gv = ga0(ws.tp, ws.dx, dqh + (size_t)2 * H * P * hd, nullptr, nullptr, P, hd, P, ws.Pp, E, hd, 0, GEMM_ACT_NONE);
+        GemmArgs gv = gemm_args(ws.tp, ws.dx, dqh + (size_t)2 * H * P * hd, nullptr, nullptr, P, hd, P, ws.Pp, E, hd, 0, GEMM_ACT_NONE);
         gv.Kld = ws.Pp; gv.zdiv = H;
         gv.sA = (long long)H * P * ws.Pp; gv.sA2 = (long long)P * ws.Pp;
         gv.sB = (long long)P * E; gv.sB2 = hd;
         gv.sC = (long long)3 * H * P * hd; gv.sC2 = (long long)P * hd;
-        TRYD(excel_launch_gemm(gv, false, B * H, st));
+        TRY(excel_launch_gemm(gv, false, B * H, st));
         //   dS = scale * P .* (dP - rowsum(dP .* P))
         hipLaunchKernelGGL(tr_softmax_bwd_kernel, dim3((unsigned)cdivl((long long)B * H * P, 4)), dim3(256), 0, st, pm, ws.dpm, (long long)B * H * P, P,
                            ws.Pp, scale);
         //   dQ = dS K (NN) ; dK = dS^T Q (transpose + NN)
-        GemmArgs gq = ga0(ws.dpm, qkv + (size_t)H * P * hd, dqh, nullptr, nullptr, P, hd, P, ws.Pp, hd, hd, 0, GEMM_ACT_NONE);
+        GemmArgs gq = gemm_args(ws.dpm, qkv + (size_t)H * P * hd, dqh, nullptr, nullptr, P, hd, P, ws.Pp, hd, hd, 0, GEMM_ACT_NONE);
         gq.Kld = ws.Pp; gq.zdiv = H;
         gq.sA = (long long)H * P * ws.Pp; gq.sA2 = (long long)P * ws.Pp;
         gq.sB = (long long)3 * H * P * hd; gq.sB2 = (long long)P * hd;
         gq.sC = (long long)3 * H * P * hd; gq.sC2 = (long long)P * hd;
-        TRYD(excel_launch_gemm(gq, false, B * H, st));
-        TRYD(excel_launch_dec_transpose(ws.dpm, ws.tp, B * H, P, P, ws.Pp, ws.Pp, st));
-        GemmArgs gk = ga0(ws.tp, qkv, dqh + (size_t)H * P * hd, nullptr, nullptr, P, hd, P, ws.Pp, hd, hd, 0, GEMM_ACT_NONE);
+        TRY(excel_launch_gemm(gq, false, B * H, st));
+        TRY(excel_launch_dec_transpose(ws.dpm, ws.tp, B * H, P, P, ws.Pp, ws.Pp, st));
+        GemmArgs gk = gemm_args(ws.tp, qkv, dqh + (size_t)H * P * hd, nullptr, nullptr, P, hd, P, ws.Pp, hd, hd, 0, GEMM_ACT_NONE);
         gk.Kld = ws.Pp; gk.zdiv = H;
         gk.sA = (long long)H * P * ws.Pp; gk.sA2 = (long long)P * ws.Pp;
         gk.sB = (long long)3 * H * P * hd; gk.sB2 = (long long)P * hd;
         gk.sC = (long long)3 * H * P * hd; gk.sC2 = (long long)P * hd;
-        TRYD(excel_launch_gemm(gk, false, B * H, st));
+        TRY(excel_launch_gemm(gk, false, B * H, st));
         hipLaunchKernelGGL(tr_headmajor_to_rows_kernel, dim3((unsigned)cdivl((long long)M * 3 * E, 256)), dim3(256), 0, st, dqh, ws.dqkvr, B, H, P, hd);
         // y1 = LN1(xin) recomputed into dx (free now) for dW_in; dy1 -> dfn
-        TRYD(excel_launch_layernorm(xin, nullptr, 1, bw.ln1_w, bw.ln1_b, ws.dx, M, E, 1e-5f, st));
-        TRYD(tr_linear_bwd(ws.dqkvr, 3 * E, ws.dx, E, bw.in_proj_w, W(gb.in_proj_w), W(gb.in_proj_b), ws.dfn, E, M, 3 * E, E, ws, st));
+        TRY(excel_launch_layernorm(xin, nullptr, 1, bw.ln1_w, bw.ln1_b, ws.dx, M, E, 1e-5f, st));
+        TRY(tr_linear_bwd(ws.dqkvr, 3 * E, ws.dx, E, bw.in_proj_w, W(gb.in_proj_w), W(gb.in_proj_b), ws.dfn, E, M, 3 * E, E, ws, st));
         // dxin = dx1 + LN1_bwd(dy1) -> dx
         hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, xin, ws.dfn, bw.ln1_w, ws.dt1, ws.dx, ws.stat, M, E, 1e-5f);
         hipLaunchKernelGGL(tr_ln_param_grad_kernel, dim3(cdiv(E, 64)), dim3(256), 0, st, xin, ws.dfn, ws.stat, W(gb.ln1_w), W(gb.ln1_b), M, E);
@@ -708,9 +700,9 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         hipLaunchKernelGGL(tr_mean_finish_kernel, dim3(1), dim3(64), 0, st, ws.partial, np, nap, ws.mean);
         hipLaunchKernelGGL(tr_symmetrize_grad_kernel, dim3((unsigned)cdivl(nap, 256)), dim3(256), 0, st, ws.dpm, ws.mean, ws.tp, B, P, 1.f, 3.f);
         // dfn[b] = G[b] . fn[b]   (batched NN, K = P)
-        GemmArgs gf = ga0(ws.tp, ws.fn, ws.dfn, nullptr, nullptr, P, E, P, P, E, E, 0, GEMM_ACT_NONE);
+        GemmArgs gf = gemm_args(ws.tp, ws.fn, ws.dfn, nullptr, nullptr, P, E, P, P, E, E, 0, GEMM_ACT_NONE);
         gf.sA = (long long)P * P; gf.sB = (long long)P * E; gf.sC = (long long)P * E;
-        TRYD(excel_launch_gemm(gf, false, B, st));
+        TRY(excel_launch_gemm(gf, false, B, st));
         hipLaunchKernelGGL(tr_row_normalize_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, ws.fn, ws.dfn, ws.inv, ws.dx, M, E);
         EXCEL_CHECK_LAUNCH("train/attn_pred_bwd");
     }
@@ -718,18 +710,18 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         hipLaunchKernelGGL(tr_dropout2d_kernel, dim3((unsigned)cdivl((long long)ME, 256)), dim3(256), 0, st, ws.dx, B, P, E, dropout_p, dropout_seed);
     // linear_fuse: fts = cat . Wf^T + bf  ->  dcat [M, L*E] in hq (free now; train_ws_layout sizes it for max(4E*nl, L*E))
     float* dcat = ws.hq;
-    TRYD(tr_linear_bwd(ws.dx, E, ws.cat, L * E, h->w.fuse_w, W(grads->fuse_w), W(grads->fuse_b), dcat, L * E, M, E, L * E, ws, st));
+    TRY(tr_linear_bwd(ws.dx, E, ws.cat, L * E, h->w.fuse_w, W(grads->fuse_w), W(grads->fuse_b), dcat, L * E, M, E, L * E, ws, st));
     for (int l = 0; l < L; ++l) {
         const excel_fuse_layer_weights& fw = h->fuse[l];
         const excel_fuse_layer_weights& gfw = grads->fuse[l];
         // z2_l = h1_l . W2^T + b2 (slice l of cat): dh1 = dz2 . W2 ; dW2 = dz2^T h1
-        TRYD(tr_linear_bwd(dcat + (size_t)l * E, L * E, ws.h1 + l * ME, E, fw.proj2_w, W(gfw.proj2_w), W(gfw.proj2_b), ws.dt1, E, M, E, E, ws, st));
+        TRY(tr_linear_bwd(dcat + (size_t)l * E, L * E, ws.h1 + l * ME, E, fw.proj2_w, W(gfw.proj2_w), W(gfw.proj2_b), ws.dt1, E, M, E, E, ws, st));
         hipLaunchKernelGGL(tr_act_bwd_kernel, dim3((unsigned)cdivl((long long)ME, 256)), dim3(256), 0, st, ws.z1 + l * ME, ws.dt1, (long long)ME, 0);
         // z1_l = tok_l . W1^T + b1 with tok_l = rows 1..P of each image of all_feats[l]: dW1 = dz1^T tok (batched over images, summed)
         // -> gather the token rows once into dt4 ([M, max(4E, D)] floats)
         hipMemcpy2DAsync(ws.dt4, sizeof(float) * (size_t)P * D, all_feats + ((size_t)l * B * N + 1) * D, sizeof(float) * (size_t)N * D,
                          sizeof(float) * (size_t)P * D, B, hipMemcpyDeviceToDevice, st);
-        TRYD(tr_linear_bwd(ws.dt1, E, ws.dt4, D, fw.proj_w, W(gfw.proj_w), W(gfw.proj_b), nullptr, 0, M, E, D, ws, st));
+        TRY(tr_linear_bwd(ws.dt1, E, ws.dt4, D, fw.proj_w, W(gfw.proj_w), W(gfw.proj_b), nullptr, 0, M, E, D, ws, st));
     }
     return EXCEL_OK;
 }
