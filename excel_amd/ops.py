@@ -1580,6 +1580,37 @@ def confusion_accumulate_masked(gt_u8, pred_u8, num_classes, skip, hist=None, pl
     return hist
 
 
+# ------------------------------------------------------------------ per-image scores (include/excel_hip.h, "per-image scores")
+def image_scores(gt_u8, pred_u8, num_classes, skip=None, plan=None, out=None):
+    """-> int32 [B,3,nc] (device): per image the ground-truth area, the predicted area and the intersection of every class over the pixels
+    with gt < nc and pred < nc - the margins of the image's own confusion matrix (utils/evaluate.image_score_rows turns them into IoU,
+    mIoU and pixel accuracy).  plan=None: gt / pred are uniform [B,H,W] maps; with a RaggedPlan they are its tight label maps back to
+    back.  skip: int32 [B] (device) or None - the rows of an image with skip[b] != 0 are zero.  out: a buffer of B*3*nc int32, fully
+    overwritten.  One launch, no scratch memory, no synchronisation."""
+    gt = gt_u8.contiguous()
+    pr = pred_u8.contiguous()
+    if gt.numel() != pr.numel():
+        raise ValueError(f"image_scores: gt holds {gt.numel()} pixels, pred {pr.numel()}")
+    nc = int(num_classes)
+    if not 1 <= nc <= 256:
+        raise ValueError(f"image_scores: num_classes = {nc} is outside [1, 256]")
+    B = plan.B if plan is not None else (int(gt.shape[0]) if gt.dim() > 0 else 0)
+    if B < 1:
+        raise ValueError(f"image_scores: B = {B}: at least one image is needed (gt {tuple(gt.shape)})")
+    if plan is not None and gt.numel() != plan.total_label_pix:
+        raise ValueError(f"image_scores: {gt.numel()} pixels, the plan holds {plan.total_label_pix}")
+    if skip is not None and skip.numel() != B:
+        raise ValueError(f"image_scores: skip holds {skip.numel()} flags for {B} images")
+    if out is not None and (out.numel() != B * 3 * nc or out.dtype != torch.int32):
+        raise ValueError(f"image_scores: out must hold {B * 3 * nc} int32 (got {out.numel()} {out.dtype})")
+    counts = torch.empty((B, 3, nc), dtype=torch.int32, device=gt.device) if out is None else out.view(B, 3, nc)
+    check(lib().excel_image_scores(_p(gt, torch.uint8), _p(pr, torch.uint8), B, gt.numel() // B,
+                                   _p(plan.table, torch.int32) if plan is not None else None,
+                                   C.byref(plan.info) if plan is not None else None, _p(skip, torch.int32), nc,
+                                   _p(counts, torch.int32), _stream()), "excel_image_scores")
+    return counts
+
+
 # ------------------------------------------------------------------ one-time / auxiliary
 def attr_aggregate(text_features, bank, num_fg, topK=0.9):
     """text [T,C], bank [C,K] -> text_attr [C,T] (model/load_attr.py:86-119)."""

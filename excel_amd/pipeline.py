@@ -119,6 +119,34 @@ class TagTicket:
         return self._onehot.numpy(), self._scores.numpy()
 
 
+class ScoreTicket:
+    """The per-image score counts of one step on their way to the host (the GuardTicket pattern): per matrix the step scored - "main"
+    (self.hist), "conf" (self.hist_conf), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
+    event recorded behind the last copy on the step's stream.  ready() never blocks; counts() waits for the event."""
+
+    def __init__(self):
+        self._parts, self._event = {}, None
+
+    def launch(self, which, gts, labels, num_classes, skip=None, plan=None, out=None):
+        """ops.image_scores over (gts, labels) on the current stream, its copy to pinned memory and the event behind it -> self"""
+        dev = ops.image_scores(gts, labels, num_classes, skip=skip, plan=plan, out=out)
+        host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(dev, non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record()
+        self._parts[which] = host
+        return self
+
+    def ready(self):
+        return self._event is None or self._event.query()
+
+    def counts(self):
+        """-> {"main": int32 [B,3,nc], ...} as numpy arrays: the matrices this step scored"""
+        if self._event is not None:
+            self._event.synchronize()
+        return {k: v.numpy() for k, v in self._parts.items()}
+
+
 def check_tagger(tagger, smax, num_classes):
     """tagger = dict(thre=, kmax=, scale=) of the predicted image tags (ops.clip_tags; defaults 0.2 / smax / 100.0) -> the complete dict,
     or None.  Refused, naming `tagger`: an unknown key, thre outside [0, 1], scale <= 0, kmax outside [1, num_classes - 1] and
@@ -159,7 +187,7 @@ def check_num_classes(num_classes):
 
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -178,7 +206,13 @@ class TrainingFreePipeline:
         launch).  With it, run_batch / run_batch_ragged ignore the values of `cls_labels` (None is accepted): right after the scale-1.0
         forward, model.image_tags predicts the one-hot rows on the device (ops.clip_tags over CLIP's image embedding and the text rows)
         and those go to ops.cls_compact.  They stay in `last_tags` = (onehot, scores) (device [B,F], until the next step) and travel to
-        the host behind `last_tag_ticket` (a TagTicket) - no synchronisation.  Everything behind cls_compact is untouched."""
+        the host behind `last_tag_ticket` (a TagTicket) - no synchronisation.  Everything behind cls_compact is untouched.
+        `image_scores` = per-image scores, off by default (False: today's step, launch for launch).  With it, every matrix run_batch /
+        run_batch_ragged score (hist, hist_conf, a ValidationPipeline's hist_seg) also gets ops.image_scores on the same arrays - with the
+        step's guard flags as `skip` when guard == "skip" - and the counts travel to the host behind `last_score_ticket` (a ScoreTicket:
+        counts() -> {"main": ..., "conf": ..., "seg": ...}, int32 [B,3,nc] each) - no synchronisation."""
+        self.image_scores = bool(image_scores)
+        self.last_score_ticket = None
         if guard not in GUARD_MODES:
             raise ValueError(f"guard must be one of {GUARD_MODES} (got {guard!r})")
         self.guard = guard
@@ -269,9 +303,22 @@ class TrainingFreePipeline:
     def _score(self, gts, labels, flags, plan=None, into="hist"):
         """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
         hist = getattr(self, into)
+        if self.image_scores:
+            self._image_scores({"hist": "main", "hist_conf": "conf"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
         if self.guard == "skip":
             return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, hist, plan=plan)
         return ops.confusion_accumulate(gts, labels, self.num_classes, hist)                       # evaluate.py:9-20
+
+    def _image_scores(self, which, gts, labels, skip=None, plan=None):
+        """image_scores set: the per-image counts of one scored matrix, added to the step's ScoreTicket (on the step's stream)."""
+        B = plan.B if plan is not None else int(gts.shape[0])
+        out = self._buf("image_scores_" + which, B * 3 * self.num_classes, torch.int32, gts.device)
+        self.last_score_ticket.launch(which, gts, labels, self.num_classes, skip=skip, plan=plan, out=out)
+
+    def _no_image_scores(self, what):
+        if self.image_scores:
+            raise ValueError(f"{what} has no per-image scores (image_scores=True): its sub-batches run on streams of their own - use "
+                             "run_batch or run_batch_ragged, or build the pipeline without image_scores")
 
     def _no_guard(self, what):
         if self.guard is not None:
@@ -351,6 +398,8 @@ class TrainingFreePipeline:
         B, _, S, _ = inputs.shape
         g = S // 16
         H, W = (gts.shape[-2:] if gts is not None else (label_hw or (S, S)))
+        if self.image_scores:
+            self.last_score_ticket = ScoreTicket()
         if self.tta:
             attr, attn_w, cls_labels = self._tta_attr(S, lambda S_s: self._tta_uniform_input(inputs, S_s), cls_labels)
         else:
@@ -400,6 +449,8 @@ class TrainingFreePipeline:
         dev = hwc_packed.device
         B = plan.B
         g = S // 16
+        if self.image_scores:
+            self.last_score_ticket = ScoreTicket()
         if self.tta:
             first = []                      # the scale-1.0 input: its un-mirrored half is what PAR reads
 
@@ -467,6 +518,7 @@ class TrainingFreePipeline:
         self._no_guard("run_batch_split")
         self._no_tta("run_batch_split")
         self._no_tagger("run_batch_split")
+        self._no_image_scores("run_batch_split")
         B, _, S, _ = inputs.shape
         nsplit = max(1, min(nsplit, B))
         if nsplit == 1:
@@ -512,6 +564,7 @@ class TrainingFreePipeline:
         self._no_guard("run_batch_overlapped")
         self._no_tta("run_batch_overlapped")
         self._no_tagger("run_batch_overlapped")
+        self._no_image_scores("run_batch_overlapped")
         sa, sb = self._streams()
         cur = torch.cuda.current_stream()
         B, _, S, _ = inputs.shape
@@ -570,14 +623,15 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         _refuse_tagger("OptimisedLamPipeline", tagger)
         if getattr(model, "_dec", None) is None:
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
-        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard)
+        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard,
+                         image_scores=image_scores)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -592,6 +646,8 @@ class OptimisedLamPipeline(TrainingFreePipeline):
         dev = hwc_packed.device
         B = plan.B
         g = S // 16
+        if self.image_scores:
+            self.last_score_ticket = ScoreTicket()
         model = self.model
         dec = model._dec
         inputs2 = ops.normalize_resize_u8_ragged_mirror(hwc_packed, plan, S,
@@ -639,7 +695,7 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         _refuse_tagger("ValidationPipeline", tagger)
@@ -648,7 +704,8 @@ class ValidationPipeline(TrainingFreePipeline):
         if guard is not None:
             raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
                              "histograms per step and is out of the guard's scope")
-        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax)
+        super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax,
+                         image_scores=image_scores)
         self.attn_layers = attn_layers
         self.hist_seg = None
 
@@ -664,6 +721,8 @@ class ValidationPipeline(TrainingFreePipeline):
         dev = hwc_packed.device
         B = plan.B
         g = S // 16
+        if self.image_scores:
+            self.last_score_ticket = ScoreTicket()
         model = self.model
         h = model.encoder.visual.handle()
         inputs = ops.normalize_resize_u8_ragged(hwc_packed, plan, S, out=self._buf("inputs", B * 3 * S * S, device=dev).view(B, 3, S, S))  # :20
@@ -677,6 +736,8 @@ class ValidationPipeline(TrainingFreePipeline):
         del r
         seg_labels = ops.seg_resize_argmax_uniform(seg, plan)                                        # :27, :37
         if gts_packed is not None:
+            if self.image_scores:
+                self._image_scores("seg", gts_packed, seg_labels, None, plan)
             self.hist_seg = ops.confusion_accumulate(gts_packed, seg_labels, self.num_classes, self.hist_seg)
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # :33

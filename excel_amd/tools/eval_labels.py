@@ -8,7 +8,8 @@ reads `<pred_dir>/<name>.png` (what `infer_lam --save_label true` writes, or any
 the files are decoded in a thread pool, the matrix is accumulated on the device (ops.confusion_accumulate), ranks take names r, r+R, ...
 and exchange their matrices once.  Without a GPU the matrix is computed with numpy (np.bincount, the arithmetic of utils/evaluate.py:9-20):
 file handling is the point of this program, not compute.  A missing prediction and a prediction whose size differs from the ground truth
-are errors that name the file.
+are errors that name the file.  `--per_image_scores PATH` also writes every image's own scores (utils/image_scores.py: a CSV in list
+order and PATH.npz with the per-class counts; ops.image_scores on the device, np.bincount without one).
 """
 import argparse
 import concurrent.futures as cf
@@ -33,6 +34,8 @@ def get_parser():
     p.add_argument("--class_names", default=None, type=str, help="one foreground class name per line: the rows of the table (infer_lam --class_names)")
     p.add_argument("--num_workers", default=8, type=int, help="PNG decode threads")
     p.add_argument("--batch_size", default=64, type=int, help="images decoded per device accumulation")
+    from ..utils import image_scores
+    image_scores.add_flags(p)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -56,7 +59,7 @@ def _load_pair(args, name):
     pred = np.asarray(Image.open(pred_path))
     if pred.shape != gt.shape or pred.ndim != 2:
         raise ValueError(f"eval_labels: {pred_path} is {pred.shape}, the ground truth {gt_path} is {gt.shape}")
-    return np.ascontiguousarray(gt, np.uint8).reshape(-1), np.ascontiguousarray(pred, np.uint8).reshape(-1)
+    return np.ascontiguousarray(gt, np.uint8).reshape(-1), np.ascontiguousarray(pred, np.uint8).reshape(-1), gt.shape
 
 
 def _hist_numpy(gt, pred, nc):
@@ -68,8 +71,9 @@ def _hist_numpy(gt, pred, nc):
 
 def validate(args):
     """-> {"score": scores_from_hist of the gathered matrix, "hist": [nc,nc] int64 (CPU tensor), "images": scored on this rank,
-    "seconds"}: the layout of infer_seg_voc.validate."""
-    from ..utils import evaluate
+    "seconds"}: the layout of infer_seg_voc.validate (+ "image_scores" with --per_image_scores)."""
+    from ..utils import evaluate, image_scores
+    image_scores.refuse(args)
     names_fg = None
     if getattr(args, "class_names", None):
         from .infer_lam import _read_names
@@ -88,7 +92,9 @@ def validate(args):
         torch.distributed.init_process_group(backend=args.backend if on_gpu else "gloo")
     with open(os.path.join(args.list_folder, args.infer_set) + ".txt") as f:
         names = [x.split()[0] for x in f.read().split("\n") if x.strip()]
-    mine = [names[i] for i in shard_indices(len(names), rank, world)]
+    idx = shard_indices(len(names), rank, world)
+    mine = [names[i] for i in idx]
+    scores = image_scores.ImageScoreLog(nc) if getattr(args, "per_image_scores", None) else None
     hist = torch.zeros((nc, nc), dtype=torch.int64, device=device)
     t0 = time.time()
     with cf.ThreadPoolExecutor(max_workers=max(1, int(args.num_workers))) as pool:
@@ -98,24 +104,38 @@ def validate(args):
             pred = np.concatenate([p[1] for p in pairs])
             if on_gpu:
                 from .. import ops
-                hist = ops.confusion_accumulate(torch.from_numpy(gt).to(device), torch.from_numpy(pred).to(device), nc, hist)
+                gt_d, pred_d = torch.from_numpy(gt).to(device), torch.from_numpy(pred).to(device)
+                hist = ops.confusion_accumulate(gt_d, pred_d, nc, hist)
+                if scores is not None:                                                           # the batch as one ragged plan, behind a ticket
+                    from ..pipeline import ScoreTicket
+                    hws = [p[2] for p in pairs]
+                    scores.defer(ScoreTicket().launch("main", gt_d, pred_d, nc, plan=ops.RaggedPlan(hws, device)), idx[s:s + len(pairs)],
+                                 mine[s:s + len(pairs)], hws)
             else:
                 hist += torch.from_numpy(_hist_numpy(gt, pred, nc))
+                if scores is not None:
+                    for j, p in enumerate(pairs):
+                        scores.put(idx[s + j], mine[s + j], p[2], "main", image_scores.counts_numpy(p[0], p[1], nc))
     _, total = gather_hists(hist)
     total = total.cpu()
     score = evaluate.scores_from_hist(total)
     secs = time.time() - t0
+    cats = VOC_CLASSES
+    if "coco" in args.dataset_name:
+        from ..datasets import coco
+        cats = coco.class_list
+    if names_fg:
+        cats = [VOC_CLASSES[0]] + names_fg
+    if scores is not None:
+        merged = image_scores.finish(scores, args, cats, rank)
     if rank == 0:
-        cats = VOC_CLASSES
-        if "coco" in args.dataset_name:
-            from ..datasets import coco
-            cats = coco.class_list
-        if names_fg:
-            cats = [VOC_CLASSES[0]] + names_fg
         logging.info(f"label_score of {args.pred_dir}:")
         logging.info("\n" + format_scores_table(score, cats))
         logging.info(f"mIoU {score['miou'] * 100:.3f}  images {len(names)}  ({len(mine) / max(secs, 1e-9):.1f} img/s/rank)")
-    return {"score": score, "hist": total, "images": len(mine), "seconds": secs}
+    out = {"score": score, "hist": total, "images": len(mine), "seconds": secs}
+    if scores is not None:
+        out["image_scores"] = merged                           # the merged table (utils/image_scores.ImageScoreLog.merged)
+    return out
 
 
 if __name__ == "__main__":

@@ -62,6 +62,13 @@ Differences from the reference, all deliberate:
     (datasets/images.ImageListDataset: no SegmentationClassAug, nothing scored, so one of --save_label / --conf_label / --save_tags is
     required).  --save_cam and the CRF stages size host-side work from the class list and are refused with --tags clip: --save_tags
     first, then --tags labels.  The default --tag_thre is provisional (tag quality is unmeasured);
+  * `--per_image_scores PATH`: the reference scores at batch 1 with the labels on the host, so one print in its loop shows an image's
+    own numbers; the batched, device-resident loops here only ever had the summed matrix.  With the flag every scored matrix (main,
+    --conf_label's, --crf_inline's) also gets ops.image_scores on the same arrays - per image and class the ground-truth area, the
+    predicted area and the intersection - behind a ticket (no wait in the loop; the per-image path calls the op with B = 1); after the
+    loop one all_gather_object, rank 0 writes PATH (CSV, data-set order) and PATH.npz (the raw counts) and logs the image-averaged
+    mIoU and the --per_image_worst 20 weakest images (utils/image_scores.py).  With --overflow_guard rerun the second pass's rows
+    replace those of the flagged images (zero after the first pass).  Refused with --unlabeled true;
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -409,6 +416,8 @@ def get_parser():
                         "nothing is scored, so give --save_label, --conf_label or --save_tags")
     p.add_argument("--cpu_affinity", default="auto", choices=["auto", "off"],
                    help="auto: with several ranks on the node every rank pins itself (decode pool included) to its own share of the host cores")
+    from ..utils import image_scores
+    image_scores.add_flags(p)
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
     p.set_defaults(ragged_batches=False, run_token=None, vocab=None, num_classes_given=False)      # what the program sets itself
     return p
@@ -613,6 +622,8 @@ class _CrfInline:
         self.groups, self.calls, self.peak_ws = 0, 0, 0
         self.lab = self.pool = None
         self.futures = []
+        self.image_scores = bool(getattr(args, "per_image_scores", None))     # --per_image_scores: a ScoreTicket ("crf") per call
+        self.last_score_ticket = None
         if args.crf_label_dir:
             self.lab = _LabelSaver(args, args.crf_label_dir)
         self.rgb_dir = args.segs_crf_rgb_dir
@@ -641,6 +652,9 @@ class _CrfInline:
             self.hist = ops.confusion_accumulate_masked(gts_packed, labels, self.nc, skip, self.hist, plan=plan)
         elif gts_packed is not None:
             self.hist = ops.confusion_accumulate(gts_packed, labels, self.nc, self.hist)    # :233
+        if self.image_scores and gts_packed is not None:
+            from ..pipeline import ScoreTicket
+            self.last_score_ticket = ScoreTicket().launch("crf", gts_packed, labels, self.nc, skip=skip, plan=plan)
         if self.lab is not None:
             self.lab.ragged(names, plan, labels)
         if self.pool is not None:
@@ -659,6 +673,9 @@ class _CrfInline:
         self.calls += 1
         self.groups += 1
         self.hist = ops.confusion_accumulate(gt.to(torch.uint8), labels, self.nc, self.hist)                                  # :233
+        if self.image_scores:
+            from ..pipeline import ScoreTicket
+            self.last_score_ticket = ScoreTicket().launch("crf", gt.to(torch.uint8)[None], labels[None], self.nc)
         plan = None
         if self.lab is not None:
             self.lab.uniform([name], labels[None])
@@ -788,9 +805,13 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     tta_scales, tta_flip = resolve_tta(args)
     conf = resolve_conf(args)
     tagger = resolve_tags(args, have_dataset=True)
+    from ..utils import image_scores
+    image_scores.refuse(args, unlabeled=bool(args.unlabeled))
+    want_scores = bool(args.per_image_scores)
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
-                  smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None)
+                  smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
+                  image_scores=want_scores)
         if args.training_free:
             pipe = TrainingFreePipeline(model, tta_scales=tta_scales, tta_flip=tta_flip, tagger=tagger, **kw)
         elif ragged:
@@ -799,14 +820,19 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         # a caller's pipeline keeps the guard it was built with: without one there are no flags to act on
         logging.warning(f"--overflow_guard {policy}: the supplied pipeline was built without a guard - running unguarded")
         policy = "off"
+    if want_scores and pipe is not None and not per_image and not getattr(pipe, "image_scores", False):
+        raise ValueError("--per_image_scores: the supplied pipeline was built without image_scores=True")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
                           on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
+    # --per_image_scores: the rank's table of per-image counts, one set per matrix the run scores (utils/image_scores.py)
+    run.scores = report["image_scores"] = image_scores.ImageScoreLog(
+        args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else [])) if want_scores else None
     try:
         for wanted, needs in ((args.save_cam, "--save_cam needs the decoded images"), (conf is not None, "--conf_label runs behind the ragged step"),
                               (crf_inline_wanted(args), "--crf_inline needs the decoded images")):
@@ -832,6 +858,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         build_validation.last_guard, build_validation.last_crf_hist, build_validation.last_crf_stats, build_validation.last_cam_stats, \
             build_validation.last_conf_hist = (report[k] for k in ("guard", "crf_hist", "crf_stats", "cam_stats", "conf_hist"))
         build_validation.last_tags = report["tags"]
+        build_validation.last_image_scores = report["image_scores"]
     return out
 
 
@@ -863,6 +890,8 @@ def _per_image_loop(run):
     args, model, par, dataset, indices, device, S = run.args, run.model, run.par, run.dataset, run.indices, run.device, run.S
     training_free, tta, conf, hist = args.training_free, run.tta, run.conf, run.hist
     cam, lab, crf, conf_lab = (run.consumers.get(k) for k in ("cam", "lab", "crf", "conf_lab"))
+    from ..pipeline import ScoreTicket
+    scores = run.scores
     nimg, hist_conf = 0, None
     for s in range(0, len(indices)):
         names, imgs, gts, cls = dataset.batch(indices[s:s + 1])
@@ -890,27 +919,36 @@ def _per_image_loop(run):
                 raise RuntimeError("--training_free false needs model.feature_head (the learned decoder, SURVEY 8f #2)")
             attr_maps_raw = cure_attr_map_flip(model, inputs)                               # :85
         for i, attr_map in enumerate(attr_maps_raw):                                        # :88
+            rec = ([int(indices[s + i])], [names[i]], [gts.shape[-2:]])                     # what --per_image_scores files the counts under
             seg_attn = None if training_free else attn_pred[i][None]                        # :91-92
             refined, cls_lst = refine_cams_with_aff(attr_map, attn_weights[:, i], cls_labels[i], size=inputs.shape[2:],
                                                     seg_attn=seg_attn, caa_thre=0.79)       # :93
             labels, normed = refine_cams_with_bkg_weclip(refined, inputs[i], cls_lst, par, gts.shape[-2:])   # :94
             if crf is not None:                                                             # :179-237 without a record
                 crf.image(str(names[i]), decoded[i], normed, cls_lst, gt_dev[i])
+                if scores is not None:
+                    scores.defer(crf.last_score_ticket, *rec)
             elif args.crf_post:                                                             # :116-119 record for the CRF stage
                 from ..utils import imutils
                 imutils.save_logits(args.logits_dir, str(names[i]), normed, cls_lst, run_token=args.run_token)
             if cam is not None:                                                             # :97-111
                 cam.image(names[i], decoded[i], normed, cls_lst)
             hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
+            if scores is not None:                                                          # the op with B = 1, behind a ticket: no wait here
+                scores.defer(ScoreTicket().launch("main", gt_dev[i].to(torch.uint8)[None], labels[:1].to(torch.uint8), args.num_classes), *rec)
             if lab is not None:                                                             # :95 (uint8 as hist_from_labels scores them)
                 lab.uniform([names[i]], labels[:1].to(torch.uint8))
             if conf is not None:                                                            # affutils.py:101-158 on the image's own cams
                 from ..utils.affutils import conf_labels_image
                 kept = conf_labels_image(par, inputs[i], normed, cls_lst, conf[0], conf[1])
                 hist_conf = ops.confusion_accumulate(gt_dev[i].to(torch.uint8), kept, args.num_classes, hist_conf)
+                if scores is not None:
+                    scores.defer(ScoreTicket().launch("conf", gt_dev[i].to(torch.uint8)[None], kept[None], args.num_classes), *rec)
                 conf_lab.uniform([names[i]], kept[None])
         nimg += len(imgs)
     torch.cuda.synchronize()
+    if scores is not None:
+        scores.poll(True)
     run.report["conf_hist"] = hist_conf
     return hist, nimg, time.time() - run.t0
 
@@ -924,6 +962,8 @@ def _batched_loop(run):
     ragged, guard, conf, tagger = run.ragged, run.guard, run.conf, run.tagger
     truth_known = bool(getattr(dataset, "has_cls_labels", True))      # the samples' one-hot rows are image-level labels (not placeholders)
     step_cls = [None]           # the host one-hot rows of the step enqueued last
+    step_hw = [None]            # ... and its label sizes [(H, W)] (--per_image_scores)
+    scores = run.scores
     cam, lab, crf, conf_lab = (run.consumers.get(k) for k in ("cam", "lab", "crf", "conf_lab"))
     policy = guard["policy"]
     pipe.hist = run.hist
@@ -956,6 +996,7 @@ def _batched_loop(run):
 
     def ragged_step(names, plan, images, cls_t, labels_t):
         step_cls[0] = getattr(plan, "cls_host", None)
+        step_hw[0] = plan.hw
         if conf is None:
             out = pipe.run_batch_ragged(images, plan, cls_t, labels_t, S=S, return_intermediates=keep)
         else:                                                                           # affutils.py:101-158, same stream, step's own cams
@@ -982,6 +1023,7 @@ def _batched_loop(run):
     def uniform_step(idxs):
         names, imgs, gts, cls = dataset.batch(idxs)
         step_cls[0] = cls
+        step_hw[0] = [gts.shape[-2:]] * len(names)
         inputs = torch.from_numpy(imgs).to(device, non_blocking=True)
         if inputs.dtype == torch.uint8:                                                     # decoded images: normalise on the device
             inputs = ops.normalize_img_u8(inputs)                                           # datasets/voc.py:115-116
@@ -1008,6 +1050,13 @@ def _batched_loop(run):
 
     def enqueue(names, idxs):
         pending.append((pipe.last_guard, [str(n) for n in names], [int(i) for i in idxs]))
+
+    def score_enqueue(names, idxs):
+        """--per_image_scores: the step's tickets (the pipeline's main / conf counts, the CRF stage's) go to the table; a later row of an
+        image (the fp32 second pass) replaces the earlier one, which the guard's skip flags left zero."""
+        scores.defer(pipe.last_score_ticket, idxs, names, step_hw[0])
+        if crf is not None:
+            scores.defer(crf.last_score_ticket, idxs, names, step_hw[0])
 
     def take(wait, found, first_pass=True):
         """Read the tickets that are ready (all of them with `wait`), oldest first: flagged images -> found[dataset index] = name."""
@@ -1052,6 +1101,8 @@ def _batched_loop(run):
         if tagger is not None:
             tag_enqueue(names)
             tag_take(False)
+        if scores is not None:
+            score_enqueue(names, indices[pos:pos + len(names)])
         pos += len(names)
         nimg += len(names)
     if policy != "off":
@@ -1074,6 +1125,8 @@ def _batched_loop(run):
                     enqueue(names, order[pos:pos + len(names)])
                     if tagger is not None:
                         tag_enqueue(names)                    # the fp32 row replaces the first pass's
+                    if scores is not None:
+                        score_enqueue(names, order[pos:pos + len(names)])
                     pos += len(names)
                     guard["rerun"] += len(names)
                 take(True, still, first_pass=False)           # (also: the fp32 forwards are done before the mode goes back)
@@ -1089,6 +1142,8 @@ def _batched_loop(run):
         torch.cuda.synchronize()
     if conf is not None:
         run.report["conf_hist"] = pipe.hist_conf
+    if scores is not None:
+        scores.poll(True)
     if tagger is not None:
         tag_take(True)
         run.report["tags"] = dict(rows=tag_rows, truth=tag_truth, **tag_report(tag_rows, tag_truth, args.num_classes - 1))
@@ -1248,7 +1303,9 @@ def validate(args=None, dataset=None, pipe=None):
     flag_defaults(args)
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
-    validate.last_conf = validate.last_crf = validate.last_tags = None
+    validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = None
+    from ..utils import image_scores
+    image_scores.refuse(args, unlabeled=bool(args.unlabeled))                                # ... and per-image scores of nothing
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
@@ -1373,6 +1430,8 @@ def validate(args=None, dataset=None, pipe=None):
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
                            "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1]),
                            **({"tags": _tags_json(tags, tagger)} if tags is not None else {})}, f)
+    if args.per_image_scores:                                                               # one all_gather_object, rank 0 writes
+        validate.last_image_scores = image_scores.finish(build_validation.last_image_scores, args, cat_list, rank, what="LAM_score")
     if conf is not None:
         conf_hist = build_validation.last_conf_hist
         if conf_hist is None:                                                               # a rank with an empty shard still joins the gather

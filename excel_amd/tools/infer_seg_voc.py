@@ -22,7 +22,9 @@ Deliberate differences from the reference:
     directory is created (the reference writes ~15 MB per VOC image and reads them back);
   * output paths follow :223-240 (`<model_path before "checkpoints/">/<infer_set>/<infer_set>_<ckpt>_segs/...`); a --model_path
     without a `checkpoints/` component uses the checkpoint's own directory in place of the part before it;
-  * --scales takes a comma-separated list ("0.7,1.0,1.2,1.5").
+  * --scales takes a comma-separated list ("0.7,1.0,1.2,1.5");
+  * --per_image_scores PATH (not for --infer_set test): every image's own scores of the raw and, with --crf_post, the CRF labels
+    (excel_image_scores next to each confusion update, read behind tickets; utils/image_scores.py writes PATH and PATH.npz).
 """
 import argparse
 import logging
@@ -110,6 +112,8 @@ def get_parser():
     p.add_argument("--gemm_check_tol", default=5e-4, type=float)
     p.add_argument("--crf_batched", default=True, type=_bool, help="run the DenseCRF stage over the whole batch (false: image by image)")
     p.add_argument("--crf_ws_gb", default=16.0, type=float, help="workspace budget of the batched DenseCRF stage; a batch is cut into groups that fit")
+    from ..utils import image_scores
+    image_scores.add_flags(p)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -194,14 +198,16 @@ def _crf_batch(post, images, plan, planes, fplan, nc, budget):
 
 
 @torch.no_grad()
-def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None):
+def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None, scores=None, indices=None):
     """The loop of _validate (:58-91) and crf_proc (:103-174) over ragged batches `feed` = (names, plan, images u8, cls, labels u8)
     device tuples (datasets/loader.DeviceFeeder).  -> dict(hist, hist_crf (None without --crf_post), images).  With --crf_batched the
     CRF files of a batch are written by a thread pool while the next batch runs; it is joined, and a failed write raised, before this
-    returns."""
+    returns.  `scores` (--per_image_scores: an utils/image_scores.ImageScoreLog) receives the per-image counts of both matrices behind
+    tickets, filed under `indices` - the data-set indices `feed` runs through, in its order."""
     from concurrent.futures import ThreadPoolExecutor
     from ..utils import imutils
     from ..utils.dcrf import DenseCRF
+    from ..pipeline import ScoreTicket
     nc = int(args.num_classes)
     crf = bool(args.crf_post)
     batched = crf and bool(args.crf_batched)
@@ -230,12 +236,18 @@ def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None):
                 fplan = ops.RaggedPlan([variant.fuse_size(h, w) for h, w in plan.hw], dev)
                 planes, _ = ops.seg_msc_fuse_ragged(segs, flips, fplan, want_planes=True)
                 pred = ops.seg_resize_argmax_ragged(planes, fplan, plan, nc)
+            if scores is not None:
+                rec = ([int(i) for i in indices[nimg:nimg + len(names)]], names, plan.hw)
             if not test:
                 hist = ops.confusion_accumulate(labels, pred, nc, hist)                          # :86-87, :97
+                if scores is not None:
+                    scores.defer(ScoreTicket().launch("main", labels, pred, nc, plan=plan), *rec)
             if batched:
                 lab = _crf_batch(post, images, plan, planes, fplan, nc, budget)
                 if not test:
                     hist_crf = ops.confusion_accumulate(labels, lab, nc, hist_crf)
+                    if scores is not None:
+                        scores.defer(ScoreTicket().launch("crf", labels, lab, nc, plan=plan), *rec)
                 lab_host = lab.cpu().numpy()                                                      # the batch's one device-to-host copy
             for b, name in enumerate(names):
                 H, W = int(plan.hw[b, 0]), int(plan.hw[b, 1])
@@ -249,6 +261,8 @@ def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None):
                     lab = ops.argmax_label(q[None])[0]
                     if not test:
                         hist_crf = ops.confusion_accumulate(plan.label(labels, b), lab, nc, hist_crf)
+                        if scores is not None:
+                            scores.defer(ScoreTicket().launch("crf", plan.label(labels, b)[None], lab[None], nc), rec[0][b:b + 1], [name], [(H, W)])
                     lab_np = lab.cpu().numpy()
                     _save_png(os.path.join(dirs["seg_preds"], name + ".png"), lab_np)
                     _save_png(os.path.join(dirs["seg_preds_rgb"], name + ".png"), imutils.encode_cmap(lab_np).astype(np.uint8))
@@ -296,7 +310,9 @@ def validate(args, model=None, variant=VOC):
     from ..datasets.loader import DeviceFeeder, threaded_batches
     from ..utils import evaluate
     from . import infer_lam
+    from ..utils import image_scores
     flag_defaults(args, get_parser())
+    image_scores.refuse(args, test_split=args.infer_set == "test")
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
     torch.cuda.set_device(args.local_rank)
@@ -328,7 +344,8 @@ def validate(args, model=None, variant=VOC):
             nw = infer_lam.default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", world)))
         t0 = time.time()
         feed = DeviceFeeder(threaded_batches(dataset, idx, args.batch_size, num_threads=max(nw, 1)), device)
-        out = evaluate_batches(model, feed, args, variant, test=test, dirs=dirs)
+        scores = image_scores.ImageScoreLog(int(args.num_classes), ["main"] + (["crf"] if args.crf_post else [])) if args.per_image_scores else None
+        out = evaluate_batches(model, feed, args, variant, test=test, dirs=dirs, scores=scores, indices=idx)
         torch.cuda.synchronize()
         secs = time.time() - t0
         nc = int(args.num_classes)
@@ -336,13 +353,16 @@ def validate(args, model=None, variant=VOC):
         hist_crf = out["hist_crf"]
         if args.crf_post and hist_crf is None:
             hist_crf = torch.zeros((nc, nc), dtype=torch.int64, device=device)
-        res = {"score": None, "crf_score": None, "hist": None, "hist_crf": None, "dirs": dirs, "images": out["images"], "seconds": secs}
+        res = {"score": None, "crf_score": None, "hist": None, "hist_crf": None, "dirs": dirs, "images": out["images"], "seconds": secs,
+               "image_scores": None}
         if not test:
             _, res["hist"] = infer_lam.gather_hists(hist)                                     # the one collective of the run
             res["score"] = evaluate.scores_from_hist(res["hist"])
             if args.crf_post:
                 _, res["hist_crf"] = infer_lam.gather_hists(hist_crf)
                 res["crf_score"] = evaluate.scores_from_hist(res["hist_crf"])
+            if scores is not None:                                                            # one all_gather_object, rank 0 writes
+                res["image_scores"] = image_scores.finish(scores, args, variant.class_list(), rank, what="raw_seg_score")
             if rank == 0:
                 cats = variant.class_list()
                 log.info("raw_seg_score:")

@@ -42,6 +42,36 @@ def scores(label_trues, label_preds, num_classes=21):
     return scores_from_hist(hist_from_labels(label_trues, label_preds, num_classes))
 
 
+def image_score_rows(counts):
+    """The scores of every image on its own, from ops.image_scores' counts: int [N,3,nc] = per image and class (ground-truth area,
+    predicted area, intersection) -> {"iou" [N,nc], "miou" [N], "pacc" [N], "scored" [N]} - host-side float64 like scores_from_hist.
+      iou    = inter / (gt + pred - inter), NaN where the union is 0 (the class is in neither map);
+      miou   = the mean of iou over the classes with gt area > 0 (the `valid` rule of scores_from_hist); NaN for an image without a
+               scored pixel;
+      pacc   = sum inter / sum gt area (NaN likewise);   scored = sum gt area, the number of pixels that counted (int64)."""
+    c = np.asarray(counts)
+    if c.ndim != 3 or c.shape[1] != 3:
+        raise ValueError(f"image_score_rows: counts must be [N,3,nc], got {c.shape}")
+    c = c.astype(np.float64)
+    gt, pred, inter = c[:, 0], c[:, 1], c[:, 2]
+    valid = gt > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = inter / (gt + pred - inter)
+        miou = np.where(valid, iou, 0.0).sum(1) / valid.sum(1)
+        pacc = inter.sum(1) / gt.sum(1)
+    return {"iou": iou, "miou": miou, "pacc": pacc, "scored": np.asarray(counts)[:, 0].astype(np.int64).sum(1)}
+
+
+def hist_margins(counts):
+    """counts int [N,3,nc] -> (row sums, column sums, diagonal) int64 [nc] each, summed over the images: what the confusion matrix of
+    the same pixels must show (hist.sum(1), hist.sum(0), hist.diagonal())."""
+    c = np.asarray(counts).astype(np.int64)
+    if c.ndim != 3 or c.shape[1] != 3:
+        raise ValueError(f"hist_margins: counts must be [N,3,nc], got {c.shape}")
+    s = c.sum(0)
+    return s[0], s[1], s[2]
+
+
 def multilabel_score(y_true, y_pred):
     """utils/evaluate.py:4-6 (sklearn.metrics.f1_score on one binary row) in numpy: 2 TP / (2 TP + FP + FN), 0 where that denominator
     is 0 (sklearn's zero_division default returns 0 there too)."""

@@ -486,6 +486,22 @@ int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_t* pred, in
                                       const excel_ragged_info* info, const int32_t* skip /*device [B]*/, int num_classes, int64_t* hist,
                                       void* stream);
 
+/* ------------------------------------------------------------------ per-image scores
+ * The confusion entries above add a whole step into one matrix; this one keeps what every image contributed, as the three margins of the
+ * image's own matrix - all that IoU, mIoU and pixel accuracy of one image are computed from (utils/evaluate.py, image_score_rows).
+ * Images are addressed exactly as in excel_confusion_accumulate_masked: table == NULL means B uniform images of per_image pixels each
+ * (info unused); otherwise the tight u8 maps of the ragged plan (image b at loff_b; per_image ignored, info->B == B).  A pixel of image
+ * b with ground truth g and prediction p counts only when g < nc and p < nc (the rule of the confusion kernels: a 255 in either map
+ * drops the pixel); for a counted pixel
+ *   counts[b,0,g] += 1 (ground-truth area),   counts[b,1,p] += 1 (predicted area),   counts[b,2,g] += 1 when g == p (intersection).
+ * Every element of counts is written (cleared on the stream first); the rows of an image with skip[b] != 0 stay zero (skip may be NULL).
+ * Summed over the images, rows 0 / 1 / 2 are the row sums, column sums and diagonal of excel_confusion_accumulate's matrix (with skip:
+ * of excel_confusion_accumulate_masked's), integer for integer.  1 <= num_classes <= 256, 1 <= B <= 65535, per_image in [1, 2^31): a
+ * count fits an int32.  No workspace, no host synchronisation; one kernel, the 3 * nc counters of a workgroup live in LDS. */
+int excel_image_scores(const uint8_t* gt, const uint8_t* pred, int B, long long per_image, const int32_t* table,
+                       const excel_ragged_info* info, const int32_t* skip /*device [B] or NULL*/, int num_classes,
+                       int32_t* counts /*device [B,3,num_classes]*/, void* stream);
+
 /* ------------------------------------------------------------------ image tags: the one-hot rows excel_cls_compact reads, predicted
  * Row 0 of the tower's x_raw is CLIP's own image embedding: the reference puts the class token of the original attention path back
  * before ln_post / proj (clip/clip_surgery_model.py:442-446).  The reference never tags images itself (weakly-supervised segmentation
