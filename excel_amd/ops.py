@@ -1611,6 +1611,74 @@ def image_scores(gt_u8, pred_u8, num_classes, skip=None, plan=None, out=None):
     return counts
 
 
+# ------------------------------------------------------------------ boundary scores (include/excel_hip.h, "boundary scores")
+BOUNDARY_TILE = (16, 64)            # (TH, TW) of boundary_scores_kernel: one workgroup per tile, its halo sized by the largest radius
+
+
+def boundary_max_radius():
+    """The largest radius this build's boundary_scores accepts (72: 2 % of a 3600-pixel diagonal)."""
+    return int(lib().excel_boundary_max_radius())
+
+
+def boundary_scores(gt_u8, pred_u8, num_classes, radius, skip=None, plan=None, out=None, max_radius=None):
+    """-> int32 [B,3,nc] (device): image_scores restricted to the contour bands - per image and class the valid pixels of the ground truth
+    in the ground truth's band, those of the prediction in the prediction's band, and the pixels where both agree and both bands meet
+    (Boundary IoU's counts; utils/evaluate.image_score_rows / boundary_scores_from_counts turn them into scores).  A pixel is in the
+    band of a map iff its (2d+1) x (2d+1) window leaves the image or holds another raw value.  plan=None: gt / pred are uniform [B,H,W]
+    maps; with a RaggedPlan they are its tight label maps back to back.  radius: an int (every image), a host sequence of B ints
+    (utils/image_scores.boundary_radius per image; uploaded without a wait) or a device int32 tensor [B] - then `max_radius` may bound
+    it (default: the build's maximum), and an image whose radius is < 1 or beyond the bound gets -1 in all its entries.  Host radii
+    outside [1, boundary_max_radius()] are refused here, naming the image.  skip / out as in image_scores.  One launch, no scratch
+    memory, no synchronisation."""
+    gt = gt_u8.contiguous()
+    pr = pred_u8.contiguous()
+    if gt.numel() != pr.numel():
+        raise ValueError(f"boundary_scores: gt holds {gt.numel()} pixels, pred {pr.numel()}")
+    nc = int(num_classes)
+    if not 1 <= nc <= 256:
+        raise ValueError(f"boundary_scores: num_classes = {nc} is outside [1, 256]")
+    if plan is None:
+        if gt.dim() != 3:
+            raise ValueError(f"boundary_scores: uniform maps must be [B,H,W] (gt {tuple(gt.shape)}); a ragged batch needs its plan")
+        B, H, W = (int(x) for x in gt.shape)
+        hw = lambda b: (H, W)
+    else:
+        B, H, W = plan.B, 0, 0
+        hw = lambda b: (int(plan.hw[b, 0]), int(plan.hw[b, 1]))
+        if gt.numel() != plan.total_label_pix:
+            raise ValueError(f"boundary_scores: {gt.numel()} pixels, the plan holds {plan.total_label_pix}")
+    if B < 1 or gt.numel() < 1:
+        raise ValueError(f"boundary_scores: at least one image with a pixel is needed (gt {tuple(gt.shape)})")
+    if skip is not None and skip.numel() != B:
+        raise ValueError(f"boundary_scores: skip holds {skip.numel()} flags for {B} images")
+    if out is not None and (out.numel() != B * 3 * nc or out.dtype != torch.int32):
+        raise ValueError(f"boundary_scores: out must hold {B * 3 * nc} int32 (got {out.numel()} {out.dtype})")
+    top = boundary_max_radius()
+    if isinstance(radius, torch.Tensor):
+        if radius.dtype != torch.int32 or radius.numel() != B or radius.device != gt.device:
+            raise ValueError(f"boundary_scores: a radius tensor must hold {B} int32 on {gt.device} (got {radius.numel()} {radius.dtype} on {radius.device})")
+        rad, bound = radius.contiguous(), top if max_radius is None else int(max_radius)
+    else:
+        import numpy as np
+        host = np.full(B, int(radius), np.int32) if np.ndim(radius) == 0 else np.asarray([int(r) for r in radius], np.int32)
+        if host.shape != (B,):
+            raise ValueError(f"boundary_scores: {host.size} radii for {B} images")
+        for b in np.nonzero((host < 1) | (host > top))[0]:
+            h, w = hw(int(b))
+            raise ValueError(f"boundary_scores: image {int(b)} ({h} x {w}) has radius {int(host[b])}, outside [1, {top}] "
+                             "(ops.boundary_max_radius())")
+        bound = int(host.max()) if max_radius is None or np.ndim(radius) == 0 else int(max_radius)
+        rad = None if np.ndim(radius) == 0 else torch.from_numpy(host).to(gt.device, non_blocking=True)
+    if not 1 <= bound <= top:
+        raise ValueError(f"boundary_scores: max_radius = {bound} is outside [1, {top}]")
+    counts = torch.empty((B, 3, nc), dtype=torch.int32, device=gt.device) if out is None else out.view(B, 3, nc)
+    check(lib().excel_boundary_scores(_p(gt, torch.uint8), _p(pr, torch.uint8), B, H, W,
+                                      _p(plan.table, torch.int32) if plan is not None else None,
+                                      C.byref(plan.info) if plan is not None else None, _p(rad, torch.int32), bound,
+                                      _p(skip, torch.int32), nc, _p(counts, torch.int32), _stream()), "excel_boundary_scores")
+    return counts
+
+
 # ------------------------------------------------------------------ one-time / auxiliary
 def attr_aggregate(text_features, bank, num_fg, topK=0.9):
     """text [T,C], bank [C,K] -> text_attr [C,T] (model/load_attr.py:86-119)."""

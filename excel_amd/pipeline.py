@@ -127,11 +127,22 @@ class ScoreTicket:
     def __init__(self):
         self._parts, self._event = {}, None
 
-    def launch(self, which, gts, labels, num_classes, skip=None, plan=None, out=None):
-        """ops.image_scores over (gts, labels) on the current stream, its copy to pinned memory and the event behind it -> self"""
+    def launch(self, which, gts, labels, num_classes, skip=None, plan=None, out=None, boundary=None, out_bd=None):
+        """ops.image_scores over (gts, labels) on the current stream, its copy to pinned memory and the event behind it -> self.
+        boundary = None | dict(ratio=, px=): also ops.boundary_scores on the same arrays and stream - every image's radius by the host
+        rule utils/image_scores.boundary_radius of its own size (uniform maps must then be [B,H,W]) -, filed under which + "_bd"."""
         dev = ops.image_scores(gts, labels, num_classes, skip=skip, plan=plan, out=out)
         host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=True)
         host.copy_(dev, non_blocking=True)
+        if boundary is not None:
+            from .utils.image_scores import boundary_radius, check_boundary
+            bd = check_boundary(boundary)
+            hws = plan.hw if plan is not None else [gts.shape[-2:]] * int(gts.shape[0])
+            radii = [boundary_radius(int(h), int(w), **bd) for h, w in hws]
+            dev_bd = ops.boundary_scores(gts, labels, num_classes, radii if len(set(radii)) > 1 else radii[0], skip=skip, plan=plan, out=out_bd)
+            host_bd = torch.empty(dev_bd.shape, dtype=torch.int32, pin_memory=True)
+            host_bd.copy_(dev_bd, non_blocking=True)
+            self._parts[which + "_bd"] = host_bd
         self._event = torch.cuda.Event()
         self._event.record()
         self._parts[which] = host
@@ -187,7 +198,7 @@ def check_num_classes(num_classes):
 
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -210,8 +221,15 @@ class TrainingFreePipeline:
         `image_scores` = per-image scores, off by default (False: today's step, launch for launch).  With it, every matrix run_batch /
         run_batch_ragged score (hist, hist_conf, a ValidationPipeline's hist_seg) also gets ops.image_scores on the same arrays - with the
         step's guard flags as `skip` when guard == "skip" - and the counts travel to the host behind `last_score_ticket` (a ScoreTicket:
-        counts() -> {"main": ..., "conf": ..., "seg": ...}, int32 [B,3,nc] each) - no synchronisation."""
+        counts() -> {"main": ..., "conf": ..., "seg": ...}, int32 [B,3,nc] each) - no synchronisation.
+        `boundary` = None | dict(ratio=, px=): Boundary IoU counts, off by default (no launch).  With it - it requires image_scores=True -
+        every set that gets ops.image_scores also gets ops.boundary_scores on the same arrays and stream, every image's radius from the
+        host rule utils/image_scores.boundary_radius; the rows travel in the same ticket under "<set>_bd"."""
         self.image_scores = bool(image_scores)
+        from .utils.image_scores import check_boundary
+        self.boundary = check_boundary(boundary)
+        if self.boundary is not None and not self.image_scores:
+            raise ValueError("boundary= needs image_scores=True: the boundary counts travel in the step's ScoreTicket")
         self.last_score_ticket = None
         if guard not in GUARD_MODES:
             raise ValueError(f"guard must be one of {GUARD_MODES} (got {guard!r})")
@@ -313,7 +331,8 @@ class TrainingFreePipeline:
         """image_scores set: the per-image counts of one scored matrix, added to the step's ScoreTicket (on the step's stream)."""
         B = plan.B if plan is not None else int(gts.shape[0])
         out = self._buf("image_scores_" + which, B * 3 * self.num_classes, torch.int32, gts.device)
-        self.last_score_ticket.launch(which, gts, labels, self.num_classes, skip=skip, plan=plan, out=out)
+        out_bd = self._buf("boundary_scores_" + which, B * 3 * self.num_classes, torch.int32, gts.device) if self.boundary is not None else None
+        self.last_score_ticket.launch(which, gts, labels, self.num_classes, skip=skip, plan=plan, out=out, boundary=self.boundary, out_bd=out_bd)
 
     def _no_image_scores(self, what):
         if self.image_scores:
@@ -623,7 +642,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         _refuse_tagger("OptimisedLamPipeline", tagger)
@@ -631,7 +650,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard,
-                         image_scores=image_scores)
+                         image_scores=image_scores, boundary=boundary)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -695,7 +714,7 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         _refuse_tagger("ValidationPipeline", tagger)
@@ -705,7 +724,7 @@ class ValidationPipeline(TrainingFreePipeline):
             raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
                              "histograms per step and is out of the guard's scope")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax,
-                         image_scores=image_scores)
+                         image_scores=image_scores, boundary=boundary)
         self.attn_layers = attn_layers
         self.hist_seg = None
 

@@ -9,7 +9,9 @@ the files are decoded in a thread pool, the matrix is accumulated on the device 
 and exchange their matrices once.  Without a GPU the matrix is computed with numpy (np.bincount, the arithmetic of utils/evaluate.py:9-20):
 file handling is the point of this program, not compute.  A missing prediction and a prediction whose size differs from the ground truth
 are errors that name the file.  `--per_image_scores PATH` also writes every image's own scores (utils/image_scores.py: a CSV in list
-order and PATH.npz with the per-class counts; ops.image_scores on the device, np.bincount without one).
+order and PATH.npz with the per-class counts; ops.image_scores on the device, np.bincount without one).  `--boundary_scores true` adds
+the Boundary IoU of the directory (a boundary_score table in the log, extra columns and arrays in --per_image_scores' files):
+ops.boundary_scores on the device, image_scores.boundary_counts_numpy without one.
 """
 import argparse
 import concurrent.futures as cf
@@ -36,6 +38,7 @@ def get_parser():
     p.add_argument("--batch_size", default=64, type=int, help="images decoded per device accumulation")
     from ..utils import image_scores
     image_scores.add_flags(p)
+    image_scores.add_boundary_flags(p)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -94,7 +97,8 @@ def validate(args):
         names = [x.split()[0] for x in f.read().split("\n") if x.strip()]
     idx = shard_indices(len(names), rank, world)
     mine = [names[i] for i in idx]
-    scores = image_scores.ImageScoreLog(nc) if getattr(args, "per_image_scores", None) else None
+    boundary = image_scores.boundary_of(args)
+    scores = image_scores.ImageScoreLog(nc, boundary=boundary) if image_scores.wanted(args) else None
     hist = torch.zeros((nc, nc), dtype=torch.int64, device=device)
     t0 = time.time()
     with cf.ThreadPoolExecutor(max_workers=max(1, int(args.num_workers))) as pool:
@@ -109,13 +113,16 @@ def validate(args):
                 if scores is not None:                                                           # the batch as one ragged plan, behind a ticket
                     from ..pipeline import ScoreTicket
                     hws = [p[2] for p in pairs]
-                    scores.defer(ScoreTicket().launch("main", gt_d, pred_d, nc, plan=ops.RaggedPlan(hws, device)), idx[s:s + len(pairs)],
+                    scores.defer(ScoreTicket().launch("main", gt_d, pred_d, nc, plan=ops.RaggedPlan(hws, device), boundary=boundary), idx[s:s + len(pairs)],
                                  mine[s:s + len(pairs)], hws)
             else:
                 hist += torch.from_numpy(_hist_numpy(gt, pred, nc))
                 if scores is not None:
                     for j, p in enumerate(pairs):
                         scores.put(idx[s + j], mine[s + j], p[2], "main", image_scores.counts_numpy(p[0], p[1], nc))
+                        if boundary is not None:
+                            scores.put(idx[s + j], mine[s + j], p[2], "main_bd", image_scores.boundary_counts_numpy(
+                                p[0].reshape(p[2]), p[1].reshape(p[2]), nc, image_scores.checked_radius(mine[s + j], p[2][0], p[2][1], boundary)))
     _, total = gather_hists(hist)
     total = total.cpu()
     score = evaluate.scores_from_hist(total)

@@ -69,6 +69,12 @@ Differences from the reference, all deliberate:
     loop one all_gather_object, rank 0 writes PATH (CSV, data-set order) and PATH.npz (the raw counts) and logs the image-averaged
     mIoU and the --per_image_worst 20 weakest images (utils/image_scores.py).  With --overflow_guard rerun the second pass's rows
     replace those of the flagged images (zero after the first pass).  Refused with --unlabeled true;
+  * `--boundary_scores true` (--boundary_ratio 0.02, --boundary_px 0): region IoU is dominated by object interiors, while PAR, the
+    DenseCRF stages and --conf_label all work at the contours.  With the flag every scored set (main, conf, crf) also gets
+    ops.boundary_scores - the same counts restricted to the band within 2 % of the image diagonal of each map's own contours (Boundary
+    IoU, Cheng et al., CVPR 2021) - in the same tickets; the log gets a boundary_score table per set, --json_out a `boundary` block
+    and --per_image_scores' files `radius` / `biou` columns and `bcounts_<set>` arrays.  Works with or without --per_image_scores;
+    refused with --unlabeled true; off by default (no launch, no column);
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -418,6 +424,7 @@ def get_parser():
                    help="auto: with several ranks on the node every rank pins itself (decode pool included) to its own share of the host cores")
     from ..utils import image_scores
     image_scores.add_flags(p)
+    image_scores.add_boundary_flags(p)
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
     p.set_defaults(ragged_batches=False, run_token=None, vocab=None, num_classes_given=False)      # what the program sets itself
     return p
@@ -622,7 +629,9 @@ class _CrfInline:
         self.groups, self.calls, self.peak_ws = 0, 0, 0
         self.lab = self.pool = None
         self.futures = []
-        self.image_scores = bool(getattr(args, "per_image_scores", None))     # --per_image_scores: a ScoreTicket ("crf") per call
+        from ..utils import image_scores as _scores
+        self.image_scores = _scores.wanted(args)         # --per_image_scores / --boundary_scores: a ScoreTicket ("crf") per call
+        self.boundary = _scores.boundary_of(args)
         self.last_score_ticket = None
         if args.crf_label_dir:
             self.lab = _LabelSaver(args, args.crf_label_dir)
@@ -654,7 +663,7 @@ class _CrfInline:
             self.hist = ops.confusion_accumulate(gts_packed, labels, self.nc, self.hist)    # :233
         if self.image_scores and gts_packed is not None:
             from ..pipeline import ScoreTicket
-            self.last_score_ticket = ScoreTicket().launch("crf", gts_packed, labels, self.nc, skip=skip, plan=plan)
+            self.last_score_ticket = ScoreTicket().launch("crf", gts_packed, labels, self.nc, skip=skip, plan=plan, boundary=self.boundary)
         if self.lab is not None:
             self.lab.ragged(names, plan, labels)
         if self.pool is not None:
@@ -675,7 +684,7 @@ class _CrfInline:
         self.hist = ops.confusion_accumulate(gt.to(torch.uint8), labels, self.nc, self.hist)                                  # :233
         if self.image_scores:
             from ..pipeline import ScoreTicket
-            self.last_score_ticket = ScoreTicket().launch("crf", gt.to(torch.uint8)[None], labels[None], self.nc)
+            self.last_score_ticket = ScoreTicket().launch("crf", gt.to(torch.uint8)[None], labels[None], self.nc, boundary=self.boundary)
         plan = None
         if self.lab is not None:
             self.lab.uniform([name], labels[None])
@@ -807,11 +816,11 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     tagger = resolve_tags(args, have_dataset=True)
     from ..utils import image_scores
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))
-    want_scores = bool(args.per_image_scores)
+    want_scores, boundary = image_scores.wanted(args), image_scores.boundary_of(args)
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
                   smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
-                  image_scores=want_scores)
+                  image_scores=want_scores, **({"boundary": boundary} if boundary is not None else {}))
         if args.training_free:
             pipe = TrainingFreePipeline(model, tta_scales=tta_scales, tta_flip=tta_flip, tagger=tagger, **kw)
         elif ragged:
@@ -822,6 +831,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         policy = "off"
     if want_scores and pipe is not None and not per_image and not getattr(pipe, "image_scores", False):
         raise ValueError("--per_image_scores: the supplied pipeline was built without image_scores=True")
+    if boundary is not None and pipe is not None and not per_image and getattr(pipe, "boundary", None) != boundary:
+        raise ValueError(f"--boundary_scores: the supplied pipeline was built with boundary={getattr(pipe, 'boundary', None)!r}, the flags ask for {boundary!r}")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
                   crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
@@ -832,7 +843,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
     # --per_image_scores: the rank's table of per-image counts, one set per matrix the run scores (utils/image_scores.py)
     run.scores = report["image_scores"] = image_scores.ImageScoreLog(
-        args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else [])) if want_scores else None
+        args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else []),
+        boundary=boundary) if want_scores else None
     try:
         for wanted, needs in ((args.save_cam, "--save_cam needs the decoded images"), (conf is not None, "--conf_label runs behind the ragged step"),
                               (crf_inline_wanted(args), "--crf_inline needs the decoded images")):
@@ -892,6 +904,7 @@ def _per_image_loop(run):
     cam, lab, crf, conf_lab = (run.consumers.get(k) for k in ("cam", "lab", "crf", "conf_lab"))
     from ..pipeline import ScoreTicket
     scores = run.scores
+    boundary = scores.boundary if scores is not None else None
     nimg, hist_conf = 0, None
     for s in range(0, len(indices)):
         names, imgs, gts, cls = dataset.batch(indices[s:s + 1])
@@ -935,7 +948,7 @@ def _per_image_loop(run):
                 cam.image(names[i], decoded[i], normed, cls_lst)
             hist = evaluate.hist_from_labels([gt_dev[i]], [labels[0]], args.num_classes, device, hist)
             if scores is not None:                                                          # the op with B = 1, behind a ticket: no wait here
-                scores.defer(ScoreTicket().launch("main", gt_dev[i].to(torch.uint8)[None], labels[:1].to(torch.uint8), args.num_classes), *rec)
+                scores.defer(ScoreTicket().launch("main", gt_dev[i].to(torch.uint8)[None], labels[:1].to(torch.uint8), args.num_classes, boundary=boundary), *rec)
             if lab is not None:                                                             # :95 (uint8 as hist_from_labels scores them)
                 lab.uniform([names[i]], labels[:1].to(torch.uint8))
             if conf is not None:                                                            # affutils.py:101-158 on the image's own cams
@@ -943,7 +956,7 @@ def _per_image_loop(run):
                 kept = conf_labels_image(par, inputs[i], normed, cls_lst, conf[0], conf[1])
                 hist_conf = ops.confusion_accumulate(gt_dev[i].to(torch.uint8), kept, args.num_classes, hist_conf)
                 if scores is not None:
-                    scores.defer(ScoreTicket().launch("conf", gt_dev[i].to(torch.uint8)[None], kept[None], args.num_classes), *rec)
+                    scores.defer(ScoreTicket().launch("conf", gt_dev[i].to(torch.uint8)[None], kept[None], args.num_classes, boundary=boundary), *rec)
                 conf_lab.uniform([names[i]], kept[None])
         nimg += len(imgs)
     torch.cuda.synchronize()
@@ -1430,8 +1443,15 @@ def validate(args=None, dataset=None, pipe=None):
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
                            "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1]),
                            **({"tags": _tags_json(tags, tagger)} if tags is not None else {})}, f)
-    if args.per_image_scores:                                                               # one all_gather_object, rank 0 writes
+    if image_scores.wanted(args):                                                           # one all_gather_object, rank 0 writes
         validate.last_image_scores = image_scores.finish(build_validation.last_image_scores, args, cat_list, rank, what="LAM_score")
+        if rank == 0 and args.json_out and image_scores.boundary_of(args) is not None:       # the record above gains its `boundary` block
+            import json
+            with open(args.json_out) as f:
+                record = json.load(f)
+            record["boundary"] = image_scores.boundary_json(validate.last_image_scores, image_scores.boundary_of(args))
+            with open(args.json_out, "w") as f:
+                json.dump(record, f)
     if conf is not None:
         conf_hist = build_validation.last_conf_hist
         if conf_hist is None:                                                               # a rank with an empty shard still joins the gather

@@ -24,7 +24,9 @@ Deliberate differences from the reference:
     without a `checkpoints/` component uses the checkpoint's own directory in place of the part before it;
   * --scales takes a comma-separated list ("0.7,1.0,1.2,1.5");
   * --per_image_scores PATH (not for --infer_set test): every image's own scores of the raw and, with --crf_post, the CRF labels
-    (excel_image_scores next to each confusion update, read behind tickets; utils/image_scores.py writes PATH and PATH.npz).
+    (excel_image_scores next to each confusion update, read behind tickets; utils/image_scores.py writes PATH and PATH.npz);
+  * --boundary_scores true (not for --infer_set test): the Boundary IoU of the raw and the CRF labels (excel_boundary_scores in the
+    same tickets; a boundary_score table per set, and extra columns / arrays in --per_image_scores' files).
 """
 import argparse
 import logging
@@ -114,6 +116,7 @@ def get_parser():
     p.add_argument("--crf_ws_gb", default=16.0, type=float, help="workspace budget of the batched DenseCRF stage; a batch is cut into groups that fit")
     from ..utils import image_scores
     image_scores.add_flags(p)
+    image_scores.add_boundary_flags(p)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -209,6 +212,7 @@ def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None, scor
     from ..utils.dcrf import DenseCRF
     from ..pipeline import ScoreTicket
     nc = int(args.num_classes)
+    boundary = scores.boundary if scores is not None else None
     crf = bool(args.crf_post)
     batched = crf and bool(args.crf_batched)
     budget = int(float(args.crf_ws_gb) * 2 ** 30)
@@ -241,13 +245,13 @@ def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None, scor
             if not test:
                 hist = ops.confusion_accumulate(labels, pred, nc, hist)                          # :86-87, :97
                 if scores is not None:
-                    scores.defer(ScoreTicket().launch("main", labels, pred, nc, plan=plan), *rec)
+                    scores.defer(ScoreTicket().launch("main", labels, pred, nc, plan=plan, boundary=boundary), *rec)
             if batched:
                 lab = _crf_batch(post, images, plan, planes, fplan, nc, budget)
                 if not test:
                     hist_crf = ops.confusion_accumulate(labels, lab, nc, hist_crf)
                     if scores is not None:
-                        scores.defer(ScoreTicket().launch("crf", labels, lab, nc, plan=plan), *rec)
+                        scores.defer(ScoreTicket().launch("crf", labels, lab, nc, plan=plan, boundary=boundary), *rec)
                 lab_host = lab.cpu().numpy()                                                      # the batch's one device-to-host copy
             for b, name in enumerate(names):
                 H, W = int(plan.hw[b, 0]), int(plan.hw[b, 1])
@@ -262,7 +266,7 @@ def evaluate_batches(model, feed, args, variant=VOC, test=False, dirs=None, scor
                     if not test:
                         hist_crf = ops.confusion_accumulate(plan.label(labels, b), lab, nc, hist_crf)
                         if scores is not None:
-                            scores.defer(ScoreTicket().launch("crf", plan.label(labels, b)[None], lab[None], nc), rec[0][b:b + 1], [name], [(H, W)])
+                            scores.defer(ScoreTicket().launch("crf", plan.label(labels, b)[None], lab[None], nc, boundary=boundary), rec[0][b:b + 1], [name], [(H, W)])
                     lab_np = lab.cpu().numpy()
                     _save_png(os.path.join(dirs["seg_preds"], name + ".png"), lab_np)
                     _save_png(os.path.join(dirs["seg_preds_rgb"], name + ".png"), imutils.encode_cmap(lab_np).astype(np.uint8))
@@ -344,7 +348,8 @@ def validate(args, model=None, variant=VOC):
             nw = infer_lam.default_decode_workers(int(os.environ.get("LOCAL_WORLD_SIZE", world)))
         t0 = time.time()
         feed = DeviceFeeder(threaded_batches(dataset, idx, args.batch_size, num_threads=max(nw, 1)), device)
-        scores = image_scores.ImageScoreLog(int(args.num_classes), ["main"] + (["crf"] if args.crf_post else [])) if args.per_image_scores else None
+        scores = image_scores.ImageScoreLog(int(args.num_classes), ["main"] + (["crf"] if args.crf_post else []),
+                                            boundary=image_scores.boundary_of(args)) if image_scores.wanted(args) else None
         out = evaluate_batches(model, feed, args, variant, test=test, dirs=dirs, scores=scores, indices=idx)
         torch.cuda.synchronize()
         secs = time.time() - t0

@@ -72,6 +72,19 @@ def hist_margins(counts):
     return s[0], s[1], s[2]
 
 
+def boundary_scores_from_counts(counts):
+    """Data-set Boundary IoU from ops.boundary_scores' counts: int [N,3,nc] = per image and class (ground-truth band, predicted band,
+    their intersection).  Radii differ per image, so the COUNTS are summed over the images and image_score_rows' formula is applied to
+    the sum -> {"biou" [nc] (NaN for a class with no band pixel in either map), "mbiou" (the mean over the classes with a ground-truth
+    band; NaN without one), "band_pixels" [nc] int64 (the summed ground-truth band)}."""
+    c = np.asarray(counts)
+    if c.ndim != 3 or c.shape[1] != 3:
+        raise ValueError(f"boundary_scores_from_counts: counts must be [N,3,nc], got {c.shape}")
+    s = c.astype(np.int64).sum(0)
+    rows = image_score_rows(s[None])
+    return {"biou": rows["iou"][0], "mbiou": float(rows["miou"][0]), "band_pixels": s[0]}
+
+
 def multilabel_score(y_true, y_pred):
     """utils/evaluate.py:4-6 (sklearn.metrics.f1_score on one binary row) in numpy: 2 TP / (2 TP + FP + FN), 0 where that denominator
     is 0 (sklearn's zero_division default returns 0 there too)."""

@@ -502,6 +502,27 @@ int excel_image_scores(const uint8_t* gt, const uint8_t* pred, int B, long long 
                        const excel_ragged_info* info, const int32_t* skip /*device [B] or NULL*/, int num_classes,
                        int32_t* counts /*device [B,3,num_classes]*/, void* stream);
 
+/* ------------------------------------------------------------------ boundary scores
+ * excel_image_scores restricted to the contour bands: the counts Boundary IoU (Cheng et al., CVPR 2021) is computed from.  For a map m
+ * and an integer radius d >= 1, pixel (x,y) lies in the band of m iff some position (x',y') with max(|x'-x|, |y'-y|) <= d is outside
+ * the image or holds a value m(x',y') != m(x,y) - raw values: 255 and any value >= nc are simply different.  For the binary mask
+ * m == c that is the original implementation's mask_to_boundary: mask - erode(mask), 3x3 kernel, d iterations, a one-pixel zero border.
+ * Over the pixels with g < nc and p < nc (the rule of the confusion kernels)
+ *   counts[b,0,c] = #{g == c, in the band of gt},  counts[b,1,c] = #{p == c, in the band of pred},
+ *   counts[b,2,c] = #{g == p == c, in both bands},
+ * so utils/evaluate.image_score_rows turns a row into the image's Boundary IoU per class, unchanged.  Images: table == NULL means B
+ * uniform [H,W] maps; otherwise the tight u8 maps of the ragged plan (row pitch W_b, image b at loff_b; H, W ignored, info->B == B).
+ * radius: device int32 [B], or NULL: every image uses max_radius.  The radius is the caller's (host) arithmetic - the device does none;
+ * max_radius (host) bounds every radius[b] and sizes the halo, 1 <= max_radius <= excel_boundary_max_radius() (72: 2 % of a 3600-pixel
+ * diagonal).  Every element of counts is written (cleared on the stream first); the rows of an image with skip[b] != 0 stay zero (skip
+ * may be NULL); otherwise an image with radius[b] < 1 or radius[b] > max_radius gets -1 in all 3 * nc entries - refused, never clamped.
+ * 1 <= num_classes <= 256, 1 <= B <= 65535.  One launch behind the clearing, no workspace, no host synchronisation; positions outside
+ * an image are never read, and the maps may start at any byte address. */
+int excel_boundary_scores(const uint8_t* gt, const uint8_t* pred, int B, int H, int W, const int32_t* table, const excel_ragged_info* info,
+                          const int32_t* radius /*device [B] or NULL*/, int max_radius, const int32_t* skip /*device [B] or NULL*/,
+                          int num_classes, int32_t* counts /*device [B,3,num_classes]*/, void* stream);
+int excel_boundary_max_radius(void);
+
 /* ------------------------------------------------------------------ image tags: the one-hot rows excel_cls_compact reads, predicted
  * Row 0 of the tower's x_raw is CLIP's own image embedding: the reference puts the class token of the original attention path back
  * before ln_post / proj (clip/clip_surgery_model.py:442-446).  The reference never tags images itself (weakly-supervised segmentation
