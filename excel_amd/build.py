@@ -7,13 +7,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libexcel_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16x3.hip", "gemm_w4.hip", "gemm_plan.hip", "norm.hip", "attn.hip", "attn_f32.hip", "attn_strip.hip", "attn_plan.hip", "cam.hip", "cam_plan.hip", "aff.hip", "par.hip", "par_plan.hip", "attr.hip", "tta.hip", "lvc.hip", "decoder.hip", "train.hip", "crf.hip", "aug.hip", "segeval.hip", "conf.hip", "camviz.hip", "trainviz.hip", "png.hip", "jpeg.hip", "guard.hip", "imgscore.hip", "boundary.hip", "tag.hip", "abi.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16x3.hip", "gemm_w4.hip", "gemm_plan.hip", "norm.hip", "attn.hip", "attn_f32.hip", "attn_strip.hip", "attn_plan.hip", "cam.hip", "cam_plan.hip", "aff.hip", "par.hip", "par_plan.hip", "attr.hip", "tta.hip", "lvc.hip", "decoder.hip", "train.hip", "crf.hip", "aug.hip", "segeval.hip", "conf.hip", "camviz.hip", "trainviz.hip", "png.hip", "jpeg.hip", "guard.hip", "imgscore.hip", "boundary.hip", "tag.hip", "vit.hip", "abi.hip"]
 # the translation units that depend on the 16-bit type of the split operand planes are compiled twice: bf16 (namespace excel_bf16) and,
 # with -DEXCEL_SPLIT_F16, IEEE half (namespace excel_f16, objects *_f16.o) - the "f16x3" matrix-core mode (common.h, excel_internal.h)
 SPLIT_SOURCES = ["gemm_bf16x3.hip", "gemm_w4.hip", "norm.hip", "attn.hip", "attn_strip.hip", "cam.hip"]
 # compiled for the IEEE-half split type only (object *_f16.o): the two-product GEMM for fp16-valued weights ("f16x2")
 F16_ONLY_SOURCES = ["gemm_w4x2.hip"]
-HEADERS = ["common.h", "excel_internal.h", "jet.h", "excel_split_api.inc", "gemm_w4_body.inc", "decoder_internal.h", os.path.join("..", "..", "include", "excel_hip.h")]
 # kernels that must never touch scratch memory: a spill or a dynamically indexed accumulator array inside these turns a matrix-core loop
 # into a memory loop (round 5: one `break` in an unrolled epilogue loop sent the 320x256 GEMM's accumulators to scratch, 3.5x slower,
 # all tests green).  build() reads hipcc's kernel-resource-usage remarks and refuses to link a library that violates this.
@@ -110,7 +109,6 @@ def build(force=False, verbose=True):
     force = force or os.environ.get("EXCEL_BUILD_FORCE") == "1"      # the driver-side "does it build from source" check
     flags = FLAGS + (["-DEXCEL_DEV"] if os.environ.get("EXCEL_DEV") == "1" else [])
     sid = source_id()
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     # objects built with other flags (a dev build, another compiler) are stale whatever their time stamps say
     stamp = os.path.join(CSRC, ".build_flags")
     sig = " ".join([hipcc] + flags)

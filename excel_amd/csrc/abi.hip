@@ -1,10 +1,10 @@
-// extern "C" entry points of libexcel_hip (declared in include/excel_hip.h) and the host-side ViT driver.
+// extern "C" entry points of libexcel_hip (declared in include/excel_hip.h): error text, build id, profiling hooks and the wrappers
+// around the launchers.  The ViT (excel_vit_*) is in vit.hip; launchers that depend on the split type are reached through split_api().
 #include "../../include/excel_hip.h"
 #include "common.h"
 #include "excel_internal.h"
 
 #include <stdarg.h>
-#include <map>
 #include <vector>
 
 static thread_local char g_err[512] = "";
@@ -83,41 +83,7 @@ extern "C" int excel_prof_collect(double* ms, long long* launches, double* work)
     return EXCEL_OK;
 }
 
-static GemmBfArgs gemm_bf_args(const void* A, const unsigned short* W, float* C, void* Cs, const float* bias, const float* res,
-                               int M, int N, int K, int ldc, int ldr, int act, int out_mode) {
-    GemmBfArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = (const unsigned short*)A; g.B = W; g.C = C; g.Cs = (unsigned short*)Cs; g.bias = bias; g.res = res;
-    g.M = M; g.N = N; g.K = K; g.lda = 2 * K; g.ldb = 2 * K; g.ldc = ldc; g.ldr = ldr; g.act = act; g.out_mode = out_mode;
-    return g;
-}
-
 // ------------------------------------------------------------------------------------ small helper kernels
-__global__ void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int Cc) {
-    __shared__ float t[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-    for (int k = ty; k < 32; k += 8)
-        if (r0 + k < R && c0 + tx < Cc) t[k][tx] = in[(long long)(r0 + k) * Cc + c0 + tx];
-    __syncthreads();
-    for (int k = ty; k < 32; k += 8)
-        if (c0 + k < Cc && r0 + tx < R) out[(long long)(c0 + k) * R + r0 + tx] = t[tx][k];
-}
-
-// positional grid resize, F.interpolate(bilinear, align_corners=False) on [1,D,side,side] (clip_surgery_model.py:430-433)
-__global__ void pos_resize_kernel(const float* __restrict__ pos, float* __restrict__ out, int side, int g, int D) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long total = (long long)(g * g + 1) * D;
-    if (i >= total) return;
-    const int d = (int)(i % D);
-    const int n = (int)(i / D);
-    if (n == 0) { out[i] = pos[d]; return; }
-    const int y = (n - 1) / g, x = (n - 1) % g;
-    const BilinearTap t = bilinear_tap(x, y, side, side, g, g, 0);
-    auto at = [&](int yy, int xx) { return pos[(long long)(1 + yy * side + xx) * D + d]; };
-    out[i] = bilinear_blend(t, at(t.y0, t.x0), at(t.y0, t.x1), at(t.y1, t.x0), at(t.y1, t.x1));
-}
-
 __global__ void attn_layer_mean_kernel(const float* __restrict__ attn, int B, int N, int first, int nl, float* __restrict__ out) {
     const long long P = N - 1;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -142,46 +108,42 @@ extern "C" int excel_gemm_f32(const float* A, const float* Bm, float* C, const f
     return excel_launch_gemm(g, b_kmajor != 0, batch, ST(stream));
 }
 
+// the split-plane building blocks: `mode` (the ViT's gemm_mode numbering) picks the 16-bit type of the planes
+static int split_planes(int mode, const char* name, const float* in, void* out, long long rows, int K, void* stream) {
+    EXCEL_CHECK_ARG(in && out && rows > 0 && K > 0, "%s: bad argument", name);
+    return split_api(mode).split_bf16(in, out, rows, K, ST(stream));
+}
 extern "C" int excel_split_bf16(const float* in, void* out, long long rows, int K, void* stream) {
-    EXCEL_CHECK_ARG(in && out && rows > 0 && K > 0, "split_bf16: bad argument");
-    return excel_launch_split_bf16(in, out, rows, K, ST(stream));
+    return split_planes(1, "split_bf16", in, out, rows, K, stream);
 }
-
-extern "C" int excel_gemm_bf16x3(const void* A_split, const void* W_split, float* C, const float* bias, const float* residual,
-                                 int M, int N, int K, int act, int split_out, void* stream) {
-    EXCEL_CHECK_ARG(A_split && W_split && C, "gemm_bf16x3: null argument");
-    GemmBfArgs g = gemm_bf_args(A_split, (const unsigned short*)W_split, C, C, bias, residual, M, N, K, N, N, act,
-                                split_out ? GEMM_OUT_SPLIT_BF16 : GEMM_OUT_PLAIN);
-    return excel_launch_gemm_bf16x3(g, ST(stream));
-}
-
 extern "C" int excel_split_f16(const float* in, void* out, long long rows, int K, void* stream) {
-    EXCEL_CHECK_ARG(in && out && rows > 0 && K > 0, "split_f16: bad argument");
-    return excel_f16::excel_launch_split_bf16(in, out, rows, K, ST(stream));
-}
-
-extern "C" int excel_gemm_f16x3(const void* A_split, const void* W_split, float* C, const float* bias, const float* residual,
-                                int M, int N, int K, int act, int split_out, void* stream) {
-    EXCEL_CHECK_ARG(A_split && W_split && C, "gemm_f16x3: null argument");
-    GemmBfArgs g = gemm_bf_args(A_split, (const unsigned short*)W_split, C, C, bias, residual, M, N, K, N, N, act,
-                                split_out ? GEMM_OUT_SPLIT_BF16 : GEMM_OUT_PLAIN);
-    return excel_f16::excel_launch_gemm_bf16x3(g, ST(stream));
+    return split_planes(2, "split_f16", in, out, rows, K, stream);
 }
 
 extern "C" int excel_pack_f16(const float* in, void* out, long long rows, int K, unsigned long long* inexact_dev, void* stream) {
     EXCEL_CHECK_ARG(in && out && inexact_dev && rows > 0 && K > 0, "pack_f16: bad argument");
-    return excel_f16::excel_launch_pack_hi(in, out, rows, K, inexact_dev, ST(stream));
+    return split_api(2).pack_hi(in, out, rows, K, inexact_dev, ST(stream));
 }
 
-extern "C" int excel_gemm_f16x2(const void* A_split, const void* W_split, const void* W_half, float* C, const float* bias,
-                                const float* residual, int M, int N, int K, int act, int split_out, void* stream) {
-    EXCEL_CHECK_ARG(A_split && W_split && C, "gemm_f16x2: null argument");
+static int gemm_split(int mode, const char* name, const void* A_split, const void* W_split, const void* W_half, int w_lo_zero, float* C,
+                      const float* bias, const float* residual, int M, int N, int K, int act, int split_out, void* stream) {
+    EXCEL_CHECK_ARG(A_split && W_split && C, "%s: null argument", name);
     GemmBfArgs g = gemm_bf_args(A_split, (const unsigned short*)W_split, C, C, bias, residual, M, N, K, N, N, act,
                                 split_out ? GEMM_OUT_SPLIT_BF16 : GEMM_OUT_PLAIN);
-    g.w_lo_zero = 1;
-    g.Bh = (const unsigned short*)W_half;
-    g.ldbh = K;
-    return excel_f16::excel_launch_gemm_bf16x3(g, ST(stream));
+    if (w_lo_zero) { g.w_lo_zero = 1; g.Bh = (const unsigned short*)W_half; g.ldbh = K; }
+    return split_api(mode).gemm_bf16x3(g, ST(stream));
+}
+extern "C" int excel_gemm_bf16x3(const void* A_split, const void* W_split, float* C, const float* bias, const float* residual,
+                                 int M, int N, int K, int act, int split_out, void* stream) {
+    return gemm_split(1, "gemm_bf16x3", A_split, W_split, nullptr, 0, C, bias, residual, M, N, K, act, split_out, stream);
+}
+extern "C" int excel_gemm_f16x3(const void* A_split, const void* W_split, float* C, const float* bias, const float* residual,
+                                int M, int N, int K, int act, int split_out, void* stream) {
+    return gemm_split(2, "gemm_f16x3", A_split, W_split, nullptr, 0, C, bias, residual, M, N, K, act, split_out, stream);
+}
+extern "C" int excel_gemm_f16x2(const void* A_split, const void* W_split, const void* W_half, float* C, const float* bias,
+                                const float* residual, int M, int N, int K, int act, int split_out, void* stream) {
+    return gemm_split(3, "gemm_f16x2", A_split, W_split, W_half, 1, C, bias, residual, M, N, K, act, split_out, stream);
 }
 
 extern "C" int excel_gemm_plan(int M, int N, int K, int batch, int out_mode, int has_residual, int gemm_mode, int has_half, int n_cu, int32_t* plan) {
@@ -217,254 +179,7 @@ extern "C" int excel_patch_text_cam_plan(int B, int N, int C, int T, int gemm_mo
 }
 
 extern "C" int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream) {
-    return excel_launch_layernorm(x, nullptr, 1, w, b, y, rows, D, eps, ST(stream));
-}
-
-// ------------------------------------------------------------------------------------ ViT handle
-struct SplitBlockW {
-    unsigned short *in_proj, *out_proj, *fc1, *fc2;             // split planes [N][2][K]
-    unsigned short *h_in_proj, *h_out_proj, *h_fc1, *h_fc2;     // plain half matrices [N][K] (mode 3, "f16x2"), else null
-};
-struct excel_vit {
-    excel_vit_config cfg;
-    excel_vit_weights w;
-    std::vector<excel_vit_block_weights> blocks;
-    float* projT = nullptr;             // [C, D]
-    std::map<int, float*> pos_cache;    // g -> [1+g*g, D]
-    int gemm_mode = 0;                  // 0: exact fp32 MFMA, 1: bf16x3 (split bf16, 3 MFMAs per product), 2: f16x3 (split IEEE half), 3: f16x2 (2 + fp16-valued weights)
-    int split_type = 0;                 // what the split weights hold: 0 nothing yet, 1 bf16 planes, 2 f16 planes
-    unsigned short* split_arena = nullptr;   // all split weights in one allocation
-    std::vector<SplitBlockW> sblocks;
-    unsigned short *s_conv1 = nullptr, *s_projT = nullptr;
-    // "f16x2": the weights as plain half matrices (one allocation) and whether they are all fp16-valued (-1: not examined yet)
-    unsigned short* half_arena = nullptr;
-    unsigned short *h_conv1 = nullptr, *h_projT = nullptr;
-    int fp16_exact = -1;
-};
-
-static int vit_prepare_split_weights(excel_vit* h, int type) {
-    if (h->split_arena && h->split_type == type) return EXCEL_OK;
-    const excel_vit_config& c = h->cfg;
-    const size_t D = c.width, Kc = (size_t)3 * c.patch * c.patch;
-    const size_t per_block = 3 * D * D + D * D + 4 * D * D + 4 * D * D;       // floats == split bytes / 4
-    const size_t total = per_block * c.layers + D * Kc + (size_t)c.out_dim * D;
-    float* arena = (float*)h->split_arena;
-    if (!arena) {
-        if (hipMalloc(&arena, total * sizeof(float)) != hipSuccess) {
-            excel_set_error("excel_vit: hipMalloc(split weights) failed");
-            return EXCEL_ERR_ALLOC;
-        }
-    } else if (hipDeviceSynchronize() != hipSuccess) {      // re-splitting for the other type: nothing may still read the old planes
-        excel_set_error("excel_vit: device synchronize failed");
-        return EXCEL_ERR_LAUNCH;
-    }
-    h->split_arena = (unsigned short*)arena;
-    h->split_type = 0;               // the arena holds nothing usable until every split kernel has finished (set below, after the sync)
-    float* cur = arena;
-    int put_rc = EXCEL_OK;
-    auto put = [&](const float* src, size_t rows, size_t K) -> unsigned short* {
-        unsigned short* dst = (unsigned short*)cur;
-        const int rc = type == 2 ? excel_f16::excel_launch_split_bf16(src, dst, (long long)rows, (int)K, 0)
-                                 : excel_bf16::excel_launch_split_bf16(src, dst, (long long)rows, (int)K, 0);
-        if (rc != EXCEL_OK && put_rc == EXCEL_OK) put_rc = rc;
-        cur += rows * K;
-        return dst;
-    };
-    if (h->sblocks.size() != (size_t)c.layers) h->sblocks.assign(c.layers, SplitBlockW{});
-    for (int l = 0; l < c.layers; ++l) {
-        const excel_vit_block_weights& bw = h->blocks[l];
-        h->sblocks[l].in_proj = put(bw.in_proj_w, 3 * D, D);
-        h->sblocks[l].out_proj = put(bw.out_proj_w, D, D);
-        h->sblocks[l].fc1 = put(bw.fc1_w, 4 * D, D);
-        h->sblocks[l].fc2 = put(bw.fc2_w, D, 4 * D);
-    }
-    h->s_conv1 = put(h->w.conv1_w, D, Kc);
-    h->s_projT = put(h->projT, c.out_dim, D);
-    // (one-time set-up on the legacy stream 0, which every blocking stream orders against; the device-wide sync above / this one make it
-    // safe for callers on non-blocking streams too)
-    if (put_rc != EXCEL_OK) return put_rc;
-    if (hipStreamSynchronize(0) != hipSuccess) {
-        excel_set_error("excel_vit: splitting weights failed: %s", hipGetErrorString(hipGetLastError()));
-        return EXCEL_ERR_LAUNCH;
-    }
-    h->split_type = type;            // only now: a failed re-split leaves split_type 0, so the next set_gemm_mode splits again
-    return EXCEL_OK;
-}
-
-// Packs every GEMM weight as a plain half matrix (the compact operand of the two-product GEMM) and counts the elements that are not
-// exactly representable: fp16_exact = (count == 0).  One pass, once per handle.
-static int vit_prepare_half_weights(excel_vit* h) {
-    if (h->fp16_exact >= 0) return EXCEL_OK;
-    const excel_vit_config& c = h->cfg;
-    const size_t D = c.width, Kc = (size_t)3 * c.patch * c.patch;
-    const size_t per_block = 3 * D * D + D * D + 4 * D * D + 4 * D * D;
-    const size_t total = per_block * c.layers + D * Kc + (size_t)c.out_dim * D;        // halfs
-    unsigned short* arena = nullptr;
-    unsigned long long* cnt = nullptr;
-    if (hipMalloc(&arena, total * sizeof(unsigned short) + 256) != hipSuccess) {
-        excel_set_error("excel_vit: hipMalloc(half weights) failed");
-        return EXCEL_ERR_ALLOC;
-    }
-    cnt = (unsigned long long*)((char*)arena + align_up(total * sizeof(unsigned short), 16));
-    if (hipMemsetAsync(cnt, 0, sizeof(unsigned long long), 0) != hipSuccess) { hipFree(arena); excel_set_error("excel_vit: memset failed"); return EXCEL_ERR_LAUNCH; }
-    unsigned short* cur = arena;
-    int put_rc = EXCEL_OK;
-    auto put = [&](const float* src, size_t rows, size_t K) -> unsigned short* {
-        unsigned short* dst = cur;
-        const int rc = excel_f16::excel_launch_pack_hi(src, dst, (long long)rows, (int)K, cnt, 0);
-        if (rc != EXCEL_OK && put_rc == EXCEL_OK) put_rc = rc;
-        cur += rows * K;
-        return dst;
-    };
-    if (h->sblocks.size() != (size_t)c.layers) h->sblocks.assign(c.layers, SplitBlockW{});
-    for (int l = 0; l < c.layers; ++l) {
-        const excel_vit_block_weights& bw = h->blocks[l];
-        h->sblocks[l].h_in_proj = put(bw.in_proj_w, 3 * D, D);
-        h->sblocks[l].h_out_proj = put(bw.out_proj_w, D, D);
-        h->sblocks[l].h_fc1 = put(bw.fc1_w, 4 * D, D);
-        h->sblocks[l].h_fc2 = put(bw.fc2_w, D, 4 * D);
-    }
-    h->h_conv1 = put(h->w.conv1_w, D, Kc);
-    h->h_projT = put(h->projT, c.out_dim, D);
-    unsigned long long n_bad = 1;
-    if (put_rc != EXCEL_OK || hipMemcpy(&n_bad, cnt, sizeof(n_bad), hipMemcpyDeviceToHost) != hipSuccess) {       // (synchronises)
-        for (auto& sb : h->sblocks) sb.h_in_proj = sb.h_out_proj = sb.h_fc1 = sb.h_fc2 = nullptr;
-        h->h_conv1 = h->h_projT = nullptr;
-        hipFree(arena);
-        if (put_rc != EXCEL_OK) return put_rc;
-        excel_set_error("excel_vit: packing half weights failed: %s", hipGetErrorString(hipGetLastError()));
-        return EXCEL_ERR_LAUNCH;
-    }
-    h->fp16_exact = n_bad == 0 ? 1 : 0;
-    if (h->fp16_exact) {
-        h->half_arena = arena;
-    } else {                           // full-mantissa weights: the packed matrices are of no use (the two-product mode is refused)
-        for (auto& sb : h->sblocks) sb.h_in_proj = sb.h_out_proj = sb.h_fc1 = sb.h_fc2 = nullptr;
-        h->h_conv1 = h->h_projT = nullptr;
-        hipFree(arena);
-    }
-    return EXCEL_OK;
-}
-
-extern "C" int excel_vit_weights_fp16_exact(excel_vit_t h) {
-    EXCEL_CHECK_ARG(h, "excel_vit_weights_fp16_exact: null handle");
-    if ((h->cfg.width % 32) != 0 || ((3 * h->cfg.patch * h->cfg.patch) % 32) != 0) return 0;      // no split-plane mode for this shape at all
-    TRY(vit_prepare_half_weights(h));
-    return h->fp16_exact;
-}
-
-extern "C" int excel_vit_set_gemm_mode(excel_vit_t h, int mode) {
-    EXCEL_CHECK_ARG(h && mode >= 0 && mode <= 3, "excel_vit_set_gemm_mode: mode must be 0 (f32), 1 (bf16x3), 2 (f16x3) or 3 (f16x2)");
-    if (mode >= 1) {
-        EXCEL_CHECK_ARG((h->cfg.width % 32) == 0 && ((3 * h->cfg.patch * h->cfg.patch) % 32) == 0,
-                        "the split-plane modes need width and 3*patch^2 to be multiples of 32");
-        if (mode == 3) {
-            TRY(vit_prepare_half_weights(h));
-            EXCEL_CHECK_ARG(h->fp16_exact == 1, "excel_vit_set_gemm_mode: mode 3 (f16x2) needs fp16-valued weights (excel_vit_weights_fp16_exact); use 2 (f16x3)");
-        }
-        TRY(vit_prepare_split_weights(h, mode == 3 ? 2 : mode));
-    }
-    h->gemm_mode = mode;
-    return EXCEL_OK;
-}
-extern "C" int excel_vit_get_gemm_mode(excel_vit_t h) { return h ? h->gemm_mode : -1; }
-
-
-
-extern "C" int excel_vit_create(const excel_vit_config* cfg, const excel_vit_weights* w, excel_vit_t* out) {
-    EXCEL_CHECK_ARG(cfg && w && out, "excel_vit_create: null argument");
-    EXCEL_CHECK_ARG(cfg->heads > 0 && cfg->width == cfg->heads * 64, "excel_vit_create: head_dim must be 64 (width=%d heads=%d)", cfg->width, cfg->heads);
-    EXCEL_CHECK_ARG(cfg->layers >= 1 && cfg->n_surgery >= 0 && cfg->n_surgery <= cfg->layers, "excel_vit_create: bad layer counts");
-    EXCEL_CHECK_ARG((cfg->out_dim % 4) == 0 && (cfg->patch % 4) == 0, "excel_vit_create: out_dim and patch must be multiples of 4");
-    excel_vit* h = new excel_vit();
-    h->cfg = *cfg;
-    h->w = *w;
-    h->blocks.assign(w->blocks, w->blocks + cfg->layers);
-    h->w.blocks = h->blocks.data();
-    if (hipMalloc(&h->projT, sizeof(float) * cfg->out_dim * cfg->width) != hipSuccess) {
-        delete h;
-        excel_set_error("excel_vit_create: hipMalloc failed");
-        return EXCEL_ERR_ALLOC;
-    }
-    hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(cfg->out_dim, 32), cdiv(cfg->width, 32)), dim3(256), 0, 0, w->proj, h->projT,
-                       cfg->width, cfg->out_dim);
-    if (hipStreamSynchronize(0) != hipSuccess) {
-        excel_set_error("excel_vit_create: transpose failed: %s", hipGetErrorString(hipGetLastError()));
-        hipFree(h->projT);
-        delete h;
-        return EXCEL_ERR_LAUNCH;
-    }
-    *out = h;
-    const char* mode = getenv("EXCEL_GEMM_MODE");     // default numerics of new handles: "f32" | "bf16x3" | "f16x3" | "f16x2"
-    if (mode && (!strcmp(mode, "bf16x3") || !strcmp(mode, "f16x3") || !strcmp(mode, "f16x2")) && (cfg->width % 32) == 0 && ((3 * cfg->patch * cfg->patch) % 32) == 0) {
-        int rc = excel_vit_set_gemm_mode(h, !strcmp(mode, "f16x2") ? 3 : !strcmp(mode, "f16x3") ? 2 : 1);
-        if (rc) return rc;
-    }
-    return EXCEL_OK;
-}
-
-extern "C" void excel_vit_destroy(excel_vit_t h) {
-    if (!h) return;
-    if (h->projT) hipFree(h->projT);
-    if (h->split_arena) hipFree(h->split_arena);
-    if (h->half_arena) hipFree(h->half_arena);
-    for (auto& kv : h->pos_cache) hipFree(kv.second);
-    delete h;
-}
-
-struct VitWs {
-    float *x, *xo, *y, *ao, *qkvh, *qkvs, *hbuf, *stats, *a_sum, *vt, *fraw, *ss;
-    int NP, KP;
-    size_t total;
-};
-
-static VitWs vit_ws_layout(const excel_vit_config& c, int B, int S, char* base) {
-    const int g = S / c.patch, N = g * g + 1;
-    const size_t M = (size_t)B * N, D = c.width;
-    VitWs w;
-    w.NP = (N + 3) / 4 * 4;
-    w.KP = (N + 31) / 32 * 32;            // K of the bf16x3 A_sum.V GEMM (zero padded)
-    Workspace ws(base);
-    w.x = ws.take<float>(M * D);
-    w.xo = ws.take<float>(M * D);
-    w.y = ws.take<float>(M * D);
-    w.ao = ws.take<float>(M * D);                   // also the patch-embed GEMM output [B*P, D]
-    w.qkvh = ws.take<float>(M * 3 * D);
-    w.qkvs = ws.take<float>(M * 3 * D);             // split-bf16 copy of q|k|v for the bf16x3 attention scores (bf16x3 mode)
-    {   // MLP hidden [M,4D]; also holds the im2col matrix [B*P, 3*ps*ps]
-        const size_t col = (size_t)B * (N - 1) * 3 * c.patch * c.patch;
-        w.hbuf = ws.take<float>(M * 4 * D > col ? M * 4 * D : col);
-    }
-    w.stats = ws.take<float>((size_t)B * c.heads * 4 * N * 2);
-    w.a_sum = ws.take<float>((size_t)B * N * w.KP);              // fp32 [B,N,NP] or split bf16 [B,N][2*KP]
-    w.vt = ws.take<float>((size_t)B * D * w.KP);                 // V^T split [B][D][2*KP] (bf16x3 mode)
-    w.fraw = ws.take<float>(M * c.out_dim);
-    w.ss = ws.take<float>((size_t)B * c.out_dim);
-    w.total = ws.total();
-    return w;
-}
-
-extern "C" size_t excel_vit_workspace_bytes(excel_vit_t h, int B, int S) {
-    if (!h || B <= 0 || S <= 0 || S % h->cfg.patch) return 0;
-    return vit_ws_layout(h->cfg, B, S, nullptr).total;
-}
-
-static int vit_forward_impl(excel_vit_t h, const float* img, int B, int S, void* workspace, size_t workspace_bytes,
-                            float* image_features, float* x_raw, float* w_aff, int aff_layers, float* attn_out,
-                            int n_attn_out, float* feats_out, const float* ex_attn, int flags, void* stream);
-
-extern "C" int excel_vit_forward(excel_vit_t h, const float* img, int B, int S, void* workspace, size_t workspace_bytes,
-                                 float* image_features, float* x_raw, float* w_aff, int aff_layers, float* attn_out,
-                                 int n_attn_out, float* feats_out, void* stream) {
-    return vit_forward_impl(h, img, B, S, workspace, workspace_bytes, image_features, x_raw, w_aff, aff_layers, attn_out, n_attn_out,
-                            feats_out, nullptr, 0, stream);
-}
-
-extern "C" int excel_vit_forward_ex(excel_vit_t h, const float* img, int B, int S, void* workspace, size_t workspace_bytes,
-                                    float* image_features, float* x_raw, float* w_aff, int aff_layers, float* attn_out,
-                                    int n_attn_out, float* feats_out, const float* ex_attn, int flags, void* stream) {
-    return vit_forward_impl(h, img, B, S, workspace, workspace_bytes, image_features, x_raw, w_aff, aff_layers, attn_out, n_attn_out,
-                            feats_out, ex_attn, flags, stream);
+    return excel_launch_layernorm_f32(x, w, b, y, rows, D, eps, ST(stream));
 }
 
 extern "C" size_t excel_train_losses_workspace_bytes(int B, int nc, int H, int W) { return excel_train_losses_ws_bytes(B, nc, H, W); }
@@ -524,27 +239,6 @@ extern "C" int excel_attn_select_mean(const float* attn, int Lw, int B, int N, i
     return excel_launch_attn_select_mean(attn, Lw, B, N, first_layer, n_layers, seg_attn, w_out, workspace, ST(stream));
 }
 
-#define EXCEL_VIT_FWD_ARGS excel_vit_t h, const float* img, int B, int S, void* workspace, size_t workspace_bytes, float* image_features, \
-    float* x_raw, float* w_aff, int aff_layers, float* attn_out, int n_attn_out, float* feats_out, const float* ex_attn, int flags, void* stream
-static int vit_forward_bf16(EXCEL_VIT_FWD_ARGS) {
-#include "vit_forward_body.inc"
-}
-static int vit_forward_f16(EXCEL_VIT_FWD_ARGS) {
-    // IEEE-half split planes ("f16x3"): every split-type dependent launcher of the body comes from namespace excel_f16
-    using excel_f16::excel_launch_gemm_bf16x3; using excel_f16::excel_launch_split_bf16;
-    using excel_f16::excel_launch_vt_from_planes; using excel_f16::excel_launch_layernorm; using excel_f16::excel_launch_assemble_ln_pre;
-    using excel_f16::excel_launch_token_axis_normalize; using excel_f16::excel_launch_im2col; using excel_f16::excel_launch_attn_rowpass;
-    using excel_f16::excel_launch_attn_accum; using excel_f16::excel_launch_attn_strip;
-#include "vit_forward_body.inc"
-}
-static int vit_forward_impl(EXCEL_VIT_FWD_ARGS) {
-    EXCEL_CHECK_ARG(h, "excel_vit_forward: null handle");
-    return h->gemm_mode >= 2 ? vit_forward_f16(h, img, B, S, workspace, workspace_bytes, image_features, x_raw, w_aff, aff_layers, attn_out,
-                                               n_attn_out, feats_out, ex_attn, flags, stream)
-                             : vit_forward_bf16(h, img, B, S, workspace, workspace_bytes, image_features, x_raw, w_aff, aff_layers, attn_out,
-                                                n_attn_out, feats_out, ex_attn, flags, stream);
-}
-
 // ------------------------------------------------------------------------------------ CAM
 struct CamWs { float* S; int ldT; size_t total; };         // S [B*N, ldT]: the token-text similarities, rows padded to 4 floats
 static CamWs cam_ws_layout(int B, int N, int T, void* base) {
@@ -565,7 +259,7 @@ extern "C" int excel_clip_feature_surgery(const float* image_features, const flo
     // S[b*N+n, t] = f . text[t]  -- one NT GEMM over all B*N token rows (text shared)
     GemmArgs ga = gemm_args(image_features, text, w.S, nullptr, nullptr, B * N, T, C, C, C, w.ldT, 0, GEMM_ACT_NONE);
     TRY(excel_launch_gemm(ga, true, 1, ST(stream)));
-    return excel_launch_cam_epilogue(w.S, out_full, out_slice, B, N, T, w.ldT, F, temperature, ST(stream));
+    return split_api(0).cam_epilogue(w.S, out_full, out_slice, B, N, T, w.ldT, F, temperature, ST(stream));     // fp32 in, fp32 out
 }
 
 // Fused path (cam.hip): token-axis norm + similarity on the matrix core + surgery epilogue, straight from the un-normalised token
@@ -574,10 +268,11 @@ struct PtcWs { float *sim, *part, *colsq; unsigned short* ts; size_t total; };
 static PtcWs ptc_ws_layout(int B, int N, int C, int T, char* base) {
     PtcWs w;
     Workspace ws(base);
-    w.sim = ws.take<float>(excel_patch_text_cam_ws_floats(B, N, C, T, 0));
+    const auto ws_floats = split_api(0).patch_text_cam_ws_floats;      // host arithmetic on the shape: the same for every split type
+    w.sim = ws.take<float>(ws_floats(B, N, C, T, 0));
     w.ts = ws.take<unsigned short>((size_t)T * C * 2);        // the split text bank: hi and lo planes
-    w.part = ws.take<float>(excel_patch_text_cam_ws_floats(B, N, C, T, 1));
-    w.colsq = ws.take<float>(excel_patch_text_cam_ws_floats(B, N, C, T, 2));
+    w.part = ws.take<float>(ws_floats(B, N, C, T, 1));
+    w.colsq = ws.take<float>(ws_floats(B, N, C, T, 2));
     w.total = ws.total();
     return w;
 }
@@ -590,11 +285,8 @@ extern "C" int excel_patch_text_cam(const float* x_raw, const float* text, int B
     EXCEL_CHECK_ARG(B > 0 && N > 0 && C > 0 && T > 0, "patch_text_cam: bad shape");
     const int ldT = (T + 3) / 4 * 4;
     const PtcWs w = ptc_ws_layout(B, N, C, T, (char*)workspace);
-    if (mode == 2)
-        return excel_f16::excel_launch_patch_text_cam(x_raw, text, w.ts, w.sim, w.part, w.colsq, out_full, out_slice, image_features, B, N, C, T, F,
-                                                      ldT, temperature, 1, ST(stream));
-    return excel_launch_patch_text_cam(x_raw, text, mode == 1 ? w.ts : nullptr, w.sim, w.part, w.colsq, out_full, out_slice, image_features, B, N, C,
-                                       T, F, ldT, temperature, mode, ST(stream));
+    return split_api(mode).patch_text_cam(x_raw, text, mode ? w.ts : nullptr, w.sim, w.part, w.colsq, out_full, out_slice, image_features, B, N, C,
+                                          T, F, ldT, temperature, mode ? 1 : 0, ST(stream));
 }
 
 // ------------------------------------------------------------------------------------ affinity
@@ -889,13 +581,6 @@ extern "C" int excel_bilinear_resize(const float* in, float* out, long long plan
                                      void* stream) {
     EXCEL_CHECK_ARG(in && out && planes > 0 && h > 0 && w > 0 && H > 0 && W > 0, "bilinear_resize: bad argument");
     return excel_launch_bilinear_resize(in, out, planes, h, w, H, W, align_corners, ST(stream));
-}
-
-extern "C" int excel_pos_embed_resize(const float* pos, int side, int g, int D, float* out, void* stream) {
-    EXCEL_CHECK_ARG(pos && out && side > 0 && g > 0, "pos_embed_resize: bad argument");
-    hipLaunchKernelGGL(pos_resize_kernel, dim3((unsigned)cdivl((long long)(g * g + 1) * D, 256)), dim3(256), 0, ST(stream), pos, out, side, g, D);
-    EXCEL_CHECK_LAUNCH("pos_resize");
-    return EXCEL_OK;
 }
 
 extern "C" int excel_flip_max_normalize(const float* attr, float* out, int B, int g, int F, void* stream) {

@@ -102,14 +102,14 @@ static int preln_blocks(const excel_decoder_block_weights* blocks, int n_layers,
     const int hd = E / H, M = B * P;
     for (int l = 0; l < n_layers; ++l) {
         const excel_decoder_block_weights& bw = blocks[l];
-        TRY(excel_launch_layernorm(x, nullptr, 1, bw.ln1_w, bw.ln1_b, y, M, E, 1e-5f, st));
+        TRY(excel_launch_layernorm_f32(x, bw.ln1_w, bw.ln1_b, y, M, E, 1e-5f, st));
         GemmArgs q = gemm_args(y, bw.in_proj_w, qkv, bw.in_proj_b, nullptr, M, 3 * E, E, E, E, 3 * E, 0, GEMM_ACT_NONE);
         q.out_mode = GEMM_OUT_QKV_HEADMAJOR; q.tokN = P; q.heads = H; q.hd = hd;                 // -> [B,3,H,P,hd]
         TRY(excel_launch_gemm(q, true, 1, st));
         TRY(excel_launch_dec_attention(qkv, sbuf, ao, B, P, Pp, E, H, causal, st));
         GemmArgs op = gemm_args(ao, bw.out_proj_w, x, bw.out_proj_b, x, M, E, E, E, E, E, E, GEMM_ACT_NONE);       // x += out_proj(.)
         TRY(excel_launch_gemm(op, true, 1, st));
-        TRY(excel_launch_layernorm(x, nullptr, 1, bw.ln2_w, bw.ln2_b, y, M, E, 1e-5f, st));
+        TRY(excel_launch_layernorm_f32(x, bw.ln2_w, bw.ln2_b, y, M, E, 1e-5f, st));
         GemmArgs f1 = gemm_args(y, bw.fc1_w, hb, bw.fc1_b, nullptr, M, 4 * E, E, E, E, 4 * E, 0, GEMM_ACT_QUICKGELU);
         TRY(excel_launch_gemm(f1, true, 1, st));
         GemmArgs f2 = gemm_args(hb, bw.fc2_w, x, bw.fc2_b, x, M, E, 4 * E, 4 * E, 4 * E, E, E, GEMM_ACT_NONE);      // x += mlp(ln_2(x))
@@ -274,7 +274,7 @@ extern "C" int excel_text_encode(excel_text_t h, const int32_t* tokens, int B, f
     hipLaunchKernelGGL(text_embed_kernel, dim3(M), dim3(256), 0, st, tokens, h->w.token_embedding, h->w.positional_embedding, ws.x, P, E, c.vocab_size);
     EXCEL_CHECK_LAUNCH("text/embed");                                                                                // :552-554
     TRY(preln_blocks(h->blocks.data(), c.layers, ws.x, ws.y, ws.qkv, ws.s, ws.ao, ws.hb, B, P, ws.Pp, E, c.heads, 1, st));   // :556
-    TRY(excel_launch_layernorm(ws.x, nullptr, 1, h->w.ln_final_w, h->w.ln_final_b, ws.y, M, E, 1e-5f, st));       // :558
+    TRY(excel_launch_layernorm_f32(ws.x, h->w.ln_final_w, h->w.ln_final_b, ws.y, M, E, 1e-5f, st));       // :558
     hipLaunchKernelGGL(text_eot_gather_kernel, dim3(B), dim3(64), 0, st, tokens, ws.y, ws.rows, P, E);              // :562
     EXCEL_CHECK_LAUNCH("text/eot");
     // rows [B,E] @ text_projection [E, embed_dim]   (NN GEMM)

@@ -1,4 +1,5 @@
-// Internal (C++) launch interfaces shared between the .hip translation units.
+// Internal (C++) launch interfaces shared between the .hip translation units.  The launchers built once are declared at global scope;
+// those built per 16-bit split type live in namespaces excel_bf16 / excel_f16 and are called through the SplitApi table below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -232,8 +233,36 @@ namespace excel_f16 {
 #else
 #define EXCEL_SPLIT_NS excel_bf16
 #endif
-// unqualified calls (decoder.hip, lvc.hip, train.hip, ...: exact-fp32 paths that never write split planes) mean the bf16 build
-using namespace excel_bf16;
+// Host code outside those six translation units reaches the launchers through this table alone: no using-directive makes an unqualified
+// excel_launch_* name visible, so a call that is not routed through split_api() does not compile.  The list is written once; the
+// member types and both instances are generated from it, so a slot cannot hold the other type's function.
+#define EXCEL_SPLIT_API(X, ns)                                                                                            \
+    X(ns, gemm_bf16x3, excel_launch_gemm_bf16x3) X(ns, split_bf16, excel_launch_split_bf16) X(ns, pack_hi, excel_launch_pack_hi) \
+    X(ns, vt_from_planes, excel_launch_vt_from_planes) X(ns, layernorm, excel_launch_layernorm)                           \
+    X(ns, assemble_ln_pre, excel_launch_assemble_ln_pre) X(ns, token_axis_normalize, excel_launch_token_axis_normalize)   \
+    X(ns, im2col, excel_launch_im2col) X(ns, attn_rowpass, excel_launch_attn_rowpass) X(ns, attn_accum, excel_launch_attn_accum) \
+    X(ns, attn_strip, excel_launch_attn_strip) X(ns, cam_epilogue, excel_launch_cam_epilogue)                             \
+    X(ns, patch_text_cam, excel_launch_patch_text_cam) X(ns, patch_text_cam_ws_floats, excel_patch_text_cam_ws_floats)
+#define EXCEL_SPLIT_MEMBER(ns, member, fn) decltype(&ns::fn) member;
+#define EXCEL_SPLIT_ENTRY(ns, member, fn) &ns::fn,
+struct SplitApi { EXCEL_SPLIT_API(EXCEL_SPLIT_MEMBER, excel_bf16) };      // (function pointers carry no default arguments: callers state every one)
+inline constexpr SplitApi g_split_api[2] = {{EXCEL_SPLIT_API(EXCEL_SPLIT_ENTRY, excel_bf16)}, {EXCEL_SPLIT_API(EXCEL_SPLIT_ENTRY, excel_f16)}};
+// gemm_mode 0 (exact fp32: only the fp32-output paths of the bf16 objects run) and 1 (bf16x3): bf16; 2 (f16x3) and 3 (f16x2): IEEE half
+inline const SplitApi& split_api(int gemm_mode) { return g_split_api[gemm_mode >= 2 ? 1 : 0]; }
+// LayerNorm of fp32 rows into fp32 rows (decoder, training step, excel_layernorm).  norm.hip is built per split type, but this path
+// writes no split planes and is the same code in both objects: the bf16 object's is the one that runs.
+inline int excel_launch_layernorm_f32(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, hipStream_t st) {
+    return excel_bf16::excel_launch_layernorm(x, nullptr, 1, w, b, y, rows, D, eps, st, 0, 0);
+}
+// one unbatched split-plane GEMM over dense operand rows (lda = ldb = 2K); callers set batch strides, the head-major fields and the
+// two-product fields on the result
+inline GemmBfArgs gemm_bf_args(const void* A, const unsigned short* W, float* C, void* Cs, const float* bias, const float* res,
+                               int M, int N, int K, int ldc, int ldr, int act, int out_mode) {
+    GemmBfArgs g{};
+    g.A = (const unsigned short*)A; g.B = W; g.C = C; g.Cs = (unsigned short*)Cs; g.bias = bias; g.res = res;
+    g.M = M; g.N = N; g.K = K; g.lda = 2 * K; g.ldb = 2 * K; g.ldc = ldc; g.ldr = ldr; g.act = act; g.out_mode = out_mode;
+    return g;
+}
 
 // ---------------------------------------------------------------- the bilinear sampler: every F.interpolate(mode='bilinear') site
 // One axis of ATen's area_pixel_compute_source_index: output index d of n_out -> the two source indices in [0, n_in) and the weight

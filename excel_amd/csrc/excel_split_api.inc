@@ -1,6 +1,7 @@
 // Launch interfaces of the translation units that depend on the 16-bit type of the split operand planes (gemm_bf16x3.hip, gemm_w4.hip,
 // norm.hip, attn.hip, attn_strip.hip, cam.hip).  Included twice by excel_internal.h: inside namespace excel_bf16 and inside
 // namespace excel_f16 - the six files are compiled once per type (build.py), everything in them lives in the matching namespace.
+// Code outside the six files calls these through the SplitApi table (excel_internal.h), which lists the ones it may call.
 int excel_launch_gemm_bf16x3(const GemmBfArgs& p, hipStream_t stream);
 // the four-wave kernels (gemm_w4.hip; gemm_w4x2.hip, IEEE-half split type only: two MFMAs per product for fp16-valued weights) launching a
 // GEMM_W4 / GEMM_W4_MIX plan of gemm_plan(); excel_launch_gemm_bf16x3 routes to them

@@ -551,14 +551,14 @@ extern "C" int excel_decoder_forward_train(excel_decoder_t h, const float* all_f
         float* x1 = ws.x1 + l * ME;
         float* zm = ws.zm + (size_t)l * M * 4 * E;
         float* hq = ws.hq + (size_t)l * M * 4 * E;
-        TRY(excel_launch_layernorm(xin, nullptr, 1, bw.ln1_w, bw.ln1_b, ws.dt1, M, E, 1e-5f, st));
+        TRY(excel_launch_layernorm_f32(xin, bw.ln1_w, bw.ln1_b, ws.dt1, M, E, 1e-5f, st));
         GemmArgs q = gemm_args(ws.dt1, bw.in_proj_w, qkv, bw.in_proj_b, nullptr, M, 3 * E, E, E, E, 3 * E, 0, GEMM_ACT_NONE);
         q.out_mode = GEMM_OUT_QKV_HEADMAJOR; q.tokN = P; q.heads = H; q.hd = hd;
         TRY(excel_launch_gemm(q, true, 1, st));
         TRY(excel_launch_dec_attention(qkv, pm, ao, B, P, ws.Pp, E, H, 0, st));       // pm keeps the probabilities for the backward
         GemmArgs op = gemm_args(ao, bw.out_proj_w, x1, bw.out_proj_b, xin, M, E, E, E, E, E, E, GEMM_ACT_NONE);        // x1 = xin + out_proj(ao)
         TRY(excel_launch_gemm(op, true, 1, st));
-        TRY(excel_launch_layernorm(x1, nullptr, 1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
+        TRY(excel_launch_layernorm_f32(x1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
         GemmArgs f1 = gemm_args(ws.dt1, bw.fc1_w, zm, bw.fc1_b, nullptr, M, 4 * E, E, E, E, 4 * E, 0, GEMM_ACT_NONE);
         TRY(excel_launch_gemm(f1, true, 1, st));
         TRY(tr_launch_act(zm, hq, (long long)M * 4 * E, 1, st));
@@ -641,7 +641,7 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         TRY(tr_linear_bwd(ws.dx, E, hq, 4 * E, bw.fc2_w, W(gb.fc2_w), W(gb.fc2_b), ws.dt4, 4 * E, M, E, 4 * E, ws, st));
         hipLaunchKernelGGL(tr_act_bwd_kernel, dim3((unsigned)cdivl((long long)M * 4 * E, 256)), dim3(256), 0, st, zm, ws.dt4, (long long)M * 4 * E, 1);
         // y2 = LN2(x1) recomputed (cheap) into dt1 for dW1
-        TRY(excel_launch_layernorm(x1, nullptr, 1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
+        TRY(excel_launch_layernorm_f32(x1, bw.ln2_w, bw.ln2_b, ws.dt1, M, E, 1e-5f, st));
         TRY(tr_linear_bwd(ws.dt4, 4 * E, ws.dt1, E, bw.fc1_w, W(gb.fc1_w), W(gb.fc1_b), ws.dfn, E, M, 4 * E, E, ws, st));   // dfn <- dy2
         // dx1 = dx + LN2_bwd(dy2)
         hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, x1, ws.dfn, bw.ln2_w, ws.dx, ws.dt1, ws.stat, M, E, 1e-5f);
@@ -684,7 +684,7 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
         TRY(excel_launch_gemm(gk, false, B * H, st));
         hipLaunchKernelGGL(tr_headmajor_to_rows_kernel, dim3((unsigned)cdivl((long long)M * 3 * E, 256)), dim3(256), 0, st, dqh, ws.dqkvr, B, H, P, hd);
         // y1 = LN1(xin) recomputed into dx (free now) for dW_in; dy1 -> dfn
-        TRY(excel_launch_layernorm(xin, nullptr, 1, bw.ln1_w, bw.ln1_b, ws.dx, M, E, 1e-5f, st));
+        TRY(excel_launch_layernorm_f32(xin, bw.ln1_w, bw.ln1_b, ws.dx, M, E, 1e-5f, st));
         TRY(tr_linear_bwd(ws.dqkvr, 3 * E, ws.dx, E, bw.in_proj_w, W(gb.in_proj_w), W(gb.in_proj_b), ws.dfn, E, M, 3 * E, E, ws, st));
         // dxin = dx1 + LN1_bwd(dy1) -> dx
         hipLaunchKernelGGL(tr_ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, xin, ws.dfn, bw.ln1_w, ws.dt1, ws.dx, ws.stat, M, E, 1e-5f);
