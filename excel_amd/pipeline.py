@@ -198,7 +198,7 @@ def check_num_classes(num_classes):
 
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -224,7 +224,19 @@ class TrainingFreePipeline:
         counts() -> {"main": ..., "conf": ..., "seg": ...}, int32 [B,3,nc] each) - no synchronisation.
         `boundary` = None | dict(ratio=, px=): Boundary IoU counts, off by default (no launch).  With it - it requires image_scores=True -
         every set that gets ops.image_scores also gets ops.boundary_scores on the same arrays and stream, every image's radius from the
-        host rule utils/image_scores.boundary_radius; the rows travel in the same ticket under "<set>_bd"."""
+        host rule utils/image_scores.boundary_radius; the rows travel in the same ticket under "<set>_bd".
+        `bkg_scale` = the factor on the background plane of the arg-max (utils/bkg_sweep.py), 1.0 by default (today's step, launch for
+        launch).  With another value run_batch_ragged takes its labels from bkg_sweep.sweep_ragged at that scale - PAR is linear per
+        channel, so they are the labels PAR of the scaled background would have given - and everything behind them (confusion, per-image
+        and boundary scores, what the caller saves) reads those; the conf labels and a CRF stage are built from the cams and do not change.
+        `bkg_sweep` = a tuple of scales (bkg_sweep.check_scales), None by default (no launch).  With it and ground truth, one more launch
+        per ragged step adds the step's counts at every scale into `sweep_totals` (int64 [K,3,nc]: ground-truth area, predicted area and
+        intersection per class - bkg_sweep.scores_from_totals), with the guard's flags as `skip` exactly when the confusion matrix gets
+        them.  Both are for run_batch_ragged; the uniform and multi-stream paths refuse them."""
+        from .utils import bkg_sweep as _bkg
+        self.bkg_sweep = _bkg.check_scales(bkg_sweep) if bkg_sweep is not None else None
+        self.bkg_scale = _bkg.check_scale(bkg_scale)
+        self.sweep_totals = None
         self.image_scores = bool(image_scores)
         from .utils.image_scores import check_boundary
         self.boundary = check_boundary(boundary)
@@ -263,6 +275,7 @@ class TrainingFreePipeline:
         self.drain()
         self.hist = None
         self.hist_conf = None
+        self.sweep_totals = None
 
     def _buf(self, name, numel, dtype=torch.float32, device=None):
         """Step-persistent scratch (cams, PAR output, PAR workspace): one grow-only flat buffer per (name, launch stream), so a step
@@ -339,6 +352,14 @@ class TrainingFreePipeline:
             raise ValueError(f"{what} has no per-image scores (image_scores=True): its sub-batches run on streams of their own - use "
                              "run_batch or run_batch_ragged, or build the pipeline without image_scores")
 
+    def _no_bkg(self, what):
+        if self.bkg_sweep is not None:
+            raise ValueError(f"{what} has no background sweep (bkg_sweep={self.bkg_sweep}): it runs behind the ragged step - use "
+                             "run_batch_ragged, or build the pipeline without bkg_sweep")
+        if self.bkg_scale != 1.0:
+            raise ValueError(f"{what} has no background scale (bkg_scale={self.bkg_scale}): it runs behind the ragged step - use "
+                             "run_batch_ragged, or build the pipeline with bkg_scale=1.0")
+
     def _no_guard(self, what):
         if self.guard is not None:
             raise ValueError(f"{what} has no overflow guard (guard={self.guard!r}): it is a bench / training path - use run_batch or "
@@ -414,6 +435,7 @@ class TrainingFreePipeline:
     def run_batch(self, inputs, cls_labels, gts=None, label_hw=None, return_intermediates=False):
         """inputs [B,3,S,S] f32 (normalised, already at the network size), cls_labels [B,F] f32 one-hot (ignored, and may be None, when the
         pipeline has a tagger), gts [B,H,W] uint8 (255 = ignore) or None.  Returns labels [B,H,W] uint8 (device)."""
+        self._no_bkg("run_batch")
         B, _, S, _ = inputs.shape
         g = S // 16
         H, W = (gts.shape[-2:] if gts is not None else (label_hw or (S, S)))
@@ -504,9 +526,18 @@ class TrainingFreePipeline:
         ws = self._buf("par_ws", ops.lib().excel_par_ragged_workspace_bytes(plan.total_pix, C), torch.uint8, dev)
         par_out = ops.par_forward_ragged(inputs, cams, plan, C, self.dilations, self.num_iter, nchan=nchan, ws=ws,
                                          out=None if keep else self._buf("par_out", C * plan.total_pix, device=dev))   # affutils.py:84
-        labels = ops.argmax_label_ragged(par_out, plan, C, nchan, idx)                              # affutils.py:86-87
+        if self.bkg_scale == 1.0:
+            labels = ops.argmax_label_ragged(par_out, plan, C, nchan, idx)                          # affutils.py:86-87
+        else:                                                 # the same arg-max with the background plane scaled (utils/bkg_sweep.py)
+            from .utils.bkg_sweep import sweep_ragged
+            labels = sweep_ragged(par_out, plan, C, (self.bkg_scale,), nchan=nchan, cls_idx=idx, label_sel=0)[1]
         if gts_packed is not None:
             self.hist = self._score(gts_packed, labels, flags, plan=plan)
+            if self.bkg_sweep is not None:                    # the step's counts at every scale of the sweep, from the same planes
+                from .utils.bkg_sweep import sweep_ragged
+                self.sweep_totals = sweep_ragged(par_out, plan, C, self.bkg_sweep, nchan=nchan, cls_idx=idx, gts=gts_packed,
+                                                 num_classes=self.num_classes, skip=flags if self.guard == "skip" else None,
+                                                 totals=self.sweep_totals)[0]
         if conf is None:
             if return_intermediates:
                 return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
@@ -538,6 +569,7 @@ class TrainingFreePipeline:
         self._no_tta("run_batch_split")
         self._no_tagger("run_batch_split")
         self._no_image_scores("run_batch_split")
+        self._no_bkg("run_batch_split")
         B, _, S, _ = inputs.shape
         nsplit = max(1, min(nsplit, B))
         if nsplit == 1:
@@ -584,6 +616,7 @@ class TrainingFreePipeline:
         self._no_tta("run_batch_overlapped")
         self._no_tagger("run_batch_overlapped")
         self._no_image_scores("run_batch_overlapped")
+        self._no_bkg("run_batch_overlapped")
         sa, sb = self._streams()
         cur = torch.cuda.current_stream()
         B, _, S, _ = inputs.shape
@@ -642,7 +675,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         _refuse_tagger("OptimisedLamPipeline", tagger)
@@ -650,7 +683,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard,
-                         image_scores=image_scores, boundary=boundary)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -714,7 +747,7 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         _refuse_tagger("ValidationPipeline", tagger)
@@ -724,7 +757,7 @@ class ValidationPipeline(TrainingFreePipeline):
             raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
                              "histograms per step and is out of the guard's scope")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax,
-                         image_scores=image_scores, boundary=boundary)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale)
         self.attn_layers = attn_layers
         self.hist_seg = None
 

@@ -75,6 +75,15 @@ Differences from the reference, all deliberate:
     IoU, Cheng et al., CVPR 2021) - in the same tickets; the log gets a boundary_score table per set, --json_out a `boundary` block
     and --per_image_scores' files `radius` / `biou` columns and `bcounts_<set>` arrays.  Works with or without --per_image_scores;
     refused with --unlabeled true; off by default (no launch, no column);
+  * `--bkg_sweep "0.5,0.7,0.85,1.0,1.2,1.5,2.0"` / `--bkg_scale 1.0`: the reference writes the background channel torch.pow(1 - max, 1.)
+    (utils/affutils.py:161-174) and its tools carry a --bkg_thre nothing reads; the strength of the background is the one knob of the
+    CAM-to-label step.  PAR is linear per channel, so the labels of a background scaled by `a` are `a * b0 >= F` on the PAR output the
+    step already has: with --bkg_sweep one more launch per ragged step (utils/bkg_sweep.sweep_ragged) counts the labels of every scale
+    against the ground truth, the totals are summed over the ranks once, and rank 0 logs a bkg_sweep_score table (pAcc, mIoU, background
+    IoU, foreground mIoU per scale) and the best scale; --json_out gains a `bkg_sweep` block.  --bkg_scale labels at one scale instead
+    of 1.0: scores, PNGs and per-image scores take those labels (the conf labels and the CRF stages are built from the cams and do not
+    change).  Ragged batches on the batched loop only; --bkg_sweep is refused with --unlabeled true, both with --api_path true; off by
+    default (no launch).  The exponent of that pow is not swept: it is not linear under PAR;
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -425,6 +434,8 @@ def get_parser():
     from ..utils import image_scores
     image_scores.add_flags(p)
     image_scores.add_boundary_flags(p)
+    from ..utils import bkg_sweep
+    bkg_sweep.add_flags(p)
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
     p.set_defaults(ragged_batches=False, run_token=None, vocab=None, num_classes_given=False)      # what the program sets itself
     return p
@@ -817,10 +828,16 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     from ..utils import image_scores
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))
     want_scores, boundary = image_scores.wanted(args), image_scores.boundary_of(args)
+    from ..utils import bkg_sweep
+    sweep, bkg_scale = bkg_sweep.resolve(args)
+    if (sweep is not None or bkg_scale != 1.0) and not ragged:
+        raise ValueError(f"{'--bkg_sweep' if sweep is not None else '--bkg_scale'} runs behind the ragged step: ragged batches (--data_folder or "
+                         "--ragged true) on the batched loop")
+    bkg_kw = {**({"bkg_sweep": sweep} if sweep is not None else {}), **({"bkg_scale": bkg_scale} if bkg_scale != 1.0 else {})}
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
                   smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
-                  image_scores=want_scores, **({"boundary": boundary} if boundary is not None else {}))
+                  image_scores=want_scores, **({"boundary": boundary} if boundary is not None else {}), **bkg_kw)
         if args.training_free:
             pipe = TrainingFreePipeline(model, tta_scales=tta_scales, tta_flip=tta_flip, tagger=tagger, **kw)
         elif ragged:
@@ -833,11 +850,14 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError("--per_image_scores: the supplied pipeline was built without image_scores=True")
     if boundary is not None and pipe is not None and not per_image and getattr(pipe, "boundary", None) != boundary:
         raise ValueError(f"--boundary_scores: the supplied pipeline was built with boundary={getattr(pipe, 'boundary', None)!r}, the flags ask for {boundary!r}")
+    for k, want in (("bkg_sweep", sweep), ("bkg_scale", bkg_scale)):
+        if bkg_kw and pipe is not None and getattr(pipe, k, None if k == "bkg_sweep" else 1.0) != want:
+            raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
-                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
@@ -871,6 +891,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
             build_validation.last_conf_hist = (report[k] for k in ("guard", "crf_hist", "crf_stats", "cam_stats", "conf_hist"))
         build_validation.last_tags = report["tags"]
         build_validation.last_image_scores = report["image_scores"]
+        build_validation.last_bkg_sweep = report["bkg_sweep"]
     return out
 
 
@@ -982,6 +1003,8 @@ def _batched_loop(run):
     pipe.hist = run.hist
     if conf is not None:
         pipe.hist_conf = torch.zeros_like(run.hist)
+    if run.sweep is not None:                                # --bkg_sweep: the pipeline adds every step's counts per scale (both passes of the guard)
+        pipe.sweep_totals = torch.zeros((len(run.sweep), 3, args.num_classes), dtype=torch.int64, device=device)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
         from ..datasets.loader import DeviceFeeder, ragged_batches, threaded_batches
@@ -1155,6 +1178,8 @@ def _batched_loop(run):
         torch.cuda.synchronize()
     if conf is not None:
         run.report["conf_hist"] = pipe.hist_conf
+    if run.sweep is not None:
+        run.report["bkg_sweep"] = pipe.sweep_totals
     if scores is not None:
         scores.poll(True)
     if tagger is not None:
@@ -1316,9 +1341,10 @@ def validate(args=None, dataset=None, pipe=None):
     flag_defaults(args)
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
-    validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = None
-    from ..utils import image_scores
+    validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = None
+    from ..utils import bkg_sweep, image_scores
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))                                # ... and per-image scores of nothing
+    sweep, _ = bkg_sweep.resolve(args)                                                       # ... and a sweep nobody can score or run
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
@@ -1392,6 +1418,11 @@ def validate(args=None, dataset=None, pipe=None):
     per_rank, total = gather_hists(hist)
     validate.last_per_rank = per_rank
     score = None if args.unlabeled else evaluate.scores_from_hist(total)                    # (no ground truth: nothing to score)
+    if sweep is not None:
+        # --bkg_sweep: the ranks' totals summed once, like the matrix (a flagged image is in them once: skipped, then counted in fp32)
+        _, sweep_total = gather_hists(build_validation.last_bkg_sweep)
+        sweep_scores = bkg_sweep.scores_from_totals(sweep_total)
+        validate.last_bkg_sweep = dict(scales=sweep, totals=sweep_total, scores=sweep_scores, best_scale=bkg_sweep.best_scale(sweep_scores, sweep)[1])
     tags = None
     if tagger is not None:
         # the predicted rows of every rank, once: every rank joins, also one whose shard is empty
@@ -1421,6 +1452,11 @@ def validate(args=None, dataset=None, pipe=None):
             logging.info(f"mIoU {score['miou'] * 100:.3f}  images {int(nimg) * world}  ({nimg / secs:.1f} img/s/rank)")
         else:
             logging.info(f"--unlabeled true: no ground truth, nothing scored  images {int(nimg) * world}  ({nimg / secs:.1f} img/s/rank)")
+        if sweep is not None:
+            logging.info("bkg_sweep_score:")
+            logging.info("\n" + bkg_sweep.format_sweep_table(sweep_scores, sweep, cat_list))
+            jb, sb = bkg_sweep.best_scale(sweep_scores, sweep)
+            logging.info(f"bkg_sweep best scale {sb:g}: mIoU {sweep_scores[jb]['miou'] * 100:.3f} (labels written and scored at --bkg_scale {args.bkg_scale:g})")
         if tags is not None:
             logging.info(f"tags (--tags clip, thre {tagger['thre']}, at most {tagger['kmax']}, scale {tagger['scale']}): {tags['images']} images, "
                          f"tags per image {dict((k, v) for k, v in enumerate(tags['tags_per_image']) if v)}"
@@ -1442,7 +1478,8 @@ def validate(args=None, dataset=None, pipe=None):
                            "hist_total": [[int(v) for v in row] for row in total.cpu().tolist()],       # the gathered confusion matrix itself
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
                            "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1]),
-                           **({"tags": _tags_json(tags, tagger)} if tags is not None else {})}, f)
+                           **({"tags": _tags_json(tags, tagger)} if tags is not None else {}),
+                           **({"bkg_sweep": bkg_sweep.sweep_json(sweep_scores, sweep)} if sweep is not None else {})}, f)
     if image_scores.wanted(args):                                                           # one all_gather_object, rank 0 writes
         validate.last_image_scores = image_scores.finish(build_validation.last_image_scores, args, cat_list, rank, what="LAM_score")
         if rank == 0 and args.json_out and image_scores.boundary_of(args) is not None:       # the record above gains its `boundary` block

@@ -523,6 +523,36 @@ int excel_boundary_scores(const uint8_t* gt, const uint8_t* pred, int B, int H, 
                           int num_classes, int32_t* counts /*device [B,3,num_classes]*/, void* stream);
 int excel_boundary_max_radius(void);
 
+/* ------------------------------------------------------------------ background-scale sweep
+ * The pseudo labels are excel_argmax_label_ragged of PAR's output, whose plane 0 is the background 1 - max_c cam_c (utils/affutils.py:
+ * 161-174: torch.pow(1 - max, 1.)).  PAR is linear per channel, PAR(a * bkg) = a * PAR(bkg), so the labels of a background scaled by
+ * `a` are a second compare on the SAME planes - no second PAR pass.  This entry scores K such scales against the ground truth in one
+ * pass over the planes, without a label map per scale, and / or writes the label map of one of them.
+ *   planes = PAR's output, Cmax pitched planes per image in the layout of excel_argmax_label_ragged (table, info, nchan, cls_idx, Smax
+ *   and Cmax as there; with cls_idx, Smax >= Cmax - 1);  gt = the tight u8 ground truth (image b at loff_b), NULL when totals is NULL.
+ * For pixel (x,y) of image b, x < W_b:  nch = nchan ? min(nchan[b], Cmax) : Cmax;  b0 = plane 0;  F = the maximum of planes 1..nch-1;
+ * ci = the first plane index that attains F;
+ *   key_j = (nch == 1 || scales[j] * b0 >= F) ? 0 : (cls_idx ? cls_idx[b*Smax + ci-1] + 1 : ci)        for j = 0..K-1
+ * - one fp32 multiply (round to nearest, nothing fused into it) and one compare.  With scales[j] == 1.0f key_j is the label
+ * excel_argmax_label_ragged writes, on finite planes: the background wins a tie, the first foreground maximum wins.  Pad columns
+ * (W_b <= x < Wp_b) and planes c >= nch are never read.
+ *   totals (device int64 [K,3,num_classes], or NULL): a pixel counts for scale j iff (skip == NULL || skip[b] == 0), g = gt < num_classes
+ *   and key_j < num_classes (the rule of the confusion kernels); then
+ *     totals[j,0,g] += 1,   totals[j,1,key_j] += 1,   totals[j,2,g] += 1 when g == key_j
+ *   - the row sums, column sums and diagonal of the [nc,nc] confusion matrix of the labels at scale j, in the row layout of
+ *   excel_image_scores (utils/evaluate.image_score_rows reads them).  totals is ADDED to, like `hist`, across calls: the caller clears it.
+ *   labels_u8 (device, tight, info->total_label_pix bytes, or NULL): key_{label_sel} of every pixel, whatever skip says.
+ * scales: HOST array of K floats, copied into the kernel arguments (no upload, no host synchronisation); any order - the result does not
+ * depend on it or on the sign of b0; increasing scales on b0 >= 0 are the fast case (bkgsweep.hip).
+ * EXCEL_ERR_ARG with a message for: null planes, table or info; neither totals nor labels_u8; totals without gt; K outside 1..16; a scale
+ * that is not finite or < 0; label_sel outside [0, K) when labels_u8 is given; num_classes outside 1..256; totals not 8-byte or planes
+ * not 16-byte aligned.  One launch on `stream`, no workspace, no scratch memory. */
+int excel_bkg_sweep_ragged(const float* planes, const int32_t* nchan /*device [B] or NULL*/, const int32_t* cls_idx /*device [B,Smax] or NULL*/,
+                           const uint8_t* gt, const int32_t* table, const excel_ragged_info* info, int Smax, int Cmax,
+                           const float* scales /*HOST [K]*/, int K, const int32_t* skip /*device [B] or NULL*/, int num_classes,
+                           int64_t* totals /*device [K,3,num_classes], ADDED to, or NULL*/, int label_sel,
+                           uint8_t* labels_u8 /*device, tight, or NULL*/, void* stream);
+
 /* ------------------------------------------------------------------ image tags: the one-hot rows excel_cls_compact reads, predicted
  * Row 0 of the tower's x_raw is CLIP's own image embedding: the reference puts the class token of the original attention path back
  * before ln_post / proj (clip/clip_surgery_model.py:442-446).  The reference never tags images itself (weakly-supervised segmentation
