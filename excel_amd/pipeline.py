@@ -121,7 +121,7 @@ class TagTicket:
 
 class ScoreTicket:
     """The per-image score counts of one step on their way to the host (the GuardTicket pattern): per matrix the step scored - "main"
-    (self.hist), "conf" (self.hist_conf), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
+    (self.hist), "conf" (self.hist_conf), "clean" (self.hist_clean), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
     event recorded behind the last copy on the step's stream.  ready() never blocks; counts() waits for the event."""
 
     def __init__(self):
@@ -196,9 +196,21 @@ def check_num_classes(num_classes):
                          f"{MAX_NUM_CLASSES} classes (254 foreground + background) fit")
 
 
+def _check_clean(clean):
+    """clean= of the pipelines -> dict(min_region=, connectivity=) checked by utils/components.py, or None."""
+    if clean is None:
+        return None
+    from .utils import components as cc
+    if not isinstance(clean, dict) or "min_region" not in clean or set(clean) - {"min_region", "connectivity"}:
+        raise ValueError(f"clean must be dict(min_region=, connectivity=8) (got {clean!r})")
+    cc.min_area_rule(clean["min_region"], 1, 1)
+    v = clean["min_region"]
+    return dict(min_region=int(v) if v >= 1 else float(v), connectivity=cc.check_connectivity(clean.get("connectivity", 8)))
+
+
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -232,7 +244,17 @@ class TrainingFreePipeline:
         `bkg_sweep` = a tuple of scales (bkg_sweep.check_scales), None by default (no launch).  With it and ground truth, one more launch
         per ragged step adds the step's counts at every scale into `sweep_totals` (int64 [K,3,nc]: ground-truth area, predicted area and
         intersection per class - bkg_sweep.scores_from_totals), with the guard's flags as `skip` exactly when the confusion matrix gets
-        them.  Both are for run_batch_ragged; the uniform and multi-stream paths refuse them."""
+        them.  Both are for run_batch_ragged; the uniform and multi-stream paths refuse them.
+        `clean` = dict(min_region=, connectivity=8) (utils/components.py), None by default (no launch).  With it run_batch_ragged labels
+        the connected regions of the step's main label map - whatever bkg_scale produced it - and turns every class region below
+        min_region (pixels, or a fraction of each image's area: components.min_area_rule) into 255: the cleaned maps stay in
+        `last_clean_labels` (flat uint8 like the labels) and the per-image counts (regions, regions removed, pixels removed) in
+        `last_clean_counts` (int32 [B,3]) on the device until the next step; with ground truth the kept pixels go into `hist_clean`,
+        and with image_scores the step's ScoreTicket gets a set named "clean".  The returned labels are untouched; the uniform and
+        multi-stream paths refuse the option."""
+        self.clean = _check_clean(clean)
+        self.hist_clean = None
+        self.last_clean_labels = self.last_clean_counts = None
         from .utils import bkg_sweep as _bkg
         self.bkg_sweep = _bkg.check_scales(bkg_sweep) if bkg_sweep is not None else None
         self.bkg_scale = _bkg.check_scale(bkg_scale)
@@ -275,6 +297,7 @@ class TrainingFreePipeline:
         self.drain()
         self.hist = None
         self.hist_conf = None
+        self.hist_clean = None
         self.sweep_totals = None
 
     def _buf(self, name, numel, dtype=torch.float32, device=None):
@@ -335,7 +358,7 @@ class TrainingFreePipeline:
         """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
         hist = getattr(self, into)
         if self.image_scores:
-            self._image_scores({"hist": "main", "hist_conf": "conf"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
+            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
         if self.guard == "skip":
             return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, hist, plan=plan)
         return ops.confusion_accumulate(gts, labels, self.num_classes, hist)                       # evaluate.py:9-20
@@ -359,6 +382,31 @@ class TrainingFreePipeline:
         if self.bkg_scale != 1.0:
             raise ValueError(f"{what} has no background scale (bkg_scale={self.bkg_scale}): it runs behind the ragged step - use "
                              "run_batch_ragged, or build the pipeline with bkg_scale=1.0")
+
+    def _no_clean(self, what):
+        if self.clean is not None:
+            raise ValueError(f"{what} has no label cleaning (clean={self.clean}): it runs behind the ragged step - use run_batch_ragged, "
+                             "or build the pipeline without clean")
+
+    def _clean(self, labels, plan, gts_packed, flags):
+        """clean set: label the step's main map, filter it, score the kept pixels (all on the step's stream, no synchronisation)."""
+        from .utils import components as cc
+        dev = labels.device
+        value = self.clean["min_region"]
+        if value >= 1:
+            thr = int(value)
+        else:                                                 # a fraction of every image's own area: host integers, cached on the plan
+            cache = plan.__dict__.setdefault("_clean_thr", {})
+            thr = cache.get(value)
+            if thr is None:
+                host = [cc.min_area_rule(value, int(h), int(w)) for h, w in plan.hw]
+                thr = cache[value] = torch.tensor(host, dtype=torch.int32).to(dev, non_blocking=True)
+        n = plan.total_label_pix
+        comp, area = cc.label_components(labels, plan=plan, connectivity=self.clean["connectivity"],
+                                         out=(self._buf("cc_comp", n, torch.int32, dev), self._buf("cc_area", n, torch.int32, dev)))
+        self.last_clean_labels, self.last_clean_counts = cc.filter_small_regions(labels, comp, area, thr, self.num_classes, plan=plan)
+        if gts_packed is not None:
+            self.hist_clean = self._score(gts_packed, self.last_clean_labels, flags, plan=plan, into="hist_clean")
 
     def _no_guard(self, what):
         if self.guard is not None:
@@ -436,6 +484,7 @@ class TrainingFreePipeline:
         """inputs [B,3,S,S] f32 (normalised, already at the network size), cls_labels [B,F] f32 one-hot (ignored, and may be None, when the
         pipeline has a tagger), gts [B,H,W] uint8 (255 = ignore) or None.  Returns labels [B,H,W] uint8 (device)."""
         self._no_bkg("run_batch")
+        self._no_clean("run_batch")
         B, _, S, _ = inputs.shape
         g = S // 16
         H, W = (gts.shape[-2:] if gts is not None else (label_hw or (S, S)))
@@ -538,6 +587,8 @@ class TrainingFreePipeline:
                 self.sweep_totals = sweep_ragged(par_out, plan, C, self.bkg_sweep, nchan=nchan, cls_idx=idx, gts=gts_packed,
                                                  num_classes=self.num_classes, skip=flags if self.guard == "skip" else None,
                                                  totals=self.sweep_totals)[0]
+        if self.clean is not None:
+            self._clean(labels, plan, gts_packed, flags)
         if conf is None:
             if return_intermediates:
                 return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
@@ -570,6 +621,7 @@ class TrainingFreePipeline:
         self._no_tagger("run_batch_split")
         self._no_image_scores("run_batch_split")
         self._no_bkg("run_batch_split")
+        self._no_clean("run_batch_split")
         B, _, S, _ = inputs.shape
         nsplit = max(1, min(nsplit, B))
         if nsplit == 1:
@@ -617,6 +669,7 @@ class TrainingFreePipeline:
         self._no_tagger("run_batch_overlapped")
         self._no_image_scores("run_batch_overlapped")
         self._no_bkg("run_batch_overlapped")
+        self._no_clean("run_batch_overlapped")
         sa, sb = self._streams()
         cur = torch.cuda.current_stream()
         B, _, S, _ = inputs.shape
@@ -675,7 +728,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         _refuse_tagger("OptimisedLamPipeline", tagger)
@@ -683,7 +736,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -747,7 +800,7 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         _refuse_tagger("ValidationPipeline", tagger)
@@ -757,7 +810,7 @@ class ValidationPipeline(TrainingFreePipeline):
             raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
                              "histograms per step and is out of the guard's scope")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean)
         self.attn_layers = attn_layers
         self.hist_seg = None
 

@@ -11,7 +11,11 @@ file handling is the point of this program, not compute.  A missing prediction a
 are errors that name the file.  `--per_image_scores PATH` also writes every image's own scores (utils/image_scores.py: a CSV in list
 order and PATH.npz with the per-class counts; ops.image_scores on the device, np.bincount without one).  `--boundary_scores true` adds
 the Boundary IoU of the directory (a boundary_score table in the log, extra columns and arrays in --per_image_scores' files):
-ops.boundary_scores on the device, image_scores.boundary_counts_numpy without one.
+ops.boundary_scores on the device, image_scores.boundary_counts_numpy without one.  `--clean_min_region VALUE` (with --clean_connectivity
+8|4) cleans the maps of --pred_dir first - every connected class region below VALUE (pixels, or a fraction of the image area) becomes 255:
+utils/components.label_components + filter_small_regions on the device, components.clean_numpy without one -, scores the cleaned maps as
+a second table (clean_label_score, with the coverage and the region counts) and, with `--clean_label_dir DIR`, writes them there as
+palette PNGs.  The first table is unchanged.  This is the route for CRF labels and for labels from elsewhere.
 """
 import argparse
 import concurrent.futures as cf
@@ -39,6 +43,8 @@ def get_parser():
     from ..utils import image_scores
     image_scores.add_flags(p)
     image_scores.add_boundary_flags(p)
+    from ..utils import components
+    components.add_flags(p)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -65,6 +71,15 @@ def _load_pair(args, name):
     return np.ascontiguousarray(gt, np.uint8).reshape(-1), np.ascontiguousarray(pred, np.uint8).reshape(-1), gt.shape
 
 
+def _save_index_png(path, label):
+    """One [H,W] uint8 map as a palette PNG (the VOC colour map; index 255 is the ignore colour)."""
+    from PIL import Image
+    from ..utils.imutils import colormap
+    im = Image.fromarray(np.ascontiguousarray(label, np.uint8))          # mode L; the palette makes it P with the same indices
+    im.putpalette(np.asarray(colormap(256), np.uint8).reshape(-1).tolist())
+    im.save(path)
+
+
 def _hist_numpy(gt, pred, nc):
     """_fast_hist (utils/evaluate.py:9-20): rows = ground truth, columns = prediction, labels >= nc (255 = ignore) dropped."""
     gt, pred = gt.astype(np.int64), pred.astype(np.int64)
@@ -75,8 +90,9 @@ def _hist_numpy(gt, pred, nc):
 def validate(args):
     """-> {"score": scores_from_hist of the gathered matrix, "hist": [nc,nc] int64 (CPU tensor), "images": scored on this rank,
     "seconds"}: the layout of infer_seg_voc.validate (+ "image_scores" with --per_image_scores)."""
-    from ..utils import evaluate, image_scores
+    from ..utils import components, evaluate, image_scores
     image_scores.refuse(args)
+    clean = components.resolve(args, program="eval_labels")
     names_fg = None
     if getattr(args, "class_names", None):
         from .infer_lam import _read_names
@@ -100,6 +116,9 @@ def validate(args):
     boundary = image_scores.boundary_of(args)
     scores = image_scores.ImageScoreLog(nc, boundary=boundary) if image_scores.wanted(args) else None
     hist = torch.zeros((nc, nc), dtype=torch.int64, device=device)
+    hist_clean, clean_rows = (torch.zeros_like(hist) if clean is not None else None), []
+    if clean is not None and clean["label_dir"]:
+        os.makedirs(clean["label_dir"], exist_ok=True)
     t0 = time.time()
     with cf.ThreadPoolExecutor(max_workers=max(1, int(args.num_workers))) as pool:
         for s in range(0, len(mine), args.batch_size):
@@ -123,6 +142,26 @@ def validate(args):
                         if boundary is not None:
                             scores.put(idx[s + j], mine[s + j], p[2], "main_bd", image_scores.boundary_counts_numpy(
                                 p[0].reshape(p[2]), p[1].reshape(p[2]), nc, image_scores.checked_radius(mine[s + j], p[2][0], p[2][1], boundary)))
+            if clean is not None:                                # the cleaned maps of the batch: scored into a matrix of their own, written
+                hws = [p[2] for p in pairs]
+                thr = [components.min_area_rule(clean["min_region"], h, w) for h, w in hws]
+                if on_gpu:
+                    plan = ops.RaggedPlan(hws, device)
+                    comp, area = components.label_components(pred_d, plan=plan, connectivity=clean["connectivity"])
+                    cleaned_d, counts_d = components.filter_small_regions(pred_d, comp, area, thr, nc, plan=plan)
+                    hist_clean = ops.confusion_accumulate(gt_d, cleaned_d, nc, hist_clean)
+                    cleaned, counts = cleaned_d.cpu().numpy(), counts_d.cpu().numpy()
+                else:
+                    done = [components.clean_numpy(p[1].reshape(p[2]), t, nc, clean["connectivity"]) for p, t in zip(pairs, thr)]
+                    cleaned = np.concatenate([d[0].reshape(-1) for d in done])
+                    counts = np.stack([d[1] for d in done])
+                    hist_clean += torch.from_numpy(_hist_numpy(gt, cleaned, nc))
+                clean_rows.extend(np.asarray(counts, np.int64).reshape(-1, 3).tolist())
+                if clean["label_dir"]:
+                    off = 0
+                    for n, (h, w) in zip(mine[s:s + len(pairs)], hws):
+                        _save_index_png(os.path.join(clean["label_dir"], n + ".png"), cleaned[off:off + h * w].reshape(h, w))
+                        off += h * w
     _, total = gather_hists(hist)
     total = total.cpu()
     score = evaluate.scores_from_hist(total)
@@ -140,6 +179,23 @@ def validate(args):
         logging.info("\n" + format_scores_table(score, cats))
         logging.info(f"mIoU {score['miou'] * 100:.3f}  images {len(names)}  ({len(mine) / max(secs, 1e-9):.1f} img/s/rank)")
     out = {"score": score, "hist": total, "images": len(mine), "seconds": secs}
+    if clean is not None:
+        _, clean_total = gather_hists(hist_clean)
+        clean_total = clean_total.cpu()
+        parts = [clean_rows]
+        if world > 1:
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, clean_rows)
+        counts = np.asarray([r for part in parts for r in part], np.int64).reshape(-1, 3)
+        out["clean"] = dict(score=evaluate.scores_from_hist(clean_total), hist=clean_total, coverage=components.coverage(clean_total, total),
+                            counts=counts, stats=components.region_stats(counts), min_region=clean["min_region"],
+                            connectivity=clean["connectivity"])
+        if rank == 0:
+            logging.info(f"clean_label_score of {args.pred_dir} (--clean_min_region {clean['min_region']:g}, connectivity {clean['connectivity']}):")
+            logging.info("\n" + format_scores_table(out["clean"]["score"], cats))
+            logging.info(components.format_clean_summary(out["clean"]["stats"], out["clean"]["coverage"]))
+            if clean["label_dir"]:
+                logging.info(f"cleaned label maps -> {clean['label_dir']}")
     if scores is not None:
         out["image_scores"] = merged                           # the merged table (utils/image_scores.ImageScoreLog.merged)
     return out

@@ -84,6 +84,16 @@ Differences from the reference, all deliberate:
     of 1.0: scores, PNGs and per-image scores take those labels (the conf labels and the CRF stages are built from the cams and do not
     change).  Ragged batches on the batched loop only; --bkg_sweep is refused with --unlabeled true, both with --api_path true; off by
     default (no launch).  The exponent of that pow is not swept: it is not linear under PAR;
+  * `--clean_min_region VALUE` (`--clean_connectivity 8|4`, `--clean_label_dir DIR`): the arg-max leaves islands of a few pixels and
+    pin-holes; the reference has no remedy.  Behind the arg-max of every ragged step, utils/components.label_components labels the
+    connected regions of the step's main label map (equal raw value, 8- or 4-neighbours) and filter_small_regions turns every class
+    region below VALUE - pixels, or with 0 < VALUE < 1 a fraction of the image's own area - into 255.  The cleaned maps go to
+    `<clean_label_dir>/<name>.png` through the device encoder, their kept pixels into a second device-side confusion matrix: the log
+    gains a clean_label_score table, the coverage (kept over labelled pixels) and the regions / regions removed per image, --json_out a
+    `clean` block, --per_image_scores the clean_* columns plus regions, regions_removed and pixels_removed.  The main labels, scores and
+    PNGs are untouched.  Ragged batches on the batched loop only (refused with --api_path true); with --unlabeled true nothing is
+    scored and --clean_label_dir is required; off by default (no launch, no key, no column).  The conf and crf label sets are not
+    cleaned here: their PNGs can go through eval_labels --clean_min_region;
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -178,7 +188,7 @@ def resolve_tags(args, have_dataset=False):
             raise ValueError("--unlabeled true has no ground truth to score: --crf_post scores the DenseCRF labels against it - drop one of the two")
         if args.api_path:
             raise ValueError("--unlabeled true runs on the batched loop: --api_path true scores every image against its ground truth")
-        if not (args.save_label or args.conf_label or args.save_tags):
+        if not (args.save_label or args.conf_label or args.save_tags or getattr(args, "clean_label_dir", None)):
             raise ValueError("--unlabeled true scores nothing, so the run must write something: give at least one of --save_label true, "
                              "--conf_label true, --save_tags PATH")
     if args.save_tags and args.tags != "clip":
@@ -436,6 +446,8 @@ def get_parser():
     image_scores.add_boundary_flags(p)
     from ..utils import bkg_sweep
     bkg_sweep.add_flags(p)
+    from ..utils import components
+    components.add_flags(p)
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
     p.set_defaults(ragged_batches=False, run_token=None, vocab=None, num_classes_given=False)      # what the program sets itself
     return p
@@ -834,6 +846,13 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError(f"{'--bkg_sweep' if sweep is not None else '--bkg_scale'} runs behind the ragged step: ragged batches (--data_folder or "
                          "--ragged true) on the batched loop")
     bkg_kw = {**({"bkg_sweep": sweep} if sweep is not None else {}), **({"bkg_scale": bkg_scale} if bkg_scale != 1.0 else {})}
+    from ..utils import components
+    clean = components.resolve(args)
+    if clean is not None and not ragged:
+        raise ValueError("--clean_min_region runs behind the ragged step: ragged batches (--data_folder or --ragged true) on the batched loop")
+    clean_kw = dict(min_region=clean["min_region"], connectivity=clean["connectivity"]) if clean is not None else None
+    if clean is not None:
+        bkg_kw = {**bkg_kw, "clean": clean_kw}
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
                   smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
@@ -850,21 +869,24 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError("--per_image_scores: the supplied pipeline was built without image_scores=True")
     if boundary is not None and pipe is not None and not per_image and getattr(pipe, "boundary", None) != boundary:
         raise ValueError(f"--boundary_scores: the supplied pipeline was built with boundary={getattr(pipe, 'boundary', None)!r}, the flags ask for {boundary!r}")
+    if clean is not None and pipe is not None and getattr(pipe, "clean", None) != clean_kw:
+        raise ValueError(f"--clean_min_region: the supplied pipeline was built with clean={getattr(pipe, 'clean', None)!r}, the flags ask for {clean_kw!r}")
     for k, want in (("bkg_sweep", sweep), ("bkg_scale", bkg_scale)):
-        if bkg_kw and pipe is not None and getattr(pipe, k, None if k == "bkg_sweep" else 1.0) != want:
+        if (sweep is not None or bkg_scale != 1.0) and pipe is not None and getattr(pipe, k, None if k == "bkg_sweep" else 1.0) != want:
             raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
-                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
     # --per_image_scores: the rank's table of per-image counts, one set per matrix the run scores (utils/image_scores.py)
     run.scores = report["image_scores"] = image_scores.ImageScoreLog(
-        args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else []),
-        boundary=boundary) if want_scores else None
+        args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else [])
+        + (["clean"] if clean is not None and not args.unlabeled else []),
+        boundary=boundary, **({"regions": True} if clean is not None else {})) if want_scores else None
     try:
         for wanted, needs in ((args.save_cam, "--save_cam needs the decoded images"), (conf is not None, "--conf_label runs behind the ragged step"),
                               (crf_inline_wanted(args), "--crf_inline needs the decoded images")):
@@ -880,6 +902,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         if conf is not None:
             run.consumers["conf_lab"] = _LabelSaver(args, args.conf_label_dir or conf_label_output_dir(
                 args.model_path, args.infer_set, bool(args.training_free), bool(args.refine_with_aff)))
+        if clean is not None and clean["label_dir"]:
+            run.consumers["clean_lab"] = _LabelSaver(args, clean["label_dir"])
         out = (_per_image_loop if per_image else _batched_loop)(run)
     except BaseException:
         _close_consumers(run, failed=True)
@@ -892,6 +916,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         build_validation.last_tags = report["tags"]
         build_validation.last_image_scores = report["image_scores"]
         build_validation.last_bkg_sweep = report["bkg_sweep"]
+        build_validation.last_clean = report["clean"]
     return out
 
 
@@ -1005,6 +1030,10 @@ def _batched_loop(run):
         pipe.hist_conf = torch.zeros_like(run.hist)
     if run.sweep is not None:                                # --bkg_sweep: the pipeline adds every step's counts per scale (both passes of the guard)
         pipe.sweep_totals = torch.zeros((len(run.sweep), 3, args.num_classes), dtype=torch.int64, device=device)
+    clean_lab = run.consumers.get("clean_lab")
+    clean_pending, clean_rows = deque(), {}                  # --clean_min_region: (pinned counts, event, dataset indices, names) -> index: (name, row)
+    if run.clean is not None:
+        pipe.hist_clean = torch.zeros_like(run.hist)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
         from ..datasets.loader import DeviceFeeder, ragged_batches, threaded_batches
@@ -1048,6 +1077,8 @@ def _batched_loop(run):
             crf.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, pipe.last_nchan, nchan_host, pipe.last_cls_idx, labels_t, skip)
         if lab is not None:                                                             # :95, same stream, the labels just scored
             lab.ragged(names, plan, out[0] if keep else out)
+        if clean_lab is not None:                                                       # same stream, the step's cleaned maps
+            clean_lab.ragged(names, plan, pipe.last_clean_labels)
         if keep:                                                                        # :116-119 record for the CRF stage
             inter = out[1]
             cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
@@ -1129,8 +1160,34 @@ def _batched_loop(run):
                 if truth is not None:
                     tag_truth[n] = np.array(truth[b], np.float32)
 
+    def clean_enqueue(names, idxs):
+        """The filter's per-image counts of the step just enqueued, on their way to the host behind an event (no wait here)."""
+        dev = pipe.last_clean_counts
+        host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=on_gpu)
+        host.copy_(dev, non_blocking=True)
+        ev = None
+        if on_gpu:
+            ev = torch.cuda.Event()
+            ev.record()
+        clean_pending.append((host, ev, [int(i) for i in idxs], [str(n) for n in names], [tuple(int(x) for x in hw) for hw in step_hw[0]]))
+        clean_take(False)
+
+    def clean_take(wait):
+        """A later row of an image (the fp32 second pass) replaces the earlier one."""
+        while clean_pending and (wait or clean_pending[0][1] is None or clean_pending[0][1].query()):
+            host, ev, idxs, names, hws = clean_pending.popleft()
+            if ev is not None:
+                ev.synchronize()
+            rows = host.numpy()
+            for b, i in enumerate(idxs):
+                clean_rows[i] = (names[b], rows[b].astype(np.int64))
+            if scores is not None:
+                scores.put_regions(idxs, names, hws, rows)
+
     nimg, pos, flagged = 0, 0, {}
     for names in steps(indices):
+        if run.clean is not None:
+            clean_enqueue(names, indices[pos:pos + len(names)])
         if policy != "off":
             enqueue(names, indices[pos:pos + len(names)])
             take(False, flagged)                              # never a wait inside the loop
@@ -1159,6 +1216,8 @@ def _batched_loop(run):
                 pos = 0
                 for names in steps(np.asarray(order, dtype=np.asarray(indices).dtype)):
                     enqueue(names, order[pos:pos + len(names)])
+                    if run.clean is not None:
+                        clean_enqueue(names, order[pos:pos + len(names)])
                     if tagger is not None:
                         tag_enqueue(names)                    # the fp32 row replaces the first pass's
                     if scores is not None:
@@ -1180,6 +1239,9 @@ def _batched_loop(run):
         run.report["conf_hist"] = pipe.hist_conf
     if run.sweep is not None:
         run.report["bkg_sweep"] = pipe.sweep_totals
+    if run.clean is not None:
+        clean_take(True)
+        run.report["clean"] = dict(hist=pipe.hist_clean, rows=clean_rows)
     if scores is not None:
         scores.poll(True)
     if tagger is not None:
@@ -1341,10 +1403,11 @@ def validate(args=None, dataset=None, pipe=None):
     flag_defaults(args)
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
-    validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = None
-    from ..utils import bkg_sweep, image_scores
+    validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = validate.last_clean = None
+    from ..utils import bkg_sweep, components, image_scores
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))                                # ... and per-image scores of nothing
     sweep, _ = bkg_sweep.resolve(args)                                                       # ... and a sweep nobody can score or run
+    clean = components.resolve(args)                                                         # ... and a cleaning nobody can run or see
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
@@ -1423,6 +1486,23 @@ def validate(args=None, dataset=None, pipe=None):
         _, sweep_total = gather_hists(build_validation.last_bkg_sweep)
         sweep_scores = bkg_sweep.scores_from_totals(sweep_total)
         validate.last_bkg_sweep = dict(scales=sweep, totals=sweep_total, scores=sweep_scores, best_scale=bkg_sweep.best_scale(sweep_scores, sweep)[1])
+    if clean is not None:
+        # --clean_min_region: the kept pixels' matrix summed over the ranks once, the per-image rows gathered once (every rank joins)
+        mine = build_validation.last_clean or {"hist": torch.zeros_like(hist), "rows": {}}
+        _, clean_total = gather_hists(mine["hist"] if mine["hist"] is not None else torch.zeros_like(hist))
+        parts = [mine["rows"]]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, mine["rows"])
+        rows = {}
+        for part in parts:
+            rows.update(part)
+        order = sorted(rows)
+        counts = np.stack([rows[i][1] for i in order]) if order else np.zeros((0, 3), np.int64)
+        clean_score = None if args.unlabeled else evaluate.scores_from_hist(clean_total)
+        validate.last_clean = dict(min_region=clean["min_region"], connectivity=clean["connectivity"], score=clean_score, hist=clean_total,
+                                   coverage=None if args.unlabeled else components.coverage(clean_total, total),
+                                   names=[rows[i][0] for i in order], counts=counts, stats=components.region_stats(counts))
     tags = None
     if tagger is not None:
         # the predicted rows of every rank, once: every rank joins, also one whose shard is empty
@@ -1457,6 +1537,14 @@ def validate(args=None, dataset=None, pipe=None):
             logging.info("\n" + bkg_sweep.format_sweep_table(sweep_scores, sweep, cat_list))
             jb, sb = bkg_sweep.best_scale(sweep_scores, sweep)
             logging.info(f"bkg_sweep best scale {sb:g}: mIoU {sweep_scores[jb]['miou'] * 100:.3f} (labels written and scored at --bkg_scale {args.bkg_scale:g})")
+        if clean is not None:
+            c = validate.last_clean
+            if c["score"] is not None:
+                logging.info(f"clean_label_score (--clean_min_region {clean['min_region']:g}, connectivity {clean['connectivity']}):")
+                logging.info("\n" + format_scores_table(c["score"], cat_list))
+            logging.info(components.format_clean_summary(c["stats"], c["coverage"]))
+            if clean["label_dir"]:
+                logging.info(f"cleaned label maps -> {clean['label_dir']}")
         if tags is not None:
             logging.info(f"tags (--tags clip, thre {tagger['thre']}, at most {tagger['kmax']}, scale {tagger['scale']}): {tags['images']} images, "
                          f"tags per image {dict((k, v) for k, v in enumerate(tags['tags_per_image']) if v)}"
@@ -1479,7 +1567,10 @@ def validate(args=None, dataset=None, pipe=None):
                            "batch_size": args.batch_size, "ragged": bool(args.ragged_batches), "resize_size": args.resize_size,
                            "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1]),
                            **({"tags": _tags_json(tags, tagger)} if tags is not None else {}),
-                           **({"bkg_sweep": bkg_sweep.sweep_json(sweep_scores, sweep)} if sweep is not None else {})}, f)
+                           **({"bkg_sweep": bkg_sweep.sweep_json(sweep_scores, sweep)} if sweep is not None else {}),
+                           **({"clean": components.clean_json(clean["min_region"], clean["connectivity"], validate.last_clean["stats"],
+                                                              validate.last_clean["score"], validate.last_clean["coverage"])}
+                              if clean is not None else {})}, f)
     if image_scores.wanted(args):                                                           # one all_gather_object, rank 0 writes
         validate.last_image_scores = image_scores.finish(build_validation.last_image_scores, args, cat_list, rank, what="LAM_score")
         if rank == 0 and args.json_out and image_scores.boundary_of(args) is not None:       # the record above gains its `boundary` block

@@ -18,6 +18,10 @@ boundary_radius(H, W): 2 % of the image diagonal unless --boundary_px fixes it. 
 log gets a boundary_score table per set (Boundary IoU per class from the SUMMED counts, the mean, the ground-truth band pixels), and
 the files, when written, gain `radius`, `biou` and `<set>_biou` columns and `radius`, `bcounts_<set>` arrays.  Without the flag nothing
 here changes: same columns, same bytes.
+
+--clean_min_region (infer_lam; utils/components.py): the cleaned labels are one more set, "clean", and every image also has a row
+(regions, regions removed, pixels removed) of the filter: the files gain `clean_pacc, clean_miou, clean_scored` and, last, `regions,
+regions_removed, pixels_removed`, the npz `counts_clean` and `regions`.  Without the flag, again, nothing changes.
 """
 import csv
 import logging
@@ -29,7 +33,7 @@ import numpy as np
 
 from .evaluate import boundary_scores_from_counts, image_score_rows
 
-SETS = ("main", "crf", "conf")
+SETS = ("main", "crf", "conf", "clean")
 MAX_RADIUS = 72              # what ops.boundary_max_radius() answers (boundary.hip's halo); the CPU path refuses the same radii
 
 
@@ -164,9 +168,11 @@ class ImageScoreLog:
     """The records of one rank: index -> (name, (H, W), {set: counts int64 [3,nc]}).  put() replaces what an earlier pass recorded for the
     same image and set (the overflow guard's exact-fp32 second pass); defer() takes a ticket and reads it when it is ready."""
 
-    def __init__(self, num_classes, sets=("main",), boundary=None):
+    def __init__(self, num_classes, sets=("main",), boundary=None, regions=False):
         """boundary = None | dict(ratio=, px=): with it every set has a twin "<set>_bd" (ops.boundary_scores' counts) that is recorded
-        and required like the set itself, and merged() adds the radius of every image."""
+        and required like the set itself, and merged() adds the radius of every image.  regions (--clean_min_region): every image also
+        has a row (regions, regions removed, pixels removed) of utils/components.filter_small_regions, put_regions() records it."""
+        self.regions = bool(regions)
         bad = [s for s in sets if s not in SETS]
         if bad or "main" not in sets:
             raise ValueError(f"image score sets {tuple(sets)}: 'main' plus any of {SETS[1:]}")
@@ -184,6 +190,12 @@ class ImageScoreLog:
             raise ValueError(f"image scores: counts of {name!r} are {c.shape}, expected (3, {self.nc})")
         rec = self.records.setdefault(int(index), (str(name), (int(hw[0]), int(hw[1])), {}))
         rec[2][which] = c
+
+    def put_regions(self, indices, names, hws, counts):
+        """counts [B,3]: the filter's rows of one step; a later row of an image replaces the earlier one."""
+        for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
+            rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
+            rec[2]["regions"] = np.array(counts[b], np.int64).reshape(3)
 
     def put_batch(self, indices, names, hws, which, counts):
         for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
@@ -218,7 +230,7 @@ class ImageScoreLog:
             allrec.update(p)
         order = sorted(allrec)
         for i in order:
-            missing = [s for s in self.sets + self.twins if s not in allrec[i][2]]
+            missing = [s for s in self.sets + self.twins + (("regions",) if self.regions else ()) if s not in allrec[i][2]]
             if missing:
                 raise RuntimeError(f"image scores: {allrec[i][0]!r} has no counts for {missing}")
         stack = lambda s: np.stack([allrec[i][2][s] for i in order]) if order else np.zeros((0, 3, self.nc), np.int64)
@@ -227,6 +239,8 @@ class ImageScoreLog:
         if self.boundary is not None:                         # only then: a table without the flag has the keys it always had
             out["radius"] = np.asarray([boundary_radius(*allrec[i][1], **self.boundary) for i in order], np.int32)
             out["bcounts"] = {s: stack(s + "_bd") for s in self.sets}
+        if self.regions:                                      # likewise
+            out["regions"] = np.stack([allrec[i][2]["regions"] for i in order]) if order else np.zeros((0, 3), np.int64)
         return out
 
 
@@ -243,22 +257,27 @@ def write_files(path, merged, class_names):
     main, extra = rows["main"], [s for s in merged["counts"] if s != "main"]
     brows = {s: image_score_rows(c) for s, c in merged.get("bcounts", {}).items()}
     bhead = ["radius", "biou"] + [f"{s}_biou" for s in extra] if brows else []
+    regions = merged.get("regions")
+    rhead = ["regions", "regions_removed", "pixels_removed"] if regions is not None else []
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["name", "height", "width", "scored", "pacc", "miou", "present"] + ["iou_" + c for c in cats]
-                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead)
+                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead + rhead)
         for i, name in enumerate(merged["names"]):
             present = "|".join(cats[c] for c in np.nonzero(merged["counts"]["main"][i, 0])[0])
             w.writerow([name, int(merged["hw"][i, 0]), int(merged["hw"][i, 1]), int(main["scored"][i]), _fmt(main["pacc"][i]),
                         _fmt(main["miou"][i]), present] + [_fmt(v) for v in main["iou"][i]]
                        + [x for s in extra for x in (_fmt(rows[s]["pacc"][i]), _fmt(rows[s]["miou"][i]), int(rows[s]["scored"][i]))]
                        + ([int(merged["radius"][i]), _fmt(brows["main"]["miou"][i])] + [_fmt(brows[s]["miou"][i]) for s in extra]
-                          if brows else []))
+                          if brows else [])
+                       + ([int(v) for v in regions[i]] if regions is not None else []))
     more = {}
     if brows:
         more = dict(radius=merged["radius"].astype(np.int32), **{"bcounts_" + s: c.astype(np.int64) for s, c in merged["bcounts"].items()})
+    if regions is not None:
+        more["regions"] = np.asarray(regions, np.int64)
     np.savez(path + ".npz", names=np.asarray(merged["names"], dtype=str), hw=merged["hw"],
              **{"counts_" + s: c.astype(np.int64) for s, c in merged["counts"].items()}, **more)
     return main
@@ -283,7 +302,7 @@ def report_lines(merged, rows, k, what="label_score"):
     return lines
 
 
-BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels"}
+BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels", "clean": "cleaned labels"}
 
 
 def boundary_summary(merged):

@@ -553,6 +553,40 @@ int excel_bkg_sweep_ragged(const float* planes, const int32_t* nchan /*device [B
                            int64_t* totals /*device [K,3,num_classes], ADDED to, or NULL*/, int label_sel,
                            uint8_t* labels_u8 /*device, tight, or NULL*/, void* stream);
 
+/* ------------------------------------------------------------------ connected components
+ * The regions of label maps, and the filter that turns the small ones into ignore (255).  Images are addressed exactly as in
+ * excel_boundary_scores: table == NULL means B uniform [H,W] maps; otherwise the tight u8 maps of the ragged plan (row pitch W_b, image b
+ * at loff_b; H, W ignored, info->B == B).  The maps may start at any byte address; comp and area use the same pixel indexing, 4-byte
+ * aligned.
+ *
+ * excel_label_components: two pixels of ONE image are connected when they are 4- or 8-neighbours (connectivity 4 or 8) and hold the same
+ * raw value - every raw value forms components, 0 and 255 included, and nothing connects across images (not even the last pixel of
+ * image b and the first of image b + 1 in the tight layout).
+ *   comp[i] = the image-local linear index y * W_b + x of the first pixel, in raster order, of i's component - canonical: it does not
+ *             depend on tiling, scheduling or the order of the atomics;
+ *   area[i] = the number of pixels of i's component, at every pixel.
+ * Every element of both outputs is written, neither is read before it is written (area is cleared on the stream).  Block union-find in
+ * four launches (tile pieces in LDS, seams, flatten + count, broadcast; csrc/components.hip) with no waiting between workgroups: every
+ * link ever stored satisfies parent <= child, so every loop is bounded by construction.  No workspace, no host synchronisation, no
+ * scratch memory.  EXCEL_ERR_ARG before any launch for: a null labels, comp or area; connectivity other than 4 or 8; B outside
+ * [1, 65535]; a uniform H * W or a ragged total outside [1, 2^31); comp or area not 4-byte aligned. */
+int excel_label_components(const uint8_t* labels, int B, int H, int W, const int32_t* table, const excel_ragged_info* info,
+                           int connectivity, int32_t* comp /*device, one per pixel*/, int32_t* area /*device, one per pixel*/,
+                           void* stream);
+
+/* excel_filter_small_regions: with thr = min_area ? min_area[b] : min_area_all, for every pixel of image b
+ *   out = 255 if labels < num_classes and area < thr, else out = labels
+ * - a region of exactly thr pixels stays; pixels with a value >= num_classes (255 included) pass through and their components are never
+ * counted.  counts (device int32 [B,3], cleared on the stream): counts[b,0] = components with a value < num_classes, counts[b,1] = those
+ * removed, counts[b,2] = pixels set to 255; a component is counted once, at its root pixel (comp[i] == i).  An image with thr < 1 is
+ * refused, never clamped: its counts row is -1 and its map is copied unchanged.  comp / area: excel_label_components' outputs for the
+ * same maps and addressing.  out may not overlap labels.  One launch behind the clearing, no workspace, no host synchronisation.
+ * EXCEL_ERR_ARG before any launch for: a null labels, comp, area, out or counts; out overlapping labels; num_classes outside 1..256; B or
+ * the sizes as above; comp, area, counts or min_area not 4-byte aligned. */
+int excel_filter_small_regions(const uint8_t* labels, const int32_t* comp, const int32_t* area, int B, int H, int W, const int32_t* table,
+                               const excel_ragged_info* info, const int32_t* min_area /*device [B] or NULL*/, int min_area_all,
+                               int num_classes, uint8_t* out, int32_t* counts /*device [B,3]*/, void* stream);
+
 /* ------------------------------------------------------------------ image tags: the one-hot rows excel_cls_compact reads, predicted
  * Row 0 of the tower's x_raw is CLIP's own image embedding: the reference puts the class token of the original attention path back
  * before ln_post / proj (clip/clip_surgery_model.py:442-446).  The reference never tags images itself (weakly-supervised segmentation
