@@ -562,13 +562,6 @@ extern "C" int excel_argmax_label(const float* cams, const int32_t* nchan, const
     return excel_launch_argmax_label(cams, nchan, cls_idx, B, Smax, Cmax, HW, labels_u8, (long long*)labels_i64, ST(stream));
 }
 
-extern "C" int excel_confusion_accumulate(const uint8_t* gt, const uint8_t* pred, long long n, int num_classes, int64_t* hist,
-                                          void* stream) {
-    EXCEL_CHECK_ARG(gt && pred && hist && n >= 0, "confusion_accumulate: null argument");
-    if (n == 0) return EXCEL_OK;
-    return excel_launch_confusion(gt, pred, n, num_classes, (unsigned long long*)hist, ST(stream));
-}
-
 // ------------------------------------------------------------------------------------ one-time / auxiliary
 extern "C" int excel_attr_aggregate(const float* text, const float* bank, int F, int T, int C, int K, double topK, float* out,
                                     void* stream) {

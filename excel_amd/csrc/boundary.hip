@@ -1,6 +1,6 @@
 // Boundary scores (include/excel_hip.h, "boundary scores"): the counts Boundary IoU (Cheng et al., CVPR 2021) is computed from.
 //
-// image_scores_kernel (imgscore.hip) counts every valid pixel; the kernel here counts only those in the BAND of their map - the pixels
+// image_scores_kernel (confusion.hip) counts every valid pixel; the kernel here counts only those in the BAND of their map - the pixels
 // whose (2d+1) x (2d+1) window leaves the image or holds another raw value:
 //
 //   boundary_scores_kernel : counts[b,0,g] = valid pixels with ground truth g in the band of the ground truth
@@ -20,13 +20,13 @@
 //           uniform iff the run that ends at x + d is at least 2d + 1 long.  It writes v(r,x) = the value, or 256 for "not uniform";
 //   columns the same walk down v for a quarter of a tile column: the window of (y,x) is uniform iff the run of equal v < 256 that ends
 //           at row y + d is at least 2d + 1 long.  The band flag and the centre value go to two 1 KB arrays per map.
-// Cost per pixel is independent of d up to the halo; LDS is sized by max_radius (10 KB at 13, 55 KB at 72).  The count is
-// image_scores_kernel's: 3 * nc u32 bins in LDS, one flush of the non-zero bins.  No workspace, no scratch.
+// Cost per pixel is independent of d up to the halo; LDS is sized by max_radius (10 KB at 13, 55 KB at 72).  The count goes
+// into image_scores_kernel's bins (margin_count, label_maps.h).  No workspace, no scratch.
 #include "../../include/excel_hip.h"
 #include "common.h"
 #include "excel_internal.h"
+#include "label_maps.h"
 
-#define BND_MAXNC 256
 #define BND_TH 16
 #define BND_TW 64
 #define BND_MAXR 72                              // the largest halo whose LDS (55 KB + 7 KB static) stays under the 64 KB of a plain launch
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void boundary_scores_kernel(const unsigned cha
                                                               TileGeo geo, const int* __restrict__ radius, int max_radius,
                                                               const int* __restrict__ skip, int nc, int* __restrict__ counts) {
     extern __shared__ unsigned int bnd_dyn[];                 // the staged map [RH][P] bytes, then v [RH][BND_VP] u16
-    __shared__ unsigned int lh[3 * BND_MAXNC];
+    __shared__ unsigned int lh[3 * LABEL_MAXNC];
     __shared__ unsigned char edge[2][BND_TH * BND_TW], centre[2][BND_TH * BND_TW];
     const Tile t = tile_of<RAGGED>(geo);
     const int b = t.b;
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void boundary_scores_kernel(const unsigned cha
     const int ys = t.y0 - d, xs = t.x0 - d;                  // image position of the staged region's corner
     unsigned char* M = reinterpret_cast<unsigned char*>(bnd_dyn);
     unsigned short* V = reinterpret_cast<unsigned short*>(M + bnd_map_bytes(max_radius));
-    for (int i = threadIdx.x; i < bins; i += 256) lh[i] = 0;
+    label_bins_clear(lh, bins);
 
     for (int m = 0; m < 2; ++m) {
         const unsigned char* __restrict__ src = (m ? pred : gt) + t.lab;
@@ -141,25 +141,17 @@ __global__ __launch_bounds__(256) void boundary_scores_kernel(const unsigned cha
         }
         __syncthreads();                                     // the next map overwrites M and V
     }
-    // ---- count: image_scores_kernel's bins, band pixels only
+    // ---- count: band pixels only
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int i = threadIdx.x + 256 * k;
         const int ty = i >> 6, tx = i & 63;
         if (t.y0 + ty < H && t.x0 + tx < W) {                 // centre[] of a pixel outside the image was never staged
-            const int g = centre[0][i], p = centre[1][i];
-            if (g < nc && p < nc) {
-                const int eg = edge[0][i], ep = edge[1][i];
-                if (eg) atomicAdd(&lh[g], 1u);
-                if (ep) atomicAdd(&lh[nc + p], 1u);
-                if (g == p && eg && ep) atomicAdd(&lh[2 * nc + g], 1u);
-            }
+            margin_count(lh, nc, centre[0][i], centre[1][i], edge[0][i] != 0, edge[1][i] != 0);
         }
     }
     __syncthreads();
-    int* out = counts + (long long)b * bins;
-    for (int i = threadIdx.x; i < bins; i += 256)
-        if (lh[i]) atomicAdd(&out[i], (int)lh[i]);
+    margin_flush(lh, nc, counts + (long long)b * bins);
 }
 
 extern "C" int excel_boundary_max_radius(void) { return BND_MAXR; }
@@ -168,31 +160,17 @@ extern "C" int excel_boundary_scores(const uint8_t* gt, const uint8_t* pred, int
                                      const excel_ragged_info* info, const int32_t* radius, int max_radius, const int32_t* skip,
                                      int num_classes, int32_t* counts, void* stream) {
     EXCEL_CHECK_ARG(gt && pred && counts, "boundary_scores: null argument (gt, pred and counts are required)");
-    EXCEL_CHECK_ARG(B >= 1 && B <= 65535, "boundary_scores: need 1 <= B <= 65535 (B = %d)", B);
-    EXCEL_CHECK_ARG(num_classes >= 1 && num_classes <= BND_MAXNC, "boundary_scores: need 1 <= num_classes <= %d (got %d)", BND_MAXNC,
+    EXCEL_CHECK_ARG(num_classes >= 1 && num_classes <= LABEL_MAXNC, "boundary_scores: need 1 <= num_classes <= %d (got %d)", LABEL_MAXNC,
                     num_classes);
     EXCEL_CHECK_ARG(max_radius >= 1 && max_radius <= BND_MAXR, "boundary_scores: need 1 <= max_radius <= %d (got %d)", BND_MAXR, max_radius);
     EXCEL_CHECK_ARG(((uintptr_t)counts & 3) == 0 && ((uintptr_t)skip & 3) == 0 && ((uintptr_t)radius & 3) == 0,
                     "boundary_scores: counts, skip and radius must be 4-byte aligned");
     TileGeo geo;
-    geo.tab = table; geo.B = B; geo.H = H; geo.W = W;
     dim3 grid;
-    if (table) {
-        EXCEL_CHECK_ARG(info && info->B == B, "boundary_scores: the plan holds %d images, B = %d", info ? info->B : -1, B);
-        EXCEL_CHECK_ARG(info->total_tiles >= 1, "boundary_scores: the plan holds no tile");
-        grid = dim3((unsigned)info->total_tiles);
-    } else {
-        EXCEL_CHECK_ARG(H >= 1 && W >= 1, "boundary_scores: need H >= 1 and W >= 1 (got %d x %d)", H, W);
-        EXCEL_CHECK_ARG((long long)H * W < (1LL << 31) && cdiv(H, BND_TH) <= 65535, "boundary_scores: %d x %d is too large an image", H, W);
-        grid = dim3((unsigned)cdiv(W, BND_TW), (unsigned)cdiv(H, BND_TH), (unsigned)B);
-    }
+    TRY(label_tile_geometry("boundary_scores", B, H, W, table, info, &geo, &grid, nullptr));
     hipStream_t st = ST(stream);
     ProfScope prof__(PROF_OTHER, st);
-    const hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)B * 3 * (size_t)num_classes, st);
-    if (e != hipSuccess) {
-        excel_set_error("boundary_scores: clearing the counts failed: %s", hipGetErrorString(e));
-        return EXCEL_ERR_LAUNCH;
-    }
+    TRY(clear_on_stream("boundary_scores", "counts", counts, sizeof(int32_t) * (size_t)B * 3 * (size_t)num_classes, st));
     const size_t lds = bnd_lds_bytes(max_radius);            // 55 040 B at 72: with the 7 KB of static arrays under the 64 KB of a plain launch
     if (table)
         hipLaunchKernelGGL(boundary_scores_kernel<true>, grid, dim3(256), lds, st, gt, pred, geo, radius, max_radius, skip, num_classes, counts);

@@ -27,6 +27,7 @@
 #include "../../include/excel_hip.h"
 #include "common.h"
 #include "excel_internal.h"
+#include "label_maps.h"
 
 #define CC_TH 16
 #define CC_TW 64
@@ -349,27 +350,6 @@ __global__ __launch_bounds__(256) void cc_filter_kernel(const unsigned char* __r
 }
 
 // ---------------------------------------------------------------- host entries
-// the launch geometry both entries share: refusals first, then the grid of one workgroup per 64 x 16 tile
-static int cc_geometry(const char* who, int B, int H, int W, const int32_t* table, const excel_ragged_info* info, TileGeo* geo, dim3* grid,
-                       long long* total) {
-    EXCEL_CHECK_ARG(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (B = %d)", who, B);
-    geo->tab = table; geo->B = B; geo->H = H; geo->W = W;
-    if (table) {
-        EXCEL_CHECK_ARG(info && info->B == B, "%s: the plan holds %d images, B = %d", who, info ? info->B : -1, B);
-        EXCEL_CHECK_ARG(info->total_tiles >= 1, "%s: the plan holds no tile", who);
-        EXCEL_CHECK_ARG(info->total_label_pix >= 1 && info->total_label_pix < (1LL << 31),
-                        "%s: the plan holds %lld pixels, outside [1, 2^31)", who, (long long)info->total_label_pix);
-        *grid = dim3((unsigned)info->total_tiles);
-        *total = info->total_label_pix;
-    } else {
-        EXCEL_CHECK_ARG(H >= 1 && W >= 1, "%s: need H >= 1 and W >= 1 (got %d x %d)", who, H, W);
-        EXCEL_CHECK_ARG((long long)H * W < (1LL << 31) && cdiv(H, CC_TH) <= 65535, "%s: %d x %d is too large an image", who, H, W);
-        *grid = dim3((unsigned)cdiv(W, CC_TW), (unsigned)cdiv(H, CC_TH), (unsigned)B);
-        *total = (long long)B * H * W;
-    }
-    return EXCEL_OK;
-}
-
 extern "C" int excel_label_components(const uint8_t* labels, int B, int H, int W, const int32_t* table, const excel_ragged_info* info,
                                       int connectivity, int32_t* comp, int32_t* area, void* stream) {
     EXCEL_CHECK_ARG(labels && comp && area, "label_components: null argument (labels, comp and area are required)");
@@ -379,14 +359,10 @@ extern "C" int excel_label_components(const uint8_t* labels, int B, int H, int W
     TileGeo geo;
     dim3 grid;
     long long total;
-    TRY(cc_geometry("label_components", B, H, W, table, info, &geo, &grid, &total));
+    TRY(label_tile_geometry("label_components", B, H, W, table, info, &geo, &grid, &total));
     hipStream_t st = ST(stream);
     ProfScope prof__(PROF_OTHER, st);
-    const hipError_t e = hipMemsetAsync(area, 0, sizeof(int32_t) * (size_t)total, st);      // the root slots are added to
-    if (e != hipSuccess) {
-        excel_set_error("label_components: clearing the areas failed: %s", hipGetErrorString(e));
-        return EXCEL_ERR_LAUNCH;
-    }
+    TRY(clear_on_stream("label_components", "areas", area, sizeof(int32_t) * (size_t)total, st));      // the root slots are added to
     const int conn8 = connectivity == 8;
     if (table) {
         hipLaunchKernelGGL(cc_tile_kernel<true>, grid, dim3(256), 0, st, labels, geo, conn8, comp);
@@ -415,16 +391,12 @@ extern "C" int excel_filter_small_regions(const uint8_t* labels, const int32_t* 
     TileGeo geo;
     dim3 grid;
     long long total;
-    TRY(cc_geometry("filter_small_regions", B, H, W, table, info, &geo, &grid, &total));
+    TRY(label_tile_geometry("filter_small_regions", B, H, W, table, info, &geo, &grid, &total));
     EXCEL_CHECK_ARG((uintptr_t)out + (size_t)total <= (uintptr_t)labels || (uintptr_t)labels + (size_t)total <= (uintptr_t)out,
                     "filter_small_regions: out overlaps labels (the filter does not run in place)");
     hipStream_t st = ST(stream);
     ProfScope prof__(PROF_OTHER, st);
-    const hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)B * 3, st);
-    if (e != hipSuccess) {
-        excel_set_error("filter_small_regions: clearing the counts failed: %s", hipGetErrorString(e));
-        return EXCEL_ERR_LAUNCH;
-    }
+    TRY(clear_on_stream("filter_small_regions", "counts", counts, sizeof(int32_t) * (size_t)B * 3, st));
     if (table)
         hipLaunchKernelGGL(cc_filter_kernel<true>, grid, dim3(256), 0, st, labels, comp, area, geo, min_area, min_area_all, num_classes, out, counts);
     else

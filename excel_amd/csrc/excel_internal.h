@@ -189,8 +189,6 @@ int excel_launch_normalize_resize_u8_ragged_mirror(const unsigned char* hwc, flo
 int excel_launch_bilinear_ac(const float* in, float* out, int planes, int h, int w, int H, int W, hipStream_t st);
 int excel_launch_argmax_label(const float* cams, const int* nchan, const int* cls_idx, int B, int Smax, int Cmax, long long HW,
                               unsigned char* lab8, long long* lab64, hipStream_t st);
-int excel_launch_confusion(const unsigned char* gt, const unsigned char* pred, long long n, int nc, unsigned long long* hist,
-                           hipStream_t st);
 int excel_launch_attr_aggregate(const float* text, const float* bank, int F, int T, int C, int K, int drop, float* out,
                                 hipStream_t st);
 int excel_launch_bilinear_resize(const float* in, float* out, long long planes, int h, int w, int H, int W, int align_corners,

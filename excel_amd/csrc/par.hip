@@ -1,5 +1,4 @@
-// Pixel-adaptive refinement (utils/PAR.py:26-92) + arg-max labelling (utils/affutils.py:80-89) +
-// confusion-matrix accumulation (utils/evaluate.py:9-20).
+// Pixel-adaptive refinement (utils/PAR.py:26-92) + arg-max labelling (utils/affutils.py:80-89).
 //
 //   par_affinity       : guide image -> per pixel: 48 edge-clamped dilated taps per channel, unbiased std over the taps,
 //                        -(|I_nb - I|/(std+1e-8)/w1)^2, mean over RGB, softmax over taps + w2 * softmax(position term)   (PAR.py:70-86)
@@ -10,7 +9,6 @@
 //                        does not take (W % 4 != 0 in the un-pitched uniform layout, other dilation sets) and the bit-exactness
 //                        reference of the recomputing kernel (same operations in the same order -> same bits)
 //   argmax_label       : label = valid_key[argmax_c]                                      (affutils.py:86-87)
-//   confusion          : hist[nc*gt + pred] += 1 over gt < nc                             (evaluate.py:10-14)
 //
 // Algorithmic traffic of one step = (48 + 2C) * H * W * 4 bytes; the recomputing kernel moves (5 + 3 + 2C) * 4 B/pixel.
 // The exponent is evaluated in base 2: log2(e)/3 (the RGB mean) is folded into the per-channel scale k2_c, so one tap costs
@@ -618,7 +616,7 @@ __global__ __launch_bounds__(256) void argmax_label_kernel(const float* __restri
     if (lab64) lab64[(long long)b * HW + i] = key;
 }
 
-// ragged: pitched cams -> TIGHT u8 labels (image b at loff_b, row pitch W_b): the confusion kernel then runs over one flat array
+// ragged: pitched cams -> TIGHT u8 labels (image b at loff_b, row pitch W_b): the confusion kernel (confusion.hip) then runs over one flat array
 __global__ __launch_bounds__(256) void argmax_label_ragged_kernel(const float* __restrict__ cams, const int* __restrict__ nchan,
                                                                   const int* __restrict__ cls_idx, int Smax, int Cmax, TileGeo geo,
                                                                   unsigned char* __restrict__ lab8) {
@@ -633,65 +631,6 @@ __global__ __launch_bounds__(256) void argmax_label_ragged_kernel(const float* _
         const int y = t.y0 + (threadIdx.x >> 6) + 4 * r;
         if (y < t.H) lab8[t.lab + (long long)y * t.W + x] = (unsigned char)argmax_key(cb + (long long)y * t.Wp + x, t.HW, nch, cls_row);
     }
-}
-
-#define CONF_MAXBINS 8192
-#define CONF_MAXNC 256
-// BAND (nc * nc > CONF_MAXBINS): the histogram does not fit one workgroup's LDS, so blockIdx.y selects a band of CONF_MAXBINS / nc
-// ground-truth rows; a workgroup reads the same pixels as its twins of the other bands and counts those whose gt lies in its own.
-// Every pixel is counted by exactly one band, in 32-bit LDS counters a workgroup's share of the pixels cannot wrap (its stride loop
-// covers n / gridDim.x pixels: 2^32 of them would need n > 2^43), so the counts stay integer-exact.
-// (a macro: as a function the narrow kernel's byte-select operands come out as separate instructions)
-#define CONF_COUNT(g, p)                                                              \
-    do {                                                                              \
-        if (BAND) {                                                                   \
-            const unsigned int gr_ = (unsigned int)((g) - r0);                        \
-            if (gr_ < (unsigned int)rows && (p) < nc) atomicAdd(&lh[gr_ * nc + (p)], 1u); \
-        } else {                                                                      \
-            if ((g) < nc && (p) < nc) atomicAdd(&lh[(g) * nc + (p)], 1u);             \
-        }                                                                             \
-    } while (0)
-template <bool BAND>
-__global__ __launch_bounds__(256) void confusion_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ pred,
-                                                        long long n, int nc, unsigned long long* __restrict__ hist, int head) {
-    __shared__ unsigned int lh[CONF_MAXBINS];
-    const int band_rows = BAND ? CONF_MAXBINS / nc : nc;
-    const int r0 = BAND ? (int)blockIdx.y * band_rows : 0, rows = BAND ? min(band_rows, nc - r0) : nc;
-    const int bins = rows * nc;
-    for (int i = threadIdx.x; i < bins; i += 256) lh[i] = 0;
-    __syncthreads();
-    // gt / pred slices of a larger tensor need not be 16-byte aligned: when both share the same misalignment a scalar head brings
-    // them to a 16-byte boundary, otherwise (`head` < 0) the whole range goes through the scalar path
-    if (head > 0 && blockIdx.x == 0 && threadIdx.x < head && threadIdx.x < n) {
-        const int g = gt[threadIdx.x], p = pred[threadIdx.x];
-        CONF_COUNT(g, p);
-    }
-    if (head >= 0) {
-        gt += head; pred += head; n -= head;
-        if (n < 0) n = 0;
-    }
-    const long long stride = (long long)gridDim.x * 256 * 16;
-    for (long long base = ((long long)blockIdx.x * 256 + threadIdx.x) * 16; base < n; base += stride) {
-        if (head >= 0 && base + 16 <= n) {
-            const uint4 g4 = *reinterpret_cast<const uint4*>(gt + base);
-            const uint4 p4 = *reinterpret_cast<const uint4*>(pred + base);
-            const unsigned int gw[4] = {g4.x, g4.y, g4.z, g4.w}, pw[4] = {p4.x, p4.y, p4.z, p4.w};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int g = (gw[k >> 2] >> (8 * (k & 3))) & 255, p = (pw[k >> 2] >> (8 * (k & 3))) & 255;
-                CONF_COUNT(g, p);
-            }
-        } else {
-            const long long end = (base + 16 < n) ? base + 16 : n;
-            for (long long j = base; j < end; ++j) {
-                const int g = gt[j], p = pred[j];
-                CONF_COUNT(g, p);
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < bins; i += 256)
-        if (lh[i]) atomicAdd(&hist[(BAND ? r0 * nc : 0) + i], (unsigned long long)lh[i]);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -824,22 +763,5 @@ int excel_launch_argmax_label_ragged(const float* cams, const int* nchan, const 
     ProfScope prof__(PROF_ARGMAX, st);
     hipLaunchKernelGGL(argmax_label_ragged_kernel, dim3(total_tiles), dim3(256), 0, st, cams, nchan, cls_idx, Smax, Cmax, geo, lab8);
     EXCEL_CHECK_LAUNCH("argmax_label_ragged");
-    return EXCEL_OK;
-}
-
-int excel_launch_confusion(const unsigned char* gt, const unsigned char* pred, long long n, int nc, unsigned long long* hist,
-                           hipStream_t st) {
-    ProfScope prof__(PROF_CONFUSION, st);
-    EXCEL_CHECK_ARG(nc >= 1 && nc <= CONF_MAXNC, "confusion: need 1 <= num_classes <= %d (got %d)", CONF_MAXNC, nc);
-    // scalar elements in front of the first 16-byte boundary (same for both pointers), or -1: no common alignment -> scalar path
-    const int mg = (int)((16 - ((uintptr_t)gt & 15)) & 15), mp = (int)((16 - ((uintptr_t)pred & 15)) & 15);
-    const int head = (mg == mp) ? mg : -1;
-    const int blocks = (int)((cdivl(n, 256 * 16) < 2048) ? cdivl(n, 256 * 16) : 2048);
-    if (nc * nc <= CONF_MAXBINS)
-        hipLaunchKernelGGL(confusion_kernel<false>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, gt, pred, n, nc, hist, head);
-    else
-        hipLaunchKernelGGL(confusion_kernel<true>, dim3(blocks > 0 ? blocks : 1, cdiv(nc, CONF_MAXBINS / nc)), dim3(256), 0, st, gt, pred, n, nc,
-                           hist, head);
-    EXCEL_CHECK_LAUNCH("confusion");
     return EXCEL_OK;
 }

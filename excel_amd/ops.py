@@ -1560,23 +1560,31 @@ def clip_tags(x, text_rows, num_fg, scale=100.0, thre=0.2, kmax=6, want_scores=T
     return onehot, scores
 
 
+def _label_pair(who, gt_u8, pred_u8, plan, skip):
+    """What the ops over (gt, pred, plan, skip) share -> (gt, pred, B, table pointer, info pointer): contiguous maps of equal size, B from
+    the plan or the first dimension, the pixel count the plan holds, one skip flag per image."""
+    gt = gt_u8.contiguous()
+    pr = pred_u8.contiguous()
+    if gt.numel() != pr.numel():
+        raise ValueError(f"{who}: gt holds {gt.numel()} pixels, pred {pr.numel()}")
+    B = plan.B if plan is not None else (int(gt.shape[0]) if gt.dim() > 0 else 0)
+    if plan is not None and gt.numel() != plan.total_label_pix:
+        raise ValueError(f"{who}: {gt.numel()} pixels, the plan holds {plan.total_label_pix}")
+    if skip is not None and skip.numel() != B:
+        raise ValueError(f"{who}: skip holds {skip.numel()} flags for {B} images")
+    return gt, pr, B, _p(plan.table, torch.int32) if plan is not None else None, C.byref(plan.info) if plan is not None else None
+
+
 def confusion_accumulate_masked(gt_u8, pred_u8, num_classes, skip, hist=None, plan=None):
     """confusion_accumulate over the images with skip[b] == 0 (skip: int32 [B], device - e.g. nonfinite_count's counters).
     plan=None: gt / pred are uniform [B,H,W] maps; with a RaggedPlan they are its tight label maps back to back."""
-    gt = gt_u8.contiguous()
-    pr = pred_u8.contiguous()
-    assert gt.numel() == pr.numel()
-    B = plan.B if plan is not None else int(gt.shape[0])
-    if skip.numel() != B:
-        raise ValueError(f"confusion_accumulate_masked: skip holds {skip.numel()} flags for {B} images")
-    if plan is not None and gt.numel() != plan.total_label_pix:
-        raise ValueError(f"confusion_accumulate_masked: {gt.numel()} pixels, the plan holds {plan.total_label_pix}")
+    assert gt_u8.numel() == pred_u8.numel()
+    gt, pr, B, table, info = _label_pair("confusion_accumulate_masked", gt_u8, pred_u8, plan, skip)
     if hist is None:
         hist = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=gt.device)
-    check(lib().excel_confusion_accumulate_masked(_p(gt, torch.uint8), _p(pr, torch.uint8), B, gt.numel() // B,
-                                                  _p(plan.table, torch.int32) if plan is not None else None,
-                                                  C.byref(plan.info) if plan is not None else None, _p(skip, torch.int32), num_classes,
-                                                  _p(hist, torch.int64), _stream()), "excel_confusion_accumulate_masked")
+    check(lib().excel_confusion_accumulate_masked(_p(gt, torch.uint8), _p(pr, torch.uint8), B, gt.numel() // B, table, info,
+                                                  _p(skip, torch.int32), num_classes, _p(hist, torch.int64), _stream()),
+          "excel_confusion_accumulate_masked")
     return hist
 
 
@@ -1587,26 +1595,16 @@ def image_scores(gt_u8, pred_u8, num_classes, skip=None, plan=None, out=None):
     mIoU and pixel accuracy).  plan=None: gt / pred are uniform [B,H,W] maps; with a RaggedPlan they are its tight label maps back to
     back.  skip: int32 [B] (device) or None - the rows of an image with skip[b] != 0 are zero.  out: a buffer of B*3*nc int32, fully
     overwritten.  One launch, no scratch memory, no synchronisation."""
-    gt = gt_u8.contiguous()
-    pr = pred_u8.contiguous()
-    if gt.numel() != pr.numel():
-        raise ValueError(f"image_scores: gt holds {gt.numel()} pixels, pred {pr.numel()}")
     nc = int(num_classes)
     if not 1 <= nc <= 256:
         raise ValueError(f"image_scores: num_classes = {nc} is outside [1, 256]")
-    B = plan.B if plan is not None else (int(gt.shape[0]) if gt.dim() > 0 else 0)
+    gt, pr, B, table, info = _label_pair("image_scores", gt_u8, pred_u8, plan, skip)
     if B < 1:
         raise ValueError(f"image_scores: B = {B}: at least one image is needed (gt {tuple(gt.shape)})")
-    if plan is not None and gt.numel() != plan.total_label_pix:
-        raise ValueError(f"image_scores: {gt.numel()} pixels, the plan holds {plan.total_label_pix}")
-    if skip is not None and skip.numel() != B:
-        raise ValueError(f"image_scores: skip holds {skip.numel()} flags for {B} images")
     if out is not None and (out.numel() != B * 3 * nc or out.dtype != torch.int32):
         raise ValueError(f"image_scores: out must hold {B * 3 * nc} int32 (got {out.numel()} {out.dtype})")
     counts = torch.empty((B, 3, nc), dtype=torch.int32, device=gt.device) if out is None else out.view(B, 3, nc)
-    check(lib().excel_image_scores(_p(gt, torch.uint8), _p(pr, torch.uint8), B, gt.numel() // B,
-                                   _p(plan.table, torch.int32) if plan is not None else None,
-                                   C.byref(plan.info) if plan is not None else None, _p(skip, torch.int32), nc,
+    check(lib().excel_image_scores(_p(gt, torch.uint8), _p(pr, torch.uint8), B, gt.numel() // B, table, info, _p(skip, torch.int32), nc,
                                    _p(counts, torch.int32), _stream()), "excel_image_scores")
     return counts
 
@@ -1630,27 +1628,20 @@ def boundary_scores(gt_u8, pred_u8, num_classes, radius, skip=None, plan=None, o
     it (default: the build's maximum), and an image whose radius is < 1 or beyond the bound gets -1 in all its entries.  Host radii
     outside [1, boundary_max_radius()] are refused here, naming the image.  skip / out as in image_scores.  One launch, no scratch
     memory, no synchronisation."""
-    gt = gt_u8.contiguous()
-    pr = pred_u8.contiguous()
-    if gt.numel() != pr.numel():
-        raise ValueError(f"boundary_scores: gt holds {gt.numel()} pixels, pred {pr.numel()}")
     nc = int(num_classes)
     if not 1 <= nc <= 256:
         raise ValueError(f"boundary_scores: num_classes = {nc} is outside [1, 256]")
+    if plan is None and gt_u8.dim() != 3:
+        raise ValueError(f"boundary_scores: uniform maps must be [B,H,W] (gt {tuple(gt_u8.shape)}); a ragged batch needs its plan")
+    gt, pr, B, table, info = _label_pair("boundary_scores", gt_u8, pred_u8, plan, skip)
     if plan is None:
-        if gt.dim() != 3:
-            raise ValueError(f"boundary_scores: uniform maps must be [B,H,W] (gt {tuple(gt.shape)}); a ragged batch needs its plan")
-        B, H, W = (int(x) for x in gt.shape)
+        H, W = int(gt.shape[1]), int(gt.shape[2])
         hw = lambda b: (H, W)
     else:
-        B, H, W = plan.B, 0, 0
+        H, W = 0, 0
         hw = lambda b: (int(plan.hw[b, 0]), int(plan.hw[b, 1]))
-        if gt.numel() != plan.total_label_pix:
-            raise ValueError(f"boundary_scores: {gt.numel()} pixels, the plan holds {plan.total_label_pix}")
     if B < 1 or gt.numel() < 1:
         raise ValueError(f"boundary_scores: at least one image with a pixel is needed (gt {tuple(gt.shape)})")
-    if skip is not None and skip.numel() != B:
-        raise ValueError(f"boundary_scores: skip holds {skip.numel()} flags for {B} images")
     if out is not None and (out.numel() != B * 3 * nc or out.dtype != torch.int32):
         raise ValueError(f"boundary_scores: out must hold {B * 3 * nc} int32 (got {out.numel()} {out.dtype})")
     top = boundary_max_radius()
@@ -1672,9 +1663,7 @@ def boundary_scores(gt_u8, pred_u8, num_classes, radius, skip=None, plan=None, o
     if not 1 <= bound <= top:
         raise ValueError(f"boundary_scores: max_radius = {bound} is outside [1, {top}]")
     counts = torch.empty((B, 3, nc), dtype=torch.int32, device=gt.device) if out is None else out.view(B, 3, nc)
-    check(lib().excel_boundary_scores(_p(gt, torch.uint8), _p(pr, torch.uint8), B, H, W,
-                                      _p(plan.table, torch.int32) if plan is not None else None,
-                                      C.byref(plan.info) if plan is not None else None, _p(rad, torch.int32), bound,
+    check(lib().excel_boundary_scores(_p(gt, torch.uint8), _p(pr, torch.uint8), B, H, W, table, info, _p(rad, torch.int32), bound,
                                       _p(skip, torch.int32), nc, _p(counts, torch.int32), _stream()), "excel_boundary_scores")
     return counts
 

@@ -1,4 +1,4 @@
-"""Per-image scores on the GPU: excel_image_scores (imgscore.hip) against numpy, integer for integer, at every size, class count, label
+"""Per-image scores on the GPU: excel_image_scores (confusion.hip) against numpy, integer for integer, at every size, class count, label
 value, alignment and addressing mode the kernel has a path for; then --per_image_scores of infer_lam and infer_seg_voc end to end
 against the label PNGs the same run wrote."""
 import ctypes as C
@@ -84,6 +84,101 @@ def test_alignment_of_both_maps(gpu, offs, per_image):
     assert gd.data_ptr() % 16 == offs[0] and pd.data_ptr() % 16 == offs[1]
     got = ops.image_scores(gd.view(3, per_image), pd.view(3, per_image), nc)
     assert torch.equal(got.cpu(), torch.from_numpy(_ref(list(g.reshape(3, -1)), list(p.reshape(3, -1)), nc)))
+
+
+def _hist_ref(gs, ps, nc):
+    """gs / ps: lists of flat uint8 arrays (one per image) -> int64 [nc,nc], the confusion matrix over the pixels with g < nc and p < nc"""
+    h = np.zeros(nc * nc, np.int64)
+    for g, p in zip(gs, ps):
+        g, p = g.astype(np.int32), p.astype(np.int32)
+        m = (g < nc) & (p < nc)
+        h += np.bincount(nc * g[m] + p[m], minlength=nc * nc)
+    return h.reshape(nc, nc)
+
+
+SWEEP_RAGGED = [(5, 7), (16, 64), (17, 65), (1, 1)]
+
+
+@pytest.mark.parametrize("offs", [(0, 0), (3, 3), (1, 2), (5, 0)])
+@pytest.mark.parametrize("layout", [1, 15, 16, 17, 4101, "ragged"])
+@pytest.mark.parametrize("nc", [21, 151])
+def test_the_three_entries_agree_on_the_same_arrays(gpu, offs, layout, nc):
+    """confusion_accumulate, confusion_accumulate_masked and image_scores run one sweep: on the same slices - a shared 16-byte phase or
+    none (the scalar-only path), uniform B = 3 images of `layout` pixels or one ragged plan, a whole matrix in LDS (21) or bands (151) -
+    the masked matrix with an all-zero skip is the plain one bit for bit and numpy's, the margins of image_scores are that matrix's,
+    and a skipped image is dropped by both per-image entries, exactly."""
+    from excel_amd import ops
+    from excel_amd.utils.evaluate import hist_margins
+    if layout == "ragged":
+        plan, pix = ops.RaggedPlan(SWEEP_RAGGED, "cuda"), [h * w for h, w in SWEEP_RAGGED]
+    else:
+        plan, pix = None, [layout] * 3
+    B = len(pix)
+    rs = np.random.RandomState(sum(pix) * 31 + offs[0] * 16 + offs[1] + nc)
+    g, p = _maps(rs, sum(pix), nc)
+    cuts = np.cumsum(pix)[:-1]
+    gs, ps = np.split(g, cuts), np.split(p, cuts)
+    gd, pd = _at_offset(g, offs[0]), _at_offset(p, offs[1])
+    assert gd.data_ptr() % 16 == offs[0] and pd.data_ptr() % 16 == offs[1]
+    if plan is None:
+        gd, pd = gd.view(B, -1), pd.view(B, -1)
+    zeros = torch.zeros(B, dtype=torch.int32, device="cuda")
+    plain = ops.confusion_accumulate(gd, pd, nc)
+    masked = ops.confusion_accumulate_masked(gd, pd, nc, zeros, plan=plan)
+    assert plain.dtype == masked.dtype == torch.int64 and torch.equal(masked, plain)
+    assert np.array_equal(plain.cpu().numpy(), _hist_ref(gs, ps, nc))
+    counts = ops.image_scores(gd, pd, nc, skip=zeros, plan=plan).cpu().numpy()
+    assert np.array_equal(counts, _ref(gs, ps, nc))
+    rows, cols, diag = hist_margins(counts)
+    hist = plain.cpu().numpy()
+    assert np.array_equal(rows, hist.sum(1)) and np.array_equal(cols, hist.sum(0)) and np.array_equal(diag, np.diagonal(hist))
+    # image 1 skipped
+    skip = torch.tensor([0, 5] + [0] * (B - 2), dtype=torch.int32, device="cuda")
+    kept = [b for b in range(B) if b != 1]
+    masked = ops.confusion_accumulate_masked(gd, pd, nc, skip, plan=plan).cpu().numpy()
+    assert np.array_equal(masked, _hist_ref([gs[b] for b in kept], [ps[b] for b in kept], nc))
+    counts = ops.image_scores(gd, pd, nc, skip=skip, plan=plan).cpu().numpy()
+    want = _ref(gs, ps, nc)
+    want[1] = 0
+    assert np.array_equal(counts, want)
+
+
+def _noise(rs, n, nc):
+    """n label pairs, cheap to draw: uniform over the classes, 255 and (nc < 255) one value in [nc, 255)"""
+    def one():
+        v = rs.randint(0, nc + 2, size=n).astype(np.uint8)
+        v[v == nc + 1] = 255
+        return v
+    return one(), one()
+
+
+def test_two_rounds_of_the_stride_loop_per_image(gpu):
+    """700 uniform images of 3 * 4096 + 5 pixels: the chunk rule gives 2048 // 700 = 2 chunks per image where the image has 4 groups of
+    4096 pixels, so every workgroup of the masked confusion and of image_scores goes round its stride loop twice."""
+    from excel_amd import ops
+    B, per_image, nc = 700, 3 * 4096 + 5, 21
+    rs = np.random.RandomState(700)
+    g, p = _noise(rs, B * per_image, nc)
+    gs, ps = list(g.reshape(B, -1)), list(p.reshape(B, -1))
+    gd, pd = torch.from_numpy(g).cuda().view(B, per_image), torch.from_numpy(p).cuda().view(B, per_image)
+    skip_h = np.zeros(B, np.int32)
+    skip_h[[3, 698]] = 1
+    skip = torch.from_numpy(skip_h).cuda()
+    kept = np.nonzero(skip_h == 0)[0]
+    hist = ops.confusion_accumulate_masked(gd, pd, nc, skip).cpu().numpy()
+    assert np.array_equal(hist, _hist_ref([gs[b] for b in kept], [ps[b] for b in kept], nc))
+    want = _ref(gs, ps, nc)
+    want[skip_h != 0] = 0
+    assert np.array_equal(ops.image_scores(gd, pd, nc, skip=skip).cpu().numpy(), want)
+
+
+def test_two_rounds_of_the_stride_loop_of_the_plain_entry(gpu):
+    """2048 * 4096 * 2 + 5 pixels in one range: the grid stops at 2048 chunks, so every workgroup makes two rounds and chunk 0 a third."""
+    from excel_amd import ops
+    n, nc = 2048 * 4096 * 2 + 5, 21
+    g, p = _noise(np.random.RandomState(2048), n, nc)
+    hist = ops.confusion_accumulate(torch.from_numpy(g).cuda(), torch.from_numpy(p).cuda(), nc).cpu().numpy()
+    assert np.array_equal(hist, _hist_ref([g], [p], nc))
 
 
 def _ragged_case(sizes, nc, seed):

@@ -6,7 +6,7 @@ ops.image_scores next to ops.confusion_accumulate_masked on the label arrays of 
 alternating rounds; these calls can be bound by the Python wrapper - kernel durations come from a rocprofv3 --kernel-trace run over the
 arrays this script leaves in step_labels.npz next to OUT.json).  AB_LIB: a shared library whose entry
 `int imgscore_arm(gt, pred, B, per_image, table, max_pix, skip, nc, counts, stream)` launches an experimental arm of the kernel, timed
-beside them and checked equal (the run-folding arm of EXPERIMENTS.md was imgscore.hip's kernel compiled that way)."""
+beside them and checked equal (the run-folding arm of EXPERIMENTS.md was image_scores_kernel compiled that way)."""
 import ctypes as C
 import json
 import logging
