@@ -121,7 +121,7 @@ class TagTicket:
 
 class ScoreTicket:
     """The per-image score counts of one step on their way to the host (the GuardTicket pattern): per matrix the step scored - "main"
-    (self.hist), "conf" (self.hist_conf), "clean" (self.hist_clean), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
+    (self.hist), "conf" (self.hist_conf), "clean" (self.hist_clean), "fill" (self.hist_fill), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
     event recorded behind the last copy on the step's stream.  ready() never blocks; counts() waits for the event."""
 
     def __init__(self):
@@ -208,9 +208,24 @@ def _check_clean(clean):
     return dict(min_region=int(v) if v >= 1 else float(v), connectivity=cc.check_connectivity(clean.get("connectivity", 8)))
 
 
+def _check_fill(fill, clean):
+    """fill= of the pipelines -> dict(radius=None | int) checked by utils/label_fill.py, or None.  It fills what the cleaning removed."""
+    if fill is None:
+        return None
+    from .utils import label_fill as lf
+    if not isinstance(fill, dict) or set(fill) - {"radius"}:
+        raise ValueError(f"fill must be dict(radius=None | pixels) (got {fill!r})")
+    radius = fill.get("radius")
+    radius = None if radius is None or (isinstance(radius, str) and radius == "inf") else radius
+    lf.radius_rule(radius)
+    if clean is None:
+        raise ValueError(f"fill needs clean (fill={fill!r}): the main arg-max map has no 255 pixel, there is nothing to fill")
+    return dict(radius=None if radius is None else int(radius))
+
+
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -251,10 +266,19 @@ class TrainingFreePipeline:
         `last_clean_labels` (flat uint8 like the labels) and the per-image counts (regions, regions removed, pixels removed) in
         `last_clean_counts` (int32 [B,3]) on the device until the next step; with ground truth the kept pixels go into `hist_clean`,
         and with image_scores the step's ScoreTicket gets a set named "clean".  The returned labels are untouched; the uniform and
-        multi-stream paths refuse the option."""
+        multi-stream paths refuse the option.
+        `fill` = dict(radius=None | pixels) (utils/label_fill.py), None by default (no launch); it needs `clean`.  Behind the cleaning,
+        every pixel the cleaning turned into 255 takes the value of the nearest class pixel of its image (within `radius`, None =
+        unlimited; the main labels are the mask, so a 255 they already had stays): the filled maps stay in `last_fill_labels`, the
+        squared distances in `last_fill_dist2` (int32, like the labels) and the per-image counts (holes, filled, largest squared
+        distance) in `last_fill_counts` (int32 [B,3]) until the next step; with ground truth the filled maps go into `hist_fill`, and
+        with image_scores the step's ScoreTicket gets a set named "fill".  The main and cleaned outputs are untouched."""
         self.clean = _check_clean(clean)
         self.hist_clean = None
         self.last_clean_labels = self.last_clean_counts = None
+        self.fill = _check_fill(fill, self.clean)
+        self.hist_fill = None
+        self.last_fill_labels = self.last_fill_counts = self.last_fill_dist2 = None
         from .utils import bkg_sweep as _bkg
         self.bkg_sweep = _bkg.check_scales(bkg_sweep) if bkg_sweep is not None else None
         self.bkg_scale = _bkg.check_scale(bkg_scale)
@@ -298,6 +322,7 @@ class TrainingFreePipeline:
         self.hist = None
         self.hist_conf = None
         self.hist_clean = None
+        self.hist_fill = None
         self.sweep_totals = None
 
     def _buf(self, name, numel, dtype=torch.float32, device=None):
@@ -358,7 +383,7 @@ class TrainingFreePipeline:
         """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
         hist = getattr(self, into)
         if self.image_scores:
-            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
+            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean", "hist_fill": "fill"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
         if self.guard == "skip":
             return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, hist, plan=plan)
         return ops.confusion_accumulate(gts, labels, self.num_classes, hist)                       # evaluate.py:9-20
@@ -407,6 +432,18 @@ class TrainingFreePipeline:
         self.last_clean_labels, self.last_clean_counts = cc.filter_small_regions(labels, comp, area, thr, self.num_classes, plan=plan)
         if gts_packed is not None:
             self.hist_clean = self._score(gts_packed, self.last_clean_labels, flags, plan=plan, into="hist_clean")
+
+    def _fill(self, labels, plan, gts_packed, flags):
+        """fill set: what _clean removed takes the nearest class of its image, the step's main labels as the mask; score the filled maps
+        (all on the step's stream, no synchronisation)."""
+        from .utils import label_fill as lf
+        dev, n = labels.device, plan.total_label_pix
+        self.last_fill_labels, self.last_fill_dist2, self.last_fill_counts = lf.fill_nearest_label(
+            self.last_clean_labels, self.num_classes, plan=plan, mask=labels, radius=self.fill["radius"],
+            out=(self._buf("fill_labels", n, torch.uint8, dev), self._buf("fill_dist2", n, torch.int32, dev),
+                 self._buf("fill_counts", 3 * plan.B, torch.int32, dev)))
+        if gts_packed is not None:
+            self.hist_fill = self._score(gts_packed, self.last_fill_labels, flags, plan=plan, into="hist_fill")
 
     def _no_guard(self, what):
         if self.guard is not None:
@@ -589,6 +626,8 @@ class TrainingFreePipeline:
                                                  totals=self.sweep_totals)[0]
         if self.clean is not None:
             self._clean(labels, plan, gts_packed, flags)
+            if self.fill is not None:
+                self._fill(labels, plan, gts_packed, flags)
         if conf is None:
             if return_intermediates:
                 return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
@@ -728,7 +767,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         _refuse_tagger("OptimisedLamPipeline", tagger)
@@ -736,7 +775,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -800,7 +839,7 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         _refuse_tagger("ValidationPipeline", tagger)
@@ -810,7 +849,7 @@ class ValidationPipeline(TrainingFreePipeline):
             raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
                              "histograms per step and is out of the guard's scope")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill)
         self.attn_layers = attn_layers
         self.hist_seg = None
 

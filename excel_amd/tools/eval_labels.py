@@ -15,7 +15,12 @@ ops.boundary_scores on the device, image_scores.boundary_counts_numpy without on
 8|4) cleans the maps of --pred_dir first - every connected class region below VALUE (pixels, or a fraction of the image area) becomes 255:
 utils/components.label_components + filter_small_regions on the device, components.clean_numpy without one -, scores the cleaned maps as
 a second table (clean_label_score, with the coverage and the region counts) and, with `--clean_label_dir DIR`, writes them there as
-palette PNGs.  The first table is unchanged.  This is the route for CRF labels and for labels from elsewhere.
+palette PNGs.  The first table is unchanged.  This is the route for CRF labels and for labels from elsewhere.  `--fill_ignore inf|PIXELS`
+gives 255 pixels the value of the nearest class pixel of their image (utils/label_fill.fill_nearest_label on the device, fill_numpy
+without one; exact squared Euclidean distance, ties to the first pixel in raster order, at most PIXELS away): with --clean_min_region
+the pixels the cleaning removed (the map before the cleaning is the mask: a 255 it already had stays), without it every 255 of the
+predictions.  The filled maps are scored as one more table (fill_label_score, with holes, filled, largest distance and coverage) and,
+with `--fill_label_dir DIR`, written there.  Same tables and files with and without a GPU.
 """
 import argparse
 import concurrent.futures as cf
@@ -45,6 +50,8 @@ def get_parser():
     image_scores.add_boundary_flags(p)
     from ..utils import components
     components.add_flags(p)
+    from ..utils import label_fill
+    label_fill.add_flags(p)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -90,9 +97,10 @@ def _hist_numpy(gt, pred, nc):
 def validate(args):
     """-> {"score": scores_from_hist of the gathered matrix, "hist": [nc,nc] int64 (CPU tensor), "images": scored on this rank,
     "seconds"}: the layout of infer_seg_voc.validate (+ "image_scores" with --per_image_scores)."""
-    from ..utils import components, evaluate, image_scores
+    from ..utils import components, evaluate, image_scores, label_fill
     image_scores.refuse(args)
     clean = components.resolve(args, program="eval_labels")
+    fill = label_fill.resolve(args, program="eval_labels")
     names_fg = None
     if getattr(args, "class_names", None):
         from .infer_lam import _read_names
@@ -119,12 +127,16 @@ def validate(args):
     hist_clean, clean_rows = (torch.zeros_like(hist) if clean is not None else None), []
     if clean is not None and clean["label_dir"]:
         os.makedirs(clean["label_dir"], exist_ok=True)
+    hist_fill, fill_rows = (torch.zeros_like(hist) if fill is not None else None), []
+    if fill is not None and fill["label_dir"]:
+        os.makedirs(fill["label_dir"], exist_ok=True)
     t0 = time.time()
     with cf.ThreadPoolExecutor(max_workers=max(1, int(args.num_workers))) as pool:
         for s in range(0, len(mine), args.batch_size):
             pairs = list(pool.map(lambda n: _load_pair(args, n), mine[s:s + args.batch_size]))       # raises the first error, in order
             gt = np.concatenate([p[0] for p in pairs])
             pred = np.concatenate([p[1] for p in pairs])
+            hws = [p[2] for p in pairs]
             if on_gpu:
                 from .. import ops
                 gt_d, pred_d = torch.from_numpy(gt).to(device), torch.from_numpy(pred).to(device)
@@ -162,6 +174,28 @@ def validate(args):
                     for n, (h, w) in zip(mine[s:s + len(pairs)], hws):
                         _save_index_png(os.path.join(clean["label_dir"], n + ".png"), cleaned[off:off + h * w].reshape(h, w))
                         off += h * w
+            if fill is not None:                                 # the filled maps: what the cleaning removed, or every 255 of the predictions
+                if on_gpu:
+                    src_d, mask_d = (cleaned_d, pred_d) if clean is not None else (pred_d, None)
+                    filled_d, _, counts_d = label_fill.fill_nearest_label(src_d, nc, plan=ops.RaggedPlan(hws, device), mask=mask_d, radius=fill["radius"])
+                    hist_fill = ops.confusion_accumulate(gt_d, filled_d, nc, hist_fill)
+                    filled, counts = filled_d.cpu().numpy(), counts_d.cpu().numpy()
+                else:
+                    src, off, done = (cleaned if clean is not None else pred), 0, []
+                    for p in pairs:
+                        n_pix = p[2][0] * p[2][1]
+                        done.append(label_fill.fill_numpy(src[off:off + n_pix].reshape(p[2]), nc, radius=fill["radius"],
+                                                          mask=p[1].reshape(p[2]) if clean is not None else None))
+                        off += n_pix
+                    filled = np.concatenate([d[0].reshape(-1) for d in done])
+                    counts = np.stack([d[2] for d in done])
+                    hist_fill += torch.from_numpy(_hist_numpy(gt, filled, nc))
+                fill_rows.extend(np.asarray(counts, np.int64).reshape(-1, 3).tolist())
+                if fill["label_dir"]:
+                    off = 0
+                    for n, (h, w) in zip(mine[s:s + len(pairs)], hws):
+                        _save_index_png(os.path.join(fill["label_dir"], n + ".png"), filled[off:off + h * w].reshape(h, w))
+                        off += h * w
     _, total = gather_hists(hist)
     total = total.cpu()
     score = evaluate.scores_from_hist(total)
@@ -196,6 +230,22 @@ def validate(args):
             logging.info(components.format_clean_summary(out["clean"]["stats"], out["clean"]["coverage"]))
             if clean["label_dir"]:
                 logging.info(f"cleaned label maps -> {clean['label_dir']}")
+    if fill is not None:
+        _, fill_total = gather_hists(hist_fill)
+        fill_total = fill_total.cpu()
+        parts = [fill_rows]
+        if world > 1:
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, fill_rows)
+        counts = np.asarray([r for part in parts for r in part], np.int64).reshape(-1, 3)
+        out["fill"] = dict(score=evaluate.scores_from_hist(fill_total), hist=fill_total, coverage=components.coverage(fill_total, total),
+                           counts=counts, stats=label_fill.fill_stats(counts), radius=fill["radius"])
+        if rank == 0:
+            logging.info(f"fill_label_score of {args.pred_dir} (--fill_ignore {'inf' if fill['radius'] is None else fill['radius']}):")
+            logging.info("\n" + format_scores_table(out["fill"]["score"], cats))
+            logging.info(label_fill.format_fill_summary(out["fill"]["stats"], out["fill"]["coverage"]))
+            if fill["label_dir"]:
+                logging.info(f"filled label maps -> {fill['label_dir']}")
     if scores is not None:
         out["image_scores"] = merged                           # the merged table (utils/image_scores.ImageScoreLog.merged)
     return out

@@ -94,6 +94,14 @@ Differences from the reference, all deliberate:
     PNGs are untouched.  Ragged batches on the batched loop only (refused with --api_path true); with --unlabeled true nothing is
     scored and --clean_label_dir is required; off by default (no launch, no key, no column).  The conf and crf label sets are not
     cleaned here: their PNGs can go through eval_labels --clean_min_region;
+  * `--fill_ignore inf|PIXELS` (`--fill_label_dir DIR`; needs --clean_min_region): the other half of the cleaning.  Behind the filter,
+    utils/label_fill.fill_nearest_label gives every pixel the cleaning turned into 255 the value of the nearest class pixel of its image
+    (exact squared Euclidean distance, ties to the first pixel in raster order, at most PIXELS away), so a pin-hole inside an object
+    becomes object again; an ignore pixel the main map already had would stay.  The filled maps are one more scored label set, by the
+    cleaned set's route: `<fill_label_dir>/<name>.png`, a fill_label_score table, one summary line (holes, filled, largest distance,
+    coverage), a `fill` block in --json_out, fill_* columns plus holes, filled and max_fill_dist in --per_image_scores.  The main, conf,
+    crf and clean outputs are untouched.  Refused without --clean_min_region, with --api_path true, and with --unlabeled true unless
+    --fill_label_dir is given; off by default (no launch, no key, no column).  Conf and crf PNGs go through eval_labels --fill_ignore;
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -188,7 +196,8 @@ def resolve_tags(args, have_dataset=False):
             raise ValueError("--unlabeled true has no ground truth to score: --crf_post scores the DenseCRF labels against it - drop one of the two")
         if args.api_path:
             raise ValueError("--unlabeled true runs on the batched loop: --api_path true scores every image against its ground truth")
-        if not (args.save_label or args.conf_label or args.save_tags or getattr(args, "clean_label_dir", None)):
+        if not (args.save_label or args.conf_label or args.save_tags or getattr(args, "clean_label_dir", None)
+                or getattr(args, "fill_label_dir", None)):
             raise ValueError("--unlabeled true scores nothing, so the run must write something: give at least one of --save_label true, "
                              "--conf_label true, --save_tags PATH")
     if args.save_tags and args.tags != "clip":
@@ -448,6 +457,8 @@ def get_parser():
     bkg_sweep.add_flags(p)
     from ..utils import components
     components.add_flags(p)
+    from ..utils import label_fill
+    label_fill.add_flags(p)
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
     p.set_defaults(ragged_batches=False, run_token=None, vocab=None, num_classes_given=False)      # what the program sets itself
     return p
@@ -853,6 +864,11 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     clean_kw = dict(min_region=clean["min_region"], connectivity=clean["connectivity"]) if clean is not None else None
     if clean is not None:
         bkg_kw = {**bkg_kw, "clean": clean_kw}
+    from ..utils import label_fill
+    fill = label_fill.resolve(args)
+    fill_kw = dict(radius=fill["radius"]) if fill is not None else None
+    if fill is not None:
+        bkg_kw = {**bkg_kw, "fill": fill_kw}
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
                   smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
@@ -871,22 +887,24 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError(f"--boundary_scores: the supplied pipeline was built with boundary={getattr(pipe, 'boundary', None)!r}, the flags ask for {boundary!r}")
     if clean is not None and pipe is not None and getattr(pipe, "clean", None) != clean_kw:
         raise ValueError(f"--clean_min_region: the supplied pipeline was built with clean={getattr(pipe, 'clean', None)!r}, the flags ask for {clean_kw!r}")
+    if fill is not None and pipe is not None and getattr(pipe, "fill", None) != fill_kw:
+        raise ValueError(f"--fill_ignore: the supplied pipeline was built with fill={getattr(pipe, 'fill', None)!r}, the flags ask for {fill_kw!r}")
     for k, want in (("bkg_sweep", sweep), ("bkg_scale", bkg_scale)):
         if (sweep is not None or bkg_scale != 1.0) and pipe is not None and getattr(pipe, k, None if k == "bkg_sweep" else 1.0) != want:
             raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None, fill=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
-                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean, fill=fill,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
     # --per_image_scores: the rank's table of per-image counts, one set per matrix the run scores (utils/image_scores.py)
     run.scores = report["image_scores"] = image_scores.ImageScoreLog(
         args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else [])
-        + (["clean"] if clean is not None and not args.unlabeled else []),
-        boundary=boundary, **({"regions": True} if clean is not None else {})) if want_scores else None
+        + (["clean"] if clean is not None and not args.unlabeled else []) + (["fill"] if fill is not None and not args.unlabeled else []),
+        boundary=boundary, **({"regions": True} if clean is not None else {}), **({"fills": True} if fill is not None else {})) if want_scores else None
     try:
         for wanted, needs in ((args.save_cam, "--save_cam needs the decoded images"), (conf is not None, "--conf_label runs behind the ragged step"),
                               (crf_inline_wanted(args), "--crf_inline needs the decoded images")):
@@ -904,6 +922,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
                 args.model_path, args.infer_set, bool(args.training_free), bool(args.refine_with_aff)))
         if clean is not None and clean["label_dir"]:
             run.consumers["clean_lab"] = _LabelSaver(args, clean["label_dir"])
+        if fill is not None and fill["label_dir"]:
+            run.consumers["fill_lab"] = _LabelSaver(args, fill["label_dir"])
         out = (_per_image_loop if per_image else _batched_loop)(run)
     except BaseException:
         _close_consumers(run, failed=True)
@@ -917,6 +937,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         build_validation.last_image_scores = report["image_scores"]
         build_validation.last_bkg_sweep = report["bkg_sweep"]
         build_validation.last_clean = report["clean"]
+        build_validation.last_fill = report["fill"]
     return out
 
 
@@ -1030,10 +1051,13 @@ def _batched_loop(run):
         pipe.hist_conf = torch.zeros_like(run.hist)
     if run.sweep is not None:                                # --bkg_sweep: the pipeline adds every step's counts per scale (both passes of the guard)
         pipe.sweep_totals = torch.zeros((len(run.sweep), 3, args.num_classes), dtype=torch.int64, device=device)
-    clean_lab = run.consumers.get("clean_lab")
+    clean_lab, fill_lab = run.consumers.get("clean_lab"), run.consumers.get("fill_lab")
     clean_pending, clean_rows = deque(), {}                  # --clean_min_region: (pinned counts, event, dataset indices, names) -> index: (name, row)
+    fill_pending, fill_rows = deque(), {}                    # --fill_ignore: the same, for the fill's rows
     if run.clean is not None:
         pipe.hist_clean = torch.zeros_like(run.hist)
+    if run.fill is not None:
+        pipe.hist_fill = torch.zeros_like(run.hist)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
         from ..datasets.loader import DeviceFeeder, ragged_batches, threaded_batches
@@ -1079,6 +1103,8 @@ def _batched_loop(run):
             lab.ragged(names, plan, out[0] if keep else out)
         if clean_lab is not None:                                                       # same stream, the step's cleaned maps
             clean_lab.ragged(names, plan, pipe.last_clean_labels)
+        if fill_lab is not None:                                                        # likewise, the step's filled maps
+            fill_lab.ragged(names, plan, pipe.last_fill_labels)
         if keep:                                                                        # :116-119 record for the CRF stage
             inter = out[1]
             cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
@@ -1160,29 +1186,34 @@ def _batched_loop(run):
                 if truth is not None:
                     tag_truth[n] = np.array(truth[b], np.float32)
 
+    # what differs between the two sets of per-image rows: (the pipeline's device rows, the queue, the collected rows, the table's sink)
+    row_sets = {"clean": ("last_clean_counts", clean_pending, clean_rows, "put_regions"), "fill": ("last_fill_counts", fill_pending, fill_rows, "put_fills")}
+
     def clean_enqueue(names, idxs):
-        """The filter's per-image counts of the step just enqueued, on their way to the host behind an event (no wait here)."""
-        dev = pipe.last_clean_counts
-        host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=on_gpu)
-        host.copy_(dev, non_blocking=True)
-        ev = None
-        if on_gpu:
-            ev = torch.cuda.Event()
-            ev.record()
-        clean_pending.append((host, ev, [int(i) for i in idxs], [str(n) for n in names], [tuple(int(x) for x in hw) for hw in step_hw[0]]))
+        """The filter's (and the fill's) per-image counts of the step just enqueued, on their way to the host behind an event (no wait here)."""
+        for which in (["clean"] + (["fill"] if run.fill is not None else [])):
+            dev = getattr(pipe, row_sets[which][0])
+            host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=on_gpu)
+            host.copy_(dev, non_blocking=True)
+            ev = None
+            if on_gpu:
+                ev = torch.cuda.Event()
+                ev.record()
+            row_sets[which][1].append((host, ev, [int(i) for i in idxs], [str(n) for n in names], [tuple(int(x) for x in hw) for hw in step_hw[0]]))
         clean_take(False)
 
     def clean_take(wait):
         """A later row of an image (the fp32 second pass) replaces the earlier one."""
-        while clean_pending and (wait or clean_pending[0][1] is None or clean_pending[0][1].query()):
-            host, ev, idxs, names, hws = clean_pending.popleft()
-            if ev is not None:
-                ev.synchronize()
-            rows = host.numpy()
-            for b, i in enumerate(idxs):
-                clean_rows[i] = (names[b], rows[b].astype(np.int64))
-            if scores is not None:
-                scores.put_regions(idxs, names, hws, rows)
+        for _, pending, rows_of, sink in row_sets.values():
+            while pending and (wait or pending[0][1] is None or pending[0][1].query()):
+                host, ev, idxs, names, hws = pending.popleft()
+                if ev is not None:
+                    ev.synchronize()
+                rows = host.numpy()
+                for b, i in enumerate(idxs):
+                    rows_of[i] = (names[b], rows[b].astype(np.int64))
+                if scores is not None:
+                    getattr(scores, sink)(idxs, names, hws, rows)
 
     nimg, pos, flagged = 0, 0, {}
     for names in steps(indices):
@@ -1242,6 +1273,8 @@ def _batched_loop(run):
     if run.clean is not None:
         clean_take(True)
         run.report["clean"] = dict(hist=pipe.hist_clean, rows=clean_rows)
+        if run.fill is not None:
+            run.report["fill"] = dict(hist=pipe.hist_fill, rows=fill_rows)
     if scores is not None:
         scores.poll(True)
     if tagger is not None:
@@ -1404,10 +1437,12 @@ def validate(args=None, dataset=None, pipe=None):
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
     validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = validate.last_clean = None
-    from ..utils import bkg_sweep, components, image_scores
+    validate.last_fill = None
+    from ..utils import bkg_sweep, components, image_scores, label_fill
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))                                # ... and per-image scores of nothing
     sweep, _ = bkg_sweep.resolve(args)                                                       # ... and a sweep nobody can score or run
     clean = components.resolve(args)                                                         # ... and a cleaning nobody can run or see
+    fill = label_fill.resolve(args)                                                          # ... and a fill of nothing
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
@@ -1486,10 +1521,10 @@ def validate(args=None, dataset=None, pipe=None):
         _, sweep_total = gather_hists(build_validation.last_bkg_sweep)
         sweep_scores = bkg_sweep.scores_from_totals(sweep_total)
         validate.last_bkg_sweep = dict(scales=sweep, totals=sweep_total, scores=sweep_scores, best_scale=bkg_sweep.best_scale(sweep_scores, sweep)[1])
-    if clean is not None:
-        # --clean_min_region: the kept pixels' matrix summed over the ranks once, the per-image rows gathered once (every rank joins)
-        mine = build_validation.last_clean or {"hist": torch.zeros_like(hist), "rows": {}}
-        _, clean_total = gather_hists(mine["hist"] if mine["hist"] is not None else torch.zeros_like(hist))
+    def gathered_set(mine):
+        """One more scored label set: its matrix summed over the ranks once, its per-image rows gathered once (every rank joins)."""
+        mine = mine or {"hist": torch.zeros_like(hist), "rows": {}}
+        _, set_total = gather_hists(mine["hist"] if mine["hist"] is not None else torch.zeros_like(hist))
         parts = [mine["rows"]]
         if world > 1:
             parts = [None] * world
@@ -1499,10 +1534,14 @@ def validate(args=None, dataset=None, pipe=None):
             rows.update(part)
         order = sorted(rows)
         counts = np.stack([rows[i][1] for i in order]) if order else np.zeros((0, 3), np.int64)
-        clean_score = None if args.unlabeled else evaluate.scores_from_hist(clean_total)
-        validate.last_clean = dict(min_region=clean["min_region"], connectivity=clean["connectivity"], score=clean_score, hist=clean_total,
-                                   coverage=None if args.unlabeled else components.coverage(clean_total, total),
-                                   names=[rows[i][0] for i in order], counts=counts, stats=components.region_stats(counts))
+        return dict(score=None if args.unlabeled else evaluate.scores_from_hist(set_total), hist=set_total,
+                    coverage=None if args.unlabeled else components.coverage(set_total, total), names=[rows[i][0] for i in order], counts=counts)
+    if clean is not None:                                                                   # --clean_min_region: the kept pixels
+        got = gathered_set(build_validation.last_clean)
+        validate.last_clean = dict(min_region=clean["min_region"], connectivity=clean["connectivity"], stats=components.region_stats(got["counts"]), **got)
+    if fill is not None:                                                                    # --fill_ignore: the filled maps
+        got = gathered_set(build_validation.last_fill)
+        validate.last_fill = dict(radius=fill["radius"], stats=label_fill.fill_stats(got["counts"]), **got)
     tags = None
     if tagger is not None:
         # the predicted rows of every rank, once: every rank joins, also one whose shard is empty
@@ -1545,6 +1584,14 @@ def validate(args=None, dataset=None, pipe=None):
             logging.info(components.format_clean_summary(c["stats"], c["coverage"]))
             if clean["label_dir"]:
                 logging.info(f"cleaned label maps -> {clean['label_dir']}")
+        if fill is not None:
+            c = validate.last_fill
+            if c["score"] is not None:
+                logging.info(f"fill_label_score (--fill_ignore {'inf' if fill['radius'] is None else fill['radius']}):")
+                logging.info("\n" + format_scores_table(c["score"], cat_list))
+            logging.info(label_fill.format_fill_summary(c["stats"], c["coverage"]))
+            if fill["label_dir"]:
+                logging.info(f"filled label maps -> {fill['label_dir']}")
         if tags is not None:
             logging.info(f"tags (--tags clip, thre {tagger['thre']}, at most {tagger['kmax']}, scale {tagger['scale']}): {tags['images']} images, "
                          f"tags per image {dict((k, v) for k, v in enumerate(tags['tags_per_image']) if v)}"
@@ -1570,7 +1617,9 @@ def validate(args=None, dataset=None, pipe=None):
                            **({"bkg_sweep": bkg_sweep.sweep_json(sweep_scores, sweep)} if sweep is not None else {}),
                            **({"clean": components.clean_json(clean["min_region"], clean["connectivity"], validate.last_clean["stats"],
                                                               validate.last_clean["score"], validate.last_clean["coverage"])}
-                              if clean is not None else {})}, f)
+                              if clean is not None else {}),
+                           **({"fill": label_fill.fill_json(fill["radius"], validate.last_fill["stats"], validate.last_fill["score"],
+                                                            validate.last_fill["coverage"])} if fill is not None else {})}, f)
     if image_scores.wanted(args):                                                           # one all_gather_object, rank 0 writes
         validate.last_image_scores = image_scores.finish(build_validation.last_image_scores, args, cat_list, rank, what="LAM_score")
         if rank == 0 and args.json_out and image_scores.boundary_of(args) is not None:       # the record above gains its `boundary` block

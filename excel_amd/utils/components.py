@@ -12,10 +12,11 @@ The arg-max over PAR's output leaves islands of a few pixels and pin-holes of ba
     min_area_rule          the flag's value -> pixels: an integer >= 1 is pixels, a fraction in (0, 1) is a share of the image's area
     clean_json, format_clean_summary, add_flags, resolve   what the programs report, their flags and refusals
 
-Not done here, on purpose: filling a removed region with a neighbouring class instead of 255; an ignore band along the contours; a sweep
-over several minimum sizes in one run (the API allows it: one label_components, one filter_small_regions per size); the `conf` and `crf`
-label sets of infer_lam (their PNGs can go through eval_labels).  Whether the score on the kept pixels improves on real data is
-unmeasured: no real checkpoint or data set is available to this project.
+Filling what was removed with the nearest class instead of leaving 255 is utils/label_fill.py (--fill_ignore), the step behind this one.
+Not done here, on purpose: an ignore band along the contours; a sweep over several minimum sizes in one run (the API allows it: one
+label_components, one filter_small_regions per size); the `conf` and `crf` label sets of infer_lam (their PNGs can go through eval_labels
+--clean_min_region and --fill_ignore).  Whether the score on the kept pixels improves on real data is unmeasured: no real checkpoint or
+data set is available to this project.
 """
 import ctypes as C
 

@@ -22,6 +22,10 @@ here changes: same columns, same bytes.
 --clean_min_region (infer_lam; utils/components.py): the cleaned labels are one more set, "clean", and every image also has a row
 (regions, regions removed, pixels removed) of the filter: the files gain `clean_pacc, clean_miou, clean_scored` and, last, `regions,
 regions_removed, pixels_removed`, the npz `counts_clean` and `regions`.  Without the flag, again, nothing changes.
+
+--fill_ignore (infer_lam; utils/label_fill.py): the filled labels are one more set, "fill", by the same route, and every image has a row
+(holes, holes filled, largest squared distance) of the fill: the files gain `fill_pacc, fill_miou, fill_scored` and, last of all, `holes,
+filled, max_fill_dist` (the distance in pixels), the npz `counts_fill` and `fills` (the raw rows).  Without the flag nothing changes.
 """
 import csv
 import logging
@@ -33,7 +37,7 @@ import numpy as np
 
 from .evaluate import boundary_scores_from_counts, image_score_rows
 
-SETS = ("main", "crf", "conf", "clean")
+SETS = ("main", "crf", "conf", "clean", "fill")
 MAX_RADIUS = 72              # what ops.boundary_max_radius() answers (boundary.hip's halo); the CPU path refuses the same radii
 
 
@@ -168,11 +172,14 @@ class ImageScoreLog:
     """The records of one rank: index -> (name, (H, W), {set: counts int64 [3,nc]}).  put() replaces what an earlier pass recorded for the
     same image and set (the overflow guard's exact-fp32 second pass); defer() takes a ticket and reads it when it is ready."""
 
-    def __init__(self, num_classes, sets=("main",), boundary=None, regions=False):
+    def __init__(self, num_classes, sets=("main",), boundary=None, regions=False, fills=False):
         """boundary = None | dict(ratio=, px=): with it every set has a twin "<set>_bd" (ops.boundary_scores' counts) that is recorded
         and required like the set itself, and merged() adds the radius of every image.  regions (--clean_min_region): every image also
-        has a row (regions, regions removed, pixels removed) of utils/components.filter_small_regions, put_regions() records it."""
+        has a row (regions, regions removed, pixels removed) of utils/components.filter_small_regions, put_regions() records it.
+        fills (--fill_ignore): likewise a row (holes, holes filled, largest squared distance) of utils/label_fill.fill_nearest_label,
+        put_fills() records it."""
         self.regions = bool(regions)
+        self.fills = bool(fills)
         bad = [s for s in sets if s not in SETS]
         if bad or "main" not in sets:
             raise ValueError(f"image score sets {tuple(sets)}: 'main' plus any of {SETS[1:]}")
@@ -196,6 +203,12 @@ class ImageScoreLog:
         for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
             rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
             rec[2]["regions"] = np.array(counts[b], np.int64).reshape(3)
+
+    def put_fills(self, indices, names, hws, counts):
+        """counts [B,3]: the fill's rows of one step; a later row of an image replaces the earlier one."""
+        for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
+            rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
+            rec[2]["fills"] = np.array(counts[b], np.int64).reshape(3)
 
     def put_batch(self, indices, names, hws, which, counts):
         for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
@@ -230,7 +243,7 @@ class ImageScoreLog:
             allrec.update(p)
         order = sorted(allrec)
         for i in order:
-            missing = [s for s in self.sets + self.twins + (("regions",) if self.regions else ()) if s not in allrec[i][2]]
+            missing = [s for s in self.sets + self.twins + (("regions",) if self.regions else ()) + (("fills",) if self.fills else ()) if s not in allrec[i][2]]
             if missing:
                 raise RuntimeError(f"image scores: {allrec[i][0]!r} has no counts for {missing}")
         stack = lambda s: np.stack([allrec[i][2][s] for i in order]) if order else np.zeros((0, 3, self.nc), np.int64)
@@ -241,6 +254,8 @@ class ImageScoreLog:
             out["bcounts"] = {s: stack(s + "_bd") for s in self.sets}
         if self.regions:                                      # likewise
             out["regions"] = np.stack([allrec[i][2]["regions"] for i in order]) if order else np.zeros((0, 3), np.int64)
+        if self.fills:
+            out["fills"] = np.stack([allrec[i][2]["fills"] for i in order]) if order else np.zeros((0, 3), np.int64)
         return out
 
 
@@ -259,12 +274,14 @@ def write_files(path, merged, class_names):
     bhead = ["radius", "biou"] + [f"{s}_biou" for s in extra] if brows else []
     regions = merged.get("regions")
     rhead = ["regions", "regions_removed", "pixels_removed"] if regions is not None else []
+    fills = merged.get("fills")
+    fhead = ["holes", "filled", "max_fill_dist"] if fills is not None else []
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["name", "height", "width", "scored", "pacc", "miou", "present"] + ["iou_" + c for c in cats]
-                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead + rhead)
+                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead + rhead + fhead)
         for i, name in enumerate(merged["names"]):
             present = "|".join(cats[c] for c in np.nonzero(merged["counts"]["main"][i, 0])[0])
             w.writerow([name, int(merged["hw"][i, 0]), int(merged["hw"][i, 1]), int(main["scored"][i]), _fmt(main["pacc"][i]),
@@ -272,12 +289,15 @@ def write_files(path, merged, class_names):
                        + [x for s in extra for x in (_fmt(rows[s]["pacc"][i]), _fmt(rows[s]["miou"][i]), int(rows[s]["scored"][i]))]
                        + ([int(merged["radius"][i]), _fmt(brows["main"]["miou"][i])] + [_fmt(brows[s]["miou"][i]) for s in extra]
                           if brows else [])
-                       + ([int(v) for v in regions[i]] if regions is not None else []))
+                       + ([int(v) for v in regions[i]] if regions is not None else [])
+                       + ([int(fills[i][0]), int(fills[i][1]), _fmt(np.sqrt(float(fills[i][2])))] if fills is not None else []))
     more = {}
     if brows:
         more = dict(radius=merged["radius"].astype(np.int32), **{"bcounts_" + s: c.astype(np.int64) for s, c in merged["bcounts"].items()})
     if regions is not None:
         more["regions"] = np.asarray(regions, np.int64)
+    if fills is not None:
+        more["fills"] = np.asarray(fills, np.int64)
     np.savez(path + ".npz", names=np.asarray(merged["names"], dtype=str), hw=merged["hw"],
              **{"counts_" + s: c.astype(np.int64) for s, c in merged["counts"].items()}, **more)
     return main
@@ -302,7 +322,7 @@ def report_lines(merged, rows, k, what="label_score"):
     return lines
 
 
-BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels", "clean": "cleaned labels"}
+BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels", "clean": "cleaned labels", "fill": "filled labels"}
 
 
 def boundary_summary(merged):

@@ -587,6 +587,33 @@ int excel_filter_small_regions(const uint8_t* labels, const int32_t* comp, const
                                const excel_ragged_info* info, const int32_t* min_area /*device [B] or NULL*/, int min_area_all,
                                int num_classes, uint8_t* out, int32_t* counts /*device [B,3]*/, void* stream);
 
+/* ------------------------------------------------------------------ nearest-label fill
+ * The other half of the cleaning above: a removed pixel takes the class it sits in.  An exact Euclidean nearest-label transform in
+ * integers (squared distances); the result is canonical.  Images are addressed exactly as in excel_label_components: table == NULL means
+ * B uniform [H,W] maps; otherwise the tight u8 maps of the ragged plan (row pitch W_b, image b at loff_b; H, W ignored, info->B == B).
+ * labels, mask and out may start at any byte address; dist2 uses the same pixel indexing, 4-byte aligned.
+ *   seed   a pixel with labels < num_classes (a mask never un-seeds a pixel);
+ *   hole   a pixel with labels == 255, and with mask[i] != 255 when mask is given (mask: a second map with the same addressing, e.g. the
+ *          map before the cleaning - what was 255 there stays 255); with mask == NULL every 255 pixel is a hole;
+ *   other  values in [num_classes, 255) are neither: they pass through and block nothing.
+ * For a hole p = (py, px) of image b, among the seeds q = (qy, qx) of the SAME image that minimise d2 = (py-qy)^2 + (px-qx)^2 take the
+ * first in raster order (the smallest qy, then the smallest qx).  If d2 <= max_dist2:  out[p] = labels[q], dist2[p] = d2.  Otherwise, or
+ * when the image has no seed:  out[p] = 255, dist2[p] = -1.  Every other pixel:  out = labels;  dist2 = 0 at seeds and -1 elsewhere.
+ * Nothing reaches across images (not even between the last pixel of image b and the first of image b + 1 in the tight layout).
+ *   counts[b] = (holes, holes filled, the largest d2 of a filled hole or 0), device int32 [B,3], cleared on the stream.
+ * Every element of out, dist2 and counts is written and none is read before it is written, except what this entry wrote earlier in the
+ * same call: dist2 carries the intermediate (per pixel the row of the nearest seed of its column) between the two launches - a column
+ * pass, then a row pass whose every workgroup reads only its own row of it (csrc/fill.hip).  No workspace and no size query, no host synchronisation, no
+ * scratch memory, everything on `stream`; no workgroup waits for another, every loop is bounded by a side of the image.
+ * EXCEL_ERR_ARG before any launch for: a null labels, out, dist2 or counts; out overlapping labels or mask; num_classes outside 1..255;
+ * max_dist2 < 1; B outside [1, 65535]; a uniform image higher or wider than 8192 (d2 then fits 28 bits and a row of candidates fits in
+ * LDS); a total outside [1, 2^31); dist2 or counts not 4-byte aligned.  The sizes of a ragged batch live in the device table, which the
+ * host entry does not read: there an image beyond 8192 a side is refused by the kernels, never clamped - its map is copied, its dist2 is
+ * 0 at seeds and -1 elsewhere, and its counts row is -1 (utils/label_fill.py refuses such a plan on the host). */
+int excel_fill_nearest_label(const uint8_t* labels, const uint8_t* mask /*or NULL*/, int B, int H, int W, const int32_t* table,
+                             const excel_ragged_info* info, int num_classes, int max_dist2, uint8_t* out,
+                             int32_t* dist2 /*device, one per pixel*/, int32_t* counts /*device [B,3]*/, void* stream);
+
 /* ------------------------------------------------------------------ image tags: the one-hot rows excel_cls_compact reads, predicted
  * Row 0 of the tower's x_raw is CLIP's own image embedding: the reference puts the class token of the original attention path back
  * before ln_post / proj (clip/clip_surgery_model.py:442-446).  The reference never tags images itself (weakly-supervised segmentation
