@@ -192,6 +192,8 @@ SIGNATURES = {
     "excel_label_components": (c_i, [c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f, c_f]),
     "excel_filter_small_regions": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_f, c_i, c_i, c_f, c_f, c_f]),
     "excel_fill_nearest_label": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_i, c_i, c_f, c_f, c_f, c_f]),
+    "excel_slic_superpixels": (c_i, [c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_f, c_ll, c_i, c_i, c_i, c_f, c_f, c_f]),
+    "excel_snap_labels_to_superpixels": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_f, c_ll, c_i, c_i, c_i, c_f, c_f, c_f]),
     "excel_clip_tags": (c_i, [c_f, c_ll, c_f, c_i, c_i, c_i, c_i, C.c_float, C.c_float, c_i, c_f, c_f, c_f]),
     "excel_attr_aggregate": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, C.c_double, c_f, c_f]),
     "excel_bilinear_resize": (c_i, [c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_f]),

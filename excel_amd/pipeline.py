@@ -121,7 +121,7 @@ class TagTicket:
 
 class ScoreTicket:
     """The per-image score counts of one step on their way to the host (the GuardTicket pattern): per matrix the step scored - "main"
-    (self.hist), "conf" (self.hist_conf), "clean" (self.hist_clean), "fill" (self.hist_fill), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
+    (self.hist), "conf" (self.hist_conf), "clean" (self.hist_clean), "fill" (self.hist_fill), "snap" (self.hist_snap), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
     event recorded behind the last copy on the step's stream.  ready() never blocks; counts() waits for the event."""
 
     def __init__(self):
@@ -223,9 +223,23 @@ def _check_fill(fill, clean):
     return dict(radius=None if radius is None else int(radius))
 
 
+def _check_snap(snap):
+    """snap= of the pipelines -> dict(step=, compactness=, iters=, min_share=) checked by utils/superpixels.py, or None."""
+    if snap is None:
+        return None
+    from .utils import superpixels as sx
+    if not isinstance(snap, dict) or "step" not in snap or set(snap) - {"step", "compactness", "iters", "min_share"}:
+        raise ValueError(f"snap must be dict(step=, compactness=10, iters=5, min_share=0.0) (got {snap!r})")
+    step, compactness, iters = sx.check_params(snap["step"], snap.get("compactness", sx.DEFAULTS["compactness"]),
+                                               snap.get("iters", sx.DEFAULTS["iters"]))
+    share = snap.get("min_share", sx.DEFAULTS["min_share"])
+    sx.share_rule(share)
+    return dict(step=step, compactness=compactness, iters=iters, min_share=float(share))
+
+
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -272,13 +286,24 @@ class TrainingFreePipeline:
         unlimited; the main labels are the mask, so a 255 they already had stays): the filled maps stay in `last_fill_labels`, the
         squared distances in `last_fill_dist2` (int32, like the labels) and the per-image counts (holes, filled, largest squared
         distance) in `last_fill_counts` (int32 [B,3]) until the next step; with ground truth the filled maps go into `hist_fill`, and
-        with image_scores the step's ScoreTicket gets a set named "fill".  The main and cleaned outputs are untouched."""
+        with image_scores the step's ScoreTicket gets a set named "fill".  The main and cleaned outputs are untouched.
+        `snap` = dict(step=, compactness=10, iters=5, min_share=0.0) (utils/superpixels.py), None by default (no launch).  With it
+        run_batch_ragged over-segments the step's decoded images into superpixels of grid step `step` (integer SLIC) and gives every
+        superpixel the majority class of the main arg-max labels inside it (only where that class holds at least `min_share` of the
+        votes): the snapped maps stay in `last_snap_labels` (flat uint8 like the labels), the superpixel index of every pixel in
+        `last_snap_sp` (int32) and the per-image counts (superpixels with a vote, snapped, pixels changed) in `last_snap_counts`
+        (int32 [B,3]) until the next step; with ground truth the snapped maps go into `hist_snap`, and with image_scores the step's
+        ScoreTicket gets a set named "snap".  With snap, `clean` and `fill` take the snapped map as their input and mask: the order is
+        snap -> clean -> fill.  The returned labels are untouched; the uniform and multi-stream paths refuse the option."""
         self.clean = _check_clean(clean)
         self.hist_clean = None
         self.last_clean_labels = self.last_clean_counts = None
         self.fill = _check_fill(fill, self.clean)
         self.hist_fill = None
         self.last_fill_labels = self.last_fill_counts = self.last_fill_dist2 = None
+        self.snap = _check_snap(snap)
+        self.hist_snap = None
+        self.last_snap_labels = self.last_snap_counts = self.last_snap_sp = None
         from .utils import bkg_sweep as _bkg
         self.bkg_sweep = _bkg.check_scales(bkg_sweep) if bkg_sweep is not None else None
         self.bkg_scale = _bkg.check_scale(bkg_scale)
@@ -323,6 +348,7 @@ class TrainingFreePipeline:
         self.hist_conf = None
         self.hist_clean = None
         self.hist_fill = None
+        self.hist_snap = None
         self.sweep_totals = None
 
     def _buf(self, name, numel, dtype=torch.float32, device=None):
@@ -383,7 +409,7 @@ class TrainingFreePipeline:
         """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
         hist = getattr(self, into)
         if self.image_scores:
-            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean", "hist_fill": "fill"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
+            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean", "hist_fill": "fill", "hist_snap": "snap"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
         if self.guard == "skip":
             return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, hist, plan=plan)
         return ops.confusion_accumulate(gts, labels, self.num_classes, hist)                       # evaluate.py:9-20
@@ -412,6 +438,29 @@ class TrainingFreePipeline:
         if self.clean is not None:
             raise ValueError(f"{what} has no label cleaning (clean={self.clean}): it runs behind the ragged step - use run_batch_ragged, "
                              "or build the pipeline without clean")
+        if self.snap is not None:
+            raise ValueError(f"{what} has no superpixel snap (snap={self.snap}): it runs behind the ragged step - use run_batch_ragged, "
+                             "or build the pipeline without snap")
+
+    def _snap(self, labels, hwc_packed, plan, gts_packed, flags):
+        """snap set: superpixels of the step's decoded images, the majority vote of the main labels inside each, the score of the
+        snapped maps (all on the step's stream, no synchronisation; the centre offsets are host integers, cached on the plan)."""
+        from .utils import superpixels as sx
+        if hwc_packed is None:
+            raise ValueError("snap needs the step's decoded images (hwc_packed)")
+        dev, n, k = labels.device, plan.total_label_pix, self.snap
+        cache = plan.__dict__.setdefault("_snap_cent", {})
+        cent = cache.get(k["step"])
+        if cent is None:
+            cent = cache[k["step"]] = sx.centre_table([(int(h), int(w)) for h, w in plan.hw], k["step"], dev)
+        sp, _, _ = sx.slic_superpixels(hwc_packed, k["step"], k["compactness"], k["iters"], plan=plan, cent=cent,
+                                       out=(self._buf("snap_sp", n, torch.int32, dev), self._buf("snap_centres", 5 * cent[1], torch.int32, dev)))
+        self.last_snap_sp = sp
+        self.last_snap_labels, self.last_snap_counts = sx.snap_labels(
+            labels, sp, k["step"], self.num_classes, k["min_share"], plan=plan, cent=cent,
+            out=(self._buf("snap_labels", n, torch.uint8, dev), self._buf("snap_counts", 3 * plan.B, torch.int32, dev)))
+        if gts_packed is not None:
+            self.hist_snap = self._score(gts_packed, self.last_snap_labels, flags, plan=plan, into="hist_snap")
 
     def _clean(self, labels, plan, gts_packed, flags):
         """clean set: label the step's main map, filter it, score the kept pixels (all on the step's stream, no synchronisation)."""
@@ -595,12 +644,13 @@ class TrainingFreePipeline:
         refined = ops.refine_cams_with_aff_batched(attr, attn_w.w_aff, idx, ncls, g, self.caa_thre)  # infer_lam.py:93
         flags = self._guard_count(attr, attn_w.w_aff, refined)
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=attn_w.w_aff), flags, conf=conf)
+                                      dict(attr=attr, w_aff=attn_w.w_aff), flags, conf=conf, hwc=hwc_packed)
 
-    def _ragged_back_half(self, inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates, inter, flags=None, conf=None):
+    def _ragged_back_half(self, inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates, inter, flags=None, conf=None, hwc=None):
         """Up-sampling + background, PAR, arg-max and confusion of a ragged step (tools/infer_lam.py:94), shared by every regime.
         inputs [B,3,S,S] = the network input PAR reads; `inter` = the regime's own intermediates (attr, w_aff); `flags` = the guard's
-        per-image counts (None without a guard); `conf` = run_batch_ragged's (high_thre, low_thre) or None."""
+        per-image counts (None without a guard); `conf` = run_batch_ragged's (high_thre, low_thre) or None; `hwc` = the step's decoded
+        images (what snap= segments)."""
         conf = check_conf(conf)
         dev = inputs.device
         C = self.smax + 1
@@ -624,10 +674,14 @@ class TrainingFreePipeline:
                 self.sweep_totals = sweep_ragged(par_out, plan, C, self.bkg_sweep, nchan=nchan, cls_idx=idx, gts=gts_packed,
                                                  num_classes=self.num_classes, skip=flags if self.guard == "skip" else None,
                                                  totals=self.sweep_totals)[0]
+        chain = labels                                        # what clean and fill work on: the main labels, or the snapped ones
+        if self.snap is not None:
+            self._snap(labels, hwc, plan, gts_packed, flags)
+            chain = self.last_snap_labels
         if self.clean is not None:
-            self._clean(labels, plan, gts_packed, flags)
+            self._clean(chain, plan, gts_packed, flags)
             if self.fill is not None:
-                self._fill(labels, plan, gts_packed, flags)
+                self._fill(chain, plan, gts_packed, flags)
         if conf is None:
             if return_intermediates:
                 return labels, dict(inputs=inputs.clone(), refined=refined, cams=cams, par_out=par_out, cls_idx=idx, ncls=ncls, **inter)
@@ -767,7 +821,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         _refuse_tagger("OptimisedLamPipeline", tagger)
@@ -775,7 +829,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill, snap=snap)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -822,7 +876,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
         refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # infer_lam.py:93
         flags = self._guard_count(attr, w_aff, refined)
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred), flags, conf=conf)
+                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred), flags, conf=conf, hwc=hwc_packed)
 
 
 class ValidationPipeline(TrainingFreePipeline):
@@ -839,7 +893,7 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         _refuse_tagger("ValidationPipeline", tagger)
@@ -849,7 +903,7 @@ class ValidationPipeline(TrainingFreePipeline):
             raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
                              "histograms per step and is out of the guard's scope")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill, snap=snap)
         self.attn_layers = attn_layers
         self.hist_seg = None
 
@@ -886,4 +940,4 @@ class ValidationPipeline(TrainingFreePipeline):
         idx, ncls, nchan = ops.cls_compact(cls_labels, self.smax, want_nchan=True)                  # affutils.py:203
         refined = ops.refine_cams_with_aff_batched(attr, w_aff, idx, ncls, g, self.caa_thre)         # :33
         return self._ragged_back_half(inputs, plan, g, refined, idx, ncls, nchan, gts_packed, return_intermediates,
-                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred, seg=seg, seg_labels=seg_labels), conf=conf)   # :34-36
+                                      dict(attr=attr, w_aff=w_aff, attn_pred=attn_pred, seg=seg, seg_labels=seg_labels), conf=conf, hwc=hwc_packed)   # :34-36

@@ -20,7 +20,13 @@ gives 255 pixels the value of the nearest class pixel of their image (utils/labe
 without one; exact squared Euclidean distance, ties to the first pixel in raster order, at most PIXELS away): with --clean_min_region
 the pixels the cleaning removed (the map before the cleaning is the mask: a 255 it already had stays), without it every 255 of the
 predictions.  The filled maps are scored as one more table (fill_label_score, with holes, filled, largest distance and coverage) and,
-with `--fill_label_dir DIR`, written there.  Same tables and files with and without a GPU.
+with `--fill_label_dir DIR`, written there.  Same tables and files with and without a GPU.  `--snap_superpixels STEP` (with
+--snap_compactness, --snap_iters, --snap_min_share, --snap_label_dir) snaps the maps of --pred_dir to superpixels of their images first:
+it reads `<data_folder>/JPEGImages/<name>.jpg` (a missing image, or one whose size differs from the label map, is an error that names the
+file), over-segments it (utils/superpixels.slic_superpixels on the device, slic_numpy without one) and gives every superpixel the
+majority class of the labels inside it; the snapped maps are scored as one more table (snap_label_score, with the superpixels, the
+snapped ones and the pixels changed) and written to --snap_label_dir.  With it the cleaning and the fill work on the snapped maps
+(snap -> clean -> fill).
 """
 import argparse
 import concurrent.futures as cf
@@ -52,6 +58,8 @@ def get_parser():
     components.add_flags(p)
     from ..utils import label_fill
     label_fill.add_flags(p)
+    from ..utils import superpixels
+    superpixels.add_flags(p)
     p.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)
     p.add_argument("--backend", default="nccl")
     return p
@@ -78,6 +86,18 @@ def _load_pair(args, name):
     return np.ascontiguousarray(gt, np.uint8).reshape(-1), np.ascontiguousarray(pred, np.uint8).reshape(-1), gt.shape
 
 
+def _load_image(args, name, hw):
+    """The decoded uint8 [H,W,3] image of one list entry, <data_folder>/JPEGImages/<name>.jpg, for --snap_superpixels."""
+    from PIL import Image
+    path = os.path.join(args.data_folder, "JPEGImages", name + ".jpg")
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"eval_labels: --snap_superpixels needs the image of {name!r}: {path} is missing")
+    img = np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB")), np.uint8)
+    if img.shape[:2] != tuple(hw):
+        raise ValueError(f"eval_labels: {path} is {img.shape[:2]}, the label map of {name!r} is {tuple(hw)}")
+    return img
+
+
 def _save_index_png(path, label):
     """One [H,W] uint8 map as a palette PNG (the VOC colour map; index 255 is the ignore colour)."""
     from PIL import Image
@@ -97,10 +117,11 @@ def _hist_numpy(gt, pred, nc):
 def validate(args):
     """-> {"score": scores_from_hist of the gathered matrix, "hist": [nc,nc] int64 (CPU tensor), "images": scored on this rank,
     "seconds"}: the layout of infer_seg_voc.validate (+ "image_scores" with --per_image_scores)."""
-    from ..utils import components, evaluate, image_scores, label_fill
+    from ..utils import components, evaluate, image_scores, label_fill, superpixels
     image_scores.refuse(args)
     clean = components.resolve(args, program="eval_labels")
     fill = label_fill.resolve(args, program="eval_labels")
+    snap = superpixels.resolve(args, program="eval_labels")
     names_fg = None
     if getattr(args, "class_names", None):
         from .infer_lam import _read_names
@@ -110,6 +131,8 @@ def validate(args):
     nc = args.num_classes or (len(names_fg) + 1 if names_fg else (81 if "coco" in args.dataset_name else 21))
     if not 1 <= nc <= 256:
         raise ValueError(f"--num_classes {nc}: uint8 label maps hold at most 256 classes")
+    if snap is not None and nc > 255:
+        raise ValueError(f"--snap_superpixels: --num_classes {nc} leaves no value that does not vote (at most 255)")
     world, rank = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0))
     on_gpu = torch.cuda.is_available()
     device = torch.device("cuda", args.local_rank) if on_gpu else torch.device("cpu")
@@ -128,6 +151,9 @@ def validate(args):
     if clean is not None and clean["label_dir"]:
         os.makedirs(clean["label_dir"], exist_ok=True)
     hist_fill, fill_rows = (torch.zeros_like(hist) if fill is not None else None), []
+    hist_snap, snap_rows, snap_pixels = (torch.zeros_like(hist) if snap is not None else None), [], 0
+    if snap is not None and snap["label_dir"]:
+        os.makedirs(snap["label_dir"], exist_ok=True)
     if fill is not None and fill["label_dir"]:
         os.makedirs(fill["label_dir"], exist_ok=True)
     t0 = time.time()
@@ -154,17 +180,42 @@ def validate(args):
                         if boundary is not None:
                             scores.put(idx[s + j], mine[s + j], p[2], "main_bd", image_scores.boundary_counts_numpy(
                                 p[0].reshape(p[2]), p[1].reshape(p[2]), nc, image_scores.checked_radius(mine[s + j], p[2][0], p[2][1], boundary)))
+            src, src_d = pred, (pred_d if on_gpu else None)      # what the cleaning and the fill work on: the predictions, or the snapped maps
+            if snap is not None:                                 # the snapped maps of the batch: the images decoded, segmented, voted on
+                imgs = list(pool.map(lambda nh: _load_image(args, *nh), zip(mine[s:s + len(pairs)], hws)))
+                if on_gpu:
+                    plan = ops.RaggedPlan(hws, device)
+                    hwc_d = torch.from_numpy(np.concatenate([im.reshape(-1) for im in imgs])).to(device)
+                    sp_d, _, cent = superpixels.slic_superpixels(hwc_d, snap["step"], snap["compactness"], snap["iters"], plan=plan)
+                    src_d, counts_d = superpixels.snap_labels(pred_d, sp_d, snap["step"], nc, snap["min_share"], plan=plan, cent=cent)
+                    hist_snap = ops.confusion_accumulate(gt_d, src_d, nc, hist_snap)
+                    src, counts = src_d.cpu().numpy(), counts_d.cpu().numpy()
+                else:
+                    done = superpixels.snap_batch_numpy(imgs, [p[1].reshape(p[2]) for p in pairs], snap["step"], nc, snap["compactness"],
+                                                        snap["iters"], snap["min_share"])
+                    src = np.concatenate([d[2].reshape(-1) for d in done])
+                    counts = np.stack([d[3] for d in done])
+                    hist_snap += torch.from_numpy(_hist_numpy(gt, src, nc))
+                snap_rows.extend(np.asarray(counts, np.int64).reshape(-1, 3).tolist())
+                snap_pixels += int(src.size)
+                if snap["label_dir"]:
+                    off = 0
+                    for n, (h, w) in zip(mine[s:s + len(pairs)], hws):
+                        _save_index_png(os.path.join(snap["label_dir"], n + ".png"), src[off:off + h * w].reshape(h, w))
+                        off += h * w
+            offs = np.concatenate([[0], np.cumsum([h * w for h, w in hws])])
             if clean is not None:                                # the cleaned maps of the batch: scored into a matrix of their own, written
                 hws = [p[2] for p in pairs]
                 thr = [components.min_area_rule(clean["min_region"], h, w) for h, w in hws]
                 if on_gpu:
                     plan = ops.RaggedPlan(hws, device)
-                    comp, area = components.label_components(pred_d, plan=plan, connectivity=clean["connectivity"])
-                    cleaned_d, counts_d = components.filter_small_regions(pred_d, comp, area, thr, nc, plan=plan)
+                    comp, area = components.label_components(src_d, plan=plan, connectivity=clean["connectivity"])
+                    cleaned_d, counts_d = components.filter_small_regions(src_d, comp, area, thr, nc, plan=plan)
                     hist_clean = ops.confusion_accumulate(gt_d, cleaned_d, nc, hist_clean)
                     cleaned, counts = cleaned_d.cpu().numpy(), counts_d.cpu().numpy()
                 else:
-                    done = [components.clean_numpy(p[1].reshape(p[2]), t, nc, clean["connectivity"]) for p, t in zip(pairs, thr)]
+                    done = [components.clean_numpy(src[offs[j]:offs[j + 1]].reshape(p[2]), t, nc, clean["connectivity"])
+                            for j, (p, t) in enumerate(zip(pairs, thr))]
                     cleaned = np.concatenate([d[0].reshape(-1) for d in done])
                     counts = np.stack([d[1] for d in done])
                     hist_clean += torch.from_numpy(_hist_numpy(gt, cleaned, nc))
@@ -176,16 +227,16 @@ def validate(args):
                         off += h * w
             if fill is not None:                                 # the filled maps: what the cleaning removed, or every 255 of the predictions
                 if on_gpu:
-                    src_d, mask_d = (cleaned_d, pred_d) if clean is not None else (pred_d, None)
-                    filled_d, _, counts_d = label_fill.fill_nearest_label(src_d, nc, plan=ops.RaggedPlan(hws, device), mask=mask_d, radius=fill["radius"])
+                    hole_d, mask_d = (cleaned_d, src_d) if clean is not None else (src_d, None)
+                    filled_d, _, counts_d = label_fill.fill_nearest_label(hole_d, nc, plan=ops.RaggedPlan(hws, device), mask=mask_d, radius=fill["radius"])
                     hist_fill = ops.confusion_accumulate(gt_d, filled_d, nc, hist_fill)
                     filled, counts = filled_d.cpu().numpy(), counts_d.cpu().numpy()
                 else:
-                    src, off, done = (cleaned if clean is not None else pred), 0, []
+                    hole, off, done = (cleaned if clean is not None else src), 0, []
                     for p in pairs:
                         n_pix = p[2][0] * p[2][1]
-                        done.append(label_fill.fill_numpy(src[off:off + n_pix].reshape(p[2]), nc, radius=fill["radius"],
-                                                          mask=p[1].reshape(p[2]) if clean is not None else None))
+                        done.append(label_fill.fill_numpy(hole[off:off + n_pix].reshape(p[2]), nc, radius=fill["radius"],
+                                                          mask=src[off:off + n_pix].reshape(p[2]) if clean is not None else None))
                         off += n_pix
                     filled = np.concatenate([d[0].reshape(-1) for d in done])
                     counts = np.stack([d[2] for d in done])
@@ -213,6 +264,24 @@ def validate(args):
         logging.info("\n" + format_scores_table(score, cats))
         logging.info(f"mIoU {score['miou'] * 100:.3f}  images {len(names)}  ({len(mine) / max(secs, 1e-9):.1f} img/s/rank)")
     out = {"score": score, "hist": total, "images": len(mine), "seconds": secs}
+    if snap is not None:
+        _, snap_total = gather_hists(hist_snap)
+        snap_total = snap_total.cpu()
+        parts = [(snap_rows, snap_pixels)]
+        if world > 1:
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, (snap_rows, snap_pixels))
+        counts = np.asarray([r for part in parts for r in part[0]], np.int64).reshape(-1, 3)
+        out["snap"] = dict(score=evaluate.scores_from_hist(snap_total), hist=snap_total, coverage=components.coverage(snap_total, total),
+                           counts=counts, stats=superpixels.snap_stats(counts, sum(part[1] for part in parts)),
+                           **{k: snap[k] for k in ("step", "compactness", "iters", "min_share")})
+        if rank == 0:
+            logging.info(f"snap_label_score of {args.pred_dir} (--snap_superpixels {snap['step']}, compactness {snap['compactness']}, "
+                         f"{snap['iters']} iterations, min share {snap['min_share']:g}):")
+            logging.info("\n" + format_scores_table(out["snap"]["score"], cats))
+            logging.info(superpixels.format_snap_summary(out["snap"]["stats"], out["snap"]["coverage"]))
+            if snap["label_dir"]:
+                logging.info(f"snapped label maps -> {snap['label_dir']}")
     if clean is not None:
         _, clean_total = gather_hists(hist_clean)
         clean_total = clean_total.cpu()

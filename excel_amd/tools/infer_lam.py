@@ -102,6 +102,16 @@ Differences from the reference, all deliberate:
     coverage), a `fill` block in --json_out, fill_* columns plus holes, filled and max_fill_dist in --per_image_scores.  The main, conf,
     crf and clean outputs are untouched.  Refused without --clean_min_region, with --api_path true, and with --unlabeled true unless
     --fill_label_dir is given; off by default (no launch, no key, no column).  Conf and crf PNGs go through eval_labels --fill_ignore;
+  * `--snap_superpixels STEP` (`--snap_compactness 10`, `--snap_iters 5`, `--snap_min_share 0`, `--snap_label_dir DIR`): the one stage
+    behind the arg-max that looks at the image again.  utils/superpixels.slic_superpixels over-segments the step's decoded images into
+    superpixels of grid step STEP (2..64; an integer SLIC on a fixed grid, csrc/superpixels.hip) and snap_labels gives every superpixel
+    the majority class of the main labels inside it - only where that class holds at least --snap_min_share of the votes -, so contours
+    move onto colour edges and speckle is voted away instead of ignored.  The snapped maps are one more scored label set:
+    `<snap_label_dir>/<name>.png`, a snap_label_score table, one summary line (superpixels with a vote, snapped, pixels changed and
+    their share), a `snap` block in --json_out, snap_* columns plus superpixels, snapped and pixels_changed in --per_image_scores, a
+    boundary_score table with --boundary_scores.  With it --clean_min_region and --fill_ignore work on the snapped maps (snap -> clean
+    -> fill); the main labels, scores and PNGs are untouched.  Superpixels are not made connected.  Refused with --api_path true, and
+    with --unlabeled true unless --snap_label_dir is given; off by default (0: no launch, no key, no column);
   * `--synthetic N` (no --data_folder) feeds seeded synthetic samples; seeded random weights are used ONLY in that mode and only
     when no checkpoint can be resolved (logged).  `--data_folder` without a resolvable checkpoint is an error.
 Launch: python -m torch.distributed.run --nproc-per-node R -m excel_amd.tools.infer_lam --synthetic 64 ...
@@ -197,7 +207,7 @@ def resolve_tags(args, have_dataset=False):
         if args.api_path:
             raise ValueError("--unlabeled true runs on the batched loop: --api_path true scores every image against its ground truth")
         if not (args.save_label or args.conf_label or args.save_tags or getattr(args, "clean_label_dir", None)
-                or getattr(args, "fill_label_dir", None)):
+                or getattr(args, "fill_label_dir", None) or getattr(args, "snap_label_dir", None)):
             raise ValueError("--unlabeled true scores nothing, so the run must write something: give at least one of --save_label true, "
                              "--conf_label true, --save_tags PATH")
     if args.save_tags and args.tags != "clip":
@@ -459,6 +469,8 @@ def get_parser():
     components.add_flags(p)
     from ..utils import label_fill
     label_fill.add_flags(p)
+    from ..utils import superpixels
+    superpixels.add_flags(p)
     p.add_argument("--json_out", default=None, type=str, help="rank 0 writes a one-line JSON record of the run here (rate, ranks, per-rank mass)")
     p.set_defaults(ragged_batches=False, run_token=None, vocab=None, num_classes_given=False)      # what the program sets itself
     return p
@@ -869,6 +881,13 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     fill_kw = dict(radius=fill["radius"]) if fill is not None else None
     if fill is not None:
         bkg_kw = {**bkg_kw, "fill": fill_kw}
+    from ..utils import superpixels
+    snap = superpixels.resolve(args)
+    if snap is not None and not ragged:
+        raise ValueError("--snap_superpixels runs behind the ragged step: ragged batches (--data_folder or --ragged true) on the batched loop")
+    snap_kw = {k: snap[k] for k in ("step", "compactness", "iters", "min_share")} if snap is not None else None
+    if snap is not None:
+        bkg_kw = {**bkg_kw, "snap": snap_kw}
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
                   smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
@@ -889,22 +908,26 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError(f"--clean_min_region: the supplied pipeline was built with clean={getattr(pipe, 'clean', None)!r}, the flags ask for {clean_kw!r}")
     if fill is not None and pipe is not None and getattr(pipe, "fill", None) != fill_kw:
         raise ValueError(f"--fill_ignore: the supplied pipeline was built with fill={getattr(pipe, 'fill', None)!r}, the flags ask for {fill_kw!r}")
+    if snap is not None and pipe is not None and getattr(pipe, "snap", None) != snap_kw:
+        raise ValueError(f"--snap_superpixels: the supplied pipeline was built with snap={getattr(pipe, 'snap', None)!r}, the flags ask for {snap_kw!r}")
     for k, want in (("bkg_sweep", sweep), ("bkg_scale", bkg_scale)):
         if (sweep is not None or bkg_scale != 1.0) and pipe is not None and getattr(pipe, k, None if k == "bkg_sweep" else 1.0) != want:
             raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None, fill=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None, fill=None, snap=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
-                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean, fill=fill,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean, fill=fill, snap=snap,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
     # --per_image_scores: the rank's table of per-image counts, one set per matrix the run scores (utils/image_scores.py)
     run.scores = report["image_scores"] = image_scores.ImageScoreLog(
         args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else [])
-        + (["clean"] if clean is not None and not args.unlabeled else []) + (["fill"] if fill is not None and not args.unlabeled else []),
-        boundary=boundary, **({"regions": True} if clean is not None else {}), **({"fills": True} if fill is not None else {})) if want_scores else None
+        + (["clean"] if clean is not None and not args.unlabeled else []) + (["fill"] if fill is not None and not args.unlabeled else [])
+        + (["snap"] if snap is not None and not args.unlabeled else []),
+        boundary=boundary, **({"regions": True} if clean is not None else {}), **({"fills": True} if fill is not None else {}),
+        **({"snaps": True} if snap is not None else {})) if want_scores else None
     try:
         for wanted, needs in ((args.save_cam, "--save_cam needs the decoded images"), (conf is not None, "--conf_label runs behind the ragged step"),
                               (crf_inline_wanted(args), "--crf_inline needs the decoded images")):
@@ -924,6 +947,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
             run.consumers["clean_lab"] = _LabelSaver(args, clean["label_dir"])
         if fill is not None and fill["label_dir"]:
             run.consumers["fill_lab"] = _LabelSaver(args, fill["label_dir"])
+        if snap is not None and snap["label_dir"]:
+            run.consumers["snap_lab"] = _LabelSaver(args, snap["label_dir"])
         out = (_per_image_loop if per_image else _batched_loop)(run)
     except BaseException:
         _close_consumers(run, failed=True)
@@ -938,6 +963,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         build_validation.last_bkg_sweep = report["bkg_sweep"]
         build_validation.last_clean = report["clean"]
         build_validation.last_fill = report["fill"]
+        build_validation.last_snap = report["snap"]
     return out
 
 
@@ -1051,13 +1077,17 @@ def _batched_loop(run):
         pipe.hist_conf = torch.zeros_like(run.hist)
     if run.sweep is not None:                                # --bkg_sweep: the pipeline adds every step's counts per scale (both passes of the guard)
         pipe.sweep_totals = torch.zeros((len(run.sweep), 3, args.num_classes), dtype=torch.int64, device=device)
-    clean_lab, fill_lab = run.consumers.get("clean_lab"), run.consumers.get("fill_lab")
+    clean_lab, fill_lab, snap_lab = run.consumers.get("clean_lab"), run.consumers.get("fill_lab"), run.consumers.get("snap_lab")
     clean_pending, clean_rows = deque(), {}                  # --clean_min_region: (pinned counts, event, dataset indices, names) -> index: (name, row)
     fill_pending, fill_rows = deque(), {}                    # --fill_ignore: the same, for the fill's rows
+    snap_pending, snap_rows = deque(), {}                    # --snap_superpixels: the same, for the vote's rows
+    row_pix = {}                                             # index: the pixels of the image (the share of pixels the snap changed)
     if run.clean is not None:
         pipe.hist_clean = torch.zeros_like(run.hist)
     if run.fill is not None:
         pipe.hist_fill = torch.zeros_like(run.hist)
+    if run.snap is not None:
+        pipe.hist_snap = torch.zeros_like(run.hist)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
         from ..datasets.loader import DeviceFeeder, ragged_batches, threaded_batches
@@ -1105,6 +1135,8 @@ def _batched_loop(run):
             clean_lab.ragged(names, plan, pipe.last_clean_labels)
         if fill_lab is not None:                                                        # likewise, the step's filled maps
             fill_lab.ragged(names, plan, pipe.last_fill_labels)
+        if snap_lab is not None:                                                        # likewise, the step's snapped maps
+            snap_lab.ragged(names, plan, pipe.last_snap_labels)
         if keep:                                                                        # :116-119 record for the CRF stage
             inter = out[1]
             cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
@@ -1186,12 +1218,15 @@ def _batched_loop(run):
                 if truth is not None:
                     tag_truth[n] = np.array(truth[b], np.float32)
 
-    # what differs between the two sets of per-image rows: (the pipeline's device rows, the queue, the collected rows, the table's sink)
-    row_sets = {"clean": ("last_clean_counts", clean_pending, clean_rows, "put_regions"), "fill": ("last_fill_counts", fill_pending, fill_rows, "put_fills")}
+    # what differs between the sets of per-image rows: (the pipeline's device rows, the queue, the collected rows, the table's sink)
+    row_sets = {"clean": ("last_clean_counts", clean_pending, clean_rows, "put_regions"), "fill": ("last_fill_counts", fill_pending, fill_rows, "put_fills"),
+                "snap": ("last_snap_counts", snap_pending, snap_rows, "put_snaps")}
+    row_wanted = [which for which in row_sets if getattr(run, which) is not None]
 
     def clean_enqueue(names, idxs):
-        """The filter's (and the fill's) per-image counts of the step just enqueued, on their way to the host behind an event (no wait here)."""
-        for which in (["clean"] + (["fill"] if run.fill is not None else [])):
+        """The filter's (the fill's, the vote's) per-image counts of the step just enqueued, on their way to the host behind an event (no
+        wait here)."""
+        for which in row_wanted:
             dev = getattr(pipe, row_sets[which][0])
             host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=on_gpu)
             host.copy_(dev, non_blocking=True)
@@ -1212,12 +1247,13 @@ def _batched_loop(run):
                 rows = host.numpy()
                 for b, i in enumerate(idxs):
                     rows_of[i] = (names[b], rows[b].astype(np.int64))
+                    row_pix[i] = hws[b][0] * hws[b][1]
                 if scores is not None:
                     getattr(scores, sink)(idxs, names, hws, rows)
 
     nimg, pos, flagged = 0, 0, {}
     for names in steps(indices):
-        if run.clean is not None:
+        if row_wanted:
             clean_enqueue(names, indices[pos:pos + len(names)])
         if policy != "off":
             enqueue(names, indices[pos:pos + len(names)])
@@ -1247,7 +1283,7 @@ def _batched_loop(run):
                 pos = 0
                 for names in steps(np.asarray(order, dtype=np.asarray(indices).dtype)):
                     enqueue(names, order[pos:pos + len(names)])
-                    if run.clean is not None:
+                    if row_wanted:
                         clean_enqueue(names, order[pos:pos + len(names)])
                     if tagger is not None:
                         tag_enqueue(names)                    # the fp32 row replaces the first pass's
@@ -1270,11 +1306,14 @@ def _batched_loop(run):
         run.report["conf_hist"] = pipe.hist_conf
     if run.sweep is not None:
         run.report["bkg_sweep"] = pipe.sweep_totals
-    if run.clean is not None:
+    if row_wanted:
         clean_take(True)
+    if run.clean is not None:
         run.report["clean"] = dict(hist=pipe.hist_clean, rows=clean_rows)
         if run.fill is not None:
             run.report["fill"] = dict(hist=pipe.hist_fill, rows=fill_rows)
+    if run.snap is not None:
+        run.report["snap"] = dict(hist=pipe.hist_snap, rows=snap_rows, pixels=int(sum(row_pix.values())))
     if scores is not None:
         scores.poll(True)
     if tagger is not None:
@@ -1437,12 +1476,13 @@ def validate(args=None, dataset=None, pipe=None):
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
     validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = validate.last_clean = None
-    validate.last_fill = None
-    from ..utils import bkg_sweep, components, image_scores, label_fill
+    validate.last_fill = validate.last_snap = None
+    from ..utils import bkg_sweep, components, image_scores, label_fill, superpixels
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))                                # ... and per-image scores of nothing
     sweep, _ = bkg_sweep.resolve(args)                                                       # ... and a sweep nobody can score or run
     clean = components.resolve(args)                                                         # ... and a cleaning nobody can run or see
     fill = label_fill.resolve(args)                                                          # ... and a fill of nothing
+    snap = superpixels.resolve(args)                                                         # ... and a snap nobody can run or see
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
@@ -1542,6 +1582,12 @@ def validate(args=None, dataset=None, pipe=None):
     if fill is not None:                                                                    # --fill_ignore: the filled maps
         got = gathered_set(build_validation.last_fill)
         validate.last_fill = dict(radius=fill["radius"], stats=label_fill.fill_stats(got["counts"]), **got)
+    if snap is not None:                                                                    # --snap_superpixels: the snapped maps
+        got = gathered_set(build_validation.last_snap)
+        pixels = torch.tensor([int((build_validation.last_snap or {}).get("pixels", 0))], dtype=torch.int64, device=hist.device)
+        if world > 1:
+            dist.all_reduce(pixels)
+        validate.last_snap = dict(stats=superpixels.snap_stats(got["counts"], int(pixels.item())), **{k: snap[k] for k in ("step", "compactness", "iters", "min_share")}, **got)
     tags = None
     if tagger is not None:
         # the predicted rows of every rank, once: every rank joins, also one whose shard is empty
@@ -1592,6 +1638,15 @@ def validate(args=None, dataset=None, pipe=None):
             logging.info(label_fill.format_fill_summary(c["stats"], c["coverage"]))
             if fill["label_dir"]:
                 logging.info(f"filled label maps -> {fill['label_dir']}")
+        if snap is not None:
+            c = validate.last_snap
+            if c["score"] is not None:
+                logging.info(f"snap_label_score (--snap_superpixels {snap['step']}, compactness {snap['compactness']}, {snap['iters']} iterations, "
+                             f"min share {snap['min_share']:g}):")
+                logging.info("\n" + format_scores_table(c["score"], cat_list))
+            logging.info(superpixels.format_snap_summary(c["stats"], c["coverage"]))
+            if snap["label_dir"]:
+                logging.info(f"snapped label maps -> {snap['label_dir']}")
         if tags is not None:
             logging.info(f"tags (--tags clip, thre {tagger['thre']}, at most {tagger['kmax']}, scale {tagger['scale']}): {tags['images']} images, "
                          f"tags per image {dict((k, v) for k, v in enumerate(tags['tags_per_image']) if v)}"
@@ -1619,7 +1674,9 @@ def validate(args=None, dataset=None, pipe=None):
                                                               validate.last_clean["score"], validate.last_clean["coverage"])}
                               if clean is not None else {}),
                            **({"fill": label_fill.fill_json(fill["radius"], validate.last_fill["stats"], validate.last_fill["score"],
-                                                            validate.last_fill["coverage"])} if fill is not None else {})}, f)
+                                                            validate.last_fill["coverage"])} if fill is not None else {}),
+                           **({"snap": superpixels.snap_json(snap, validate.last_snap["stats"], validate.last_snap["score"],
+                                                             validate.last_snap["coverage"])} if snap is not None else {})}, f)
     if image_scores.wanted(args):                                                           # one all_gather_object, rank 0 writes
         validate.last_image_scores = image_scores.finish(build_validation.last_image_scores, args, cat_list, rank, what="LAM_score")
         if rank == 0 and args.json_out and image_scores.boundary_of(args) is not None:       # the record above gains its `boundary` block

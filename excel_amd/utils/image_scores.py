@@ -26,6 +26,10 @@ regions_removed, pixels_removed`, the npz `counts_clean` and `regions`.  Without
 --fill_ignore (infer_lam; utils/label_fill.py): the filled labels are one more set, "fill", by the same route, and every image has a row
 (holes, holes filled, largest squared distance) of the fill: the files gain `fill_pacc, fill_miou, fill_scored` and, last of all, `holes,
 filled, max_fill_dist` (the distance in pixels), the npz `counts_fill` and `fills` (the raw rows).  Without the flag nothing changes.
+
+--snap_superpixels (infer_lam; utils/superpixels.py): the snapped labels are one more set, "snap", by the same route, and every image has
+a row (superpixels with a vote, superpixels snapped, pixels changed) of the vote: the files gain `snap_pacc, snap_miou, snap_scored` and,
+last of all, `superpixels, snapped, pixels_changed`, the npz `counts_snap` and `snaps`.  Without the flag nothing changes.
 """
 import csv
 import logging
@@ -37,7 +41,7 @@ import numpy as np
 
 from .evaluate import boundary_scores_from_counts, image_score_rows
 
-SETS = ("main", "crf", "conf", "clean", "fill")
+SETS = ("main", "crf", "conf", "clean", "fill", "snap")
 MAX_RADIUS = 72              # what ops.boundary_max_radius() answers (boundary.hip's halo); the CPU path refuses the same radii
 
 
@@ -172,14 +176,16 @@ class ImageScoreLog:
     """The records of one rank: index -> (name, (H, W), {set: counts int64 [3,nc]}).  put() replaces what an earlier pass recorded for the
     same image and set (the overflow guard's exact-fp32 second pass); defer() takes a ticket and reads it when it is ready."""
 
-    def __init__(self, num_classes, sets=("main",), boundary=None, regions=False, fills=False):
+    def __init__(self, num_classes, sets=("main",), boundary=None, regions=False, fills=False, snaps=False):
         """boundary = None | dict(ratio=, px=): with it every set has a twin "<set>_bd" (ops.boundary_scores' counts) that is recorded
         and required like the set itself, and merged() adds the radius of every image.  regions (--clean_min_region): every image also
         has a row (regions, regions removed, pixels removed) of utils/components.filter_small_regions, put_regions() records it.
         fills (--fill_ignore): likewise a row (holes, holes filled, largest squared distance) of utils/label_fill.fill_nearest_label,
-        put_fills() records it."""
+        put_fills() records it.  snaps (--snap_superpixels): likewise a row (superpixels with a vote, snapped, pixels changed) of
+        utils/superpixels.snap_labels, put_snaps() records it."""
         self.regions = bool(regions)
         self.fills = bool(fills)
+        self.snaps = bool(snaps)
         bad = [s for s in sets if s not in SETS]
         if bad or "main" not in sets:
             raise ValueError(f"image score sets {tuple(sets)}: 'main' plus any of {SETS[1:]}")
@@ -209,6 +215,12 @@ class ImageScoreLog:
         for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
             rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
             rec[2]["fills"] = np.array(counts[b], np.int64).reshape(3)
+
+    def put_snaps(self, indices, names, hws, counts):
+        """counts [B,3]: the vote's rows of one step; a later row of an image replaces the earlier one."""
+        for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
+            rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
+            rec[2]["snaps"] = np.array(counts[b], np.int64).reshape(3)
 
     def put_batch(self, indices, names, hws, which, counts):
         for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
@@ -243,7 +255,7 @@ class ImageScoreLog:
             allrec.update(p)
         order = sorted(allrec)
         for i in order:
-            missing = [s for s in self.sets + self.twins + (("regions",) if self.regions else ()) + (("fills",) if self.fills else ()) if s not in allrec[i][2]]
+            missing = [s for s in self.sets + self.twins + (("regions",) if self.regions else ()) + (("fills",) if self.fills else ()) + (("snaps",) if self.snaps else ()) if s not in allrec[i][2]]
             if missing:
                 raise RuntimeError(f"image scores: {allrec[i][0]!r} has no counts for {missing}")
         stack = lambda s: np.stack([allrec[i][2][s] for i in order]) if order else np.zeros((0, 3, self.nc), np.int64)
@@ -256,6 +268,8 @@ class ImageScoreLog:
             out["regions"] = np.stack([allrec[i][2]["regions"] for i in order]) if order else np.zeros((0, 3), np.int64)
         if self.fills:
             out["fills"] = np.stack([allrec[i][2]["fills"] for i in order]) if order else np.zeros((0, 3), np.int64)
+        if self.snaps:
+            out["snaps"] = np.stack([allrec[i][2]["snaps"] for i in order]) if order else np.zeros((0, 3), np.int64)
         return out
 
 
@@ -276,12 +290,14 @@ def write_files(path, merged, class_names):
     rhead = ["regions", "regions_removed", "pixels_removed"] if regions is not None else []
     fills = merged.get("fills")
     fhead = ["holes", "filled", "max_fill_dist"] if fills is not None else []
+    snaps = merged.get("snaps")
+    shead = ["superpixels", "snapped", "pixels_changed"] if snaps is not None else []
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["name", "height", "width", "scored", "pacc", "miou", "present"] + ["iou_" + c for c in cats]
-                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead + rhead + fhead)
+                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead + rhead + fhead + shead)
         for i, name in enumerate(merged["names"]):
             present = "|".join(cats[c] for c in np.nonzero(merged["counts"]["main"][i, 0])[0])
             w.writerow([name, int(merged["hw"][i, 0]), int(merged["hw"][i, 1]), int(main["scored"][i]), _fmt(main["pacc"][i]),
@@ -290,7 +306,8 @@ def write_files(path, merged, class_names):
                        + ([int(merged["radius"][i]), _fmt(brows["main"]["miou"][i])] + [_fmt(brows[s]["miou"][i]) for s in extra]
                           if brows else [])
                        + ([int(v) for v in regions[i]] if regions is not None else [])
-                       + ([int(fills[i][0]), int(fills[i][1]), _fmt(np.sqrt(float(fills[i][2])))] if fills is not None else []))
+                       + ([int(fills[i][0]), int(fills[i][1]), _fmt(np.sqrt(float(fills[i][2])))] if fills is not None else [])
+                       + ([int(v) for v in snaps[i]] if snaps is not None else []))
     more = {}
     if brows:
         more = dict(radius=merged["radius"].astype(np.int32), **{"bcounts_" + s: c.astype(np.int64) for s, c in merged["bcounts"].items()})
@@ -298,6 +315,8 @@ def write_files(path, merged, class_names):
         more["regions"] = np.asarray(regions, np.int64)
     if fills is not None:
         more["fills"] = np.asarray(fills, np.int64)
+    if snaps is not None:
+        more["snaps"] = np.asarray(snaps, np.int64)
     np.savez(path + ".npz", names=np.asarray(merged["names"], dtype=str), hw=merged["hw"],
              **{"counts_" + s: c.astype(np.int64) for s, c in merged["counts"].items()}, **more)
     return main
@@ -322,7 +341,7 @@ def report_lines(merged, rows, k, what="label_score"):
     return lines
 
 
-BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels", "clean": "cleaned labels", "fill": "filled labels"}
+BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels", "clean": "cleaned labels", "fill": "filled labels", "snap": "snapped labels"}
 
 
 def boundary_summary(merged):

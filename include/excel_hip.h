@@ -614,6 +614,51 @@ int excel_fill_nearest_label(const uint8_t* labels, const uint8_t* mask /*or NUL
                              const excel_ragged_info* info, int num_classes, int max_dist2, uint8_t* out,
                              int32_t* dist2 /*device, one per pixel*/, int32_t* counts /*device [B,3]*/, void* stream);
 
+/* ------------------------------------------------------------------ superpixel snap
+ * The one stage behind the arg-max that looks at the image again: over-segment the image into superpixels and give every superpixel
+ * the majority class of the labels inside it.  Integer arithmetic throughout; the result is canonical - it does not depend on tiling,
+ * scheduling or the order of any atomic.  Images are addressed exactly as in excel_label_components: table == NULL means B uniform [H,W]
+ * maps; otherwise the tight maps of the ragged plan (image b at loff_b; H, W ignored, info->B == B).  hwc holds the decoded uint8
+ * [H_b,W_b,3] images back to back, image b at byte 3 * loff_b.  hwc, labels and out may start at any byte address; sp uses the pixel
+ * indexing of the label maps, 4-byte aligned.  Nothing reaches across images.
+ *
+ * excel_slic_superpixels: integer SLIC on a fixed grid (the gSLIC form), step S in [2, 64], compactness m in [1, 64], iters T in [0, 16].
+ *   grid    gx = ceil(W_b / S), gy = ceil(H_b / S); centre k = cy * gx + cx starts at x = min(W_b - 1, cx S + S/2),
+ *           y = min(H_b - 1, cy S + S/2) with the colour of the pixel there;
+ *   assign  pixel (x, y) lies in cell (x / S, y / S) and considers the centres of the up to nine cells within +-1 of it that exist:
+ *           D = S^2 ((r-rk)^2 + (g-gk)^2 + (b-bk)^2) + m^2 ((x-xk)^2 + (y-yk)^2), the smallest D wins, the smallest k on a tie.
+ *           D < 2^31: colours give at most 3 * 255^2 = 195075; a centre stays within the 3 x 3 cells around its own cell (it is a mean
+ *           of pixels from there), so |x-xk|, |y-yk| < 3S and D <= 4096 * 195075 + 4096 * 18 * 4096 = 1 101 017 088;
+ *   update  per centre the sums of x, y, r, g, b and the count cnt over its pixels; new value = (2 sum + cnt) / (2 cnt), floor; a centre
+ *           without a pixel keeps its values;
+ *   sequence  init, T times (assign, update), a final assign.
+ * sp[i] = the image-local centre index of pixel i; centres = int32 {x, y, r, g, b} per centre at the final state, the centres of image b
+ * from centre cent_off[b] on.  cent_off: device int32 [B + 1], cent_off[b+1] - cent_off[b] = gy_b * gx_b, supplied by the caller with
+ * the host total cent_total (the sizes of a ragged batch live on the device, which the host entry does not read).  An image whose row
+ * is wrong - cent_off[b] < 0, cent_off[b+1] > cent_total or a difference other than gy * gx - is refused by the kernels, never clamped:
+ * its sp is -1 and none of its centres is written.  Superpixels are NOT made connected; excel_label_components can follow.
+ *
+ * excel_snap_labels_to_superpixels: a pixel votes iff labels < num_classes (1..255).  Per superpixel: tot = its votes, top = the largest
+ * class count, win = the smallest class that attains it; it is snapped iff tot > 0 and 1000 top >= min_share_pm tot (min_share_pm in
+ * [0, 1000]).  out = win at the voting pixels of a snapped superpixel; everywhere else out = labels: 255, values in [num_classes, 255),
+ * superpixels not snapped, pixels with sp < 0.  sp is what excel_slic_superpixels wrote for the same geometry, step and cent_off (or -1):
+ * a pixel whose sp names a centre beyond the 3 x 3 cells around its own cell is not seen by that centre and keeps its label.
+ * counts[b] = (superpixels with a vote, superpixels snapped, pixels whose value changed), device int32 [B,3], cleared on the stream; an
+ * image with a wrong cent_off row keeps its labels and counts nothing.  out may overlap neither labels nor sp.
+ *
+ * Both: everything on `stream` (2 T + 2 launches; a copy, a clearing and one launch), no host synchronisation, no workspace (centres is
+ * the only intermediate: assign reads it and writes sp, update reads sp and writes it - csrc/superpixels.hip), no scratch memory; no
+ * workgroup waits for another; every loop is bounded by the 3S x 3S window, the centres under a tile or T.  EXCEL_ERR_ARG with a message
+ * before any launch for: a null pointer; step, compactness, iters, num_classes or min_share_pm out of range; sp, centres, counts,
+ * cent_off or table not 4-byte aligned; B outside [1, 65535]; a pixel total or cent_total outside [1, 2^31), or more centres than
+ * pixels; out overlapping labels or sp. */
+int excel_slic_superpixels(const uint8_t* hwc, int B, int H, int W, const int32_t* table, const excel_ragged_info* info,
+                           const int32_t* cent_off /*device [B+1]*/, long long cent_total, int step, int compactness, int iters,
+                           int32_t* sp /*device, one per pixel*/, int32_t* centres /*device [cent_total,5]*/, void* stream);
+int excel_snap_labels_to_superpixels(const uint8_t* labels, const int32_t* sp, int B, int H, int W, const int32_t* table,
+                                     const excel_ragged_info* info, const int32_t* cent_off /*device [B+1]*/, long long cent_total, int step,
+                                     int num_classes, int min_share_pm, uint8_t* out, int32_t* counts /*device [B,3]*/, void* stream);
+
 /* ------------------------------------------------------------------ image tags: the one-hot rows excel_cls_compact reads, predicted
  * Row 0 of the tower's x_raw is CLIP's own image embedding: the reference puts the class token of the original attention path back
  * before ln_post / proj (clip/clip_surgery_model.py:442-446).  The reference never tags images itself (weakly-supervised segmentation
