@@ -100,6 +100,8 @@ extern "C" int excel_gemm_f32(const float* A, const float* Bm, float* C, const f
                               int K, int lda, int ldb, int ldc, int ldr, int b_kmajor, int act, int batch, long long sA,
                               long long sB, long long sC, long long sR, void* stream) {
     GemmArgs g = gemm_args(A, Bm, C, bias, residual, M, N, K, lda, ldb, ldc, ldr, act);
+    EXCEL_CHECK_ALIGN(A, 16, "excel_gemm_f32", "A");              // gemm_f32_kernel loads both operands as f32x4 (gemm.hip load_tile)
+    EXCEL_CHECK_ALIGN(Bm, 16, "excel_gemm_f32", "Bm");
     EXCEL_CHECK_ARG((K % 4) == 0 || !b_kmajor, "excel_gemm_f32: K must be a multiple of 4 in NT mode (K=%d)", K);
     if (!b_kmajor) {
         EXCEL_CHECK_ARG((K % 4) == 0, "excel_gemm_f32: K must be a multiple of 4 (pad A with zeros) (K=%d)", K);
@@ -128,6 +130,7 @@ extern "C" int excel_pack_f16(const float* in, void* out, long long rows, int K,
 static int gemm_split(int mode, const char* name, const void* A_split, const void* W_split, const void* W_half, int w_lo_zero, float* C,
                       const float* bias, const float* residual, int M, int N, int K, int act, int split_out, void* stream) {
     EXCEL_CHECK_ARG(A_split && W_split && C, "%s: null argument", name);
+    // (the launcher refuses A_split, W_split, C, bias and residual below 16 bytes; a W_half below 16 bytes is left unused)
     GemmBfArgs g = gemm_bf_args(A_split, (const unsigned short*)W_split, C, C, bias, residual, M, N, K, N, N, act,
                                 split_out ? GEMM_OUT_SPLIT_BF16 : GEMM_OUT_PLAIN);
     if (w_lo_zero) { g.w_lo_zero = 1; g.Bh = (const unsigned short*)W_half; g.ldbh = K; }
@@ -179,6 +182,7 @@ extern "C" int excel_patch_text_cam_plan(int B, int N, int C, int T, int gemm_mo
 }
 
 extern "C" int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream) {
+    EXCEL_CHECK_ARG(x && w && b && y, "excel_layernorm: null argument");
     return excel_launch_layernorm_f32(x, w, b, y, rows, D, eps, ST(stream));
 }
 
@@ -220,6 +224,7 @@ extern "C" size_t excel_feature_affinity_workspace_bytes(int B, int C, int P) { 
 
 extern "C" int excel_feature_affinity(const float* feats, int B, int C, int P, float beta, float gamma, int mode, float* out,
                                       void* workspace, void* stream) {
+    EXCEL_CHECK_ALIGN(workspace, 16, "feature_affinity", "workspace");      // fn, both operands of the similarity GEMM, and the double partials
     return excel_launch_feature_affinity(feats, B, C, P, beta, gamma, mode, out, workspace, ST(stream));
 }
 
@@ -229,6 +234,7 @@ extern "C" size_t excel_feature_affinity_grouped_workspace_bytes(int B, int C, i
 
 extern "C" int excel_feature_affinity_grouped(const float* feats, int B, int C, int P, int group, int member_stride, float beta, float gamma,
                                               int mode, float* out, void* workspace, void* stream) {
+    EXCEL_CHECK_ALIGN(workspace, 16, "feature_affinity_grouped", "workspace");
     return excel_launch_feature_affinity_grouped(feats, B, C, P, group, member_stride, beta, gamma, mode, out, workspace, ST(stream));
 }
 
@@ -236,6 +242,7 @@ extern "C" size_t excel_attn_select_workspace_bytes(int B, int n_layers) { retur
 
 extern "C" int excel_attn_select_mean(const float* attn, int Lw, int B, int N, int first_layer, int n_layers, const float* seg_attn,
                                       float* w_out, void* workspace, void* stream) {
+    EXCEL_CHECK_ALIGN(workspace, 8, "attn_select_mean", "workspace");       // double partials
     return excel_launch_attn_select_mean(attn, Lw, B, N, first_layer, n_layers, seg_attn, w_out, workspace, ST(stream));
 }
 
@@ -255,6 +262,9 @@ extern "C" int excel_clip_feature_surgery(const float* image_features, const flo
                                           float temperature, float* out_full, float* out_slice, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(image_features && text && workspace && (out_full || out_slice), "clip_feature_surgery: null argument");
     EXCEL_CHECK_ARG((C % 4) == 0, "clip_feature_surgery: C must be a multiple of 4");
+    EXCEL_CHECK_ALIGN(image_features, 16, "clip_feature_surgery", "image_features");      // A and B of the similarity GEMM (f32x4 loads)
+    EXCEL_CHECK_ALIGN(text, 16, "clip_feature_surgery", "text");
+    EXCEL_CHECK_ALIGN(workspace, 16, "clip_feature_surgery", "workspace");
     const CamWs w = cam_ws_layout(B, N, T, workspace);
     // S[b*N+n, t] = f . text[t]  -- one NT GEMM over all B*N token rows (text shared)
     GemmArgs ga = gemm_args(image_features, text, w.S, nullptr, nullptr, B * N, T, C, C, C, w.ldT, 0, GEMM_ACT_NONE);
@@ -283,6 +293,10 @@ extern "C" int excel_patch_text_cam(const float* x_raw, const float* text, int B
     EXCEL_CHECK_ARG(x_raw && text && workspace && (out_full || out_slice), "patch_text_cam: null argument");
     EXCEL_CHECK_ARG(mode == 0 || mode == 1 || mode == 2, "patch_text_cam: mode must be 0 (exact fp32), 1 (bf16x3) or 2 (f16x3)");
     EXCEL_CHECK_ARG(B > 0 && N > 0 && C > 0 && T > 0, "patch_text_cam: bad shape");
+    EXCEL_CHECK_ALIGN(x_raw, 16, "patch_text_cam", "x_raw");                // f32x4 loads, 16-byte LDS DMA of the split text bank (cam.hip)
+    EXCEL_CHECK_ALIGN(text, 16, "patch_text_cam", "text");
+    EXCEL_CHECK_ALIGN(image_features, 16, "patch_text_cam", "image_features");
+    EXCEL_CHECK_ALIGN(workspace, 16, "patch_text_cam", "workspace");
     const int ldT = (T + 3) / 4 * 4;
     const PtcWs w = ptc_ws_layout(B, N, C, T, (char*)workspace);
     return split_api(mode).patch_text_cam(x_raw, text, mode ? w.ts : nullptr, w.sim, w.part, w.colsq, out_full, out_slice, image_features, B, N, C,
@@ -317,6 +331,7 @@ extern "C" size_t excel_trans_mat_workspace_bytes(int B, int P) { return walk_ws
 extern "C" int excel_compute_trans_mat(const float* w_aff, int B, int P, float* trans_out, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(w_aff && trans_out && workspace, "compute_trans_mat: null argument");
     EXCEL_CHECK_ARG((P % 4) == 0, "compute_trans_mat: P must be a multiple of 4 (P=%d)", P);
+    EXCEL_CHECK_ALIGN(workspace, 16, "compute_trans_mat", "workspace");     // Tsym is both operands of the squaring GEMM
     const WalkWs w = walk_ws_layout(B, P, 0, workspace);
     TRY(excel_launch_trans_mat_sym(w_aff, w.T, w.Tsym, w.cs, B, P, ST(stream)));
     // Tsym . Tsym ; Tsym symmetric => B operand [N,K] = Tsym itself (NT form)
@@ -483,6 +498,8 @@ extern "C" int excel_par_forward(const float* imgs, int h, int w, const float* m
     EXCEL_CHECK_ARG(imgs && masks && out && workspace && dilations, "par_forward: null argument");
     EXCEL_CHECK_ARG(n_iter >= 0 && ndil >= 1 && ndil <= 8, "par_forward: bad n_iter/ndil");
     EXCEL_CHECK_ARG(B > 0 && Cmax > 0 && H > 0 && W > 0 && h > 0 && w > 0, "par_forward: bad shape");
+    // fp32 planes are carved from the workspace; 4 bytes is all the streamed kernels need (16-byte aligned buffers: see aligned16 below)
+    EXCEL_CHECK_ALIGN(workspace, 4, "par_forward", "workspace");
     const size_t hw = (size_t)H * W;
     const ParWs ws = par_ws_uniform(B, Cmax, H, W, ndil, workspace);
     float *aff = ws.aff, *pp = ws.pp, *guide = ws.guide;
@@ -515,6 +532,11 @@ extern "C" int excel_par_forward_ragged(const float* imgs, int h, int w, const f
                                         float w2, float* out, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(imgs && masks && out && workspace && dilations && table && info, "par_forward_ragged: null argument");
     EXCEL_CHECK_ARG(Cmax > 0 && h > 0 && w > 0 && info->B > 0, "par_forward_ragged: bad n_iter / shape");
+    // the tile kernels stage masks, the statistics and the guide in 16-byte pieces (par.hip).  These name the pointer; the plan's own
+    // alignment refusal (PAR_REFUSE_ALIGN, reason 3) can then no longer be met here and is kept for excel_par_plan's callers
+    EXCEL_CHECK_ALIGN(masks, 16, "par_forward_ragged", "masks");
+    EXCEL_CHECK_ALIGN(out, 16, "par_forward_ragged", "out");
+    EXCEL_CHECK_ALIGN(workspace, 16, "par_forward_ragged", "workspace");
     const ParWs ws = par_ws_ragged(info->total_pix, Cmax, workspace);
     float *stats = ws.aff, *pp = ws.pp, *guide = ws.guide;
     hipStream_t st = ST(stream);
@@ -524,7 +546,7 @@ extern "C" int excel_par_forward_ragged(const float* imgs, int h, int w, const f
     const ParPlan plan = par_plan(shape);
     EXCEL_CHECK_ARG(plan.refused != PAR_REFUSE_NITER, "par_forward_ragged: bad n_iter / shape");
     EXCEL_CHECK_ARG(!plan.refused,
-                    "par_forward_ragged: needs dilations [1,2,4,8,12,24], 16-byte aligned buffers and max(Cmax,5) * H * Wp * 4 < 2^31 per image "
+                    "par_forward_ragged: needs dilations [1,2,4,8,12,24] and max(Cmax,5) * H * Wp * 4 < 2^31 per image "
                     "(Wp = W rounded up to 4)");
     TRY(excel_launch_bilinear_ac_ragged(imgs, guide, h, w, geo, info->total_tiles, st));
     TRY(excel_launch_par_affinity(guide, stats, geo, dilations, ndil, w1, w2, plan, st));
@@ -559,6 +581,7 @@ extern "C" int excel_argmax_label_ragged(const float* cams, const int32_t* nchan
 extern "C" int excel_argmax_label(const float* cams, const int32_t* nchan, const int32_t* cls_idx, int B, int Smax, int Cmax,
                                   long long HW, uint8_t* labels_u8, int64_t* labels_i64, void* stream) {
     EXCEL_CHECK_ARG(cams && (labels_u8 || labels_i64), "argmax_label: null argument");
+    EXCEL_CHECK_ALIGN(labels_i64, 8, "argmax_label", "labels_i64");
     return excel_launch_argmax_label(cams, nchan, cls_idx, B, Smax, Cmax, HW, labels_u8, (long long*)labels_i64, ST(stream));
 }
 

@@ -98,6 +98,8 @@ extern "C" int excel_cam_overlay_ragged(const uint8_t* hwc, const float* cams, i
                                         const int32_t* table, const excel_ragged_info* info, int mode, const double* tables, uint8_t* out,
                                         void* stream) {
     EXCEL_CHECK_ARG(hwc && cams && ncls && table && info && tables && out, "cam_overlay_ragged: null argument");
+    EXCEL_CHECK_ALIGN(tables, 8, "cam_overlay_ragged", "tables");           // doubles
+    EXCEL_CHECK_ALIGN(out_off, 8, "cam_overlay_ragged", "out_off");         // int64 offsets
     EXCEL_CHECK_ARG(mode == EXCEL_CAM_OVERLAY_MAX || mode == EXCEL_CAM_OVERLAY_PER_CLASS, "cam_overlay_ragged: unknown mode %d", mode);
     EXCEL_CHECK_ARG(mode == EXCEL_CAM_OVERLAY_MAX || out_off, "cam_overlay_ragged: per-class mode needs out_off");
     EXCEL_CHECK_ARG(Cmax >= 1 && info->B >= 1, "cam_overlay_ragged: need Cmax >= 1 and B >= 1");
@@ -110,6 +112,7 @@ extern "C" int excel_cam_overlay_ragged(const uint8_t* hwc, const float* cams, i
 extern "C" int excel_cam_overlay(const uint8_t* hwc, const float* cams, int k, int H, int W, int mode, const double* tables, uint8_t* out,
                                  void* stream) {
     EXCEL_CHECK_ARG(hwc && cams && tables && out, "cam_overlay: null argument");
+    EXCEL_CHECK_ALIGN(tables, 8, "cam_overlay", "tables");                  // doubles
     EXCEL_CHECK_ARG(mode == EXCEL_CAM_OVERLAY_MAX || mode == EXCEL_CAM_OVERLAY_PER_CLASS, "cam_overlay: unknown mode %d", mode);
     EXCEL_CHECK_ARG(k >= 0 && H >= 1 && W >= 1, "cam_overlay: bad shape (k %d, %d x %d)", k, H, W);
     EXCEL_CHECK_ARG((long long)(k + 1) * H * W < (1LL << 31) && 3LL * (k > 1 ? k : 1) * H * W < (1LL << 31),

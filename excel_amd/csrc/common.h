@@ -20,6 +20,11 @@ void excel_set_error(const char* fmt, ...);
         }                                                  \
     } while (0)
 
+// The alignment contract of include/excel_hip.h: a pointer below the alignment its kernels assume is refused before anything is launched
+// (tests/_align_cases.py lists every argument).  NULL passes: an optional argument is checked where it is required.
+#define EXCEL_CHECK_ALIGN(p, bytes, who, name) \
+    EXCEL_CHECK_ARG((((uintptr_t)(p)) & ((bytes) - 1)) == 0, "%s: %s must be %d-byte aligned", who, name, (int)(bytes))
+
 #define EXCEL_CHECK_LAUNCH(name)                                                   \
     do {                                                                           \
         hipError_t e__ = hipGetLastError();                                        \

@@ -68,6 +68,7 @@ static void launch_confusion(const uint8_t* gt, const uint8_t* pred, int B, long
 extern "C" int excel_confusion_accumulate(const uint8_t* gt, const uint8_t* pred, long long n, int num_classes, int64_t* hist,
                                           void* stream) {
     EXCEL_CHECK_ARG(gt && pred && hist && n >= 0, "confusion_accumulate: null argument");
+    EXCEL_CHECK_ALIGN(hist, 8, "confusion_accumulate", "hist");             // 64-bit atomic adds
     if (n == 0) return EXCEL_OK;
     EXCEL_CHECK_ARG(num_classes >= 1 && num_classes <= LABEL_MAXNC, "confusion: need 1 <= num_classes <= %d (got %d)", LABEL_MAXNC, num_classes);
     hipStream_t st = ST(stream);
@@ -81,6 +82,7 @@ extern "C" int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_
                                                  const excel_ragged_info* info, const int32_t* skip, int num_classes, int64_t* hist,
                                                  void* stream) {
     EXCEL_CHECK_ARG(gt && pred && skip && hist, "confusion_accumulate_masked: null argument");
+    EXCEL_CHECK_ALIGN(hist, 8, "confusion_accumulate_masked", "hist");      // 64-bit atomic adds
     EXCEL_CHECK_ARG(num_classes >= 1 && num_classes <= LABEL_MAXNC, "confusion_accumulate_masked: need 1 <= num_classes <= %d (got %d)",
                     LABEL_MAXNC, num_classes);
     long long max_pix;

@@ -558,6 +558,7 @@ static int crf_run(const unsigned char* rgb_hwc, const float* prob, int prob_is_
 extern "C" int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* prob, int prob_is_energy, int H, int W, int C, int iters, float pos_w,
                                     float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q_out, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(rgb_hwc && prob && q_out && workspace && H > 0 && W > 0 && C >= 1 && iters >= 0, "dcrf_inference: bad argument");
+    EXCEL_CHECK_ALIGN(workspace, 8, "dcrf_inference", "workspace");                 // 64-bit fixed-point accumulators
     EXCEL_CHECK_ARG(pos_xy_std > 0.f && bi_xy_std > 0.f && bi_rgb_std > 0.f, "dcrf_inference: standard deviations must be positive");
     const CrfParams P{iters, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std};
     return crf_run<false>(rgb_hwc, prob, prob_is_energy, nullptr, 1, (long long)H * W, H, W, C, P, q_out, nullptr, workspace, (hipStream_t)stream);
@@ -568,6 +569,7 @@ extern "C" int excel_dcrf_inference_ragged(const uint8_t* hwc, const float* unar
                                            const excel_ragged_info* info, int C, int iters, float pos_w, float pos_xy_std, float bi_w,
                                            float bi_xy_std, float bi_rgb_std, uint8_t* labels_u8, float* q_out, void* workspace, void* stream) {
     EXCEL_CHECK_ARG(hwc && unary && table && info && workspace, "dcrf_inference_ragged: null argument");
+    EXCEL_CHECK_ALIGN(workspace, 8, "dcrf_inference_ragged", "workspace");          // 64-bit fixed-point accumulators
     EXCEL_CHECK_ARG(labels_u8 || q_out, "dcrf_inference_ragged: ask for labels, Q or both");
     EXCEL_CHECK_ARG(info->B > 0 && info->B <= CRF_MAX_IMAGES, "dcrf_inference_ragged: %d images, need 1..%d", info->B, CRF_MAX_IMAGES);
     EXCEL_CHECK_ARG(C >= 1 && iters >= 0, "dcrf_inference_ragged: need C >= 1 and iters >= 0");
@@ -611,6 +613,7 @@ extern "C" int excel_dcrf_lam_ragged(const uint8_t* hwc, const float* cams, cons
                                      float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, uint8_t* labels_u8, float* q_out,
                                      void* workspace, void* stream) {
     EXCEL_CHECK_ARG(hwc && cams && nchan && nchan_host && table && info && workspace, "dcrf_lam_ragged: null argument");
+    EXCEL_CHECK_ALIGN(workspace, 8, "dcrf_lam_ragged", "workspace");                // 64-bit fixed-point accumulators
     EXCEL_CHECK_ARG(labels_u8 || q_out, "dcrf_lam_ragged: ask for labels, Q or both");
     EXCEL_CHECK_ARG(info->B > 0 && info->B <= CRF_MAX_IMAGES, "dcrf_lam_ragged: %d images, need 1..%d", info->B, CRF_MAX_IMAGES);
     EXCEL_CHECK_ARG(Cmax >= 1 && iters >= 0, "dcrf_lam_ragged: need Cmax >= 1 and iters >= 0");

@@ -123,6 +123,17 @@ extern "C" int excel_decoder_create(const excel_decoder_config* cfg, const excel
     EXCEL_CHECK_ARG(cfg->vit_layers >= 1 && cfg->dec_layers >= 0 && cfg->heads >= 1 && cfg->embed % cfg->heads == 0 &&
                         (cfg->embed / cfg->heads) % 4 == 0 && cfg->vit_width % 4 == 0 && cfg->num_classes >= 1,
                     "excel_decoder_create: embed must split into heads of a multiple of 4, vit_width %% 4 == 0");
+    for (int l = 0; l < cfg->vit_layers; ++l) {
+        const excel_fuse_layer_weights& f = w->fuse[l];
+        const void* p[] = {f.proj_w, f.proj_b, f.proj2_w, f.proj2_b};
+        const char* name[] = {"proj_w", "proj_b", "proj2_w", "proj2_b"};
+        for (int i = 0; i < 4; ++i) EXCEL_CHECK_ARG(((uintptr_t)p[i] & 15) == 0, "excel_decoder_create: fuse[%d].%s must be 16-byte aligned", l, name[i]);
+    }
+    EXCEL_CHECK_ALIGN(w->fuse_w, 16, "excel_decoder_create", "fuse_w");
+    EXCEL_CHECK_ALIGN(w->fuse_b, 16, "excel_decoder_create", "fuse_b");
+    EXCEL_CHECK_ALIGN(w->pred_w, 16, "excel_decoder_create", "pred_w");
+    EXCEL_CHECK_ALIGN(w->pred_b, 16, "excel_decoder_create", "pred_b");
+    TRY(check_block_weights_aligned("excel_decoder_create", w->blocks, cfg->dec_layers));
     excel_decoder* h = new excel_decoder();
     h->cfg = *cfg;
     h->w = *w;
@@ -145,6 +156,8 @@ extern "C" size_t excel_decoder_workspace_bytes(excel_decoder_t h, int B, int g)
 extern "C" int excel_decoder_forward(excel_decoder_t h, const float* all_feats, int B, int g, void* workspace, size_t workspace_bytes,
                                      float* attn_fts_out, float* seg_out, void* stream) {
     EXCEL_CHECK_ARG(h && all_feats && workspace && B > 0 && g > 0, "excel_decoder_forward: bad argument");
+    EXCEL_CHECK_ALIGN(all_feats, 16, "excel_decoder_forward", "all_feats");          // the A operand of the first fuse GEMM, read in place
+    EXCEL_CHECK_ALIGN(workspace, 16, "excel_decoder_forward", "workspace");
     const excel_decoder_config& c = h->cfg;
     const int P = g * g, N = P + 1, D = c.vit_width, E = c.embed, L = c.vit_layers, H = c.heads, hd = E / H, nc = c.num_classes;
     const int M = B * P;
@@ -251,6 +264,12 @@ extern "C" int excel_text_create(const excel_text_config* cfg, const excel_text_
     EXCEL_CHECK_ARG(cfg && w && out && w->blocks && w->token_embedding && w->positional_embedding && w->text_projection, "excel_text_create: null argument");
     EXCEL_CHECK_ARG(cfg->width % cfg->heads == 0 && (cfg->width / cfg->heads) % 4 == 0 && cfg->embed_dim % 4 == 0 && cfg->context_length >= 1,
                     "excel_text_create: width must split into heads of a multiple of 4, embed_dim %% 4 == 0");
+    EXCEL_CHECK_ALIGN(w->token_embedding, 16, "excel_text_create", "token_embedding");
+    EXCEL_CHECK_ALIGN(w->positional_embedding, 16, "excel_text_create", "positional_embedding");
+    EXCEL_CHECK_ALIGN(w->ln_final_w, 16, "excel_text_create", "ln_final_w");
+    EXCEL_CHECK_ALIGN(w->ln_final_b, 16, "excel_text_create", "ln_final_b");
+    EXCEL_CHECK_ALIGN(w->text_projection, 16, "excel_text_create", "text_projection");
+    TRY(check_block_weights_aligned("excel_text_create", w->blocks, cfg->layers));
     excel_text* h = new excel_text();
     h->cfg = *cfg;
     h->w = *w;
@@ -266,6 +285,7 @@ extern "C" size_t excel_text_workspace_bytes(excel_text_t h, int B) { return (h 
 
 extern "C" int excel_text_encode(excel_text_t h, const int32_t* tokens, int B, float* out, void* workspace, size_t workspace_bytes, void* stream) {
     EXCEL_CHECK_ARG(h && tokens && out && workspace && B > 0, "excel_text_encode: bad argument");
+    EXCEL_CHECK_ALIGN(workspace, 16, "excel_text_encode", "workspace");              // GEMM operands and LayerNorm rows
     const excel_text_config& c = h->cfg;
     const int P = c.context_length, E = c.width, M = B * P;
     hipStream_t st = (hipStream_t)stream;

@@ -296,3 +296,17 @@ __device__ __forceinline__ float bilinear_blend(float ly, float lx, float p00, f
 __device__ __forceinline__ float bilinear_blend(const BilinearTap& t, float p00, float p01, float p10, float p11) {
     return bilinear_blend(t.ly, t.lx, p00, p01, p10, p11);
 }
+
+// The 12 weights of a transformer block (excel_vit_block_weights and excel_decoder_block_weights name them alike) for the *_create entries:
+// every one is read 16 bytes at a time somewhere - the matrices as GEMM operands and by the split / pack kernels, the LayerNorm weights by
+// ln_row, the biases by the split-plane GEMM's epilogue (the fp32 GEMM reads them by element: one rule per handle all the same).
+template <class BlockWeights>
+static inline int check_block_weights_aligned(const char* who, const BlockWeights* blocks, int n) {
+    static const char* const name[12] = {"ln1_w", "ln1_b", "in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b"};
+    for (int l = 0; l < n; ++l) {
+        const BlockWeights& b = blocks[l];
+        const void* p[12] = {b.ln1_w, b.ln1_b, b.in_proj_w, b.in_proj_b, b.out_proj_w, b.out_proj_b, b.ln2_w, b.ln2_b, b.fc1_w, b.fc1_b, b.fc2_w, b.fc2_b};
+        for (int i = 0; i < 12; ++i) EXCEL_CHECK_ARG(((uintptr_t)p[i] & 15) == 0, "%s: blocks[%d].%s must be 16-byte aligned", who, l, name[i]);
+    }
+    return EXCEL_OK;
+}

@@ -524,7 +524,15 @@ int excel_launch_gemm_bf16x3(const GemmBfArgs& p_in, hipStream_t stream) {
     EXCEL_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0 && (p.K % TBK) == 0, "gemm_bf16x3: K must be a multiple of %d (K=%d)", TBK, p.K);
     EXCEL_CHECK_ARG(p.out_mode != GEMM_OUT_SPLIT_BF16 || (p.N % 32) == 0, "gemm_bf16x3: split output needs N %% 32 == 0");
     EXCEL_CHECK_ARG((p.lda % 8) == 0 && (p.ldb % 8) == 0 && p.lda >= 2 * p.K && p.ldb >= 2 * p.K, "gemm_bf16x3: bad lda/ldb");
-    EXCEL_CHECK_ARG((((uintptr_t)p.A | (uintptr_t)p.B) & 15) == 0, "gemm_bf16x3: operands must be 16-byte aligned");
+    // 16-byte DMA of both operands into LDS; the epilogue reads bias / residual as f32x4 and stores fp32 rows as f32x4, split planes in
+    // 8-byte pieces.  (Bh, the half weights: below 16 bytes they are left unused - gemm_half_ok below - and the split weights serve.)
+    EXCEL_CHECK_ALIGN(p.A, 16, "gemm_bf16x3", "A_split");
+    EXCEL_CHECK_ALIGN(p.B, 16, "gemm_bf16x3", "W_split");
+    EXCEL_CHECK_ALIGN(p.C, 16, "gemm_bf16x3", "C");
+    EXCEL_CHECK_ALIGN(p.Cs, 16, "gemm_bf16x3", "C (split output)");
+    EXCEL_CHECK_ALIGN(p.qkv_split, 16, "gemm_bf16x3", "qkv_split");
+    EXCEL_CHECK_ALIGN(p.bias, 16, "gemm_bf16x3", "bias");
+    EXCEL_CHECK_ALIGN(p.res, 16, "gemm_bf16x3", "residual");
     const GemmShape s = {p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.ldr, p.hd, p.out_mode, p.res != nullptr, p.batch,
                          std::is_same<split_t, _Float16>::value, p.w_lo_zero,
                          gemm_half_ok(p.Bh && ((uintptr_t)p.Bh & 15) == 0, p.N, p.K, p.ldbh)};
@@ -561,6 +569,9 @@ int excel_launch_gemm_bf16x3(const GemmBfArgs& p_in, hipStream_t stream) {
 int excel_launch_pack_hi(const float* in, void* out, long long R, int K, unsigned long long* inexact, hipStream_t st) {
     ProfScope prof__(PROF_OTHER, st);
     EXCEL_CHECK_ARG(in && out && inexact && R > 0 && K > 0 && ((R * K) % 4) == 0, "pack_hi: bad argument (R * K must be a multiple of 4)");
+    EXCEL_CHECK_ALIGN(in, 16, "pack_f16", "in");                  // pack_hi_kernel: f32x4 loads, 8-byte stores, a 64-bit atomic counter
+    EXCEL_CHECK_ALIGN(out, 8, "pack_f16", "out");
+    EXCEL_CHECK_ALIGN(inexact, 8, "pack_f16", "inexact_dev");
     hipLaunchKernelGGL(pack_hi_kernel, dim3((unsigned)cdivl(R * K / 4, 256)), dim3(256), 0, st, in, (u16*)out, R * K, inexact);
     EXCEL_CHECK_LAUNCH("pack_hi");
     return EXCEL_OK;
@@ -569,6 +580,8 @@ int excel_launch_pack_hi(const float* in, void* out, long long R, int K, unsigne
 int excel_launch_split_bf16(const float* in, void* out, long long R, int K, hipStream_t st) {
     ProfScope prof__(PROF_OTHER, st);
     EXCEL_CHECK_ARG((K % 32) == 0, "split_bf16: K must be a multiple of 32 (blocked hi/lo layout)");
+    EXCEL_CHECK_ALIGN(in, 16, "split_bf16", "in");                // split_bf16_kernel: f32x4 loads, 8-byte plane stores
+    EXCEL_CHECK_ALIGN(out, 8, "split_bf16", "out");
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)cdivl(R * K / 4, 256)), dim3(256), 0, st, in, (u16*)out, R, K);
     EXCEL_CHECK_LAUNCH("split_bf16");
     return EXCEL_OK;

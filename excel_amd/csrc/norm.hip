@@ -181,6 +181,13 @@ int excel_launch_layernorm(const float* x, const float* cls_src, int tokN, const
                            int rows, int D, float eps, hipStream_t st, int split_out, long long in_stride) {
     ProfScope prof__(PROF_LAYERNORM, st);
     EXCEL_CHECK_ARG(rows > 0 && D > 0 && (D % 4) == 0, "layernorm: D must be a multiple of 4 (D=%d)", D);
+    // ln_row / ln_row_reg touch memory as f32x4 only (the split output in 8-byte halves of the same 16 bytes)
+    EXCEL_CHECK_ALIGN(x, 16, "layernorm", "x");
+    EXCEL_CHECK_ALIGN(cls_src, 16, "layernorm", "cls_src");
+    EXCEL_CHECK_ALIGN(w, 16, "layernorm", "w");
+    EXCEL_CHECK_ALIGN(b, 16, "layernorm", "b");
+    EXCEL_CHECK_ALIGN(y, 16, "layernorm", "y");
+    EXCEL_CHECK_ARG((in_stride % 4) == 0, "layernorm: in_stride must be a multiple of 4");
     hipLaunchKernelGGL(layernorm_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, cls_src, tokN, w, b, y, rows, D, eps, split_out, in_stride > 0 ? in_stride : (long long)D);
     EXCEL_CHECK_LAUNCH("layernorm_rows");
     return EXCEL_OK;
@@ -190,6 +197,8 @@ int excel_launch_assemble_ln_pre(const float* patch, const float* cls_emb, const
                                  float* x, int B, int tokN, int D, float eps, hipStream_t st) {
     ProfScope prof__(PROF_EMBED, st);
     EXCEL_CHECK_ARG((D % 4) == 0, "assemble_ln_pre: D must be a multiple of 4");
+    EXCEL_CHECK_ARG((((uintptr_t)patch | (uintptr_t)cls_emb | (uintptr_t)pos | (uintptr_t)w | (uintptr_t)b | (uintptr_t)x) & 15) == 0,
+                    "assemble_ln_pre: patch, class_emb, pos_emb, ln_pre_w, ln_pre_b and x must be 16-byte aligned");
     hipLaunchKernelGGL(assemble_ln_pre_kernel, dim3(cdiv(B * tokN, 4)), dim3(256), 0, st, patch, cls_emb, pos, w, b, x, B, tokN, D, eps);
     EXCEL_CHECK_LAUNCH("assemble_ln_pre");
     return EXCEL_OK;
@@ -198,6 +207,7 @@ int excel_launch_assemble_ln_pre(const float* patch, const float* cls_emb, const
 int excel_launch_token_axis_normalize(const float* f, float* ss, float* out, int B, int tokN, int C, hipStream_t st) {
     ProfScope prof__(PROF_TOKEN_NORM, st);
     EXCEL_CHECK_ARG((C % 4) == 0, "token_axis_normalize: C must be a multiple of 4");
+    EXCEL_CHECK_ARG((((uintptr_t)f | (uintptr_t)ss | (uintptr_t)out) & 15) == 0, "token_axis_normalize: f, ss and out must be 16-byte aligned");
     hipLaunchKernelGGL(token_axis_sumsq_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, st, f, ss, tokN, C);
     EXCEL_CHECK_LAUNCH("token_axis_sumsq");
     const long long total4 = (long long)B * tokN * C / 4;
@@ -209,6 +219,7 @@ int excel_launch_token_axis_normalize(const float* f, float* ss, float* out, int
 int excel_launch_im2col(const float* img, float* col, int B, int S, int ps, hipStream_t st, int split_out) {
     ProfScope prof__(PROF_EMBED, st);
     EXCEL_CHECK_ARG(S % ps == 0 && (ps % 4) == 0, "im2col: S must be a multiple of the patch size, patch %% 4 == 0");
+    EXCEL_CHECK_ARG((((uintptr_t)img | (uintptr_t)col) & 15) == 0, "im2col: img and col must be 16-byte aligned");
     const int g = S / ps;
     const long long total4 = (long long)B * g * g * 3 * ps * ps / 4;
     hipLaunchKernelGGL(im2col_kernel, dim3((unsigned)cdivl(total4, 256)), dim3(256), 0, st, img, col, S, g, ps, total4, split_out);

@@ -183,6 +183,7 @@ int excel_launch_train_losses(const float* seg, const float* attn_pred, const un
     if (!aff_labels) aff_labels = pseudo;
     ProfScope prof__(PROF_OTHER, st);
     EXCEL_CHECK_ARG(seg && attn_pred && pseudo && losses && d_seg && d_attn_pred && ws, "train_losses: null argument");
+    EXCEL_CHECK_ALIGN(ws, 8, "train_losses", "workspace");                          // double partial sums
     EXCEL_CHECK_ARG(B > 0 && nc > 1 && g_h > 0 && g_w > 0 && H % g_h == 0 && W % g_w == 0 && H / g_h == W / g_w, "train_losses: label size must be a multiple of the token grid");
     const LossWs lw = loss_ws_layout(B, nc, H, W, ws);
     float *up = lw.up, *stats = lw.stats;
@@ -507,6 +508,8 @@ extern "C" int excel_decoder_forward_train(excel_decoder_t h, const float* all_f
     EXCEL_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "excel_decoder_forward_train: dropout_p must be in [0,1)");
     EXCEL_CHECK_ARG(h && all_feats && workspace && seg_out && attn_pred_out && B > 0 && g > 0 && (g * g) % 4 == 0,
                     "excel_decoder_forward_train: bad argument (the token count g*g must be a multiple of 4)");
+    EXCEL_CHECK_ALIGN(all_feats, 16, "excel_decoder_forward_train", "all_feats");    // the A operand of the first fuse GEMM, read in place
+    EXCEL_CHECK_ALIGN(workspace, 16, "excel_decoder_forward_train", "workspace");
     const excel_decoder_config& c = h->cfg;
     const int P = g * g, N = P + 1, D = c.vit_width, E = c.embed, L = c.vit_layers, H = c.heads, hd = E / H, nc = c.num_classes, nl = c.dec_layers;
     const int M = B * P;
@@ -600,6 +603,7 @@ static int tr_linear_bwd(const float* dY, int ldy, const float* X, int ldx, cons
 extern "C" int excel_decoder_train_attn_fts(excel_decoder_t h, int B, int g, const void* workspace, size_t workspace_bytes, float* attn_fts_out,
                                             void* stream) {
     EXCEL_CHECK_ARG(h && workspace && attn_fts_out && B > 0 && g > 0, "excel_decoder_train_attn_fts: bad argument");
+    EXCEL_CHECK_ALIGN(workspace, 16, "excel_decoder_train_attn_fts", "workspace");
     const excel_decoder_config& c = h->cfg;
     TrainWs ws = train_ws_layout(c, B, g, (char*)workspace);
     EXCEL_CHECK_ARG(workspace_bytes >= ws.total, "excel_decoder_train_attn_fts: workspace too small");
@@ -611,6 +615,7 @@ extern "C" int excel_decoder_backward(excel_decoder_t h, const float* all_feats,
                                       unsigned dropout_seed, void* stream) {
     EXCEL_CHECK_ARG(h && all_feats && workspace && d_seg && grads && grads->fuse && grads->blocks && B > 0 && g > 0 && (g * g) % 4 == 0,
                     "excel_decoder_backward: bad argument (the token count g*g must be a multiple of 4)");
+    EXCEL_CHECK_ALIGN(workspace, 16, "excel_decoder_backward", "workspace");          // (all_feats is only copied from here: 4 bytes)
     const excel_decoder_config& c = h->cfg;
     const int P = g * g, N = P + 1, D = c.vit_width, E = c.embed, L = c.vit_layers, H = c.heads, hd = E / H, nc = c.num_classes, nl = c.dec_layers;
     const int M = B * P;

@@ -156,6 +156,7 @@ extern "C" int excel_train_panels(const float* img, const float* attr, const flo
     const int rc = tv_check_shape("train_panels", B, nrow, S, g, panel_mask);
     if (rc != EXCEL_OK) return rc;
     EXCEL_CHECK_ARG(out && palette && jet && mean && std, "train_panels: null argument");
+    EXCEL_CHECK_ALIGN(jet, 8, "train_panels", "jet");                       // doubles
     const int m = panel_mask;
     const int want_img = (m >> EXCEL_TRAIN_PANEL_IMG1) & 1, want_cam = (m >> EXCEL_TRAIN_PANEL_CAM1) & 1;
     EXCEL_CHECK_ARG(!(want_img || want_cam) || img, "train_panels: img1 / cam1 requested without the input images");

@@ -188,6 +188,15 @@ extern "C" int excel_vit_create(const excel_vit_config* cfg, const excel_vit_wei
     EXCEL_CHECK_ARG(cfg->heads > 0 && cfg->width == cfg->heads * 64, "excel_vit_create: head_dim must be 64 (width=%d heads=%d)", cfg->width, cfg->heads);
     EXCEL_CHECK_ARG(cfg->layers >= 1 && cfg->n_surgery >= 0 && cfg->n_surgery <= cfg->layers, "excel_vit_create: bad layer counts");
     EXCEL_CHECK_ARG((cfg->out_dim % 4) == 0 && (cfg->patch % 4) == 0, "excel_vit_create: out_dim and patch must be multiples of 4");
+    // every weight is read 16 bytes at a time somewhere on the path: matrices by the GEMMs' operand loads and the split / pack kernels,
+    // LayerNorm weights, class_emb and pos_emb by ln_row, biases by the split-plane GEMM's epilogue
+    EXCEL_CHECK_ARG(w->blocks, "excel_vit_create: null argument");
+    {
+        const void* top[] = {w->conv1_w, w->class_emb, w->pos_emb, w->ln_pre_w, w->ln_pre_b, w->ln_post_w, w->ln_post_b, w->proj};
+        const char* top_name[] = {"conv1_w", "class_emb", "pos_emb", "ln_pre_w", "ln_pre_b", "ln_post_w", "ln_post_b", "proj"};
+        for (int i = 0; i < 8; ++i) EXCEL_CHECK_ALIGN(top[i], 16, "excel_vit_create", top_name[i]);
+        TRY(check_block_weights_aligned("excel_vit_create", w->blocks, cfg->layers));
+    }
     excel_vit* h = new excel_vit();
     h->cfg = *cfg;
     h->w = *w;
@@ -274,6 +283,13 @@ static int vit_forward(const SplitApi& k, excel_vit_t h, const float* img, int B
     const int ps = c.patch, g = S / ps, P = g * g, N = P + 1, D = c.width, H = c.heads, L = c.layers, C = c.out_dim;
     EXCEL_CHECK_ARG(n_attn_out >= 0 && n_attn_out <= L && (n_attn_out == 0 || attn_out), "excel_vit_forward: bad attn_out request");
     EXCEL_CHECK_ARG(!w_aff || (aff_layers >= 1 && aff_layers <= L), "excel_vit_forward: bad aff_layers");
+    // img: im2col reads f32x4; x_raw: the projection GEMM's f32x4 stores and token_axis_scale's f32x4 loads; image_features: its f32x4
+    // stores; the workspace holds every GEMM operand.  w_aff, attn_out and ex_attn are touched one element at a time and feats_out by
+    // copies: 4 bytes.
+    EXCEL_CHECK_ALIGN(img, 16, "excel_vit_forward", "img");
+    EXCEL_CHECK_ALIGN(workspace, 16, "excel_vit_forward", "workspace");
+    EXCEL_CHECK_ALIGN(image_features, 16, "excel_vit_forward", "image_features");
+    EXCEL_CHECK_ALIGN(x_raw, 16, "excel_vit_forward", "x_raw");
     hipStream_t st = ST(stream);
     VitWs ws = vit_ws_layout(c, B, S, (char*)workspace);
     EXCEL_CHECK_ARG(workspace_bytes >= ws.total, "excel_vit_forward: workspace too small (%zu < %zu)", workspace_bytes, ws.total);

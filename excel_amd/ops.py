@@ -35,16 +35,37 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
-def f32c(t):
-    return t.to(dtype=torch.float32).contiguous()
+def _realign(t, align=16):
+    """An INPUT of an op whose kernels read `align` bytes at a time (the per-op audit is tests/_align_cases.py): `t` itself when it
+    starts on such a boundary - one integer test, nothing else - and otherwise a copy in fresh storage, which the allocator aligns to
+    256 bytes or more.  A contiguous view into a pooled buffer (buf[1:1 + n].view(shape)) is the case: same values, same kernels, same
+    bits.  The copy is queued on the current stream like the launch that reads it."""
+    if t is None or t.data_ptr() % align == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
+def _written(t, who, name, align=16):
+    """An argument the op WRITES cannot be copied: one that starts below the alignment the kernels assume is refused here, by name,
+    before anything is allocated or launched."""
+    if t is not None and t.data_ptr() % align:
+        raise ValueError(f"{who}: {name} must be {align}-byte aligned (it starts {t.data_ptr() % align} bytes past a {align}-byte boundary: "
+                         "a view into a larger buffer?); the kernels write it in wider pieces and it cannot be copied")
+    return t
+
+
+def f32c(t, align=4):
+    """fp32 and contiguous; align=16 for the inputs of ops whose kernels read 16 bytes at a time (_realign)."""
+    t = t.to(dtype=torch.float32).contiguous()
+    return t if align <= 4 else _realign(t, align)
 
 
 # ------------------------------------------------------------------ building blocks
 def gemm(A, Bm, bias=None, residual=None, act=0, b_kmajor=True):
     """C = act(A @ op(B) + bias) + residual.  A [M,K] (or [batch,M,K]); B [N,K] if b_kmajor else [K,N]."""
     batched = A.dim() == 3
-    A3 = A if batched else A[None]
-    B3 = Bm if Bm.dim() == 3 else Bm[None]
+    A3 = _realign(A if batched else A[None])         # both operands are loaded 16 bytes at a time; C, bias and residual by element
+    B3 = _realign(Bm if Bm.dim() == 3 else Bm[None])
     batch, M, K = A3.shape
     N = B3.shape[1] if b_kmajor else B3.shape[2]
     out = torch.empty((batch, M, N), dtype=torch.float32, device=A.device)
@@ -59,7 +80,7 @@ GEMM_MODES = {"f32": 0, "bf16x3": 1, "f16x3": 2, "f16x2": 3}      # excel_vit_se
 
 def split_bf16(x, f16=False):
     """fp32 [R,K] -> split operand [R,2,K] (bf16 - or, with f16, IEEE-half - bit patterns in an int16 tensor)."""
-    x = f32c(x)
+    x = f32c(x, 16)
     R, K = x.shape
     out = torch.empty((R, 2, K), dtype=torch.int16, device=x.device)
     fn = lib().excel_split_f16 if f16 else lib().excel_split_bf16
@@ -69,6 +90,8 @@ def split_bf16(x, f16=False):
 
 def gemm_bf16x3(A_split, W_split, bias=None, residual=None, act=0, split_out=False, f16=False):
     """C = act(A . W^T + bias) + residual from two split operands (three 16-bit MFMAs per product); f16: IEEE-half planes (split_bf16(f16=True))."""
+    # 16-byte DMA of the operands into LDS; the epilogue reads bias and residual 16 bytes at a time
+    A_split, W_split, bias, residual = _realign(A_split), _realign(W_split), _realign(bias), _realign(residual)
     M, _, K = A_split.shape
     N = W_split.shape[0]
     out = torch.empty((M, N), dtype=torch.float32, device=A_split.device)
@@ -81,7 +104,7 @@ def gemm_bf16x3(A_split, W_split, bias=None, residual=None, act=0, split_out=Fal
 def pack_f16(x):
     """fp32 [R,K] -> (the hi plane as a plain IEEE-half matrix [R,K] (int16 bit patterns), number of elements NOT representable in
     half).  The second value is 0 exactly when `x` is fp16-valued - the precondition of gemm_f16x2 (every published CLIP archive)."""
-    x = f32c(x)
+    x = f32c(x, 16)
     R, K = x.shape
     out = torch.empty((R, K), dtype=torch.int16, device=x.device)
     cnt = torch.zeros(1, dtype=torch.int64, device=x.device)
@@ -92,6 +115,8 @@ def pack_f16(x):
 def gemm_f16x2(A_split, W_split, W_half=None, bias=None, residual=None, act=0, split_out=False):
     """gemm_bf16x3(..., f16=True) for fp16-VALUED weights (the lo plane of W_split is all zero): two MFMAs per product, the same bits.
     W_half (pack_f16 of the same weights) lets the large-tile kernel stream half the weight bytes."""
+    # as gemm_bf16x3; W_half goes as it is: the library leaves a half matrix below 16 bytes unused (the split weights serve, same bits)
+    A_split, W_split, bias, residual = _realign(A_split), _realign(W_split), _realign(bias), _realign(residual)
     M, _, K = A_split.shape
     N = W_split.shape[0]
     out = torch.empty((M, N), dtype=torch.float32, device=A_split.device)
@@ -144,6 +169,7 @@ def cam_plan(B, N, C_, T, mode="bf16x3"):
 
 
 def layernorm(x, w, b, eps=1e-5):
+    x, w, b = _realign(x), _realign(w), _realign(b)      # a row, the weight and the bias are read 16 bytes at a time
     D = x.shape[-1]
     y = torch.empty_like(x)
     check(lib().excel_layernorm(_p(x), _p(w), _p(b), _p(y), x.numel() // D, D, eps, _stream()), "excel_layernorm")
@@ -159,7 +185,7 @@ class VitHandle:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("excel_amd.VitHandle needs a GPU device: the HIP library is the only compute path")
-        g = lambda k: f32c(torch.as_tensor(state_dict[prefix + k])).to(self.device)
+        g = lambda k: _realign(f32c(torch.as_tensor(state_dict[prefix + k])).to(self.device))      # excel_vit_create: 16-byte aligned weights
         self.cfg = dict(width=width, layers=layers, heads=heads, patch=patch, out_dim=out_dim, n_surgery=n_surgery)
         self.t = {}
         top = {"conv1_w": "conv1.weight", "class_emb": "class_embedding", "pos_emb": "positional_embedding",
@@ -257,7 +283,7 @@ class VitHandle:
         """-> dict(image_features [B,N,C], w_aff [B,P,P]|None, attn [n,B,N,N]|None, feats [L,B,N,D]|None, x_raw|None)
         ex_attn [B,P,P]: LVC cue added to every head of every surgery block (clip_surgery_model.py:127-141).
         feats_as_reference: `feats` as the reference's decoder receives them (in-place aliasing quirk, include/excel_hip.h)."""
-        imgs = f32c(imgs)
+        imgs = f32c(imgs, 16)          # im2col reads 16 bytes at a time; ex_attn is read by element
         B, _, S, S2 = imgs.shape
         assert S == S2
         c = self.cfg
@@ -291,7 +317,7 @@ class DecoderHandle:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("excel_amd.DecoderHandle needs a GPU device: the HIP library is the only compute path")
-        g = lambda sd, k: f32c(torch.as_tensor(sd[k])).to(self.device)
+        g = lambda sd, k: _realign(f32c(torch.as_tensor(sd[k])).to(self.device))       # excel_decoder_create: 16-byte aligned weights
         self.t = {}
         L = 0
         while f"linears_modulelist.{L}.proj.weight" in fuse_sd:
@@ -458,7 +484,7 @@ class DecoderHandle:
 
     def forward_train(self, all_feats, dropout_p=0.0, dropout_seed=0):
         """-> (seg [B,nc,g,g], attn_pred [B,P,P], ctx) ; ctx goes to backward().  dropout_p: the head's Dropout2d (0.1 in the reference)."""
-        all_feats = f32c(all_feats)
+        all_feats = f32c(all_feats, 16)        # read in place as the A operand of the fuse GEMMs
         L, B, N, D = all_feats.shape
         g = int(round((N - 1) ** 0.5))
         c = self.cfg
@@ -501,7 +527,7 @@ class DecoderHandle:
 
     def forward(self, all_feats, want_seg=True):
         """all_feats [L,B,N,D] -> (attn_fts [B,E,g,g], seg [B,nc,g,g] | None)"""
-        all_feats = f32c(all_feats)
+        all_feats = f32c(all_feats, 16)
         L, B, N, D = all_feats.shape
         c = self.cfg
         g = int(round((N - 1) ** 0.5))
@@ -529,7 +555,7 @@ class TextHandle:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("excel_amd.TextHandle needs a GPU device: the HIP library is the only compute path")
-        g = lambda k: f32c(torch.as_tensor(sd[k])).to(self.device)
+        g = lambda k: _realign(f32c(torch.as_tensor(sd[k])).to(self.device))           # excel_text_create: 16-byte aligned weights
         self.t = {}
         nl = 0
         while f"transformer.resblocks.{nl}.ln_1.weight" in sd:
@@ -748,8 +774,8 @@ def seg_softmax_resize_ragged(planes, src_plan, dst_plan, nc):
 # ------------------------------------------------------------------ CAM
 def clip_feature_surgery(image_features, text_features, num_fg=None, t=2.0, want_full=True):
     """image_features [B,N,C], text_features [T,C] -> (full [B,N,T] | None, slice [B,N-1,F] | None)."""
-    image_features = f32c(image_features)
-    text_features = f32c(text_features)
+    image_features = f32c(image_features, 16)      # the operands of the similarity GEMM
+    text_features = f32c(text_features, 16)
     B, N, Cc = image_features.shape
     T = text_features.shape[0]
     dev = image_features.device
@@ -765,8 +791,8 @@ def clip_feature_surgery(image_features, text_features, num_fg=None, t=2.0, want
 def patch_text_cam(x_raw, text_features, num_fg=None, t=2.0, want_full=False, want_features=False, mode="bf16x3"):
     """Fused path (excel_patch_text_cam): un-normalised token features x_raw [B,N,C] (VitHandle.forward(want_raw=True)) + text [T,C]
     -> (full [B,N,T] | None, slice [B,N-1,F] | None, image_features [B,N,C] | None): clip.py:353 + :288-310 (column-norm pass, similarity tiles, finish)."""
-    x_raw = f32c(x_raw)
-    text_features = f32c(text_features)
+    x_raw = f32c(x_raw, 16)
+    text_features = f32c(text_features, 16)
     B, N, Cc = x_raw.shape
     T = text_features.shape[0]
     dev = x_raw.device
@@ -910,6 +936,9 @@ def par_forward(imgs, masks, dilations=PAR_DILATIONS, num_iter=20, nchan=None, w
     """stream_affinities: stream the 8*ndil affinity planes instead of recomputing them per step (bit-identical outputs; the
     reference form of the recomputing kernel, and what shapes / dilation sets outside its envelope use anyway).
     Channels >= nchan[b] of `out` are not written (zero in a fresh tensor)."""
+    # imgs, masks and out go as they are: the library plans the streamed-plane kernels when one of them is not 16-byte aligned (same
+    # bits); the workspace is carved into fp32 planes
+    _written(ws, "par_forward", "ws", 4)
     imgs = f32c(imgs)
     masks = f32c(masks)
     B, Cmax, H, W = masks.shape
@@ -1239,6 +1268,8 @@ def png_encode_labels_ragged(labels_flat, plan, palette=None, out=None, ws=None)
         out = torch.empty(need, dtype=torch.uint8, device=dev)
     elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
         raise ValueError("out= must be a flat contiguous uint8 tensor")
+    _written(out, "png_encode_labels_ragged", "out", 4)      # the arena is cleared and filled in 32-bit words
+    _written(ws, "png_encode_labels_ragged", "ws", 8)        # 8-byte row records
     ws_need = int(lib().excel_png_labels_workspace_bytes(plan.B, int(hw[:, 0].max())))
     if ws is None:
         ws = _ws(ws_need, dev)
@@ -1296,6 +1327,7 @@ def jpeg_encode_rgb_ragged(rgb_flat, items, quality=75, out=None, ws=None):
         out = torch.empty(max(int(lib().excel_jpeg_rgb_arena_bytes(hw_p, n)), 1), dtype=torch.uint8, device=dev)
     elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
         raise ValueError("out= must be a flat contiguous uint8 tensor")
+    _written(ws, "jpeg_encode_rgb_ragged", "ws")             # records, coefficients and 16-byte chunks of stream words
     if ws is None:
         ws = _ws(max(int(lib().excel_jpeg_rgb_workspace_bytes(hw_p, n)), 1), dev)
     table = torch.empty((n, 2), dtype=torch.int64, device=dev)
@@ -1405,6 +1437,7 @@ def train_augment_image(images_u8, plan, params, crop_size, aug_plan=None, mean=
 def cam_upsample_bkg_ragged(refined, ncls, g, plan, out=None, zero_unused=True):
     """refined [B,Smax,P] -> packed cams: (Smax+1) pitched planes per image at its own (H_b, W_b).  The pad columns (x >= W_b) of the
     pitched rows are not written, and with zero_unused=False neither are the planes > ncls[b]: every consumer stops at W_b and nchan[b]."""
+    _written(out, "cam_upsample_bkg_ragged", "out")      # pitched planes: every row starts on a 16-byte boundary
     refined = f32c(refined)
     B, smax, P = refined.shape
     assert B == plan.B
@@ -1417,7 +1450,11 @@ def cam_upsample_bkg_ragged(refined, ncls, g, plan, out=None, zero_unused=True):
 
 def par_forward_ragged(imgs, masks, plan, Cmax, dilations=PAR_DILATIONS, num_iter=20, nchan=None, w1=0.3, w2=0.01, out=None, ws=None):
     """imgs [B,3,h,w] (uniform), masks = Cmax pitched planes per image -> refined masks, same layout."""
+    # only the tile kernel exists for ragged batches: it stages masks, out and the workspace in 16-byte pieces
+    _written(out, "par_forward_ragged", "out")
+    _written(ws, "par_forward_ragged", "ws")
     imgs = f32c(imgs)
+    masks = _realign(masks)
     assert imgs.shape[0] == plan.B and imgs.shape[1] == 3 and masks.numel() == Cmax * plan.total_pix
     h, w = imgs.shape[-2:]
     out = _out(out, masks.shape, torch.float32, masks.device, zero=True)
@@ -1543,16 +1580,13 @@ def clip_tags(x, text_rows, num_fg, scale=100.0, thre=0.2, kmax=6, want_scores=T
     the lower index).  A row with a non-finite logit gets class 0 alone and NaN scores.  One launch, no scratch memory, no synchronisation."""
     if x.dim() not in (2, 3):
         raise ValueError(f"clip_tags: x must be [B,N,C] or [B,C], got {tuple(x.shape)}")
-    x = f32c(x)
-    text_rows = f32c(text_rows)
+    x = f32c(x, 16)                 # the kernel reads both 16 bytes at a time
+    text_rows = f32c(text_rows, 16)
     B, C_ = int(x.shape[0]), int(x.shape[-1])
     stride = int(x.shape[1]) * C_ if x.dim() == 3 else C_
     T = int(text_rows.shape[0])
     if text_rows.dim() != 2 or int(text_rows.shape[1]) != C_:
         raise ValueError(f"clip_tags: text_rows must be [T,{C_}], got {tuple(text_rows.shape)}")
-    if x.data_ptr() % 16 or text_rows.data_ptr() % 16:       # a view at an odd offset: the kernel reads 16 bytes at a time
-        x = x.clone() if x.data_ptr() % 16 else x
-        text_rows = text_rows.clone() if text_rows.data_ptr() % 16 else text_rows
     onehot = torch.empty((B, int(num_fg)), dtype=torch.float32, device=x.device)
     scores = torch.empty((B, int(num_fg)), dtype=torch.float32, device=x.device) if want_scores else None
     check(lib().excel_clip_tags(_p(x), stride, _p(text_rows), B, C_, T, int(num_fg), float(scale), float(thre), int(kmax), _p(onehot),

@@ -12,6 +12,10 @@
  *     except excel_vit_create / excel_vit_destroy
  *   - return 0 on success, <0 on error (-1 bad argument, -2 launch failure, -3 allocation failure);
  *     excel_last_error() returns a thread-local message
+ *   - alignment: a device pointer needs the alignment of its element type (4 bytes for fp32 / int32, 8 for int64 / double, 1 for
+ *     uint8) unless the entry's comment asks for more.  Where it does ("16-byte aligned", "8-byte aligned"), a pointer below that is
+ *     refused with EXCEL_ERR_ARG, the message names the argument, and nothing has been launched.  excel_amd/ops.py copies a misaligned
+ *     INPUT into fresh storage first and refuses a misaligned OUTPUT (tests/_align_cases.py has one row per op)
  *   - B images, S x S input, g = S/patch, P = g*g patches, N = P+1 tokens, D = width, H = heads (D/H must be 64),
  *     C = out_dim, T text rows, F foreground classes, L layers
  */
@@ -36,14 +40,18 @@ const char* excel_build_id(void);
 /* C = act(A . op(B) + bias) + residual on the f32-input matrix core (exact-fp32 numerics).
  * b_kmajor=1: B is [N,K] (torch nn.Linear weight layout); 0: B is [K,N].  act: 0 none, 1 QuickGELU
  * (clip/clip_surgery_model.py:280-282).  Batched: `batch` problems with element strides sA/sB/sC.
- * Replaces the cuBLAS GEMMs behind nn.Linear / torch.matmul on the path. */
+ * Replaces the cuBLAS GEMMs behind nn.Linear / torch.matmul on the path.
+ * A and Bm 16-byte aligned with lda, ldb and the batch strides multiples of 4 (both operands are loaded 16 bytes at a time); C, bias and
+ * residual are touched by element: 4 bytes. */
 int excel_gemm_f32(const float* A, const float* Bm, float* C, const float* bias, const float* residual,
                    int M, int N, int K, int lda, int ldb, int ldc, int ldr, int b_kmajor, int act,
                    int batch, long long sA, long long sB, long long sC, long long sR, void* stream);
 
 /* "bf16x3" building blocks: excel_split_bf16 turns fp32 [rows,K] into the split operand format [rows][2][K] bf16
  * (hi plane, lo plane; same number of bytes); excel_gemm_bf16x3 computes C = act(A.W^T + bias) + residual from two split
- * operands with three bf16 MFMAs per product (fp32 accumulate).  C is fp32 [M,N], or a split tensor when split_out. */
+ * operands with three bf16 MFMAs per product (fp32 accumulate).  C is fp32 [M,N], or a split tensor when split_out.
+ * excel_split_*: `in` 16-byte aligned, `out` 8-byte aligned.  excel_gemm_*: A_split and W_split 16-byte aligned (16-byte DMA into LDS),
+ * and so are C, bias and residual (the epilogue moves 16 bytes at a time). */
 int excel_split_bf16(const float* in, void* out, long long rows, int K, void* stream);
 int excel_gemm_bf16x3(const void* A_split, const void* W_split, float* C, const float* bias, const float* residual,
                       int M, int N, int K, int act, int split_out, void* stream);
@@ -59,7 +67,9 @@ int excel_gemm_f16x3(const void* A_split, const void* W_split, float* C, const f
  *   excel_pack_f16: fp32 [rows,K] -> the hi plane as a plain half matrix [rows,K]; adds to *inexact_dev (device, zero it first) the
  *                   number of elements that are NOT representable in IEEE half - the mode's precondition is that count == 0.
  *   excel_gemm_f16x2: W_split as excel_split_f16 wrote it (its lo plane must be all zero: not checked here); W_half (optional, may be
- *                   NULL) = the excel_pack_f16 matrix of the same weights: the large-tile kernel then streams half the weight bytes. */
+ *                   NULL) = the excel_pack_f16 matrix of the same weights: the large-tile kernel then streams half the weight bytes.
+ * excel_pack_f16: `in` 16-byte aligned, `out` and inexact_dev 8-byte aligned.  excel_gemm_f16x2: as excel_gemm_f16x3; a W_half that is
+ * not 16-byte aligned is not refused but left unused (the split weights serve: the same bits). */
 int excel_pack_f16(const float* in, void* out, long long rows, int K, unsigned long long* inexact_dev, void* stream);
 int excel_gemm_f16x2(const void* A_split, const void* W_split, const void* W_half, float* C, const float* bias, const float* residual,
                      int M, int N, int K, int act, int split_out, void* stream);
@@ -100,7 +110,8 @@ int excel_attn_plan(int B, int H, int N, int gemm_mode, int surgery, int want_w,
 #define EXCEL_CAM_PLAN_INTS 14
 int excel_patch_text_cam_plan(int B, int N, int C, int T, int gemm_mode, int32_t* plan /*host*/);
 
-/* LayerNorm over the last dim, fp32, eps as given (clip/clip_surgery_model.py:271-277). */
+/* LayerNorm over the last dim, fp32, eps as given (clip/clip_surgery_model.py:271-277).  D % 4 == 0; x, w, b and y 16-byte aligned
+ * (a row is read and written 16 bytes at a time). */
 int excel_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, void* stream);
 
 /* ------------------------------------------------------------------ ViT "surgery" forward */
@@ -134,7 +145,8 @@ typedef struct excel_vit* excel_vit_t;
 
 /* Binds device weight pointers (NOT copied, must outlive the handle) and prepares derived weights
  * (proj^T; bilinearly resized positional grids are cached per g on first use, clip_surgery_model.py:426-435).
- * Replaces ExCEL_CLIP.visual construction + reload_self_attn (clip/clip_surgery_model.py:396-416). */
+ * Replaces ExCEL_CLIP.visual construction + reload_self_attn (clip/clip_surgery_model.py:396-416).
+ * Every weight pointer 16-byte aligned (the message names the first one that is not). */
 int excel_vit_create(const excel_vit_config* cfg, const excel_vit_weights* w, excel_vit_t* out);
 void excel_vit_destroy(excel_vit_t h);
 
@@ -172,6 +184,7 @@ size_t excel_vit_workspace_bytes(excel_vit_t h, int B, int S);
  *                           for nn.MultiheadAttention blocks, head-SUM for surgery blocks    (optional)
  *   attn_out       [n_attn_out,B,N,N] per-layer weights of the LAST n_attn_out layers (0..L) (optional)
  *   feats_out      [L,B,N,D] per-block original-path features ("all_feats", clean copies)   (optional)
+ * img, workspace, image_features and x_raw 16-byte aligned; w_aff, attn_out and feats_out 4 bytes.
  */
 int excel_vit_forward(excel_vit_t h, const float* img, int B, int S, void* workspace, size_t workspace_bytes,
                       float* image_features, float* x_raw, float* w_aff, int aff_layers,
@@ -183,7 +196,8 @@ int excel_vit_forward(excel_vit_t h, const float* img, int B, int S, void* works
  *   flags: EXCEL_VIT_FEATS_AS_REFERENCE = feats_out holds what the reference's decoder receives: the reference stacks
  *          its per-block list after the forward, and in-place updates (clip_surgery_model.py:317,319,329,442) have by then
  *          rewritten the entries of the last single-path block (= final new-path x incl. the cls swap) and of every
- *          surgery block but the last (= x_ori + the next block's attention residual).  Default: clean block outputs. */
+ *          surgery block but the last (= x_ori + the next block's attention residual).  Default: clean block outputs.
+ * Alignment as for excel_vit_forward (img, workspace, image_features, x_raw 16-byte aligned); ex_attn 4 bytes. */
 #define EXCEL_VIT_FEATS_AS_REFERENCE 1
 int excel_vit_forward_ex(excel_vit_t h, const float* img, int B, int S, void* workspace, size_t workspace_bytes,
                          float* image_features, float* x_raw, float* w_aff, int aff_layers,
@@ -193,7 +207,8 @@ int excel_vit_forward_ex(excel_vit_t h, const float* img, int B, int S, void* wo
  * (clip/clip_surgery_model.py:128-137):  feats [B,C,P] -> F.normalize over C -> sim = f^T f [B,P,P]
  *   -> z = (sim - mean(sim over the WHOLE batch tensor) * beta) * gamma
  *   mode 0: out = sigmoid(z)                                  (attn_pred: beta 1, gamma 3)
- *   mode 1: z < 0 -> -inf, out = softmax(z, dim=-1)           (ex_attn:   beta 1, gamma 3)                       */
+ *   mode 1: z < 0 -> -inf, out = softmax(z, dim=-1)           (ex_attn:   beta 1, gamma 3)
+ * workspace 16-byte aligned (it holds both operands of the similarity GEMM); feats and out 4 bytes.              */
 size_t excel_feature_affinity_workspace_bytes(int B, int C, int P);
 int excel_feature_affinity(const float* feats, int B, int C, int P, float beta, float gamma, int mode, float* out,
                            void* workspace, void* stream);
@@ -211,7 +226,7 @@ int excel_feature_affinity(const float* feats, int B, int C, int P, float beta, 
  *   ceil(n / 4096)) chunks of ceil(n / nparts) values in member order, each summed by 256 strided lanes and a tree, the chunk sums
  *   added in order (mode 1 masks z < 0, so one last bit of the mean can change the mask).
  * One launch sequence per call (normalise, one batched similarity GEMM, partial sums over a (chunk, group) grid, per-group mean,
- * finish); workspace: excel_feature_affinity_grouped_workspace_bytes(B, C, P, group).                                     */
+ * finish); workspace: excel_feature_affinity_grouped_workspace_bytes(B, C, P, group), 16-byte aligned; feats and out 4 bytes.    */
 size_t excel_feature_affinity_grouped_workspace_bytes(int B, int C, int P, int group);
 int excel_feature_affinity_grouped(const float* feats, int B, int C, int P, int group, int member_stride, float beta, float gamma,
                                    int mode, float* out, void* workspace, void* stream);
@@ -221,7 +236,8 @@ int excel_feature_affinity_grouped(const float* feats, int B, int C, int P, int 
  * tokens, channel concat, 1x1 conv L*E -> E) and DecoderTransformer (model/decoder/TransDecoder.py:105-124: dec_layers
  * pre-LN blocks of MHA(heads) + QuickGELU MLP(4E), then the 1x1 linear_pred E -> num_classes), exact fp32.
  * Weight pointers are device pointers in the reference modules' state_dict layout (Linear: [out,in]; 1x1 conv:
- * [out,in,1,1] == [out,in]) and must stay valid for the life of the handle.                                    */
+ * [out,in,1,1] == [out,in]) and must stay valid for the life of the handle.  Every weight pointer 16-byte aligned
+ * (the GEMMs and LayerNorm read them 16 bytes at a time); all_feats and the workspace of excel_decoder_forward 16-byte aligned. */
 typedef struct excel_decoder* excel_decoder_t;
 typedef struct { int vit_layers, vit_width, embed, dec_layers, heads, num_classes; } excel_decoder_config;
 typedef struct { const float *proj_w, *proj_b, *proj2_w, *proj2_b; } excel_fuse_layer_weights;
@@ -245,7 +261,8 @@ int excel_decoder_forward(excel_decoder_t h, const float* all_feats, int B, int 
 /* ------------------------------------------------------------------ CLIP text tower (one-time text bank)
  * encode_text (clip/clip_surgery_model.py:551-564): tokens [B,context_length] int32 -> token + positional embedding ->
  * `layers` causal pre-LN blocks (nn.MultiheadAttention + QuickGELU MLP) -> ln_final -> row of the EOT token (first arg-max of
- * the ids) @ text_projection [width, embed_dim] -> out [B, embed_dim].  Exact fp32.  Weights: device pointers, state_dict layout. */
+ * the ids) @ text_projection [width, embed_dim] -> out [B, embed_dim].  Exact fp32.  Weights: device pointers, state_dict layout,
+ * every one 16-byte aligned; the workspace of excel_text_encode 16-byte aligned, tokens and out 4 bytes. */
 typedef struct excel_text* excel_text_t;
 typedef struct { int vocab_size, context_length, width, layers, heads, embed_dim; } excel_text_config;
 typedef struct {
@@ -266,7 +283,8 @@ int excel_prompt_ensemble(const float* emb, int n, int E, float* out, void* stre
  *                        (utils/camutils.py:438-476; nearest down-sampling by H/g_h, 255 outside the window / on ignored tokens)
  *   losses[0] = seg_loss, losses[1] = aff ("diver") loss (device floats); d_seg, d_attn_pred = gradients of
  *   w_seg*seg_loss + w_diver*aff_loss.  aff_labels (NULL = pseudo): the map the affinity labels are built from -- the reference
- *   switches it to the arg-max of the up-sampled seg logits after 24 000 iterations (train_voc.py:210).  Fixed-order reductions. */
+ *   switches it to the arg-max of the up-sampled seg logits after 24 000 iterations (train_voc.py:210).  Fixed-order reductions.
+ *   workspace 8-byte aligned (double partial sums). */
 size_t excel_train_losses_workspace_bytes(int B, int nc, int H, int W);
 int excel_train_losses(const float* seg, const float* attn_pred, const unsigned char* pseudo, const unsigned char* aff_labels, int B, int nc,
                        int g_h, int g_w, int H, int W, int radius, int ignore_index, float w_seg, float w_diver, float* losses,
@@ -279,7 +297,8 @@ int excel_train_losses(const float* seg, const float* attn_pred, const unsigned 
  *   dropout_p / dropout_seed: the head's Dropout2d (segformer_head.py:66,75; the reference trains with p = 0.1) as a counter-based
  *   channel mask, a pure function of (seed, image, channel): pass the same pair to forward_train and backward.  g*g % 4 == 0.
  * excel_adamw_step: torch.optim.AdamW update of one tensor (decoupled weight decay, bias correction with `step` >= 1), the
- * arithmetic under utils/optimizer.py's PolyWarmupAdamW; the learning-rate schedule stays on the host. */
+ * arithmetic under utils/optimizer.py's PolyWarmupAdamW; the learning-rate schedule stays on the host.
+ * The workspace of all three entries and forward_train's all_feats 16-byte aligned; everything else, the gradient table included, 4 bytes. */
 size_t excel_decoder_train_workspace_bytes(excel_decoder_t h, int B, int g);
 int excel_decoder_forward_train(excel_decoder_t h, const float* all_feats, int B, int g, void* workspace, size_t workspace_bytes,
                                 float* seg_out, float* attn_pred_out, float dropout_p, unsigned dropout_seed, void* stream);
@@ -321,7 +340,8 @@ int excel_seg_scale_accumulate(const float* segs, float* acc, int B, int nc, int
 /* clip_feature_surgery (clip/clip.py:288-310, redundant_feats=None) on normalised features:
  *   image_features [B,N,C], text [T,C] (unit rows) -> out_full [B,N,T] and/or the caller's slice
  *   out_slice [B,N-1,F] = out_full[:, 1:, :F] (model/model_excel.py:58).  workspace: B*N*ldT floats, ldT = T rounded up to 4.
- * 1 <= F <= T <= 512 (above 128 rows a kernel with eight class columns per lane takes over; up to 128 nothing changes). */
+ * 1 <= F <= T <= 512 (above 128 rows a kernel with eight class columns per lane takes over; up to 128 nothing changes).
+ * image_features, text and the workspace 16-byte aligned (the operands and the output of the similarity GEMM); out_full, out_slice 4 bytes. */
 size_t excel_cam_workspace_bytes(int B, int N, int T);
 int excel_clip_feature_surgery(const float* image_features, const float* text, int B, int N, int C, int T, int F,
                                float temperature, float* out_full, float* out_slice, void* workspace, void* stream);
@@ -348,7 +368,8 @@ int excel_patch_text_cam(const float* x_raw, const float* text, int B, int N, in
  * addPairwiseBilateral(sxy = bi_xy_std, srgb = bi_rgb_std, rgbim, compat = bi_w) + inference(iters) of pydensecrf (DIAG kernels,
  * symmetric normalisation, Potts compatibilities): mean-field inference with permutohedral-lattice message passing, all on the device.
  *   rgb_hwc [H,W,3] uint8, prob [C,H,W]: probabilities (prob_is_energy = 0: unary = -log(clip(p, 1e-5, 1)), pydensecrf's
- *   unary_from_softmax) or the unary energies themselves (prob_is_energy = 1, e.g. unary_from_labels)  ->  q_out [C,H,W]. */
+ *   unary_from_softmax) or the unary energies themselves (prob_is_energy = 1, e.g. unary_from_labels)  ->  q_out [C,H,W].
+ * workspace 8-byte aligned (64-bit fixed-point accumulators); rgb_hwc at any byte. */
 size_t excel_dcrf_workspace_bytes(int H, int W, int C);
 int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* prob, int prob_is_energy, int H, int W, int C, int iters, float pos_w,
                          float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, float* q_out, void* workspace, void* stream);
@@ -360,15 +381,17 @@ int excel_dcrf_inference(const unsigned char* rgb_hwc, const float* prob, int pr
 /* mean over layers of attn[l, 1:, 1:] for one stacked tensor [Lw,B,N,N] -> [B,P,P] (utils/affutils.py:180,197). */
 int excel_attn_layer_mean(const float* attn, int Lw, int B, int N, int first_layer, int n_layers, float* w_aff, void* stream);
 
-/* compute_trans_mat (utils/affutils.py:8-24): 3x(col,row) normalise, symmetrise, square (batched fp32 MFMA GEMM).
- * workspace: (2*B*P*P + B*P) floats. */
 /* seg_attn branch of refine_cams_with_aff (utils/affutils.py:182-195): of the n_layers per-layer maps
  * attn[first_layer .. first_layer+n_layers) ([Lw,B,N,N] stacked, [1:,1:] used) keep those whose total difference to
- * seg_attn [B,P,P] is <= the mean difference, average them (/ (count + 1e-5)) and gate by seg_attn -> w_out [B,P,P]. */
+ * seg_attn [B,P,P] is <= the mean difference, average them (/ (count + 1e-5)) and gate by seg_attn -> w_out [B,P,P].
+ * workspace 8-byte aligned (double partial sums). */
 size_t excel_attn_select_workspace_bytes(int B, int n_layers);
 int excel_attn_select_mean(const float* attn, int Lw, int B, int N, int first_layer, int n_layers, const float* seg_attn,
                            float* w_out, void* workspace, void* stream);
 
+/* compute_trans_mat (utils/affutils.py:8-24): 3x(col,row) normalise, symmetrise, square (batched fp32 MFMA GEMM).
+ * workspace: (2*B*P*P + B*P) floats, 16-byte aligned (the symmetrised matrix is both operands of the squaring GEMM); w_aff and
+ * trans_out 4 bytes. */
 size_t excel_trans_mat_workspace_bytes(int B, int P);
 int excel_compute_trans_mat(const float* w_aff, int B, int P, float* trans_out, void* workspace, void* stream);
 
@@ -408,7 +431,7 @@ int excel_cam_upsample_bkg(const float* refined, const int32_t* ncls, int B, int
  * workspace: excel_par_workspace_bytes (aff planes + ping-pong + resized guide).
  * Affinities: by default the 8*ndil weights of a pixel are recomputed inside every Jacobi step from the guide image and 5 per-pixel
  * statistics (20 B/pixel instead of 192 B/pixel of HBM traffic per step) where the tiled kernel applies (dilations [1,2,4,8,12,24] -
- * the only set the reference uses: tools/infer_lam.py:168 - W % 4 == 0, 16-byte aligned buffers); otherwise, or with
+ * the only set the reference uses: tools/infer_lam.py:168 - W % 4 == 0, imgs, masks, out and the workspace 16-byte aligned); otherwise, or with
  * flags & EXCEL_PAR_STREAM_AFFINITIES, they are streamed as planes.  Same arithmetic in the same order: the outputs are bit-identical. */
 #define EXCEL_PAR_STREAM_AFFINITIES 1
 size_t excel_par_workspace_bytes(int B, int Cmax, int H, int W, int ndil);
@@ -437,14 +460,15 @@ int excel_par_forward(const float* imgs, int h, int w, const float* masks, const
 int excel_par_plan(int B, int Cmax, int h, int w, int H, int W, const int32_t* dilations /*host*/, int ndil, int n_iter, int flags,
                    int ragged, int aligned16, int32_t* plan /*host*/);
 
-/* refined.argmax(1) -> valid_key lookup (utils/affutils.py:86-87, :168).  cls_idx may be NULL (identity keys). */
+/* refined.argmax(1) -> valid_key lookup (utils/affutils.py:86-87, :168).  cls_idx may be NULL (identity keys).  labels_i64 8-byte aligned. */
 int excel_argmax_label(const float* cams, const int32_t* nchan, const int32_t* cls_idx, int B, int Smax, int Cmax,
                        long long HW, uint8_t* labels_u8, int64_t* labels_i64, void* stream);
 
 /* _fast_hist accumulated on device (utils/evaluate.py:9-20): hist[nc*gt+pred] += 1 for gt < nc; hist is int64 [nc*nc].
  * 1 <= num_classes <= 256 (at 256 the label 255 is a class like any other).  Up to 90 classes (nc*nc <= 8192) a workgroup keeps the whole
  * histogram in LDS; above, the same launch runs one set of workgroups per band of 8192 / nc ground-truth rows, each reading all pixels
- * (2 bytes per pixel and band) and counting those of its band.  Integer-exact either way. */
+ * (2 bytes per pixel and band) and counting those of its band.  Integer-exact either way.  gt and pred may start at any byte (a scalar head
+ * in front of the 16-byte body); hist 8-byte aligned (64-bit atomic adds). */
 int excel_confusion_accumulate(const uint8_t* gt, const uint8_t* pred, long long n, int num_classes, int64_t* hist, void* stream);
 
 /* ------------------------------------------------------------------ ragged batches: B images of DIFFERENT label sizes in one launch
@@ -481,7 +505,8 @@ int excel_nonfinite_count(const float* x, int B, long long per_image, int32_t* c
 /* excel_confusion_accumulate restricted to the images with skip[b] == 0 (skip: e.g. the counts above).  table == NULL: B uniform images
  * of per_image pixels each (info unused); otherwise the tight label maps of the ragged plan (image b at loff_b; per_image ignored,
  * info->B == B).  Integer counts: with nothing skipped the result equals excel_confusion_accumulate over the whole array bit for bit,
- * otherwise excel_confusion_accumulate over the concatenation of the kept images.  1 <= num_classes <= 256, banded above 90 likewise. */
+ * otherwise excel_confusion_accumulate over the concatenation of the kept images.  1 <= num_classes <= 256, banded above 90 likewise.
+ * gt and pred at any byte, hist 8-byte aligned as there. */
 int excel_confusion_accumulate_masked(const uint8_t* gt, const uint8_t* pred, int B, long long per_image, const int32_t* table,
                                       const excel_ragged_info* info, const int32_t* skip /*device [B]*/, int num_classes, int64_t* hist,
                                       void* stream);
@@ -692,7 +717,8 @@ int excel_normalize_resize_u8_ragged(const uint8_t* hwc, const int32_t* table, i
 int excel_normalize_resize_u8_ragged_mirror(const uint8_t* hwc, const int32_t* table, int B, int S, const double* mean3 /*host*/,
                                             const double* std3 /*host*/, float* out, void* stream);
 
-/* excel_cam_upsample_bkg for a ragged batch: refined [B,Smax,P] -> cams = (Smax+1) pitched planes per image. workspace: B*Smax*P floats. */
+/* excel_cam_upsample_bkg for a ragged batch: refined [B,Smax,P] -> cams = (Smax+1) pitched planes per image. workspace: B*Smax*P floats.
+ * cams 16-byte aligned (every pitched row then is: the layout's premise). */
 int excel_cam_upsample_bkg_ragged(const float* refined, const int32_t* ncls, const int32_t* table, const excel_ragged_info* info, int g,
                                   int Smax, float* cams, void* workspace, int flags, void* stream);
 
@@ -702,7 +728,7 @@ int excel_cam_upsample_bkg_ragged(const float* refined, const int32_t* ncls, con
  * fallback): returns EXCEL_ERR_ARG (-1) unless
  *   - n_iter >= 1            (excel_par_forward copies masks to out for n_iter == 0; here that is an error),
  *   - dilations == [1,2,4,8,12,24] (what the reference always uses, PAR.py callers),
- *   - every buffer is 16-byte aligned and max(Cmax,5) * H_b * Wp_b * 4 < 2^31 for every image (Wp_b = W_b rounded up to 4).
+ *   - masks, out and the workspace are 16-byte aligned and max(Cmax,5) * H_b * Wp_b * 4 < 2^31 for every image (Wp_b = W_b rounded up to 4).
  * The pad columns (W_b <= x < Wp_b) of `out` and its planes c >= nchan[b] are UNDEFINED on return (masks' pad columns are never read
  * as neighbours); consumers clamp to W_b - 1 and nchan[b] (excel_argmax_label_ragged does). */
 size_t excel_par_ragged_workspace_bytes(long long total_pix, int Cmax);
@@ -798,7 +824,8 @@ int excel_conf_merge_ragged(const float* planes, const int32_t* nchan, const int
  * is part of every lattice key, so no lattice point is shared and no blur neighbour crosses an image, and the splat sums in fixed point.
  * Refused: B <= 0 or B > 32767, null pointers, neither output, and a group of more than 2^30 / 6 pixels (vertex indices are 32-bit).
  * The workspace depends on the group's pixel count alone; for one image it is exactly excel_dcrf_workspace_bytes(H, W, C).  Callers
- * with a memory budget split a batch into consecutive groups (excel_amd.ops.dcrf_groups); the results do not depend on the split. */
+ * with a memory budget split a batch into consecutive groups (excel_amd.ops.dcrf_groups); the results do not depend on the split.
+ * workspace 8-byte aligned; hwc, unary, labels_u8 and q_out are slices of the batch's tensors: element alignment (1 / 4 bytes). */
 int excel_dcrf_ragged_workspace_bytes(long long total_label_pix, int C, size_t* bytes /*host, out*/);
 int excel_dcrf_inference_ragged(const uint8_t* hwc, const float* unary, int unary_is_energy, const int32_t* table,
                                 const excel_ragged_info* info, int C, int iters, float pos_w, float pos_xy_std, float bi_w,
@@ -828,7 +855,7 @@ int excel_dcrf_inference_ragged(const uint8_t* hwc, const float* unary, int unar
  * image with fewer classes costs memory and idle lanes, not memory traffic.  Workspace = that of excel_dcrf_ragged_workspace_bytes at
  * C = Cg plus one int32 per lattice vertex (9 per pixel, each array rounded up to 256 bytes): the class count of every lattice point.
  * Refused: null pointers, neither output, B outside 1..32767, non-positive standard deviations, a group of more than 2^30 / 6 pixels.
- * No host synchronisation; everything on `stream`. */
+ * No host synchronisation; everything on `stream`.  workspace 8-byte aligned. */
 int excel_dcrf_lam_ragged_workspace_bytes(const int32_t* hw /*host [B,2]*/, const int32_t* nchan /*host [B]*/, int B, size_t* bytes /*host, out*/);
 int excel_dcrf_lam_ragged(const uint8_t* hwc, const float* cams, const int32_t* nchan /*device [B]*/, const int32_t* nchan_host /*host [B]*/,
                           const int32_t* cls_idx /*device [B,smax] or NULL*/, const int32_t* table, const excel_ragged_info* info, int smax,
@@ -849,7 +876,8 @@ int excel_dcrf_lam_ragged(const uint8_t* hwc, const float* cams, const int32_t* 
  * cams = Cmax pitched planes per image (the excel_cam_upsample_bkg_ragged layout; plane 0 = background, never read).  Only x < W_b and
  * planes 1..k_b are read (pad columns and unused planes of the pipeline's step buffers may hold anything).
  * ncls (device int32 [B]) = k_b, which the caller guarantees to be <= Cmax - 1; out_off (device int64 [B]) is needed in per-class mode.
- * excel_cam_overlay is the same for ONE image whose cams are tight [1+k, H, W] (the per-image path's normed maps): out at byte 0. */
+ * excel_cam_overlay is the same for ONE image whose cams are tight [1+k, H, W] (the per-image path's normed maps): out at byte 0.
+ * tables (doubles) and out_off (int64) 8-byte aligned; hwc and out at any byte. */
 #define EXCEL_CAM_OVERLAY_MAX 0
 #define EXCEL_CAM_OVERLAY_PER_CLASS 1
 int excel_cam_overlay_ragged(const uint8_t* hwc, const float* cams, int Cmax, const int32_t* ncls, const int64_t* out_off,
@@ -867,7 +895,7 @@ int excel_cam_overlay(const uint8_t* hwc, const float* cams, int k, int H, int W
  *   CAM1      utils/tbutils.py:39, :52-58: attr f32 [B,P,F] read as [B,F,g,g] (P == g*g), every class plane sampled bilinearly
  *             (align_corners = False) at the pixel, times cls_label[b,f] (f32 [B,F]), max over f (NaN propagates, torch.max), jet index
  *             as in excel_cam_overlay, out = (uint8) trunc(jet[idx][ch] + 0.5 * img1 byte) in float64; jet (device float64 [256][3]) =
- *             0.5 * (jet_lut * 255), pre-scaled on the host as the reference computes it
+ *             0.5 * (jet_lut * 255), pre-scaled on the host as the reference computes it; 8-byte aligned
  *   PSEU_AFF, SEG_GT, SEG_PRED   utils/tbutils.py:88-93: uint8 [B,S,S] label maps through `palette` (device uint8 [256][3])
  *   PSEU_MID  the same for a uint8 [B,g,g] label map: a grid of g x g cells
  * excel_train_panels_plan (a HOST function: no device work) -> out[3*k .. 3*k+2] = (Hg, Wg, byte offset) of panel k (0, 0, 0 when bit k of
@@ -933,7 +961,7 @@ int excel_png_encode_labels_ragged(const uint8_t* labels, const int32_t* table, 
  * (not proven) to stay below - hence the -1; tiny images do exceed it (the file of a 1 x 1 image has 631 bytes, its bound 628).  excel_jpeg_rgb_workspace_bytes: coefficients, block start bits and the unstuffed stream at
  * its worst case of 208 bytes per 8 x 8 block.  Both return 0 for sizes out of range.
  * off (HOST int64 [n]) and hw (HOST int32 [n][2] = H_i, W_i) are read before the call returns (they travel as kernel arguments).
- * workspace 16-byte aligned.  Limits: 1 <= n <= 65535, 1 <= H_i, W_i <= 65535, 3 H_i W_i < 2^31, 1 <= quality <= 100. */
+ * workspace 16-byte aligned, out_table 8-byte aligned.  Limits: 1 <= n <= 65535, 1 <= H_i, W_i <= 65535, 3 H_i W_i < 2^31, 1 <= quality <= 100. */
 size_t excel_jpeg_rgb_arena_bytes(const int32_t* hw /*host*/, int n);
 size_t excel_jpeg_rgb_workspace_bytes(const int32_t* hw /*host*/, int n);
 int excel_jpeg_encode_rgb_ragged(const uint8_t* rgb, const int64_t* off /*host*/, const int32_t* hw /*host*/, int n, int quality, uint8_t* arena,

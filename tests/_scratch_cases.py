@@ -83,12 +83,15 @@ def _torch():
     return torch
 
 
+UPLOADER = []       # tests/_align_cases.py: while this holds a function, dev() uploads through it (a view one element into its storage)
+
+
 def dev(a, dtype=None):
     torch = _torch()
     t = torch.as_tensor(np.ascontiguousarray(a))
     if dtype is not None:
         t = t.to(dtype)
-    return t.cuda()
+    return UPLOADER[-1](t, "cuda") if UPLOADER else t.cuda()
 
 
 # ------------------------------------------------------------------ shared input builders (also used by test_gpu_padded_shapes.py)
