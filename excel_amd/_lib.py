@@ -189,6 +189,8 @@ SIGNATURES = {
     "excel_boundary_max_radius": (c_i, []),
     "excel_bkg_sweep_ragged": (c_i, [c_f, c_f, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_i, C.POINTER(C.c_float), c_i, c_f, c_i, c_f, c_i,
                                      c_f, c_f]),
+    "excel_margin_sweep_ragged": (c_i, [c_f, c_f, c_f, c_f, c_f, C.POINTER(RaggedInfo), c_i, c_i, C.c_float, C.POINTER(C.c_float), c_i, c_f, c_i, c_f, c_f,
+                                        C.c_float, c_f, c_f, c_f]),
     "excel_label_components": (c_i, [c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_i, c_f, c_f, c_f]),
     "excel_filter_small_regions": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_f, c_i, c_i, c_f, c_f, c_f]),
     "excel_fill_nearest_label": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, C.POINTER(RaggedInfo), c_i, c_i, c_f, c_f, c_f, c_f]),

@@ -239,7 +239,7 @@ def _check_snap(snap):
 
 class TrainingFreePipeline:
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None, margin_sweep=None, margin_min=None):
         """`smax` = the largest number of present classes of any image that will be fed (known from the host-side
         image-level labels; VOC train_aug: 6).  run_batch* do not check it: an image with more present classes is processed with
         its first `smax` classes in ascending order and the others are dropped (include/excel_hip.h, excel_cls_compact;
@@ -294,7 +294,16 @@ class TrainingFreePipeline:
         `last_snap_sp` (int32) and the per-image counts (superpixels with a vote, snapped, pixels changed) in `last_snap_counts`
         (int32 [B,3]) until the next step; with ground truth the snapped maps go into `hist_snap`, and with image_scores the step's
         ScoreTicket gets a set named "snap".  With snap, `clean` and `fill` take the snapped map as their input and mask: the order is
-        snap -> clean -> fill.  The returned labels are untouched; the uniform and multi-stream paths refuse the option."""
+        snap -> clean -> fill.  The returned labels are untouched; the uniform and multi-stream paths refuse the option.
+        `margin_sweep` = a tuple of arg-max margin thresholds (utils/margin.check_thresholds), `margin_min` = one such value; both None by
+        default (no launch).  With either, run_batch_ragged runs ONE margin.margin_ragged launch behind the arg-max, on the step's PAR
+        output with bkg_scale: margin_sweep adds the step's pixel counts per threshold into `margin_kept` (int64 [K+1], no ground truth
+        needed; coverage = margin.coverage_from_kept) and, with ground truth, the counts of the kept pixels into `margin_totals` (int64
+        [K,3,nc], bkg_sweep.scores_from_totals), with the guard's flags as `skip` exactly when the confusion matrix gets them;
+        margin_min leaves the labels with 255 where the margin is below it in `last_margin_labels` (flat uint8 like the labels, until
+        the next step) and, with ground truth, their kept pixels in `hist_margin`; with image_scores the step's ScoreTicket gets a set
+        named "margin".  The returned labels, hist and the snap -> clean -> fill chain are untouched; the uniform and multi-stream
+        paths refuse both."""
         self.clean = _check_clean(clean)
         self.hist_clean = None
         self.last_clean_labels = self.last_clean_counts = None
@@ -304,6 +313,10 @@ class TrainingFreePipeline:
         self.snap = _check_snap(snap)
         self.hist_snap = None
         self.last_snap_labels = self.last_snap_counts = self.last_snap_sp = None
+        from .utils import margin as _mrg
+        self.margin_sweep = _mrg.check_thresholds(margin_sweep) if margin_sweep is not None else None
+        self.margin_min = _mrg.check_min(margin_min) if margin_min is not None else None
+        self.margin_totals = self.margin_kept = self.hist_margin = self.last_margin_labels = None
         from .utils import bkg_sweep as _bkg
         self.bkg_sweep = _bkg.check_scales(bkg_sweep) if bkg_sweep is not None else None
         self.bkg_scale = _bkg.check_scale(bkg_scale)
@@ -350,6 +363,7 @@ class TrainingFreePipeline:
         self.hist_fill = None
         self.hist_snap = None
         self.sweep_totals = None
+        self.margin_totals = self.margin_kept = self.hist_margin = None
 
     def _buf(self, name, numel, dtype=torch.float32, device=None):
         """Step-persistent scratch (cams, PAR output, PAR workspace): one grow-only flat buffer per (name, launch stream), so a step
@@ -409,7 +423,7 @@ class TrainingFreePipeline:
         """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
         hist = getattr(self, into)
         if self.image_scores:
-            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean", "hist_fill": "fill", "hist_snap": "snap"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
+            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean", "hist_fill": "fill", "hist_snap": "snap", "hist_margin": "margin"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
         if self.guard == "skip":
             return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, hist, plan=plan)
         return ops.confusion_accumulate(gts, labels, self.num_classes, hist)                       # evaluate.py:9-20
@@ -433,6 +447,33 @@ class TrainingFreePipeline:
         if self.bkg_scale != 1.0:
             raise ValueError(f"{what} has no background scale (bkg_scale={self.bkg_scale}): it runs behind the ragged step - use "
                              "run_batch_ragged, or build the pipeline with bkg_scale=1.0")
+
+    def _no_margin(self, what):
+        if self.margin_sweep is not None:
+            raise ValueError(f"{what} has no margin sweep (margin_sweep={self.margin_sweep}): it runs behind the ragged step - use "
+                             "run_batch_ragged, or build the pipeline without margin_sweep")
+        if self.margin_min is not None:
+            raise ValueError(f"{what} has no margin labels (margin_min={self.margin_min}): they are made behind the ragged step - use "
+                             "run_batch_ragged, or build the pipeline without margin_min")
+
+    def _margin(self, par_out, plan, C, nchan, idx, gts_packed, flags):
+        """margin_sweep / margin_min set: one launch over the step's PAR output - the counts per threshold, the labels cut at margin_min -
+        and the score of those labels (all on the step's stream, no synchronisation)."""
+        from .utils.margin import margin_ragged
+        sweep = self.margin_sweep or ()
+        out = self._buf("margin_labels", plan.total_label_pix, torch.uint8, par_out.device) if self.margin_min is not None else None
+        counted = bool(sweep) and gts_packed is not None
+        totals, kept, self.last_margin_labels, _ = margin_ragged(
+            par_out, plan, C, sweep, nchan=nchan, cls_idx=idx, gts=gts_packed if counted else None, num_classes=self.num_classes,
+            skip=flags if self.guard == "skip" else None, totals=self.margin_totals if counted else None,
+            kept=(self.margin_kept if self.margin_kept is not None else True) if sweep else None,
+            label_thre=self.margin_min, labels_out=out, bkg_scale=self.bkg_scale)
+        if counted:
+            self.margin_totals = totals
+        if sweep:
+            self.margin_kept = kept
+        if self.margin_min is not None and gts_packed is not None:
+            self.hist_margin = self._score(gts_packed, self.last_margin_labels, flags, plan=plan, into="hist_margin")
 
     def _no_clean(self, what):
         if self.clean is not None:
@@ -571,6 +612,7 @@ class TrainingFreePipeline:
         pipeline has a tagger), gts [B,H,W] uint8 (255 = ignore) or None.  Returns labels [B,H,W] uint8 (device)."""
         self._no_bkg("run_batch")
         self._no_clean("run_batch")
+        self._no_margin("run_batch")
         B, _, S, _ = inputs.shape
         g = S // 16
         H, W = (gts.shape[-2:] if gts is not None else (label_hw or (S, S)))
@@ -674,6 +716,8 @@ class TrainingFreePipeline:
                 self.sweep_totals = sweep_ragged(par_out, plan, C, self.bkg_sweep, nchan=nchan, cls_idx=idx, gts=gts_packed,
                                                  num_classes=self.num_classes, skip=flags if self.guard == "skip" else None,
                                                  totals=self.sweep_totals)[0]
+        if self.margin_sweep is not None or self.margin_min is not None:
+            self._margin(par_out, plan, C, nchan, idx, gts_packed, flags)
         chain = labels                                        # what clean and fill work on: the main labels, or the snapped ones
         if self.snap is not None:
             self._snap(labels, hwc, plan, gts_packed, flags)
@@ -715,6 +759,7 @@ class TrainingFreePipeline:
         self._no_image_scores("run_batch_split")
         self._no_bkg("run_batch_split")
         self._no_clean("run_batch_split")
+        self._no_margin("run_batch_split")
         B, _, S, _ = inputs.shape
         nsplit = max(1, min(nsplit, B))
         if nsplit == 1:
@@ -763,6 +808,7 @@ class TrainingFreePipeline:
         self._no_image_scores("run_batch_overlapped")
         self._no_bkg("run_batch_overlapped")
         self._no_clean("run_batch_overlapped")
+        self._no_margin("run_batch_overlapped")
         sa, sb = self._streams()
         cur = torch.cuda.current_stream()
         B, _, S, _ = inputs.shape
@@ -821,7 +867,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
     entry (one image for attn_pred, the pair (x_b, flip x_b) for ex_attn), which is what the reference's batch-1 harness computes."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.79, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None, margin_sweep=None, margin_min=None):
         check_num_classes(num_classes)
         _refuse_tta("OptimisedLamPipeline", tta_scales, tta_flip)
         _refuse_tagger("OptimisedLamPipeline", tagger)
@@ -829,7 +875,7 @@ class OptimisedLamPipeline(TrainingFreePipeline):
             raise ValueError("OptimisedLamPipeline needs the trained decoder head: build ExCEL_model(..., decoder_state_dict=) "
                              "(--training_free false --model_path)")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax, guard=guard,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill, snap=snap)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill, snap=snap, margin_sweep=margin_sweep, margin_min=margin_min)
         self.attn_layers = attn_layers
 
     def _tower(self, imgs, n_attn_out=0):
@@ -893,7 +939,7 @@ class ValidationPipeline(TrainingFreePipeline):
     every image's label size and through the arg-max in one launch (ops.seg_resize_argmax_uniform); no host round trip inside a batch."""
 
     def __init__(self, model, num_classes=21, dilations=ops.PAR_DILATIONS, num_iter=20, caa_thre=0.75, smax=6, attn_layers=6, guard=None,
-                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None):
+                 tta_scales=None, tta_flip=False, tagger=None, image_scores=False, boundary=None, bkg_sweep=None, bkg_scale=1.0, clean=None, fill=None, snap=None, margin_sweep=None, margin_min=None):
         check_num_classes(num_classes)
         _refuse_tta("ValidationPipeline", tta_scales, tta_flip)
         _refuse_tagger("ValidationPipeline", tagger)
@@ -903,7 +949,7 @@ class ValidationPipeline(TrainingFreePipeline):
             raise ValueError(f"ValidationPipeline has no overflow guard (guard={guard!r}): the in-training validation pass scores two "
                              "histograms per step and is out of the guard's scope")
         super().__init__(model, num_classes=num_classes, dilations=dilations, num_iter=num_iter, caa_thre=caa_thre, smax=smax,
-                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill, snap=snap)
+                         image_scores=image_scores, boundary=boundary, bkg_sweep=bkg_sweep, bkg_scale=bkg_scale, clean=clean, fill=fill, snap=snap, margin_sweep=margin_sweep, margin_min=margin_min)
         self.attn_layers = attn_layers
         self.hist_seg = None
 

@@ -84,6 +84,14 @@ Differences from the reference, all deliberate:
     of 1.0: scores, PNGs and per-image scores take those labels (the conf labels and the CRF stages are built from the cams and do not
     change).  Ragged batches on the batched loop only; --bkg_sweep is refused with --unlabeled true, both with --api_path true; off by
     default (no launch).  The exponent of that pow is not swept: it is not linear under PAR;
+  * `--margin_sweep "0,0.05,0.1,0.2,0.3"` / `--margin_min T` (`--margin_label_dir DIR`): the margin of a pixel is the winning PAR plane
+    minus the runner-up (utils/margin.py), a confidence the step's PAR output already holds.  With --margin_sweep one more launch per
+    ragged step counts, per threshold, the pixels with margin >= t (coverage: no ground truth needed, so --unlabeled true is allowed)
+    and their counts against the ground truth; the ranks' counts are summed once and rank 0 logs a margin_sweep_score table,
+    --json_out gains a `margin_sweep` block.  --margin_min makes a further label set (255 where the margin is below T) by the cleaned
+    set's route: PNGs, a margin_label_score table and its coverage, a `margin` block, the margin_* columns of --per_image_scores.
+    The values are illustrations: no default is chosen, nothing has been measured on real data.  Ragged batches on the batched loop
+    only; off by default (no launch, no key, no column);
   * `--clean_min_region VALUE` (`--clean_connectivity 8|4`, `--clean_label_dir DIR`): the arg-max leaves islands of a few pixels and
     pin-holes; the reference has no remedy.  Behind the arg-max of every ragged step, utils/components.label_components labels the
     connected regions of the step's main label map (equal raw value, 8- or 4-neighbours) and filter_small_regions turns every class
@@ -465,6 +473,8 @@ def get_parser():
     image_scores.add_boundary_flags(p)
     from ..utils import bkg_sweep
     bkg_sweep.add_flags(p)
+    from ..utils import margin as margin_flags
+    margin_flags.add_flags(p)
     from ..utils import components
     components.add_flags(p)
     from ..utils import label_fill
@@ -888,6 +898,10 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     snap_kw = {k: snap[k] for k in ("step", "compactness", "iters", "min_share")} if snap is not None else None
     if snap is not None:
         bkg_kw = {**bkg_kw, "snap": snap_kw}
+    from ..utils import margin as margin_mod
+    msweep, mcut = margin_mod.resolve(args, ragged=ragged)
+    margin_kw = {**({"margin_sweep": msweep} if msweep is not None else {}), **({"margin_min": mcut["min"]} if mcut is not None else {})}
+    bkg_kw = {**bkg_kw, **margin_kw}
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
                   smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
@@ -910,14 +924,17 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError(f"--fill_ignore: the supplied pipeline was built with fill={getattr(pipe, 'fill', None)!r}, the flags ask for {fill_kw!r}")
     if snap is not None and pipe is not None and getattr(pipe, "snap", None) != snap_kw:
         raise ValueError(f"--snap_superpixels: the supplied pipeline was built with snap={getattr(pipe, 'snap', None)!r}, the flags ask for {snap_kw!r}")
+    for k, want in margin_kw.items():
+        if pipe is not None and getattr(pipe, k, None) != want:
+            raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     for k, want in (("bkg_sweep", sweep), ("bkg_scale", bkg_scale)):
         if (sweep is not None or bkg_scale != 1.0) and pipe is not None and getattr(pipe, k, None if k == "bkg_sweep" else 1.0) != want:
             raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None, fill=None, snap=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None, fill=None, snap=None, margin=None)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
-                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean, fill=fill, snap=snap,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean, fill=fill, snap=snap, msweep=msweep, mcut=mcut,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
@@ -925,7 +942,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     run.scores = report["image_scores"] = image_scores.ImageScoreLog(
         args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else [])
         + (["clean"] if clean is not None and not args.unlabeled else []) + (["fill"] if fill is not None and not args.unlabeled else [])
-        + (["snap"] if snap is not None and not args.unlabeled else []),
+        + (["snap"] if snap is not None and not args.unlabeled else []) + (["margin"] if mcut is not None and not args.unlabeled else []),
         boundary=boundary, **({"regions": True} if clean is not None else {}), **({"fills": True} if fill is not None else {}),
         **({"snaps": True} if snap is not None else {})) if want_scores else None
     try:
@@ -949,6 +966,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
             run.consumers["fill_lab"] = _LabelSaver(args, fill["label_dir"])
         if snap is not None and snap["label_dir"]:
             run.consumers["snap_lab"] = _LabelSaver(args, snap["label_dir"])
+        if mcut is not None and mcut["label_dir"]:
+            run.consumers["margin_lab"] = _LabelSaver(args, mcut["label_dir"])
         out = (_per_image_loop if per_image else _batched_loop)(run)
     except BaseException:
         _close_consumers(run, failed=True)
@@ -964,6 +983,7 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         build_validation.last_clean = report["clean"]
         build_validation.last_fill = report["fill"]
         build_validation.last_snap = report["snap"]
+        build_validation.last_margin = report["margin"]
     return out
 
 
@@ -1088,6 +1108,12 @@ def _batched_loop(run):
         pipe.hist_fill = torch.zeros_like(run.hist)
     if run.snap is not None:
         pipe.hist_snap = torch.zeros_like(run.hist)
+    margin_lab = run.consumers.get("margin_lab")
+    if run.msweep is not None:                               # --margin_sweep: the pipeline adds every step's counts per threshold (both passes of the guard)
+        pipe.margin_kept = torch.zeros((len(run.msweep) + 1,), dtype=torch.int64, device=device)
+        pipe.margin_totals = None if args.unlabeled else torch.zeros((len(run.msweep), 3, args.num_classes), dtype=torch.int64, device=device)
+    if run.mcut is not None:
+        pipe.hist_margin = torch.zeros_like(run.hist)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
         from ..datasets.loader import DeviceFeeder, ragged_batches, threaded_batches
@@ -1137,6 +1163,8 @@ def _batched_loop(run):
             fill_lab.ragged(names, plan, pipe.last_fill_labels)
         if snap_lab is not None:                                                        # likewise, the step's snapped maps
             snap_lab.ragged(names, plan, pipe.last_snap_labels)
+        if margin_lab is not None:                                                      # likewise, the step's margin labels
+            margin_lab.ragged(names, plan, pipe.last_margin_labels)
         if keep:                                                                        # :116-119 record for the CRF stage
             inter = out[1]
             cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
@@ -1314,6 +1342,8 @@ def _batched_loop(run):
             run.report["fill"] = dict(hist=pipe.hist_fill, rows=fill_rows)
     if run.snap is not None:
         run.report["snap"] = dict(hist=pipe.hist_snap, rows=snap_rows, pixels=int(sum(row_pix.values())))
+    if run.msweep is not None or run.mcut is not None:
+        run.report["margin"] = dict(totals=pipe.margin_totals, kept=pipe.margin_kept, hist=pipe.hist_margin)
     if scores is not None:
         scores.poll(True)
     if tagger is not None:
@@ -1476,13 +1506,15 @@ def validate(args=None, dataset=None, pipe=None):
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
     validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = validate.last_clean = None
-    validate.last_fill = validate.last_snap = None
+    validate.last_fill = validate.last_snap = validate.last_margin = None
     from ..utils import bkg_sweep, components, image_scores, label_fill, superpixels
+    from ..utils import margin as margin_mod
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))                                # ... and per-image scores of nothing
     sweep, _ = bkg_sweep.resolve(args)                                                       # ... and a sweep nobody can score or run
     clean = components.resolve(args)                                                         # ... and a cleaning nobody can run or see
     fill = label_fill.resolve(args)                                                          # ... and a fill of nothing
     snap = superpixels.resolve(args)                                                         # ... and a snap nobody can run or see
+    msweep, mcut = margin_mod.resolve(args)                                                  # ... and margins nobody can run or see
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
@@ -1588,6 +1620,27 @@ def validate(args=None, dataset=None, pipe=None):
         if world > 1:
             dist.all_reduce(pixels)
         validate.last_snap = dict(stats=superpixels.snap_stats(got["counts"], int(pixels.item())), **{k: snap[k] for k in ("step", "compactness", "iters", "min_share")}, **got)
+    if msweep is not None or mcut is not None:
+        # --margin_sweep / --margin_min: the ranks' counts summed once, like the matrix (a flagged image is in them once: skipped, then
+        # counted in fp32); every rank joins, also one whose shard is empty
+        mine = build_validation.last_margin or {}
+        m = validate.last_margin = dict(thresholds=msweep, margin_min=None if mcut is None else mcut["min"])
+        if msweep is not None:
+            kept = mine.get("kept")
+            _, m["kept"] = gather_hists(kept if kept is not None else torch.zeros((len(msweep) + 1,), dtype=torch.int64, device=hist.device))
+            m["coverage"] = margin_mod.coverage_from_kept(m["kept"])
+            m["totals"] = m["scores"] = None
+            if not args.unlabeled:
+                tot = mine.get("totals")
+                _, m["totals"] = gather_hists(tot if tot is not None else torch.zeros((len(msweep), 3, args.num_classes), dtype=torch.int64, device=hist.device))
+                m["scores"] = bkg_sweep.scores_from_totals(m["totals"])
+        if mcut is not None:
+            m["hist"] = m["score"] = m["label_coverage"] = None
+            if not args.unlabeled:
+                mh = mine.get("hist")
+                _, m["hist"] = gather_hists(mh if mh is not None else torch.zeros_like(hist))
+                m["score"] = evaluate.scores_from_hist(m["hist"])
+                m["label_coverage"] = components.coverage(m["hist"], total)
     tags = None
     if tagger is not None:
         # the predicted rows of every rank, once: every rank joins, also one whose shard is empty
@@ -1647,6 +1700,18 @@ def validate(args=None, dataset=None, pipe=None):
             logging.info(superpixels.format_snap_summary(c["stats"], c["coverage"]))
             if snap["label_dir"]:
                 logging.info(f"snapped label maps -> {snap['label_dir']}")
+        if msweep is not None:
+            m = validate.last_margin
+            logging.info("margin_sweep_score (kept: arg-max margin >= the threshold; coverage over all pixels):")
+            logging.info("\n" + margin_mod.format_margin_table(msweep, m["kept"], m["scores"], cat_list))
+        if mcut is not None:
+            m = validate.last_margin
+            if m["score"] is not None:
+                logging.info(f"margin_label_score (--margin_min {mcut['min']:g}):")
+                logging.info("\n" + format_scores_table(m["score"], cat_list))
+                logging.info(f"margin coverage (kept pixels over labelled pixels): {m['label_coverage'] * 100:.3f} %")
+            if mcut["label_dir"]:
+                logging.info(f"margin label maps -> {mcut['label_dir']}")
         if tags is not None:
             logging.info(f"tags (--tags clip, thre {tagger['thre']}, at most {tagger['kmax']}, scale {tagger['scale']}): {tags['images']} images, "
                          f"tags per image {dict((k, v) for k, v in enumerate(tags['tags_per_image']) if v)}"
@@ -1670,6 +1735,10 @@ def validate(args=None, dataset=None, pipe=None):
                            "cam_scales": [float(x) for x in (tta[0] or (1.0,))], "cam_flip": bool(tta[1]),
                            **({"tags": _tags_json(tags, tagger)} if tags is not None else {}),
                            **({"bkg_sweep": bkg_sweep.sweep_json(sweep_scores, sweep)} if sweep is not None else {}),
+                           **({"margin_sweep": margin_mod.margin_json(msweep, validate.last_margin["kept"], validate.last_margin["scores"])}
+                              if msweep is not None else {}),
+                           **({"margin": margin_mod.margin_min_json(mcut["min"], validate.last_margin["score"], validate.last_margin["label_coverage"])}
+                              if mcut is not None else {}),
                            **({"clean": components.clean_json(clean["min_region"], clean["connectivity"], validate.last_clean["stats"],
                                                               validate.last_clean["score"], validate.last_clean["coverage"])}
                               if clean is not None else {}),

@@ -30,6 +30,8 @@ filled, max_fill_dist` (the distance in pixels), the npz `counts_fill` and `fill
 --snap_superpixels (infer_lam; utils/superpixels.py): the snapped labels are one more set, "snap", by the same route, and every image has
 a row (superpixels with a vote, superpixels snapped, pixels changed) of the vote: the files gain `snap_pacc, snap_miou, snap_scored` and,
 last of all, `superpixels, snapped, pixels_changed`, the npz `counts_snap` and `snaps`.  Without the flag nothing changes.
+--margin_min (infer_lam; utils/margin.py): the labels cut at an arg-max margin are one more set, "margin": the files gain `margin_pacc,
+margin_miou, margin_scored` (and `margin_biou` with --boundary_scores), the npz `counts_margin`.  Without the flag nothing changes.
 """
 import csv
 import logging
@@ -41,7 +43,7 @@ import numpy as np
 
 from .evaluate import boundary_scores_from_counts, image_score_rows
 
-SETS = ("main", "crf", "conf", "clean", "fill", "snap")
+SETS = ("main", "crf", "conf", "clean", "fill", "snap", "margin")
 MAX_RADIUS = 72              # what ops.boundary_max_radius() answers (boundary.hip's halo); the CPU path refuses the same radii
 
 
@@ -341,7 +343,7 @@ def report_lines(merged, rows, k, what="label_score"):
     return lines
 
 
-BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels", "clean": "cleaned labels", "fill": "filled labels", "snap": "snapped labels"}
+BOUNDARY_SET_NAMES = {"main": "labels", "conf": "confident labels", "crf": "CRF labels", "clean": "cleaned labels", "fill": "filled labels", "snap": "snapped labels", "margin": "margin labels"}
 
 
 def boundary_summary(merged):

@@ -578,6 +578,44 @@ int excel_bkg_sweep_ragged(const float* planes, const int32_t* nchan /*device [B
                            int64_t* totals /*device [K,3,num_classes], ADDED to, or NULL*/, int label_sel,
                            uint8_t* labels_u8 /*device, tight, or NULL*/, void* stream);
 
+/* ------------------------------------------------------------------ arg-max margin
+ * By how much the winning plane of the arg-max won: a confidence per pixel that PAR's output already holds.  One pass over the planes
+ * scores the labels cut at K margin thresholds (a risk-coverage sweep) and / or writes the label map cut at one value and / or the
+ * margins themselves.  planes, nchan, cls_idx, gt, table, info, Smax, Cmax and skip are those of excel_bkg_sweep_ragged, and so are the
+ * tiles; pad columns and planes c >= nch are never read.
+ * For pixel (x,y) of image b, x < W_b, with nch = nchan ? min(nchan[b], Cmax) : Cmax and a = bkg_scale:
+ *   v0 = a * plane 0 (one fp32 multiply, round to nearest);  for nch > 1:  F = the maximum of planes 1..nch-1, ci = the first plane index
+ *   that attains it, key_fg = cls_idx ? cls_idx[b*Smax + ci-1] + 1 : ci.
+ *   The pixel is background iff nch == 1 or v0 >= F or key_fg == 0: key = 0; otherwise key = key_fg - the labels of
+ *   excel_bkg_sweep_ragged at scale a, bit for bit.
+ *   Runner-up R:  background: R = F;  foreground: R = max(v0, S), S = the maximum of the foreground planes other than ci (nch == 2 has
+ *   none: R = v0).
+ *   margin = winner - R (winner = v0 or F): one fp32 subtract, round to nearest, nothing fused into it.  nch == 1: margin = +inf, plane 0
+ *   plays no part.  When nch > 1 and v0 or one of the planes 1..nch-1 is NaN the margin is NaN, and inf - inf is NaN: a NaN margin fails
+ *   every comparison below.  A negative margin is possible only for the key_fg == 0 case (v0 < F) and stays as it is.
+ * thresholds: HOST array of K floats (0 <= K <= 16), finite, >= 0, strictly increasing, copied into the kernel arguments.  The pixel is
+ * kept at j iff margin >= thresholds[j]; the kept sets are nested.
+ *   totals (device int64 [K,3,num_classes], ADDED to, or NULL; needs gt): over the pixels kept at j with g = gt < num_classes and
+ *     key < num_classes of the images with skip == NULL || skip[b] == 0:  totals[j,0,g] += 1, totals[j,1,key] += 1, totals[j,2,g] += 1
+ *     when g == key - the row sums, column sums and diagonal of the confusion matrix of "key, with 255 where the pixel is dropped", in
+ *     the layout of excel_bkg_sweep_ragged's totals.
+ *   kept (device int64 [K+1], ADDED to, or NULL; needs no gt): kept[j] += the pixels kept at j, kept[K] += all pixels, of the images
+ *     with skip == NULL || skip[b] == 0, whatever their ground truth.  Coverage at j = kept[j] / kept[K].
+ *   labels_u8 (device, tight, info->total_label_pix bytes, or NULL): margin >= label_thre ? key : 255, for every image whatever skip
+ *     says.  label_thre is independent of `thresholds` (any value but NaN; -inf keeps every pixel whose margin is not NaN).
+ *   margin_out (device float [info->total_label_pix], tight, or NULL): the margin.
+ * EXCEL_ERR_ARG with a message, before any launch, for: null planes, table or info; none of the four outputs; totals without gt; K
+ * outside 0..16; K == 0 with totals or kept; a threshold that is not finite, is < 0 or does not increase; labels_u8 with a NaN
+ * label_thre; bkg_scale not finite or < 0; num_classes outside 1..256; planes not 16-byte aligned; totals or kept not 8-byte aligned;
+ * margin_out, nchan, cls_idx, skip or table not 4-byte aligned; a plan without a tile.  labels_u8 and gt may start at any byte.
+ * One launch on `stream`, no workspace, no host synchronisation, no scratch memory (csrc/margin.hip). */
+int excel_margin_sweep_ragged(const float* planes, const int32_t* nchan /*device [B] or NULL*/, const int32_t* cls_idx /*device [B,Smax] or NULL*/,
+                              const uint8_t* gt, const int32_t* table, const excel_ragged_info* info, int Smax, int Cmax, float bkg_scale,
+                              const float* thresholds /*HOST [K]*/, int K, const int32_t* skip /*device [B] or NULL*/, int num_classes,
+                              int64_t* totals /*device [K,3,num_classes], ADDED to, or NULL*/, int64_t* kept /*device [K+1], ADDED to, or NULL*/,
+                              float label_thre, uint8_t* labels_u8 /*device, tight, or NULL*/, float* margin_out /*device, tight, or NULL*/,
+                              void* stream);
+
 /* ------------------------------------------------------------------ connected components
  * The regions of label maps, and the filter that turns the small ones into ignore (255).  Images are addressed exactly as in
  * excel_boundary_scores: table == NULL means B uniform [H,W] maps; otherwise the tight u8 maps of the ragged plan (row pitch W_b, image b
