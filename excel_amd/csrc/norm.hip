@@ -8,6 +8,17 @@
 
 namespace EXCEL_SPLIT_NS {     // compiled once per 16-bit split type (excel_internal.h, build.py)
 
+// An fp32 mean carries the rounding of its own sum and of its last place (6e-5 for a row around 1e3), and (x - mean) passes that on in
+// full.  dm = mean(x - mean) is what `mean` is off by (the corrected two-pass algorithm; mean + dm is never formed).  It is taken off the
+// centred values and the variance only where it moves a normalised value by more than 2^-20: every other row keeps the plain two-pass
+// result bit for bit (x - 0 is x).  -> the correction to subtract; rstd of the row.
+__device__ __forceinline__ float ln_mean_correction(float dm, float var, float eps, float& rstd) {
+    rstd = 1.f / sqrtf(var + eps);
+    if (!(fabsf(dm) * rstd > 0x1p-20f)) return 0.f;
+    rstd = 1.f / sqrtf(fmaxf(var - dm * dm, 0.f) + eps);
+    return dm;
+}
+
 __device__ __forceinline__ void ln_row(const float* __restrict__ src, const float* __restrict__ add,
                                        const float* __restrict__ w, const float* __restrict__ b,
                                        float* __restrict__ dst, int D, float eps, int lane, bool split = false) {
@@ -19,21 +30,23 @@ __device__ __forceinline__ void ln_row(const float* __restrict__ src, const floa
         s += (v[0] + v[1]) + (v[2] + v[3]);
     }
     const float mean = wave_sum(s) / (float)D;
-    // pass 2: biased variance of (x - mean)
-    float q = 0.f;
+    // pass 2: biased variance of (x - mean), and the mean of (x - mean) for ln_mean_correction
+    float q = 0.f, r = 0.f;
     for (int c = lane * 4; c < D; c += 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(src + c);
         if (add) v += *reinterpret_cast<const f32x4*>(add + c);
         v -= mean;
+        r += (v[0] + v[1]) + (v[2] + v[3]);
         q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
     }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)D + eps);
+    float rstd;
+    const float dm = ln_mean_correction(wave_sum(r) / (float)D, wave_sum(q) / (float)D, eps, rstd);
     for (int c = lane * 4; c < D; c += 256) {
         f32x4 v = *reinterpret_cast<const f32x4*>(src + c);
         if (add) v += *reinterpret_cast<const f32x4*>(add + c);
         const f32x4 ww = *reinterpret_cast<const f32x4*>(w + c);
         const f32x4 bb = *reinterpret_cast<const f32x4*>(b + c);
-        v = (v - mean) * rstd * ww + bb;
+        v = ((v - mean) - dm) * rstd * ww + bb;
         if (split) {   // bf16 hi/lo planes [2][D] in the same D*4 bytes (operand format of the bf16x3 GEMM)
             split_t hi[4], lo[4];
 #pragma unroll
@@ -63,19 +76,21 @@ __device__ __forceinline__ void ln_row_reg(const float* __restrict__ src, const 
 #pragma unroll
     for (int i = 0; i < NCH; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
+    float q = 0.f, r = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         v[i] -= mean;
+        r += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
         q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
     }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)D + eps);
+    float rstd;
+    const float dm = ln_mean_correction(wave_sum(r) / (float)D, wave_sum(q) / (float)D, eps, rstd);
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c = lane * 4 + 256 * i;
         const f32x4 ww = *reinterpret_cast<const f32x4*>(w + c);
         const f32x4 bb = *reinterpret_cast<const f32x4*>(b + c);
-        const f32x4 o4 = v[i] * rstd * ww + bb;
+        const f32x4 o4 = (v[i] - dm) * rstd * ww + bb;
         if (split) {
             split_t hi[4], lo[4];
 #pragma unroll

@@ -1,5 +1,6 @@
 """Shared by test_gpu_attn_shapes.py (GPU sweep) and test_host_attn_plan.py (the gates' own sensitivity, on the CPU): the dispatch
-arithmetic of the ViT attention as a table, the two test nets with their float64 references, and the comparison functions.
+arithmetic of the ViT attention as a table, the two test nets with their float64 references, and the comparison functions.  The nets,
+references and gates take the ViT as cfg= (default: TINY, what those two files run); tests/_vit_configs.py runs them at other geometries.
 
 Dispatch (attn_plan.hip), for N = g*g + 1 tokens, cdiv(a, b) = ceil(a / b):
     tiles = cdiv(N, 32)                         key tiles of 32 (= KP / 32; also the number of 32-row query strips)
@@ -69,26 +70,26 @@ DISPATCH = {
     48: (2305, 73, 0, 0, 0, 1),
 }
 
-NETS = {"flat": 0.25, "peaked": None}       # attn_gain of make_vit_weights(TINY, seed=31): 0.25 = nearly uniform rows, None = the default (4.0)
+NETS = {"flat": 0.25, "peaked": None}       # attn_gain of make_vit_weights(cfg, seed=31): 0.25 = nearly uniform rows, None = the default (4.0)
 
 
-def net_weights(net, feat_size=None):
+def net_weights(net, feat_size=None, cfg=TINY):
     gain = NETS[net]
-    w = make_vit_weights(TINY, seed=31) if gain is None else make_vit_weights(TINY, seed=31, attn_gain=gain)
-    return w if feat_size is None else oracle.vit.reload_self_attn(w, TINY, feat_size=feat_size, mode="train")
+    w = make_vit_weights(cfg, seed=31) if gain is None else make_vit_weights(cfg, seed=31, attn_gain=gain)
+    return w if feat_size is None else oracle.vit.reload_self_attn(w, cfg, feat_size=feat_size, mode="train")
 
 
-def images(g, B):
-    return np.random.RandomState(1000 + g).standard_normal((B, 3, 16 * g, 16 * g)).astype(np.float32)
+def images(g, B, patch=TINY.patch):
+    return np.random.RandomState(1000 + g).standard_normal((B, 3, patch * g, patch * g)).astype(np.float32)
 
 
 def ex_features(g, B, C=24):
     return np.random.RandomState(2000 + g).standard_normal((B, C, g, g)).astype(np.float32)
 
 
-def layer_rowsum(l):
+def layer_rowsum(l, cfg=TINY):
     """Row sum of layer l's attention output: head-MEAN of an nn.MultiheadAttention block, head-SUM of a surgery block."""
-    return float(TINY.heads) if l >= TINY.layers - TINY.n_surgery else 1.0
+    return float(cfg.heads) if l >= cfg.layers - cfg.n_surgery else 1.0
 
 
 def maxabs(a, b):
@@ -123,25 +124,28 @@ def errors(out, ref):
     return e
 
 
-def reference(net, g, B, ex=False, reload=True):
+def pack(x, attn, feats, aff_layers=6):
+    """One oracle forward (vit_forward's x, attn, feats) as the dict errors() compares: w_aff is the mean of the last aff_layers layers."""
+    return dict(attn=attn, feats=feats, x_raw=x, image_features=token_normalize(x), w_aff=attn[-aff_layers:, :, 1:, 1:].mean(0))
+
+
+def reference(net, g, B, ex=False, reload=True, cfg=TINY, aff_layers=6):
     """float64 run of the oracle -> (ref dict, o dict, pmin list): the judge, the fp32 oracle's own deviation from it for every quantity
     of errors(), and every layer's smallest reference probability.  reload=False: the weights keep their native positional grid and the
-    oracle resizes it itself, as the library does for a handle used at another size."""
-    w = net_weights(net, g if reload else None)
-    imgs = images(g, B)
+    oracle resizes it itself, as the library does for a handle used at another size.  cfg: the ViT (its weights come from net_weights(cfg=cfg),
+    its inputs are g * cfg.patch pixels wide); aff_layers: how many of the last layers w_aff averages."""
+    w = net_weights(net, g if reload else None, cfg)
+    imgs = images(g, B, cfg.patch)
     exf = ex_features(g, B) if ex else None
 
-    def pack(x, attn, feats):
-        return dict(attn=attn, feats=feats, x_raw=x, image_features=token_normalize(x), w_aff=attn[-6:, :, 1:, 1:].mean(0))
-
     with oracle.vit.precision(np.float64):
-        x, attn, feats = oracle.vit.vit_forward(imgs.astype(np.float64), {k: np.asarray(v, np.float64) for k, v in w.items()}, TINY,
+        x, attn, feats = oracle.vit.vit_forward(imgs.astype(np.float64), {k: np.asarray(v, np.float64) for k, v in w.items()}, cfg,
                                                 ex_feats=None if exf is None else exf.astype(np.float64))
         assert x.dtype == np.float64 and attn.dtype == np.float64
-    ref = pack(x, attn, feats)
-    x32, attn32, feats32 = oracle.vit.vit_forward(imgs, w, TINY, ex_feats=exf)
-    o = errors(pack(x32, attn32, feats32), ref)
-    pmin = [float(attn[l].min()) for l in range(TINY.layers)]
+    ref = pack(x, attn, feats, aff_layers)
+    x32, attn32, feats32 = oracle.vit.vit_forward(imgs, w, cfg, ex_feats=exf)
+    o = errors(pack(x32, attn32, feats32, aff_layers), ref)
+    pmin = [float(attn[l].min()) for l in range(cfg.layers)]
     return ref, o, pmin
 
 
@@ -151,35 +155,35 @@ def reference(net, g, B, ex=False, reload=True):
 K_FACTOR = {"f32": 3.0, "f16x3": 3.0, "f16x2": 3.0, "bf16x3": 40.0}
 
 
-def floor_of(mode, name):
+def floor_of(mode, name, cfg=TINY):
     if name.startswith("attn") or name.startswith("rowsum"):
         l = int(name.lstrip("attnrowsum"))
-        return (2e-4 if mode == "bf16x3" else 5e-4) * layer_rowsum(l)
+        return (2e-4 if mode == "bf16x3" else 5e-4) * layer_rowsum(l, cfg)
     if mode != "bf16x3":
         return 5e-5
     return 3e-4 if name == "w_aff" else 5e-4
 
 
-def numerics_failures(err, o, mode):
+def numerics_failures(err, o, mode, cfg=TINY):
     """Quantities of `err` beyond max(floor, k x the fp32 oracle's own deviation) -> list of messages (empty = accepted).  Row sums are
     left to the masking gate (the floors are per-element tolerances)."""
     bad = []
     for name, e in err.items():
         if name.startswith("rowsum"):
             continue
-        bound = max(floor_of(mode, name), K_FACTOR[mode] * o[name])
+        bound = max(floor_of(mode, name, cfg), K_FACTOR[mode] * o[name])
         if not e <= bound:
             bad.append(f"{name}: err {e:.3e} > {bound:.3e} (o {o[name]:.3e})")
     return bad
 
 
-def masking_precondition(o, pmin, N):
+def masking_precondition(o, pmin, N, cfg=TINY):
     """On the reference alone: the flat net is flat (every valid key holds >= 0.3 of a uniform row's share) and the fp32 oracle's own
     noise is at most a quarter of the gate -> list of messages (empty = the regime is there)."""
     bad = []
     for l, p in enumerate(pmin):
-        if not p * N / layer_rowsum(l) >= 0.3:
-            bad.append(f"layer {l}: pmin*N/rowsum = {p * N / layer_rowsum(l):.3f} < 0.3")
+        if not p * N / layer_rowsum(l, cfg) >= 0.3:
+            bad.append(f"layer {l}: pmin*N/rowsum = {p * N / layer_rowsum(l, cfg):.3f} < 0.3")
         for q in (f"attn{l}", f"rowsum{l}"):
             if not 4 * o[q] <= p / 4:
                 bad.append(f"{q}: fp32 oracle deviation {o[q]:.3e} x 4 > pmin/4 = {p / 4:.3e}")
@@ -196,8 +200,8 @@ def masking_failures(err, pmin):
     return bad
 
 
-def report(tag, err, o, pmin=None):
-    L = TINY.layers
+def report(tag, err, o, pmin=None, cfg=TINY):
+    L = cfg.layers
     worst = lambda d, p: max(d[f"{p}{l}"] for l in range(L)) if f"{p}0" in d else float("nan")
     ratio = lambda q: max((err[k] / max(o[k], 1e-300) for k in err if k.startswith(q)), default=float("nan"))
     line = (f"[attn-shapes] {tag}: attn err {worst(err, 'attn'):.2e} (o {worst(o, 'attn'):.2e}, err/o {ratio('attn'):.1f}) "

@@ -89,6 +89,53 @@ def test_layernorm(ops):
     assert maxabs(host(ops.layernorm(dev(x), dev(w), dev(b))), ref) < 2e-5
 
 
+def _layernorm_f64(x, w, b, eps=1e-5):
+    """LayerNorm restated in float64: mean, biased variance, eps inside the root."""
+    x = np.asarray(x, np.float64)
+    mu = x.mean(-1, keepdims=True)
+    var = ((x - mu) ** 2).mean(-1, keepdims=True)
+    return (x - mu) / np.sqrt(var + eps) * np.asarray(w, np.float64) + np.asarray(b, np.float64)
+
+
+@pytest.mark.parametrize("D", [4, 64, 128, 252, 256, 260, 768, 1024, 1280])
+def test_layernorm_widths_rows_and_special_rows(ops, D):
+    """layernorm_rows_kernel against float64 at every trip count of ln_row's lane loop (D = 4: one lane; 64: 16 lanes; 128: 32; 252 / 256 /
+    260: the last lane's first trip missing, present, and lane 0's second trip; 1024 / 1280: 4 and 5 full trips) and on the register arm
+    (768), with 1, 5 and 301 rows: none a multiple of the 4 rows of a workgroup, so the last workgroup is partial.
+
+    Two special rows per row count (with one row: one call each).  OFFSET: 1e3 + standard_normal.  A one-pass variance E[x^2] - E[x]^2
+    loses everything on it (1e6 against 1), and so does a mean kept as one fp32 number: its last place around 1e3 is 6e-5, which
+    (x - mean) * w passes on as up to 1e-4 (what the fp32 oracle delivers on this row, see `o` below).  CONSTANT: every element 2.5, so the
+    sum 2.5 D and the mean are exact in fp32 in any summation order, x - mean = 0 exactly, the variance is 0, rstd = eps^-1/2, and the
+    output is 0 * rstd * w + b = the bias, bit for bit.
+
+    Bound (max-abs): 2e-5, test_layernorm's, at D = 768; elsewhere max(2e-5, 3 x the fp32 oracle.vit.layer_norm's own deviation from
+    float64 on the same input)."""
+    rs = np.random.RandomState(100 + D)
+    w = rs.standard_normal(D).astype(np.float32)
+    b = rs.standard_normal(D).astype(np.float32)
+    plain = lambda n: (rs.standard_normal((n, D)) * 3 + 1).astype(np.float32)
+    offset = lambda: (1e3 + rs.standard_normal(D)).astype(np.float32)
+    const = np.full(D, 2.5, np.float32)
+    inputs = [("rows=1 plain", plain(1), None), ("rows=1 offset", offset()[None], None), ("rows=1 constant", const[None].copy(), 0)]
+    for rows in (5, 301):
+        x = plain(rows)
+        x[rows - 1] = offset()                    # both in the partial last workgroup (rows % 4 == 1: the offset row is alone in it at
+        x[rows - 2] = const                       # 5 and 301; the constant row closes the last full one)
+        inputs.append((f"rows={rows}", x, rows - 2))
+    for tag, x, const_row in inputs:
+        ref = _layernorm_f64(x, w, b)
+        o = maxabs(oracle.vit.layer_norm(x, w, b), ref)
+        bound = 2e-5 if D == 768 else max(2e-5, 3 * o)
+        got = host(ops.layernorm(dev(x), dev(w), dev(b)))
+        assert got.shape == x.shape and got.dtype == np.float32
+        err = maxabs(got, ref)
+        print(f"[layernorm] D={D} {tag}: err {err:.2e} (fp32 oracle {o:.2e}, bound {bound:.2e})")
+        assert err <= bound, (tag, err, bound)
+        if const_row is not None:
+            assert np.array_equal(got[const_row], b), (tag, maxabs(got[const_row], b))
+
+
 # ------------------------------------------------------------------ ViT
 def _check_vit(ops, cfg, w, imgs, tol_rel, check_feats=True):
     L = cfg.layers
