@@ -51,6 +51,12 @@ __device__ __forceinline__ int crf_getk(const CrfKey& k, int i) {
 template <int D>
 __global__ __launch_bounds__(256) void crf_lattice_kernel(const unsigned char* __restrict__ rgb, const int* __restrict__ tab, int B, long long N, int H,
                                                           int W, float sxy, float srgb, CrfKey* __restrict__ keys, float* __restrict__ bary) {
+    // Contraction is off in this kernel: the roundings of the construction decide the simplex and the weights, and they are the ones
+    // written here, as permutohedral.cpp and oracle/dcrf.py make them.  Plain operators, not __fmul_rn / __fsub_rn: those are inlined
+    // as plain operations that carry their header's contraction flag into this body, and hipcc -O3 made fma(-j, cf, sm) of
+    // elevated[j] = __fsub_rn(sm, __fmul_rn(j, cf)), which moved barycentric weights by up to 2e-5 at bi_rgb_std 1 and a message by
+    // 2e-6 where two pixels couple through one blur neighbour (tests/test_gpu_dcrf_filter.py, `distinct`).
+#pragma clang fp contract(off)
     const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
     int img = 0, loc = (int)n;
@@ -74,16 +80,16 @@ __global__ __launch_bounds__(256) void crf_lattice_kernel(const unsigned char* _
 #pragma unroll
     for (int j = D; j > 0; --j) {
         const float scale = (float)(1.0 / sqrt((double)((j + 1) * j))) * inv_std;
-        const float cf = __fmul_rn(f[j - 1], scale);
-        elevated[j] = __fsub_rn(sm, __fmul_rn((float)j, cf));
-        sm = __fadd_rn(sm, cf);
+        const float cf = f[j - 1] * scale;
+        elevated[j] = sm - (float)j * cf;
+        sm = sm + cf;
     }
     elevated[0] = sm;
     const float down = 1.0f / (float)(D + 1), up = (float)(D + 1);
     int rem0[D + 1], rank[D + 1], sum = 0;
 #pragma unroll
     for (int i = 0; i <= D; ++i) {
-        const float v = __fmul_rn(down, elevated[i]);
+        const float v = down * elevated[i];
         const float u = ceilf(v) * up, dn = floorf(v) * up;
         rem0[i] = (u - elevated[i] < elevated[i] - dn) ? (int)u : (int)dn;
         sum += rem0[i] / (D + 1);
@@ -106,7 +112,7 @@ __global__ __launch_bounds__(256) void crf_lattice_kernel(const unsigned char* _
     for (int i = 0; i <= D + 1; ++i) bc[i] = 0.f;
 #pragma unroll
     for (int i = 0; i <= D; ++i) {
-        const float v = __fmul_rn(elevated[i] - (float)rem0[i], down);
+        const float v = (elevated[i] - (float)rem0[i]) * down;
 #pragma unroll
         for (int q = 0; q <= D + 1; ++q) {       // static indexing (a dynamically indexed register array goes to scratch)
             if (q == D - rank[i]) bc[q] += v;

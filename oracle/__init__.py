@@ -25,7 +25,9 @@ Pinning status (see DESIGN.md "Oracle"):
     1.0rc3, requirements.txt:4) is third-party, absent from /root/reference and
     from this image, and the reference holds no vector for it; the published
     mean-field / permutohedral-lattice algorithm is restated and covered by
-    property tests (constant preservation, symmetry, partition of unity).
+    property tests (constant preservation, symmetry, partition of unity), and
+    its messages are pinned to the exact Gaussian kernel they approximate and
+    to a float64 filter over the same lattice (tests/test_host_dcrf_filter.py).
 """
 
 from . import interp, vit, cam, attr, aff, par, evaluate, pipeline, decoder, text, dcrf  # noqa: F401

@@ -1,9 +1,17 @@
 """Fully-connected CRF mean-field inference (utils/dcrf.py of the reference) restated in numpy (oracle; test infrastructure only).
 
-PARITY UNPINNED: the reference calls pydensecrf (conda pin pydensecrf=1.0rc3, requirements.txt:4), a wrapper of Kraehenbuehl & Koltun's
-densecrf ("Efficient Inference in Fully Connected CRFs with Gaussian Edge Potentials", NIPS 2011; permutohedral lattice filtering of Adams,
-Baek & Davis 2010).  The library is a third-party dependency absent from /root/reference and from this image, and the reference has no
-test or golden vector for this stage, so what is restated here is the PUBLISHED algorithm as that library implements it:
+PARITY WITH PYDENSECRF'S OWN BITS UNPINNED: the reference calls pydensecrf (conda pin pydensecrf=1.0rc3, requirements.txt:4), a wrapper of
+Kraehenbuehl & Koltun's densecrf ("Efficient Inference in Fully Connected CRFs with Gaussian Edge Potentials", NIPS 2011; permutohedral
+lattice filtering of Adams, Baek & Davis 2010).  The library is a third-party dependency absent from the reference snapshot and from the
+test machines, and the reference has no test or golden vector for this stage, so what is restated here is the PUBLISHED algorithm as
+that library implements it (below).  What IS pinned (tests/_dcrf_filter_ref.py, tests/test_host_dcrf_filter.py; the device kernels are
+held to the same in tests/test_gpu_dcrf_filter.py):
+  * the kernel it approximates: one message of this filter lies within a few percent of the dense exp(-|f_i - f_j|^2 / 2) with the same
+    symmetric normalisation, and closer at the nominal standard deviations than at 1.25 or 0.8 times them - a misreading of the feature
+    scaling or of the neighbour offsets fails that;
+  * its fp32 arithmetic: one message, read back through softmax at iters = 1, equals a float64 splat / blur / slice over the same
+    lattice within 1e-6.
+Still not pinned: pydensecrf's bits - the order of its sums, its hash and rounding of the lattice coordinates where they differ from here.
 
   unary_from_softmax      U = -log(clip(p, 1e-5, 1))                                        (pydensecrf/utils.py)
   DenseCRF2D features     Gaussian: (x/sxy, y/sxy); bilateral: (x/sxy, y/sxy, r/srgb, g/srgb, b/srgb)   (densecrf.cpp addPairwise*)

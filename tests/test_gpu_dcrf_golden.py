@@ -1,6 +1,9 @@
 """excel_dcrf_inference against recorded bits: tests/golden/dcrf_per_image.npz holds inputs and the marginals the per-image entry gave
 on an MI355X BEFORE the kernels learned to run groups of images (they now serve both entries).  The per-image path must still give
-exactly those bits, and a group of one must as well."""
+exactly those bits, and a group of one must as well.
+The marginals were recorded again, on the same inputs, when crf_lattice_kernel stopped contracting elevated[j] = sm - j * cf into an
+fma (tests/test_gpu_dcrf_filter.py found the barycentric weights off the algorithm's by up to 2e-5): the lattice weights changed in
+their last bits, so every marginal after a message did (figures in DESIGN.md, "One message at a time")."""
 import os
 
 import numpy as np

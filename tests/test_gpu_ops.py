@@ -663,14 +663,21 @@ def test_ragged_par_ignores_row_padding(ops):
         assert torch.equal(plan.planes(out, b, 2), ref[0])
 
 
-@pytest.mark.parametrize("H,W,C,params", [(24, 30, 3, (10, 3, 1, 4, 67, 3)), (37, 29, 5, (5, 3, 3, 10, 80, 13)), (50, 64, 2, (10, 3, 1, 4, 67, 3))])
-def test_dcrf_vs_oracle(ops, H, W, C, params):
+@pytest.mark.parametrize("H,W,C,params,kind", [(24, 30, 3, (10, 3, 1, 4, 67, 3), "noise_half"), (37, 29, 5, (5, 3, 3, 10, 80, 13), "noise_half"),
+                                               (50, 64, 2, (10, 3, 1, 4, 67, 3), "noise_half"), (37, 29, 5, (10, 3, 3, 10, 80, 13), "smooth"),
+                                               (24, 30, 3, (10, 3, 1, 4, 67, 3), "uniform")],
+                         ids=["24-30-3-params0", "37-29-5-params1", "50-64-2-params2", "37-29-5-smooth", "24-30-3-uniform"])
+def test_dcrf_vs_oracle(ops, H, W, C, params, kind):
     """excel_dcrf_inference (utils/dcrf.py:42-68 with the parameter sets of tools/infer_lam.py:191-198 and utils/dcrf.py:20-21) against
     the numpy restatement of the published mean-field / permutohedral-lattice algorithm; marginals within 2e-4, labels equal except
-    where the two top marginals tie."""
+    where the two top marginals tie.  `smooth` and `uniform` (tests/_dcrf_filter_ref.py) give long vertex lists per lattice point; one
+    message at a time is held far tighter in tests/test_gpu_dcrf_filter.py."""
     rs = np.random.RandomState(H + C)
     img = (rs.rand(H, W, 3) * 255).astype(np.uint8)
     img[:, : W // 2] = (img[:, : W // 2] * 0.15 + 140).astype(np.uint8)           # a smooth half and a noisy half
+    if kind != "noise_half":
+        import _dcrf_filter_ref
+        img = _dcrf_filter_ref.image(kind, H, W, H + C)
     p = rs.rand(C, H, W).astype(np.float32) ** 2 + 1e-3
     p /= p.sum(0, keepdims=True)
     ref = oracle.dcrf.dense_crf_2d(img, oracle.dcrf.unary_from_softmax(p), *params)
