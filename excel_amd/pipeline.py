@@ -10,6 +10,7 @@ import contextlib
 import torch
 
 from . import ops
+from .utils.label_stages import STAGES
 
 GUARD_MODES = (None, "skip", "observe")
 TTA_MAX_SCALES = ops.TTA_MAX_SCALES
@@ -121,8 +122,8 @@ class TagTicket:
 
 class ScoreTicket:
     """The per-image score counts of one step on their way to the host (the GuardTicket pattern): per matrix the step scored - "main"
-    (self.hist), "conf" (self.hist_conf), "clean" (self.hist_clean), "fill" (self.hist_fill), "snap" (self.hist_snap), "seg" (self.hist_seg) - a pinned int32 [B,3,nc] copy of ops.image_scores' result, and the
-    event recorded behind the last copy on the step's stream.  ready() never blocks; counts() waits for the event."""
+    (self.hist), "seg" (self.hist_seg), otherwise "<set>" for self.hist_<set> - a pinned int32 [B,3,nc] copy of ops.image_scores' result,
+    and the event recorded behind the last copy on the step's stream.  ready() never blocks; counts() waits for the event."""
 
     def __init__(self):
         self._parts, self._event = {}, None
@@ -305,18 +306,18 @@ class TrainingFreePipeline:
         named "margin".  The returned labels, hist and the snap -> clean -> fill chain are untouched; the uniform and multi-stream
         paths refuse both."""
         self.clean = _check_clean(clean)
-        self.hist_clean = None
-        self.last_clean_labels = self.last_clean_counts = None
         self.fill = _check_fill(fill, self.clean)
-        self.hist_fill = None
-        self.last_fill_labels = self.last_fill_counts = self.last_fill_dist2 = None
         self.snap = _check_snap(snap)
-        self.hist_snap = None
-        self.last_snap_labels = self.last_snap_counts = self.last_snap_sp = None
         from .utils import margin as _mrg
         self.margin_sweep = _mrg.check_thresholds(margin_sweep) if margin_sweep is not None else None
         self.margin_min = _mrg.check_min(margin_min) if margin_min is not None else None
-        self.margin_totals = self.margin_kept = self.hist_margin = self.last_margin_labels = None
+        for stage in STAGES.values():                   # what every label stage leaves behind (utils/label_stages.py)
+            setattr(self, "hist_" + stage.name, None)
+            setattr(self, f"last_{stage.name}_labels", None)
+            if stage.rows is not None:
+                setattr(self, f"last_{stage.name}_counts", None)
+        self.last_fill_dist2 = self.last_snap_sp = None
+        self.margin_totals = self.margin_kept = None
         from .utils import bkg_sweep as _bkg
         self.bkg_sweep = _bkg.check_scales(bkg_sweep) if bkg_sweep is not None else None
         self.bkg_scale = _bkg.check_scale(bkg_scale)
@@ -359,11 +360,10 @@ class TrainingFreePipeline:
         self.drain()
         self.hist = None
         self.hist_conf = None
-        self.hist_clean = None
-        self.hist_fill = None
-        self.hist_snap = None
+        for name in STAGES:
+            setattr(self, "hist_" + name, None)
         self.sweep_totals = None
-        self.margin_totals = self.margin_kept = self.hist_margin = None
+        self.margin_totals = self.margin_kept = None
 
     def _buf(self, name, numel, dtype=torch.float32, device=None):
         """Step-persistent scratch (cams, PAR output, PAR workspace): one grow-only flat buffer per (name, launch stream), so a step
@@ -420,10 +420,11 @@ class TrainingFreePipeline:
                              "the pipeline without tagger")
 
     def _score(self, gts, labels, flags, plan=None, into="hist"):
-        """-> the confusion matrix `into` (self.hist, self.hist_conf) with this step's pixels added."""
+        """-> the confusion matrix `into` (self.hist, self.hist_conf, a label stage's self.hist_<name>) with this step's pixels added.
+        The score set of the per-image counts is "main" for hist, else what follows "hist_"."""
         hist = getattr(self, into)
         if self.image_scores:
-            self._image_scores({"hist": "main", "hist_conf": "conf", "hist_clean": "clean", "hist_fill": "fill", "hist_snap": "snap", "hist_margin": "margin"}[into], gts, labels, flags if self.guard == "skip" else None, plan)
+            self._image_scores("main" if into == "hist" else into[len("hist_"):], gts, labels, flags if self.guard == "skip" else None, plan)
         if self.guard == "skip":
             return ops.confusion_accumulate_masked(gts, labels, self.num_classes, flags, hist, plan=plan)
         return ops.confusion_accumulate(gts, labels, self.num_classes, hist)                       # evaluate.py:9-20

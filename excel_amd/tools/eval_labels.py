@@ -114,14 +114,58 @@ def _hist_numpy(gt, pred, nc):
     return np.bincount(nc * gt[m] + pred[m], minlength=nc * nc).reshape(nc, nc)
 
 
+def _split(flat, hws):
+    """A flat numpy batch -> its [H,W] maps."""
+    offs = np.concatenate([[0], np.cumsum([h * w for h, w in hws])])
+    return [flat[offs[j]:offs[j + 1]].reshape(hw) for j, hw in enumerate(hws)]
+
+
+# One batch of one stage -> (maps, counts [B,3]).  The maps of a batch are flat: a device tensor (the device arm, ops through the stage's
+# utils module) or a numpy array (the numpy arm, its restatement); what comes back is of the same kind.
+def _snap_batch(snap, src, imgs, hws, nc):
+    from ..utils import superpixels
+    if torch.is_tensor(src):
+        from .. import ops
+        plan = ops.RaggedPlan(hws, src.device)
+        hwc_d = torch.from_numpy(np.concatenate([im.reshape(-1) for im in imgs])).to(src.device)
+        sp_d, _, cent = superpixels.slic_superpixels(hwc_d, snap["step"], snap["compactness"], snap["iters"], plan=plan)
+        return superpixels.snap_labels(src, sp_d, snap["step"], nc, snap["min_share"], plan=plan, cent=cent)
+    done = superpixels.snap_batch_numpy(imgs, _split(src, hws), snap["step"], nc, snap["compactness"], snap["iters"], snap["min_share"])
+    return np.concatenate([d[2].reshape(-1) for d in done]), np.stack([d[3] for d in done])
+
+
+def _clean_batch(clean, src, hws, nc):
+    from ..utils import components
+    thr = [components.min_area_rule(clean["min_region"], h, w) for h, w in hws]
+    if torch.is_tensor(src):
+        from .. import ops
+        plan = ops.RaggedPlan(hws, src.device)
+        comp, area = components.label_components(src, plan=plan, connectivity=clean["connectivity"])
+        return components.filter_small_regions(src, comp, area, thr, nc, plan=plan)
+    done = [components.clean_numpy(m, t, nc, clean["connectivity"]) for m, t in zip(_split(src, hws), thr)]
+    return np.concatenate([d[0].reshape(-1) for d in done]), np.stack([d[1] for d in done])
+
+
+def _fill_batch(fill, hole, mask, hws, nc):
+    """mask: the map in which a 255 is to stay, or None: every 255 of `hole` is a hole."""
+    from ..utils import label_fill
+    if torch.is_tensor(hole):
+        from .. import ops
+        filled_d, _, counts_d = label_fill.fill_nearest_label(hole, nc, plan=ops.RaggedPlan(hws, hole.device), mask=mask, radius=fill["radius"])
+        return filled_d, counts_d
+    masks = _split(mask, hws) if mask is not None else [None] * len(hws)
+    done = [label_fill.fill_numpy(h, nc, radius=fill["radius"], mask=m) for h, m in zip(_split(hole, hws), masks)]
+    return np.concatenate([d[0].reshape(-1) for d in done]), np.stack([d[2] for d in done])
+
+
 def validate(args):
     """-> {"score": scores_from_hist of the gathered matrix, "hist": [nc,nc] int64 (CPU tensor), "images": scored on this rank,
-    "seconds"}: the layout of infer_seg_voc.validate (+ "image_scores" with --per_image_scores)."""
-    from ..utils import components, evaluate, image_scores, label_fill, superpixels
+    "seconds"}: the layout of infer_seg_voc.validate (+ "image_scores" with --per_image_scores, + one entry per label stage that is on)."""
+    from ..utils import components, evaluate, image_scores, label_stages
     image_scores.refuse(args)
-    clean = components.resolve(args, program="eval_labels")
-    fill = label_fill.resolve(args, program="eval_labels")
-    snap = superpixels.resolve(args, program="eval_labels")
+    on = {name: label_stages.STAGES[name].resolve(args, program="eval_labels") for name in ("clean", "fill", "snap")}
+    clean, fill, snap = on["clean"], on["fill"], on["snap"]
+    stages = {name: on[name] for name in label_stages.EVAL_LABELS_ORDER if on[name] is not None}     # those that run, in the order of the report
     names_fg = None
     if getattr(args, "class_names", None):
         from .infer_lam import _read_names
@@ -147,19 +191,31 @@ def validate(args):
     boundary = image_scores.boundary_of(args)
     scores = image_scores.ImageScoreLog(nc, boundary=boundary) if image_scores.wanted(args) else None
     hist = torch.zeros((nc, nc), dtype=torch.int64, device=device)
-    hist_clean, clean_rows = (torch.zeros_like(hist) if clean is not None else None), []
-    if clean is not None and clean["label_dir"]:
-        os.makedirs(clean["label_dir"], exist_ok=True)
-    hist_fill, fill_rows = (torch.zeros_like(hist) if fill is not None else None), []
-    hist_snap, snap_rows, snap_pixels = (torch.zeros_like(hist) if snap is not None else None), [], 0
-    if snap is not None and snap["label_dir"]:
-        os.makedirs(snap["label_dir"], exist_ok=True)
-    if fill is not None and fill["label_dir"]:
-        os.makedirs(fill["label_dir"], exist_ok=True)
+    stage_hist, stage_rows, pixels = {name: torch.zeros_like(hist) for name in stages}, {name: [] for name in stages}, 0
+    for resolved in stages.values():
+        if resolved["label_dir"]:
+            os.makedirs(resolved["label_dir"], exist_ok=True)
+
+    def scored(name, maps, counts):
+        """The shared end of a stage's batch: its maps into the stage's matrix, its rows kept, its PNGs written -> the maps as they came."""
+        if on_gpu:
+            from .. import ops
+            stage_hist[name] = ops.confusion_accumulate(gt_d, maps, nc, stage_hist[name])
+            host, counts = maps.cpu().numpy(), counts.cpu().numpy()
+        else:
+            host = maps
+            stage_hist[name] += torch.from_numpy(_hist_numpy(gt, host, nc))
+        stage_rows[name].extend(np.asarray(counts, np.int64).reshape(-1, 3).tolist())
+        if stages[name]["label_dir"]:
+            for n, m in zip(batch, _split(host, hws)):
+                _save_index_png(os.path.join(stages[name]["label_dir"], n + ".png"), m)
+        return maps
+
     t0 = time.time()
     with cf.ThreadPoolExecutor(max_workers=max(1, int(args.num_workers))) as pool:
         for s in range(0, len(mine), args.batch_size):
-            pairs = list(pool.map(lambda n: _load_pair(args, n), mine[s:s + args.batch_size]))       # raises the first error, in order
+            batch = mine[s:s + args.batch_size]
+            pairs = list(pool.map(lambda n: _load_pair(args, n), batch))                             # raises the first error, in order
             gt = np.concatenate([p[0] for p in pairs])
             pred = np.concatenate([p[1] for p in pairs])
             hws = [p[2] for p in pairs]
@@ -169,84 +225,27 @@ def validate(args):
                 hist = ops.confusion_accumulate(gt_d, pred_d, nc, hist)
                 if scores is not None:                                                           # the batch as one ragged plan, behind a ticket
                     from ..pipeline import ScoreTicket
-                    hws = [p[2] for p in pairs]
                     scores.defer(ScoreTicket().launch("main", gt_d, pred_d, nc, plan=ops.RaggedPlan(hws, device), boundary=boundary), idx[s:s + len(pairs)],
-                                 mine[s:s + len(pairs)], hws)
+                                 batch, hws)
             else:
                 hist += torch.from_numpy(_hist_numpy(gt, pred, nc))
                 if scores is not None:
                     for j, p in enumerate(pairs):
-                        scores.put(idx[s + j], mine[s + j], p[2], "main", image_scores.counts_numpy(p[0], p[1], nc))
+                        scores.put(idx[s + j], batch[j], p[2], "main", image_scores.counts_numpy(p[0], p[1], nc))
                         if boundary is not None:
-                            scores.put(idx[s + j], mine[s + j], p[2], "main_bd", image_scores.boundary_counts_numpy(
-                                p[0].reshape(p[2]), p[1].reshape(p[2]), nc, image_scores.checked_radius(mine[s + j], p[2][0], p[2][1], boundary)))
-            src, src_d = pred, (pred_d if on_gpu else None)      # what the cleaning and the fill work on: the predictions, or the snapped maps
-            if snap is not None:                                 # the snapped maps of the batch: the images decoded, segmented, voted on
-                imgs = list(pool.map(lambda nh: _load_image(args, *nh), zip(mine[s:s + len(pairs)], hws)))
-                if on_gpu:
-                    plan = ops.RaggedPlan(hws, device)
-                    hwc_d = torch.from_numpy(np.concatenate([im.reshape(-1) for im in imgs])).to(device)
-                    sp_d, _, cent = superpixels.slic_superpixels(hwc_d, snap["step"], snap["compactness"], snap["iters"], plan=plan)
-                    src_d, counts_d = superpixels.snap_labels(pred_d, sp_d, snap["step"], nc, snap["min_share"], plan=plan, cent=cent)
-                    hist_snap = ops.confusion_accumulate(gt_d, src_d, nc, hist_snap)
-                    src, counts = src_d.cpu().numpy(), counts_d.cpu().numpy()
-                else:
-                    done = superpixels.snap_batch_numpy(imgs, [p[1].reshape(p[2]) for p in pairs], snap["step"], nc, snap["compactness"],
-                                                        snap["iters"], snap["min_share"])
-                    src = np.concatenate([d[2].reshape(-1) for d in done])
-                    counts = np.stack([d[3] for d in done])
-                    hist_snap += torch.from_numpy(_hist_numpy(gt, src, nc))
-                snap_rows.extend(np.asarray(counts, np.int64).reshape(-1, 3).tolist())
-                snap_pixels += int(src.size)
-                if snap["label_dir"]:
-                    off = 0
-                    for n, (h, w) in zip(mine[s:s + len(pairs)], hws):
-                        _save_index_png(os.path.join(snap["label_dir"], n + ".png"), src[off:off + h * w].reshape(h, w))
-                        off += h * w
-            offs = np.concatenate([[0], np.cumsum([h * w for h, w in hws])])
-            if clean is not None:                                # the cleaned maps of the batch: scored into a matrix of their own, written
-                hws = [p[2] for p in pairs]
-                thr = [components.min_area_rule(clean["min_region"], h, w) for h, w in hws]
-                if on_gpu:
-                    plan = ops.RaggedPlan(hws, device)
-                    comp, area = components.label_components(src_d, plan=plan, connectivity=clean["connectivity"])
-                    cleaned_d, counts_d = components.filter_small_regions(src_d, comp, area, thr, nc, plan=plan)
-                    hist_clean = ops.confusion_accumulate(gt_d, cleaned_d, nc, hist_clean)
-                    cleaned, counts = cleaned_d.cpu().numpy(), counts_d.cpu().numpy()
-                else:
-                    done = [components.clean_numpy(src[offs[j]:offs[j + 1]].reshape(p[2]), t, nc, clean["connectivity"])
-                            for j, (p, t) in enumerate(zip(pairs, thr))]
-                    cleaned = np.concatenate([d[0].reshape(-1) for d in done])
-                    counts = np.stack([d[1] for d in done])
-                    hist_clean += torch.from_numpy(_hist_numpy(gt, cleaned, nc))
-                clean_rows.extend(np.asarray(counts, np.int64).reshape(-1, 3).tolist())
-                if clean["label_dir"]:
-                    off = 0
-                    for n, (h, w) in zip(mine[s:s + len(pairs)], hws):
-                        _save_index_png(os.path.join(clean["label_dir"], n + ".png"), cleaned[off:off + h * w].reshape(h, w))
-                        off += h * w
-            if fill is not None:                                 # the filled maps: what the cleaning removed, or every 255 of the predictions
-                if on_gpu:
-                    hole_d, mask_d = (cleaned_d, src_d) if clean is not None else (src_d, None)
-                    filled_d, _, counts_d = label_fill.fill_nearest_label(hole_d, nc, plan=ops.RaggedPlan(hws, device), mask=mask_d, radius=fill["radius"])
-                    hist_fill = ops.confusion_accumulate(gt_d, filled_d, nc, hist_fill)
-                    filled, counts = filled_d.cpu().numpy(), counts_d.cpu().numpy()
-                else:
-                    hole, off, done = (cleaned if clean is not None else src), 0, []
-                    for p in pairs:
-                        n_pix = p[2][0] * p[2][1]
-                        done.append(label_fill.fill_numpy(hole[off:off + n_pix].reshape(p[2]), nc, radius=fill["radius"],
-                                                          mask=src[off:off + n_pix].reshape(p[2]) if clean is not None else None))
-                        off += n_pix
-                    filled = np.concatenate([d[0].reshape(-1) for d in done])
-                    counts = np.stack([d[2] for d in done])
-                    hist_fill += torch.from_numpy(_hist_numpy(gt, filled, nc))
-                fill_rows.extend(np.asarray(counts, np.int64).reshape(-1, 3).tolist())
-                if fill["label_dir"]:
-                    off = 0
-                    for n, (h, w) in zip(mine[s:s + len(pairs)], hws):
-                        _save_index_png(os.path.join(fill["label_dir"], n + ".png"), filled[off:off + h * w].reshape(h, w))
-                        off += h * w
+                            scores.put(idx[s + j], batch[j], p[2], "main_bd", image_scores.boundary_counts_numpy(
+                                p[0].reshape(p[2]), p[1].reshape(p[2]), nc, image_scores.checked_radius(batch[j], p[2][0], p[2][1], boundary)))
+            # the chain snap -> clean -> fill (label_stages.CHAIN_ORDER), every stage on the maps of the one in front of it
+            src = pred_d if on_gpu else pred                     # what the cleaning and the fill work on: the predictions, or the snapped maps
+            pixels += int(pred.size)
+            if snap is not None:                                 # the images decoded, segmented, voted on
+                imgs = list(pool.map(lambda nh: _load_image(args, *nh), zip(batch, hws)))
+                src = scored("snap", *_snap_batch(snap, src, imgs, hws, nc))
+            if clean is not None:
+                cleaned = scored("clean", *_clean_batch(clean, src, hws, nc))
+            if fill is not None:                                 # what the cleaning removed (its input is the mask: a 255 it had stays), or every 255
+                hole, mask = (cleaned, src) if clean is not None else (src, None)
+                scored("fill", *_fill_batch(fill, hole, mask, hws, nc))
     _, total = gather_hists(hist)
     total = total.cpu()
     score = evaluate.scores_from_hist(total)
@@ -264,57 +263,24 @@ def validate(args):
         logging.info("\n" + format_scores_table(score, cats))
         logging.info(f"mIoU {score['miou'] * 100:.3f}  images {len(names)}  ({len(mine) / max(secs, 1e-9):.1f} img/s/rank)")
     out = {"score": score, "hist": total, "images": len(mine), "seconds": secs}
-    if snap is not None:
-        _, snap_total = gather_hists(hist_snap)
-        snap_total = snap_total.cpu()
-        parts = [(snap_rows, snap_pixels)]
+    for name, resolved in stages.items():                      # every rank gathers in this order
+        stage = label_stages.STAGES[name]
+        _, set_total = gather_hists(stage_hist[name])
+        set_total = set_total.cpu()
+        parts = [(stage_rows[name], pixels)]
         if world > 1:
             parts = [None] * world
-            torch.distributed.all_gather_object(parts, (snap_rows, snap_pixels))
+            torch.distributed.all_gather_object(parts, (stage_rows[name], pixels))
         counts = np.asarray([r for part in parts for r in part[0]], np.int64).reshape(-1, 3)
-        out["snap"] = dict(score=evaluate.scores_from_hist(snap_total), hist=snap_total, coverage=components.coverage(snap_total, total),
-                           counts=counts, stats=superpixels.snap_stats(counts, sum(part[1] for part in parts)),
-                           **{k: snap[k] for k in ("step", "compactness", "iters", "min_share")})
+        more = (sum(part[1] for part in parts),) if name == "snap" else ()       # the share of pixels the vote changed
+        out[name] = dict(score=evaluate.scores_from_hist(set_total), hist=set_total, coverage=components.coverage(set_total, total),
+                         counts=counts, stats=stage.stats(counts, *more), **label_stages.pipeline_value(stage, resolved))
         if rank == 0:
-            logging.info(f"snap_label_score of {args.pred_dir} (--snap_superpixels {snap['step']}, compactness {snap['compactness']}, "
-                         f"{snap['iters']} iterations, min share {snap['min_share']:g}):")
-            logging.info("\n" + format_scores_table(out["snap"]["score"], cats))
-            logging.info(superpixels.format_snap_summary(out["snap"]["stats"], out["snap"]["coverage"]))
-            if snap["label_dir"]:
-                logging.info(f"snapped label maps -> {snap['label_dir']}")
-    if clean is not None:
-        _, clean_total = gather_hists(hist_clean)
-        clean_total = clean_total.cpu()
-        parts = [clean_rows]
-        if world > 1:
-            parts = [None] * world
-            torch.distributed.all_gather_object(parts, clean_rows)
-        counts = np.asarray([r for part in parts for r in part], np.int64).reshape(-1, 3)
-        out["clean"] = dict(score=evaluate.scores_from_hist(clean_total), hist=clean_total, coverage=components.coverage(clean_total, total),
-                            counts=counts, stats=components.region_stats(counts), min_region=clean["min_region"],
-                            connectivity=clean["connectivity"])
-        if rank == 0:
-            logging.info(f"clean_label_score of {args.pred_dir} (--clean_min_region {clean['min_region']:g}, connectivity {clean['connectivity']}):")
-            logging.info("\n" + format_scores_table(out["clean"]["score"], cats))
-            logging.info(components.format_clean_summary(out["clean"]["stats"], out["clean"]["coverage"]))
-            if clean["label_dir"]:
-                logging.info(f"cleaned label maps -> {clean['label_dir']}")
-    if fill is not None:
-        _, fill_total = gather_hists(hist_fill)
-        fill_total = fill_total.cpu()
-        parts = [fill_rows]
-        if world > 1:
-            parts = [None] * world
-            torch.distributed.all_gather_object(parts, fill_rows)
-        counts = np.asarray([r for part in parts for r in part], np.int64).reshape(-1, 3)
-        out["fill"] = dict(score=evaluate.scores_from_hist(fill_total), hist=fill_total, coverage=components.coverage(fill_total, total),
-                           counts=counts, stats=label_fill.fill_stats(counts), radius=fill["radius"])
-        if rank == 0:
-            logging.info(f"fill_label_score of {args.pred_dir} (--fill_ignore {'inf' if fill['radius'] is None else fill['radius']}):")
-            logging.info("\n" + format_scores_table(out["fill"]["score"], cats))
-            logging.info(label_fill.format_fill_summary(out["fill"]["stats"], out["fill"]["coverage"]))
-            if fill["label_dir"]:
-                logging.info(f"filled label maps -> {fill['label_dir']}")
+            logging.info(label_stages.title(stage, resolved, of=args.pred_dir))
+            logging.info("\n" + format_scores_table(out[name]["score"], cats))
+            logging.info(stage.summary(out[name]["stats"], out[name]["coverage"]))
+            if resolved["label_dir"]:
+                logging.info(f"{stage.noun} label maps -> {resolved['label_dir']}")
     if scores is not None:
         out["image_scores"] = merged                           # the merged table (utils/image_scores.ImageScoreLog.merged)
     return out

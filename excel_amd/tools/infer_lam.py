@@ -879,29 +879,22 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError(f"{'--bkg_sweep' if sweep is not None else '--bkg_scale'} runs behind the ragged step: ragged batches (--data_folder or "
                          "--ragged true) on the batched loop")
     bkg_kw = {**({"bkg_sweep": sweep} if sweep is not None else {}), **({"bkg_scale": bkg_scale} if bkg_scale != 1.0 else {})}
-    from ..utils import components
-    clean = components.resolve(args)
-    if clean is not None and not ragged:
-        raise ValueError("--clean_min_region runs behind the ragged step: ragged batches (--data_folder or --ragged true) on the batched loop")
-    clean_kw = dict(min_region=clean["min_region"], connectivity=clean["connectivity"]) if clean is not None else None
-    if clean is not None:
-        bkg_kw = {**bkg_kw, "clean": clean_kw}
-    from ..utils import label_fill
-    fill = label_fill.resolve(args)
-    fill_kw = dict(radius=fill["radius"]) if fill is not None else None
-    if fill is not None:
-        bkg_kw = {**bkg_kw, "fill": fill_kw}
-    from ..utils import superpixels
-    snap = superpixels.resolve(args)
-    if snap is not None and not ragged:
-        raise ValueError("--snap_superpixels runs behind the ragged step: ragged batches (--data_folder or --ragged true) on the batched loop")
-    snap_kw = {k: snap[k] for k in ("step", "compactness", "iters", "min_share")} if snap is not None else None
-    if snap is not None:
-        bkg_kw = {**bkg_kw, "snap": snap_kw}
+    # the label stages that are on: name -> resolved flags (utils/label_stages.py); each runs behind the ragged step
+    from ..utils import label_stages
     from ..utils import margin as margin_mod
-    msweep, mcut = margin_mod.resolve(args, ragged=ragged)
-    margin_kw = {**({"margin_sweep": msweep} if msweep is not None else {}), **({"margin_min": mcut["min"]} if mcut is not None else {})}
-    bkg_kw = {**bkg_kw, **margin_kw}
+    stages, asked = {}, {}                                   # asked: pipeline keyword -> (the flag that asks for it, its value)
+    for name in label_stages.INFER_LAM_ORDER:
+        stage = label_stages.STAGES[name]
+        resolved = stage.resolve(args, ragged=ragged)
+        if resolved is None:
+            continue
+        if not ragged:
+            raise ValueError(f"{stage.flag} runs behind the ragged step: ragged batches (--data_folder or --ragged true) on the batched loop")
+        stages[name], asked[stage.kwarg] = resolved, (stage.flag, label_stages.pipeline_value(stage, resolved))
+    msweep = margin_mod.resolve(args, ragged=ragged)[0]
+    if msweep is not None:
+        asked["margin_sweep"] = ("--margin_sweep", msweep)
+    bkg_kw = {**bkg_kw, **{k: want for k, (_, want) in asked.items()}}
     if pipe is None:
         kw = dict(num_classes=args.num_classes, dilations=par.dilations, num_iter=par.num_iter, caa_thre=0.79,
                   smax=dataset.max_k() if tagger is None else tagger["kmax"], guard="skip" if policy in ("raise", "rerun") else None,
@@ -918,33 +911,26 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         raise ValueError("--per_image_scores: the supplied pipeline was built without image_scores=True")
     if boundary is not None and pipe is not None and not per_image and getattr(pipe, "boundary", None) != boundary:
         raise ValueError(f"--boundary_scores: the supplied pipeline was built with boundary={getattr(pipe, 'boundary', None)!r}, the flags ask for {boundary!r}")
-    if clean is not None and pipe is not None and getattr(pipe, "clean", None) != clean_kw:
-        raise ValueError(f"--clean_min_region: the supplied pipeline was built with clean={getattr(pipe, 'clean', None)!r}, the flags ask for {clean_kw!r}")
-    if fill is not None and pipe is not None and getattr(pipe, "fill", None) != fill_kw:
-        raise ValueError(f"--fill_ignore: the supplied pipeline was built with fill={getattr(pipe, 'fill', None)!r}, the flags ask for {fill_kw!r}")
-    if snap is not None and pipe is not None and getattr(pipe, "snap", None) != snap_kw:
-        raise ValueError(f"--snap_superpixels: the supplied pipeline was built with snap={getattr(pipe, 'snap', None)!r}, the flags ask for {snap_kw!r}")
-    for k, want in margin_kw.items():
+    for k, (flag, want) in asked.items():
         if pipe is not None and getattr(pipe, k, None) != want:
-            raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
+            raise ValueError(f"{flag}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     for k, want in (("bkg_sweep", sweep), ("bkg_scale", bkg_scale)):
         if (sweep is not None or bkg_scale != 1.0) and pipe is not None and getattr(pipe, k, None if k == "bkg_sweep" else 1.0) != want:
             raise ValueError(f"--{k}: the supplied pipeline was built with {k}={getattr(pipe, k, None)!r}, the flags ask for {want!r}")
     report = dict(guard={"policy": policy, "mode": mode, "checked": 0, "flagged": [], "rerun": 0, "nonfinite_in_f32": []},
-                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None, clean=None, fill=None, snap=None, margin=None)
+                  crf_hist=None, crf_stats=None, cam_stats=None, conf_hist=None, tags=None, image_scores=None, bkg_sweep=None,
+                  **{name: None for name in label_stages.STAGES})
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", 1)))
     run = SimpleNamespace(model=model, par=par, dataset=dataset, indices=indices, device=device, args=args, pipe=pipe, S=args.resize_size,
-                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, clean=clean, fill=fill, snap=snap, msweep=msweep, mcut=mcut,
+                          on_gpu=on_gpu, ragged=ragged, tta=(tta_scales, tta_flip), conf=conf, tagger=tagger, guard=report["guard"], report=report, sweep=sweep, stages=stages, msweep=msweep,
                           local_world=local_world, writers=default_cam_writers(local_world) if args.save_cam else 0,
                           hist=torch.zeros((args.num_classes, args.num_classes), dtype=torch.int64, device=device), t0=time.time(),
                           consumers={})       # cam, lab, crf, conf_lab: those that exist, in the order the re-run barrier and the close take them
     # --per_image_scores: the rank's table of per-image counts, one set per matrix the run scores (utils/image_scores.py)
     run.scores = report["image_scores"] = image_scores.ImageScoreLog(
         args.num_classes, ["main"] + (["conf"] if conf is not None else []) + (["crf"] if crf_inline_wanted(args) else [])
-        + (["clean"] if clean is not None and not args.unlabeled else []) + (["fill"] if fill is not None and not args.unlabeled else [])
-        + (["snap"] if snap is not None and not args.unlabeled else []) + (["margin"] if mcut is not None and not args.unlabeled else []),
-        boundary=boundary, **({"regions": True} if clean is not None else {}), **({"fills": True} if fill is not None else {}),
-        **({"snaps": True} if snap is not None else {})) if want_scores else None
+        + ([] if args.unlabeled else list(stages)), boundary=boundary,
+        rows=[label_stages.STAGES[name].rows.key for name in stages if label_stages.STAGES[name].rows is not None]) if want_scores else None
     try:
         for wanted, needs in ((args.save_cam, "--save_cam needs the decoded images"), (conf is not None, "--conf_label runs behind the ragged step"),
                               (crf_inline_wanted(args), "--crf_inline needs the decoded images")):
@@ -960,14 +946,9 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
         if conf is not None:
             run.consumers["conf_lab"] = _LabelSaver(args, args.conf_label_dir or conf_label_output_dir(
                 args.model_path, args.infer_set, bool(args.training_free), bool(args.refine_with_aff)))
-        if clean is not None and clean["label_dir"]:
-            run.consumers["clean_lab"] = _LabelSaver(args, clean["label_dir"])
-        if fill is not None and fill["label_dir"]:
-            run.consumers["fill_lab"] = _LabelSaver(args, fill["label_dir"])
-        if snap is not None and snap["label_dir"]:
-            run.consumers["snap_lab"] = _LabelSaver(args, snap["label_dir"])
-        if mcut is not None and mcut["label_dir"]:
-            run.consumers["margin_lab"] = _LabelSaver(args, mcut["label_dir"])
+        for name, resolved in stages.items():
+            if resolved["label_dir"]:
+                run.consumers[name + "_lab"] = _LabelSaver(args, resolved["label_dir"])
         out = (_per_image_loop if per_image else _batched_loop)(run)
     except BaseException:
         _close_consumers(run, failed=True)
@@ -977,13 +958,8 @@ def build_validation(model=None, par=None, dataset=None, indices=None, device="c
     finally:
         build_validation.last_guard, build_validation.last_crf_hist, build_validation.last_crf_stats, build_validation.last_cam_stats, \
             build_validation.last_conf_hist = (report[k] for k in ("guard", "crf_hist", "crf_stats", "cam_stats", "conf_hist"))
-        build_validation.last_tags = report["tags"]
-        build_validation.last_image_scores = report["image_scores"]
-        build_validation.last_bkg_sweep = report["bkg_sweep"]
-        build_validation.last_clean = report["clean"]
-        build_validation.last_fill = report["fill"]
-        build_validation.last_snap = report["snap"]
-        build_validation.last_margin = report["margin"]
+        for k in ("tags", "image_scores", "bkg_sweep", *label_stages.STAGES):
+            setattr(build_validation, "last_" + k, report[k])
     return out
 
 
@@ -1097,23 +1073,17 @@ def _batched_loop(run):
         pipe.hist_conf = torch.zeros_like(run.hist)
     if run.sweep is not None:                                # --bkg_sweep: the pipeline adds every step's counts per scale (both passes of the guard)
         pipe.sweep_totals = torch.zeros((len(run.sweep), 3, args.num_classes), dtype=torch.int64, device=device)
-    clean_lab, fill_lab, snap_lab = run.consumers.get("clean_lab"), run.consumers.get("fill_lab"), run.consumers.get("snap_lab")
-    clean_pending, clean_rows = deque(), {}                  # --clean_min_region: (pinned counts, event, dataset indices, names) -> index: (name, row)
-    fill_pending, fill_rows = deque(), {}                    # --fill_ignore: the same, for the fill's rows
-    snap_pending, snap_rows = deque(), {}                    # --snap_superpixels: the same, for the vote's rows
+    # the label stages that are on (utils/label_stages.py): the matrix of each, the PNG writers of those with a label directory, and
+    # per set of per-image rows: the queue of (pinned counts, event, dataset indices, names, sizes) and the rows read, index: (name, row)
+    from ..utils.label_stages import STAGES
+    for name in run.stages:
+        setattr(pipe, "hist_" + name, torch.zeros_like(run.hist))
+    stage_labs = [(name, run.consumers[name + "_lab"]) for name in run.stages if name + "_lab" in run.consumers]
+    row_sets = {name: (deque(), {}) for name in run.stages if STAGES[name].rows is not None}
     row_pix = {}                                             # index: the pixels of the image (the share of pixels the snap changed)
-    if run.clean is not None:
-        pipe.hist_clean = torch.zeros_like(run.hist)
-    if run.fill is not None:
-        pipe.hist_fill = torch.zeros_like(run.hist)
-    if run.snap is not None:
-        pipe.hist_snap = torch.zeros_like(run.hist)
-    margin_lab = run.consumers.get("margin_lab")
     if run.msweep is not None:                               # --margin_sweep: the pipeline adds every step's counts per threshold (both passes of the guard)
         pipe.margin_kept = torch.zeros((len(run.msweep) + 1,), dtype=torch.int64, device=device)
         pipe.margin_totals = None if args.unlabeled else torch.zeros((len(run.msweep), 3, args.num_classes), dtype=torch.int64, device=device)
-    if run.mcut is not None:
-        pipe.hist_margin = torch.zeros_like(run.hist)
     if ragged:
         # every sample at its own size: decode in background workers, everything else on the device, one launch per stage
         from ..datasets.loader import DeviceFeeder, ragged_batches, threaded_batches
@@ -1157,14 +1127,8 @@ def _batched_loop(run):
             crf.ragged(names, plan, images, pipe.last_cams, pipe.smax + 1, pipe.last_nchan, nchan_host, pipe.last_cls_idx, labels_t, skip)
         if lab is not None:                                                             # :95, same stream, the labels just scored
             lab.ragged(names, plan, out[0] if keep else out)
-        if clean_lab is not None:                                                       # same stream, the step's cleaned maps
-            clean_lab.ragged(names, plan, pipe.last_clean_labels)
-        if fill_lab is not None:                                                        # likewise, the step's filled maps
-            fill_lab.ragged(names, plan, pipe.last_fill_labels)
-        if snap_lab is not None:                                                        # likewise, the step's snapped maps
-            snap_lab.ragged(names, plan, pipe.last_snap_labels)
-        if margin_lab is not None:                                                      # likewise, the step's margin labels
-            margin_lab.ragged(names, plan, pipe.last_margin_labels)
+        for name, stage_lab in stage_labs:                                              # same stream, the maps each stage left of this step
+            stage_lab.ragged(names, plan, getattr(pipe, f"last_{name}_labels"))
         if keep:                                                                        # :116-119 record for the CRF stage
             inter = out[1]
             cls_idx, ncls = inter["cls_idx"].cpu().numpy(), inter["ncls"].cpu().numpy()
@@ -1246,28 +1210,23 @@ def _batched_loop(run):
                 if truth is not None:
                     tag_truth[n] = np.array(truth[b], np.float32)
 
-    # what differs between the sets of per-image rows: (the pipeline's device rows, the queue, the collected rows, the table's sink)
-    row_sets = {"clean": ("last_clean_counts", clean_pending, clean_rows, "put_regions"), "fill": ("last_fill_counts", fill_pending, fill_rows, "put_fills"),
-                "snap": ("last_snap_counts", snap_pending, snap_rows, "put_snaps")}
-    row_wanted = [which for which in row_sets if getattr(run, which) is not None]
-
     def clean_enqueue(names, idxs):
         """The filter's (the fill's, the vote's) per-image counts of the step just enqueued, on their way to the host behind an event (no
         wait here)."""
-        for which in row_wanted:
-            dev = getattr(pipe, row_sets[which][0])
+        for which in row_sets:
+            dev = getattr(pipe, f"last_{which}_counts")
             host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=on_gpu)
             host.copy_(dev, non_blocking=True)
             ev = None
             if on_gpu:
                 ev = torch.cuda.Event()
                 ev.record()
-            row_sets[which][1].append((host, ev, [int(i) for i in idxs], [str(n) for n in names], [tuple(int(x) for x in hw) for hw in step_hw[0]]))
+            row_sets[which][0].append((host, ev, [int(i) for i in idxs], [str(n) for n in names], [tuple(int(x) for x in hw) for hw in step_hw[0]]))
         clean_take(False)
 
     def clean_take(wait):
         """A later row of an image (the fp32 second pass) replaces the earlier one."""
-        for _, pending, rows_of, sink in row_sets.values():
+        for which, (pending, rows_of) in row_sets.items():
             while pending and (wait or pending[0][1] is None or pending[0][1].query()):
                 host, ev, idxs, names, hws = pending.popleft()
                 if ev is not None:
@@ -1277,11 +1236,11 @@ def _batched_loop(run):
                     rows_of[i] = (names[b], rows[b].astype(np.int64))
                     row_pix[i] = hws[b][0] * hws[b][1]
                 if scores is not None:
-                    getattr(scores, sink)(idxs, names, hws, rows)
+                    scores.put_rows(STAGES[which].rows.key, idxs, names, hws, rows)
 
     nimg, pos, flagged = 0, 0, {}
     for names in steps(indices):
-        if row_wanted:
+        if row_sets:
             clean_enqueue(names, indices[pos:pos + len(names)])
         if policy != "off":
             enqueue(names, indices[pos:pos + len(names)])
@@ -1311,7 +1270,7 @@ def _batched_loop(run):
                 pos = 0
                 for names in steps(np.asarray(order, dtype=np.asarray(indices).dtype)):
                     enqueue(names, order[pos:pos + len(names)])
-                    if row_wanted:
+                    if row_sets:
                         clean_enqueue(names, order[pos:pos + len(names)])
                     if tagger is not None:
                         tag_enqueue(names)                    # the fp32 row replaces the first pass's
@@ -1334,15 +1293,12 @@ def _batched_loop(run):
         run.report["conf_hist"] = pipe.hist_conf
     if run.sweep is not None:
         run.report["bkg_sweep"] = pipe.sweep_totals
-    if row_wanted:
-        clean_take(True)
-    if run.clean is not None:
-        run.report["clean"] = dict(hist=pipe.hist_clean, rows=clean_rows)
-        if run.fill is not None:
-            run.report["fill"] = dict(hist=pipe.hist_fill, rows=fill_rows)
-    if run.snap is not None:
-        run.report["snap"] = dict(hist=pipe.hist_snap, rows=snap_rows, pixels=int(sum(row_pix.values())))
-    if run.msweep is not None or run.mcut is not None:
+    clean_take(True)
+    for name, (_, rows_of) in row_sets.items():
+        run.report[name] = dict(hist=getattr(pipe, "hist_" + name), rows=rows_of)
+    if "snap" in row_sets:
+        run.report["snap"]["pixels"] = int(sum(row_pix.values()))
+    if run.msweep is not None or "margin" in run.stages:      # the sweep's counts travel with the cut's matrix
         run.report["margin"] = dict(totals=pipe.margin_totals, kept=pipe.margin_kept, hist=pipe.hist_margin)
     if scores is not None:
         scores.poll(True)
@@ -1505,16 +1461,16 @@ def validate(args=None, dataset=None, pipe=None):
     flag_defaults(args)
     # what this call reports: every attribute starts over, None where a stage does not run
     validate.last_gemm_check = validate.last_model = validate.last_guard = validate.last_per_rank = validate.last_cat_list = None
-    validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = validate.last_clean = None
-    validate.last_fill = validate.last_snap = validate.last_margin = None
-    from ..utils import bkg_sweep, components, image_scores, label_fill, superpixels
+    validate.last_conf = validate.last_crf = validate.last_tags = validate.last_image_scores = validate.last_bkg_sweep = None
+    from ..utils import bkg_sweep, components, image_scores, label_stages
     from ..utils import margin as margin_mod
+    for name in label_stages.STAGES:
+        setattr(validate, "last_" + name, None)
     image_scores.refuse(args, unlabeled=bool(args.unlabeled))                                # ... and per-image scores of nothing
     sweep, _ = bkg_sweep.resolve(args)                                                       # ... and a sweep nobody can score or run
-    clean = components.resolve(args)                                                         # ... and a cleaning nobody can run or see
-    fill = label_fill.resolve(args)                                                          # ... and a fill of nothing
-    snap = superpixels.resolve(args)                                                         # ... and a snap nobody can run or see
-    msweep, mcut = margin_mod.resolve(args)                                                  # ... and margins nobody can run or see
+    stages = {name: label_stages.STAGES[name].resolve(args) for name in label_stages.INFER_LAM_ORDER}   # ... and a label stage nobody can run or see
+    stages = {name: resolved for name, resolved in stages.items() if resolved is not None}
+    msweep, mcut = margin_mod.resolve(args)[0], stages.get("margin")                         # ... and a margin sweep likewise
     tta = resolve_tta(args)                                                                  # a bad flag combination stops here
     conf = resolve_conf(args)                                                                # ... and a bad pair of thresholds
     vocab = resolve_vocabulary(args)                                                         # ... and a vocabulary that cannot be served
@@ -1593,33 +1549,38 @@ def validate(args=None, dataset=None, pipe=None):
         _, sweep_total = gather_hists(build_validation.last_bkg_sweep)
         sweep_scores = bkg_sweep.scores_from_totals(sweep_total)
         validate.last_bkg_sweep = dict(scales=sweep, totals=sweep_total, scores=sweep_scores, best_scale=bkg_sweep.best_scale(sweep_scores, sweep)[1])
-    def gathered_set(mine):
-        """One more scored label set: its matrix summed over the ranks once, its per-image rows gathered once (every rank joins)."""
-        mine = mine or {"hist": torch.zeros_like(hist), "rows": {}}
-        _, set_total = gather_hists(mine["hist"] if mine["hist"] is not None else torch.zeros_like(hist))
-        parts = [mine["rows"]]
+    def gathered_set(name):
+        """One more scored label set: its matrix summed over the ranks once, the per-image rows of its stage - if it has any - gathered
+        once (every rank joins, also one whose shard is empty)."""
+        mine = getattr(build_validation, "last_" + name) or {}
+        _, set_total = gather_hists(mine["hist"] if mine.get("hist") is not None else torch.zeros_like(hist))
+        got = dict(score=None if args.unlabeled else evaluate.scores_from_hist(set_total), hist=set_total,
+                   coverage=None if args.unlabeled else components.coverage(set_total, total))
+        if label_stages.STAGES[name].rows is None:
+            return got
+        parts = [mine.get("rows", {})]
         if world > 1:
             parts = [None] * world
-            dist.all_gather_object(parts, mine["rows"])
+            dist.all_gather_object(parts, mine.get("rows", {}))
         rows = {}
         for part in parts:
             rows.update(part)
         order = sorted(rows)
         counts = np.stack([rows[i][1] for i in order]) if order else np.zeros((0, 3), np.int64)
-        return dict(score=None if args.unlabeled else evaluate.scores_from_hist(set_total), hist=set_total,
-                    coverage=None if args.unlabeled else components.coverage(set_total, total), names=[rows[i][0] for i in order], counts=counts)
-    if clean is not None:                                                                   # --clean_min_region: the kept pixels
-        got = gathered_set(build_validation.last_clean)
-        validate.last_clean = dict(min_region=clean["min_region"], connectivity=clean["connectivity"], stats=components.region_stats(got["counts"]), **got)
-    if fill is not None:                                                                    # --fill_ignore: the filled maps
-        got = gathered_set(build_validation.last_fill)
-        validate.last_fill = dict(radius=fill["radius"], stats=label_fill.fill_stats(got["counts"]), **got)
-    if snap is not None:                                                                    # --snap_superpixels: the snapped maps
-        got = gathered_set(build_validation.last_snap)
-        pixels = torch.tensor([int((build_validation.last_snap or {}).get("pixels", 0))], dtype=torch.int64, device=hist.device)
-        if world > 1:
-            dist.all_reduce(pixels)
-        validate.last_snap = dict(stats=superpixels.snap_stats(got["counts"], int(pixels.item())), **{k: snap[k] for k in ("step", "compactness", "iters", "min_share")}, **got)
+        return dict(**got, names=[rows[i][0] for i in order], counts=counts)
+    said = {}                                           # per stage that is on, what the log and the record say of it: score, stats, coverage
+    for name, resolved in stages.items():
+        stage = label_stages.STAGES[name]
+        if stage.rows is None:                                                              # margin: below, behind its sweep
+            continue
+        got, more = gathered_set(name), ()
+        if name == "snap":                                                                  # the share of pixels the vote changed
+            pixels = torch.tensor([int((build_validation.last_snap or {}).get("pixels", 0))], dtype=torch.int64, device=hist.device)
+            if world > 1:
+                dist.all_reduce(pixels)
+            more = (int(pixels.item()),)
+        said[name] = dict(**label_stages.pipeline_value(stage, resolved), stats=stage.stats(got["counts"], *more), **got)
+        setattr(validate, "last_" + name, said[name])
     if msweep is not None or mcut is not None:
         # --margin_sweep / --margin_min: the ranks' counts summed once, like the matrix (a flagged image is in them once: skipped, then
         # counted in fp32); every rank joins, also one whose shard is empty
@@ -1635,12 +1596,9 @@ def validate(args=None, dataset=None, pipe=None):
                 _, m["totals"] = gather_hists(tot if tot is not None else torch.zeros((len(msweep), 3, args.num_classes), dtype=torch.int64, device=hist.device))
                 m["scores"] = bkg_sweep.scores_from_totals(m["totals"])
         if mcut is not None:
-            m["hist"] = m["score"] = m["label_coverage"] = None
-            if not args.unlabeled:
-                mh = mine.get("hist")
-                _, m["hist"] = gather_hists(mh if mh is not None else torch.zeros_like(hist))
-                m["score"] = evaluate.scores_from_hist(m["hist"])
-                m["label_coverage"] = components.coverage(m["hist"], total)
+            got = gathered_set("margin") if not args.unlabeled else dict(hist=None, score=None, coverage=None)   # (no matrix without ground truth)
+            m.update(hist=got["hist"], score=got["score"], label_coverage=got["coverage"])
+            said["margin"] = dict(score=got["score"], stats=None, coverage=got["coverage"])
     tags = None
     if tagger is not None:
         # the predicted rows of every rank, once: every rank joins, also one whose shard is empty
@@ -1675,43 +1633,24 @@ def validate(args=None, dataset=None, pipe=None):
             logging.info("\n" + bkg_sweep.format_sweep_table(sweep_scores, sweep, cat_list))
             jb, sb = bkg_sweep.best_scale(sweep_scores, sweep)
             logging.info(f"bkg_sweep best scale {sb:g}: mIoU {sweep_scores[jb]['miou'] * 100:.3f} (labels written and scored at --bkg_scale {args.bkg_scale:g})")
-        if clean is not None:
-            c = validate.last_clean
+        def log_set(name):
+            stage, resolved, c = label_stages.STAGES[name], stages[name], said[name]
             if c["score"] is not None:
-                logging.info(f"clean_label_score (--clean_min_region {clean['min_region']:g}, connectivity {clean['connectivity']}):")
+                logging.info(label_stages.title(stage, resolved))
                 logging.info("\n" + format_scores_table(c["score"], cat_list))
-            logging.info(components.format_clean_summary(c["stats"], c["coverage"]))
-            if clean["label_dir"]:
-                logging.info(f"cleaned label maps -> {clean['label_dir']}")
-        if fill is not None:
-            c = validate.last_fill
-            if c["score"] is not None:
-                logging.info(f"fill_label_score (--fill_ignore {'inf' if fill['radius'] is None else fill['radius']}):")
-                logging.info("\n" + format_scores_table(c["score"], cat_list))
-            logging.info(label_fill.format_fill_summary(c["stats"], c["coverage"]))
-            if fill["label_dir"]:
-                logging.info(f"filled label maps -> {fill['label_dir']}")
-        if snap is not None:
-            c = validate.last_snap
-            if c["score"] is not None:
-                logging.info(f"snap_label_score (--snap_superpixels {snap['step']}, compactness {snap['compactness']}, {snap['iters']} iterations, "
-                             f"min share {snap['min_share']:g}):")
-                logging.info("\n" + format_scores_table(c["score"], cat_list))
-            logging.info(superpixels.format_snap_summary(c["stats"], c["coverage"]))
-            if snap["label_dir"]:
-                logging.info(f"snapped label maps -> {snap['label_dir']}")
-        if msweep is not None:
-            m = validate.last_margin
+            summary = stage.summary(c["stats"], c["coverage"])
+            if summary:
+                logging.info(summary)
+            if resolved["label_dir"]:
+                logging.info(f"{stage.noun} label maps -> {resolved['label_dir']}")
+        for name in stages:
+            if name != "margin":
+                log_set(name)
+        if msweep is not None:                              # the sweep's table stands in front of the cut's
             logging.info("margin_sweep_score (kept: arg-max margin >= the threshold; coverage over all pixels):")
-            logging.info("\n" + margin_mod.format_margin_table(msweep, m["kept"], m["scores"], cat_list))
+            logging.info("\n" + margin_mod.format_margin_table(msweep, validate.last_margin["kept"], validate.last_margin["scores"], cat_list))
         if mcut is not None:
-            m = validate.last_margin
-            if m["score"] is not None:
-                logging.info(f"margin_label_score (--margin_min {mcut['min']:g}):")
-                logging.info("\n" + format_scores_table(m["score"], cat_list))
-                logging.info(f"margin coverage (kept pixels over labelled pixels): {m['label_coverage'] * 100:.3f} %")
-            if mcut["label_dir"]:
-                logging.info(f"margin label maps -> {mcut['label_dir']}")
+            log_set("margin")
         if tags is not None:
             logging.info(f"tags (--tags clip, thre {tagger['thre']}, at most {tagger['kmax']}, scale {tagger['scale']}): {tags['images']} images, "
                          f"tags per image {dict((k, v) for k, v in enumerate(tags['tags_per_image']) if v)}"
@@ -1737,15 +1676,8 @@ def validate(args=None, dataset=None, pipe=None):
                            **({"bkg_sweep": bkg_sweep.sweep_json(sweep_scores, sweep)} if sweep is not None else {}),
                            **({"margin_sweep": margin_mod.margin_json(msweep, validate.last_margin["kept"], validate.last_margin["scores"])}
                               if msweep is not None else {}),
-                           **({"margin": margin_mod.margin_min_json(mcut["min"], validate.last_margin["score"], validate.last_margin["label_coverage"])}
-                              if mcut is not None else {}),
-                           **({"clean": components.clean_json(clean["min_region"], clean["connectivity"], validate.last_clean["stats"],
-                                                              validate.last_clean["score"], validate.last_clean["coverage"])}
-                              if clean is not None else {}),
-                           **({"fill": label_fill.fill_json(fill["radius"], validate.last_fill["stats"], validate.last_fill["score"],
-                                                            validate.last_fill["coverage"])} if fill is not None else {}),
-                           **({"snap": superpixels.snap_json(snap, validate.last_snap["stats"], validate.last_snap["score"],
-                                                             validate.last_snap["coverage"])} if snap is not None else {})}, f)
+                           **{name: label_stages.STAGES[name].json(stages[name], said[name]["stats"], said[name]["score"], said[name]["coverage"])
+                              for name in label_stages.INFER_LAM_JSON_ORDER if name in stages}}, f)
     if image_scores.wanted(args):                                                           # one all_gather_object, rank 0 writes
         validate.last_image_scores = image_scores.finish(build_validation.last_image_scores, args, cat_list, rank, what="LAM_score")
         if rank == 0 and args.json_out and image_scores.boundary_of(args) is not None:       # the record above gains its `boundary` block

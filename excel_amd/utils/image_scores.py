@@ -42,6 +42,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from .evaluate import boundary_scores_from_counts, image_score_rows
+from .label_stages import ROW_SETS
 
 SETS = ("main", "crf", "conf", "clean", "fill", "snap", "margin")
 MAX_RADIUS = 72              # what ops.boundary_max_radius() answers (boundary.hip's halo); the CPU path refuses the same radii
@@ -178,16 +179,12 @@ class ImageScoreLog:
     """The records of one rank: index -> (name, (H, W), {set: counts int64 [3,nc]}).  put() replaces what an earlier pass recorded for the
     same image and set (the overflow guard's exact-fp32 second pass); defer() takes a ticket and reads it when it is ready."""
 
-    def __init__(self, num_classes, sets=("main",), boundary=None, regions=False, fills=False, snaps=False):
+    def __init__(self, num_classes, sets=("main",), boundary=None, rows=()):
         """boundary = None | dict(ratio=, px=): with it every set has a twin "<set>_bd" (ops.boundary_scores' counts) that is recorded
-        and required like the set itself, and merged() adds the radius of every image.  regions (--clean_min_region): every image also
-        has a row (regions, regions removed, pixels removed) of utils/components.filter_small_regions, put_regions() records it.
-        fills (--fill_ignore): likewise a row (holes, holes filled, largest squared distance) of utils/label_fill.fill_nearest_label,
-        put_fills() records it.  snaps (--snap_superpixels): likewise a row (superpixels with a vote, snapped, pixels changed) of
-        utils/superpixels.snap_labels, put_snaps() records it."""
-        self.regions = bool(regions)
-        self.fills = bool(fills)
-        self.snaps = bool(snaps)
+        and required like the set itself, and merged() adds the radius of every image.  rows = the keys of the row sets the run has
+        (utils/label_stages.ROW_SETS: "regions" with --clean_min_region, "fills" with --fill_ignore, "snaps" with
+        --snap_superpixels): every image also has a row of three counts of that stage, put_rows() records it."""
+        self.rows = tuple(r.key for r in ROW_SETS if r.key in rows)
         bad = [s for s in sets if s not in SETS]
         if bad or "main" not in sets:
             raise ValueError(f"image score sets {tuple(sets)}: 'main' plus any of {SETS[1:]}")
@@ -206,23 +203,13 @@ class ImageScoreLog:
         rec = self.records.setdefault(int(index), (str(name), (int(hw[0]), int(hw[1])), {}))
         rec[2][which] = c
 
-    def put_regions(self, indices, names, hws, counts):
-        """counts [B,3]: the filter's rows of one step; a later row of an image replaces the earlier one."""
+    def put_rows(self, kind, indices, names, hws, counts):
+        """counts [B,3]: the rows of one step for the row set `kind`; a later row of an image replaces the earlier one."""
+        if kind not in self.rows:
+            raise ValueError(f"image scores: row set {kind!r} is not recorded by this run ({self.rows})")
         for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
             rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
-            rec[2]["regions"] = np.array(counts[b], np.int64).reshape(3)
-
-    def put_fills(self, indices, names, hws, counts):
-        """counts [B,3]: the fill's rows of one step; a later row of an image replaces the earlier one."""
-        for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
-            rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
-            rec[2]["fills"] = np.array(counts[b], np.int64).reshape(3)
-
-    def put_snaps(self, indices, names, hws, counts):
-        """counts [B,3]: the vote's rows of one step; a later row of an image replaces the earlier one."""
-        for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
-            rec = self.records.setdefault(int(i), (str(n), (int(hw[0]), int(hw[1])), {}))
-            rec[2]["snaps"] = np.array(counts[b], np.int64).reshape(3)
+            rec[2][kind] = np.array(counts[b], np.int64).reshape(3)
 
     def put_batch(self, indices, names, hws, which, counts):
         for b, (i, n, hw) in enumerate(zip(indices, names, hws)):
@@ -257,7 +244,7 @@ class ImageScoreLog:
             allrec.update(p)
         order = sorted(allrec)
         for i in order:
-            missing = [s for s in self.sets + self.twins + (("regions",) if self.regions else ()) + (("fills",) if self.fills else ()) + (("snaps",) if self.snaps else ()) if s not in allrec[i][2]]
+            missing = [s for s in self.sets + self.twins + self.rows if s not in allrec[i][2]]
             if missing:
                 raise RuntimeError(f"image scores: {allrec[i][0]!r} has no counts for {missing}")
         stack = lambda s: np.stack([allrec[i][2][s] for i in order]) if order else np.zeros((0, 3, self.nc), np.int64)
@@ -266,12 +253,8 @@ class ImageScoreLog:
         if self.boundary is not None:                         # only then: a table without the flag has the keys it always had
             out["radius"] = np.asarray([boundary_radius(*allrec[i][1], **self.boundary) for i in order], np.int32)
             out["bcounts"] = {s: stack(s + "_bd") for s in self.sets}
-        if self.regions:                                      # likewise
-            out["regions"] = np.stack([allrec[i][2]["regions"] for i in order]) if order else np.zeros((0, 3), np.int64)
-        if self.fills:
-            out["fills"] = np.stack([allrec[i][2]["fills"] for i in order]) if order else np.zeros((0, 3), np.int64)
-        if self.snaps:
-            out["snaps"] = np.stack([allrec[i][2]["snaps"] for i in order]) if order else np.zeros((0, 3), np.int64)
+        for k in self.rows:                                   # likewise
+            out[k] = np.stack([allrec[i][2][k] for i in order]) if order else np.zeros((0, 3), np.int64)
         return out
 
 
@@ -288,18 +271,13 @@ def write_files(path, merged, class_names):
     main, extra = rows["main"], [s for s in merged["counts"] if s != "main"]
     brows = {s: image_score_rows(c) for s, c in merged.get("bcounts", {}).items()}
     bhead = ["radius", "biou"] + [f"{s}_biou" for s in extra] if brows else []
-    regions = merged.get("regions")
-    rhead = ["regions", "regions_removed", "pixels_removed"] if regions is not None else []
-    fills = merged.get("fills")
-    fhead = ["holes", "filled", "max_fill_dist"] if fills is not None else []
-    snaps = merged.get("snaps")
-    shead = ["superpixels", "snapped", "pixels_changed"] if snaps is not None else []
+    stage_rows = [r for r in ROW_SETS if merged.get(r.key) is not None]
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["name", "height", "width", "scored", "pacc", "miou", "present"] + ["iou_" + c for c in cats]
-                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead + rhead + fhead + shead)
+                   + [f"{s}_{k}" for s in extra for k in ("pacc", "miou", "scored")] + bhead + [h for r in stage_rows for h in r.heads])
         for i, name in enumerate(merged["names"]):
             present = "|".join(cats[c] for c in np.nonzero(merged["counts"]["main"][i, 0])[0])
             w.writerow([name, int(merged["hw"][i, 0]), int(merged["hw"][i, 1]), int(main["scored"][i]), _fmt(main["pacc"][i]),
@@ -307,18 +285,12 @@ def write_files(path, merged, class_names):
                        + [x for s in extra for x in (_fmt(rows[s]["pacc"][i]), _fmt(rows[s]["miou"][i]), int(rows[s]["scored"][i]))]
                        + ([int(merged["radius"][i]), _fmt(brows["main"]["miou"][i])] + [_fmt(brows[s]["miou"][i]) for s in extra]
                           if brows else [])
-                       + ([int(v) for v in regions[i]] if regions is not None else [])
-                       + ([int(fills[i][0]), int(fills[i][1]), _fmt(np.sqrt(float(fills[i][2])))] if fills is not None else [])
-                       + ([int(v) for v in snaps[i]] if snaps is not None else []))
+                       + [c for r in stage_rows for c in r.cells(merged[r.key][i], _fmt)])
     more = {}
     if brows:
         more = dict(radius=merged["radius"].astype(np.int32), **{"bcounts_" + s: c.astype(np.int64) for s, c in merged["bcounts"].items()})
-    if regions is not None:
-        more["regions"] = np.asarray(regions, np.int64)
-    if fills is not None:
-        more["fills"] = np.asarray(fills, np.int64)
-    if snaps is not None:
-        more["snaps"] = np.asarray(snaps, np.int64)
+    for r in stage_rows:
+        more[r.key] = np.asarray(merged[r.key], np.int64)
     np.savez(path + ".npz", names=np.asarray(merged["names"], dtype=str), hw=merged["hw"],
              **{"counts_" + s: c.astype(np.int64) for s, c in merged["counts"].items()}, **more)
     return main
